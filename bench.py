@@ -26,11 +26,17 @@ With N > 1 GPUs the ranks take disjoint theta blocks (weak
 scaling, no data-path collective) and the log-likelihood vector is assembled
 with ONE all-gather over RCCL inside the timed region.
 
-`sequential` in the JSON line is the same workload run strictly one evaluation
-at a time on one stream (the optimize() objective pattern, where evaluation i+1
-depends on i); its HIP-event stage times feed `roofline`.
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times --steps steps and
+prints the headline (metric, value, unit, higher_is_better, dtype, ms_per_step,
+config). --dump-outputs DIR writes what the last timed step returned to this
+process as float64 arrays: lZ.npy (B,) and dlZ.npy (B, D+3), B the thetas of its
+block. The thetas of every step follow from the step number alone, so two runs
+with the same arguments see the same inputs.
 
-Rank 0 prints ONE JSON line. Besides the driver contract it carries
+--full also measures and checks what lies beyond the headline:
+  sequential    the same workload run strictly one evaluation at a time on one
+                stream (the optimize() objective pattern, where evaluation i+1
+                depends on i); its HIP-event stage times feed `roofline`
   roofline      achieved fp64 TFLOP/s of the dense engine (algorithmic N^3 flop
                 per evaluation / HIP-event time of the potrf+trtri+lauum stages
                 on the library's stream) against the MI355X fp64 MFMA peak
@@ -40,6 +46,7 @@ Rank 0 prints ONE JSON line. Besides the driver contract it carries
                 about 45 s on an MI355X box's 16 cores), N/2 or N/4 scaled per stage
                 only if that runs out
   configs       C2..C5 of BASELINE.json with a roofline each (tools/bench_configs.py)
+  parity_check  lZ / dlZ of member 0 of step 0 against tests/golden/g_metric.npz
 
 With --gpus 1 nothing imports torch (C ABI through ctypes only). `python bench.py
 --gpus N` as ONE process drives N GPUs through gpx_loglik_batch_multi (host thread
@@ -224,6 +231,12 @@ def main():
     ap.add_argument('--per-gpu', type=int, default=6,
                     help='independent thetas per GPU per step (6 since round 3: one group of '
                          'six members in lock-step; rounds 1-2 measured 3 per step)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check beyond the headline: sequential evaluations, '
+                         'roofline, parity against the golden fixture, C2..C5 records and the '
+                         'CPU baseline (the options below apply to it)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write lZ.npy and dlZ.npy of the last timed step to DIR')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-budget', type=float, default=150.0,
                     help='time limit (s) of the CPU-baseline child (2-3 evaluations: a new '
@@ -237,6 +250,8 @@ def main():
                          'profiles/r04_batch_small_depth3_baseline.json); off by default: the '
                          'driver\'s run creates no CU-masked stream')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     # Launch modes:
     #   torchrun (WORLD_SIZE > 1): one process per GPU, torch.distributed over RCCL
@@ -309,9 +324,10 @@ def main():
 
     lZ_local = np.empty((args.steps, per * in_lib))
     dlZ_first = None                            # gradient of member 0 of step 0 (parity_check)
-    dev.enable_timing(True)                     # HIP events around the groups' dense stages
-    if in_lib > 1:                              # ... and on the library's per-device handles
-        _lib.multi_enable_timing(in_lib, True)
+    if args.full:
+        dev.enable_timing(True)                 # HIP events around the groups' dense stages
+        if in_lib > 1:                          # ... and on the library's per-device handles
+            _lib.multi_enable_timing(in_lib, True)
     sync()
     t0 = time.perf_counter()
     for s in range(args.steps):
@@ -354,9 +370,15 @@ def main():
         batch_dense_ms = max(r['dense_ms'] for r in per_device)
         batch_members = min(r['members'] for r in per_device)
 
-    # one-at-a-time evaluations on rank 0: HIP-event stage times for the roofline
+    if rank == 0 and args.dump_outputs:
+        # what the last timed step returned to this process (in_lib > 1: every device's part)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'lZ.npy'), lZ_local[-1])
+        np.save(os.path.join(args.dump_outputs, 'dlZ.npy'), dlZ_s)
+
+    # --full: one-at-a-time evaluations on rank 0, HIP-event stage times for the roofline
     stage, seq_n, seq_s = {}, 0, 0.0
-    if rank == 0:
+    if rank == 0 and args.full:
         dev.enable_timing(True)
         evaluate_one(2 * 10 ** 6)
         seq_n = max(3, min(args.steps, 6))
@@ -369,7 +391,7 @@ def main():
         dev.enable_timing(False)
 
     big_launch = None
-    if rank == 0 and N == 16384:
+    if rank == 0 and args.full and N == 16384:
         n_, k_ = N - 1024 - 2048, 2048
         ms_ = dev.la_gemm_bench_mnk(n_, n_, k_, ta=1, tb=0, flags=1, beta=1.0, reps=3)
         big_launch = {'kernel': 'gemm_f64_kernel<1,0,Geo<128,2,4,true>> (+ its 64-tile remainder '
@@ -378,41 +400,6 @@ def main():
                       'achieved': float(n_) * n_ * k_ / ms_ * 1e-9}
     if rank == 0:
         evals = args.steps * n_gpus * per
-        dense_ms = (stage.get('potrf', 0.0) + stage.get('trtri', 0.0) +
-                    stage.get('lauum', 0.0)) / seq_n
-        traffic = traffic_src = None   # HBM bytes per evaluation from the committed PMC
-        try:                           # passes (tools/collect_profile.sh -> profiles/)
-            with open(os.path.join(ROOT, 'profiles', 'traffic.json')) as f:
-                tj = json.load(f)
-            if (tj.get('n', 16384), tj.get('d', 8)) == (N, D):   # measured at that size only
-                traffic = tj['hbm_bytes_per_eval']
-                traffic_src = ('profiles/traffic.json (%s): rocprofv3 --pmc FETCH_SIZE / '
-                               'WRITE_SIZE passes over one evaluation, FETCH_SIZE doubled '
-                               '(gfx950); counters cannot be read from inside this run'
-                               % tj.get('tag'))
-        except (OSError, KeyError, ValueError):
-            pass
-        flops = float(N) ** 3                      # potrf N^3/3 + potri 2N^3/3
-        seq_achieved = flops / (dense_ms * 1e-3) * 1e-12
-        # The timed region itself: this rank's blocks ran as groups in lock-step on one
-        # stream each, and HIP events on that stream bracket every group's factor + inverse
-        # stage (all product launches and the panel launches between them; the build, the
-        # vector and the trace kernels are outside). Without groups (rounds 1-3's contexts,
-        # or the in-library multi-device path whose handles live inside the library) the
-        # figure of the sequential evaluations stands in.
-        if batch_members > 0 and batch_dense_ms > 0:
-            achieved = flops * batch_members / (batch_dense_ms * 1e-3) * 1e-12
-            measured_on = ('the timed (batched) region: HIP events on the stream of each group '
-                           'of %d members in lock-step, around its factor + inverse stage '
-                           '(gpx_batch_timings: %.1f ms for %d evaluations%s)'
-                           % (per, batch_dense_ms, batch_members,
-                              '' if n_gpus == 1 else '; per GPU, the slowest of %d: see '
-                              'roofline.per_device' % n_gpus))
-        else:
-            achieved = seq_achieved
-            measured_on = ('sequential evaluations, HIP events on the library stream '
-                           'around the potrf (+trtri+lauum) stage: the look-ahead streams '
-                           'are joined before the stage ends')
         mode = ('torch.distributed, one process per GPU' if use_dist else
                 'one process, gpx_loglik_batch_multi over %d devices' % in_lib if in_lib > 1
                 else 'one process, C ABI only (no torch)')
@@ -446,7 +433,60 @@ def main():
                                'collective, one all-gather of lZ' % n_gpus,
                 'launch': mode,
             },
-            'roofline': {
+            'lZ_first': float(np.ravel(lZ_all)[0]),
+        }
+        if per_device is not None:
+            out['config']['safe_mode'] = any(r['safe_mode'] for r in per_device)
+        # audit of the N > 1 paths: ranks the collective saw, and what every device /
+        # rank contributed (sum of its lZ values over all steps)
+        if use_dist:
+            out['config']['collective_ranks'] = int(dist.get_world_size())
+            out['config']['backend'] = os.environ.get('GPX_BENCH_BACKEND', 'nccl')
+            out['config']['lZ_sum_per_rank'] = [float(v) for v in lZ_all.sum(axis=1)]
+        elif in_lib > 1:
+            out['config']['collective_ranks'] = int(_lib.multi_comm_size())
+            sums = []
+            for dv in range(in_lib):
+                lo, hi = _lib.batch_partition(per * in_lib, in_lib, dv)
+                sums.append(float(lZ_all[:, lo:hi].sum()))
+            out['config']['lZ_sum_per_device'] = sums
+        if args.full:
+            dense_ms = (stage.get('potrf', 0.0) + stage.get('trtri', 0.0) +
+                        stage.get('lauum', 0.0)) / seq_n
+            traffic = traffic_src = None   # HBM bytes per evaluation from the committed PMC
+            try:                           # passes (tools/collect_profile.sh -> profiles/)
+                with open(os.path.join(ROOT, 'profiles', 'traffic.json')) as f:
+                    tj = json.load(f)
+                if (tj.get('n', 16384), tj.get('d', 8)) == (N, D):   # measured at that size only
+                    traffic = tj['hbm_bytes_per_eval']
+                    traffic_src = ('profiles/traffic.json (%s): rocprofv3 --pmc FETCH_SIZE / '
+                                   'WRITE_SIZE passes over one evaluation, FETCH_SIZE doubled '
+                                   '(gfx950); counters cannot be read from inside this run'
+                                   % tj.get('tag'))
+            except (OSError, KeyError, ValueError):
+                pass
+            flops = float(N) ** 3                      # potrf N^3/3 + potri 2N^3/3
+            seq_achieved = flops / (dense_ms * 1e-3) * 1e-12
+            # The timed region itself: this rank's blocks ran as groups in lock-step on one
+            # stream each, and HIP events on that stream bracket every group's factor + inverse
+            # stage (all product launches and the panel launches between them; the build, the
+            # vector and the trace kernels are outside). Without groups (rounds 1-3's contexts,
+            # or the in-library multi-device path whose handles live inside the library) the
+            # figure of the sequential evaluations stands in.
+            if batch_members > 0 and batch_dense_ms > 0:
+                achieved = flops * batch_members / (batch_dense_ms * 1e-3) * 1e-12
+                measured_on = ('the timed (batched) region: HIP events on the stream of each '
+                               'group of %d members in lock-step, around its factor + inverse '
+                               'stage (gpx_batch_timings: %.1f ms for %d evaluations%s)'
+                               % (per, batch_dense_ms, batch_members,
+                                  '' if n_gpus == 1 else '; per GPU, the slowest of %d: see '
+                                  'roofline.per_device' % n_gpus))
+            else:
+                achieved = seq_achieved
+                measured_on = ('sequential evaluations, HIP events on the library stream '
+                               'around the potrf (+trtri+lauum) stage: the look-ahead streams '
+                               'are joined before the stage ends')
+            out['roofline'] = {
                 'bound': 'mfma',
                 'kernel': 'gemm_f64_kernel (all launches of one evaluation: rank-NB trailing '
                           'updates, row panels, inverse columns, K^-1 accumulation) + the '
@@ -459,7 +499,8 @@ def main():
                 # the same algorithmic flops against the wall clock of the TIMED (batched)
                 # region: everything included -- builds, trace passes, host syncs
                 'achieved_batched_wall': flops * evals / elapsed * 1e-12 / n_gpus,
-                'frac_batched_wall': flops * evals / elapsed * 1e-12 / n_gpus / PEAK_FP64_MFMA_TFLOPS,
+                'frac_batched_wall': (flops * evals / elapsed * 1e-12 / n_gpus /
+                                      PEAK_FP64_MFMA_TFLOPS),
                 'traffic': traffic,
                 'traffic_source': traffic_src,
                 'algorithmic_flop_per_eval': flops,
@@ -476,62 +517,48 @@ def main():
                 # trailing update of the factorisation, C (13312 x 13312, upper tiles) -=
                 # P^T P with P 2048 x 13312
                 'largest_launch': big_launch,
-            },
-            'sequential': {
+            }
+            out['sequential'] = {
                 'evals_per_s': seq_n / seq_s if seq_s > 0 else None,
-                'ms_per_eval': seq_s / seq_n * 1e3 if seq_n else None,
-                'tflops_N3_wall': flops / (seq_s / seq_n) * 1e-12 if seq_n else None,
+                'ms_per_eval': seq_s / seq_n * 1e3,
+                'tflops_N3_wall': flops / (seq_s / seq_n) * 1e-12,
                 'stage_ms_per_eval': dict((k_, v / seq_n) for k_, v in stage.items()
                                           if v > 0),
-            },
-            'lZ_first': float(np.ravel(lZ_all)[0]),
-        }
-        if per_device is not None:
-            # every device's / rank's own fraction of the fp64 MFMA peak over ITS groups
-            for r in per_device:
-                r['achieved'] = (flops * r['members'] / (r['dense_ms'] * 1e-3) * 1e-12
-                                 if r['dense_ms'] > 0 else None)
-                r['frac'] = r['achieved'] / PEAK_FP64_MFMA_TFLOPS if r['achieved'] else None
-            out['roofline']['per_device'] = per_device
-            out['config']['safe_mode'] = any(r['safe_mode'] for r in per_device)
-        # Parity of the timed call itself: member 0 of step 0 is theta_eval(D, 0), the theta1
-        # of the reference-generated fixture tests/golden/g_metric.npz (N = 16384, D = 8);
-        # lZ and every gradient component of what the timed region returned against it
-        # (tolerance of the tests: 1e-8 relative). The fixture is data, read from the repo.
-        try:
-            if (N, D) == (16384, 8) and rank == 0 and dlZ_first is not None:
-                g = np.load(os.path.join(ROOT, 'tests', 'golden', 'g_metric.npz'))
-                if np.array_equal(g['theta1'], recipes.theta_eval(D, 0)):
-                    lz0 = float(np.ravel(lZ_local)[0])
-                    out['parity_check'] = {
-                        'against': 'tests/golden/g_metric.npz lZ1 / dlZ1 (reference-generated)',
-                        'member': 'step 0, member 0 of the timed region (theta_eval(8, 0))',
-                        'lZ_rel_err': abs(lz0 - float(g['lZ1'])) / abs(float(g['lZ1'])),
-                        'dlZ_max_rel_err': float(np.max(np.abs(dlZ_first - g['dlZ1']) /
-                                                        np.abs(g['dlZ1']))),
-                        'tolerance': 1e-8}
-        except (OSError, KeyError, ValueError):
-            pass
-        # audit of the N > 1 paths: ranks the collective saw, and what every device /
-        # rank contributed (sum of its lZ values over all steps)
-        if use_dist:
-            out['config']['collective_ranks'] = int(dist.get_world_size())
-            out['config']['backend'] = os.environ.get('GPX_BENCH_BACKEND', 'nccl')
-            out['config']['lZ_sum_per_rank'] = [float(v) for v in lZ_all.sum(axis=1)]
-        elif in_lib > 1:
-            out['config']['collective_ranks'] = int(_lib.multi_comm_size())
-            sums = []
-            for dv in range(in_lib):
-                lo, hi = _lib.batch_partition(per * in_lib, in_lib, dv)
-                sums.append(float(lZ_all[:, lo:hi].sum()))
-            out['config']['lZ_sum_per_device'] = sums
-        if n_gpus == 1 and not args.no_configs:
-            # the other BASELINE configs, each with its own roofline (C2..C5)
-            sys.path.insert(0, os.path.join(ROOT, 'tools'))
-            import bench_configs
-            out['configs'] = bench_configs.run_all(dev, with_depth3=args.with_depth3)
-        if n_gpus == 1 and not args.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline(N, D, args.cpu_budget)
+            }
+            if per_device is not None:
+                # every device's / rank's own fraction of the fp64 MFMA peak over ITS groups
+                for r in per_device:
+                    r['achieved'] = (flops * r['members'] / (r['dense_ms'] * 1e-3) * 1e-12
+                                     if r['dense_ms'] > 0 else None)
+                    r['frac'] = r['achieved'] / PEAK_FP64_MFMA_TFLOPS if r['achieved'] else None
+                out['roofline']['per_device'] = per_device
+            # Parity of the timed call itself: member 0 of step 0 is theta_eval(D, 0), the
+            # theta1 of the reference-generated fixture tests/golden/g_metric.npz (N = 16384,
+            # D = 8); lZ and every gradient component of what the timed region returned
+            # against it (tolerance of the tests: 1e-8 relative). The fixture is data, read
+            # from the repo.
+            try:
+                if (N, D) == (16384, 8) and dlZ_first is not None:
+                    g = np.load(os.path.join(ROOT, 'tests', 'golden', 'g_metric.npz'))
+                    if np.array_equal(g['theta1'], recipes.theta_eval(D, 0)):
+                        lz0 = float(np.ravel(lZ_local)[0])
+                        out['parity_check'] = {
+                            'against': 'tests/golden/g_metric.npz lZ1 / dlZ1 '
+                                       '(reference-generated)',
+                            'member': 'step 0, member 0 of the timed region (theta_eval(8, 0))',
+                            'lZ_rel_err': abs(lz0 - float(g['lZ1'])) / abs(float(g['lZ1'])),
+                            'dlZ_max_rel_err': float(np.max(np.abs(dlZ_first - g['dlZ1']) /
+                                                            np.abs(g['dlZ1']))),
+                            'tolerance': 1e-8}
+            except (OSError, KeyError, ValueError):
+                pass
+            if n_gpus == 1 and not args.no_configs:
+                # the other BASELINE configs, each with its own roofline (C2..C5)
+                sys.path.insert(0, os.path.join(ROOT, 'tools'))
+                import bench_configs
+                out['configs'] = bench_configs.run_all(dev, with_depth3=args.with_depth3)
+            if n_gpus == 1 and not args.no_cpu_baseline:
+                out['cpu_baseline'] = cpu_baseline(N, D, args.cpu_budget)
         print(json.dumps(out), flush=True)
 
     if use_dist:

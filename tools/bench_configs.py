@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Timings of the BASELINE.json configs other than the headline metric on one
-MI355X, each with the roofline that bounds it. bench.py attaches
-these records to its JSON line under `configs`; run directly it prints one JSON
+MI355X, each with the roofline that bounds it. bench.py --full
+attaches these records to its JSON line under `configs`; run directly it prints one JSON
 object per config.
 usage: python tools/bench_configs.py [c2 c3 c4 c4s c5] [--with-depth3] [--out FILE]"""
 import json

@@ -7,9 +7,9 @@ set -o pipefail
 tag=${1:-r05}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/$tag; mkdir -p $out
-python3 bench.py --steps 10 --warmup 2 > $out/bench_n1.json 2> $out/bench_n1.err || exit 1
+python3 bench.py --full --steps 10 --warmup 2 > $out/bench_n1.json 2> $out/bench_n1.err || exit 1
 echo "bench done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-configs > $out/bench_under_rocprof.json 2> $out/trace.log || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-configs > $out/bench_under_rocprof.json 2> $out/trace.log || exit 1
 echo "trace (bench: groups of six + sequential) done"
 export GPX_GEMM_LOG=$out/gemmlog_seq.txt
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_seq -- python3 tools/run_eval.py 16384 6 > $out/trace_seq.log 2>&1 || exit 1

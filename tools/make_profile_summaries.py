@@ -31,7 +31,7 @@ shutil.copy(one('trace/*/*kernel_stats.csv'), os.path.join(dst, tag + '_rocprofv
 shutil.copy(os.path.join(src, 'bench_n1.json'), os.path.join(dst, tag + '_bench_n1.json'))
 shutil.copy(os.path.join(src, 'configs.json'), os.path.join(dst, tag + '_configs.json'))
 with open(os.path.join(dst, tag + '_trace_summary.txt'), 'w') as f:
-    f.write('# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 1 '
+    f.write('# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 5 --warmup 1 '
             '--no-cpu-baseline --no-configs; figures per evaluation (%s evaluations in the '
             'trace: (1+5) steps x 6 thetas, 3 in flight, + 7 sequential). Kernels of the 3 '
             'concurrent evaluations overlap, so their durations here are longer than in the '

@@ -44,7 +44,7 @@ def short(r):
 
 starts = [i for i, r in enumerate(rows) if short(r).startswith('kbuild_kernel<double, 4, true>')]
 with open(os.path.join(dst, tag + '_trace_summary.txt'), 'w') as f:
-    f.write('# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 1 '
+    f.write('# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 5 --warmup 1 '
             '--no-cpu-baseline --no-configs: (1 + 5) steps of ONE group of six members in '
             'lock-step on one stream (pygp_amd/csrc/group.hip) + 7 sequential evaluations '
             '(look-ahead streams). Figures per evaluation over all 43.\n')

@@ -8,7 +8,7 @@ tag=${1:-xcd_ab}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/$tag; mkdir -p $out
 for x in 0 1 0 1; do
-  GPX_TILE_XCD=$x python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-configs > $out/bench_x$x.json 2> $out/bench_x$x.err || exit 1
+  GPX_TILE_XCD=$x python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-configs > $out/bench_x$x.json 2> $out/bench_x$x.err || exit 1
   python3 - $out/bench_x$x.json $x <<'PY'
 import json, sys
 r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
