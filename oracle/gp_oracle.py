@@ -164,8 +164,17 @@ def _rescale(ell, X1, X2):
     return X1 / ell, (X2 / ell if X2 is not None else None)
 
 
+def _extended(*arrays):
+    """True when an operand is np.longdouble: cdist computes in fp64 only, so that case
+    (the extended-precision reference, tests/xprec.py) takes direct differences."""
+    return any(np.asarray(a).dtype == np.longdouble for a in arrays if a is not None)
+
+
 def _sqdist(X1, X2=None):
     # _distances.py:35-41: direct-difference form, exact zeros on the diagonal
+    if _extended(X1, X2):
+        X2 = X1 if X2 is None else X2
+        return sum((X1[:, i, None] - X2[None, :, i]) ** 2 for i in range(X1.shape[1]))
     return ssd.cdist(X1, X1 if X2 is None else X2, 'sqeuclidean')
 
 
@@ -173,7 +182,22 @@ def _sqdist_foreach(X1, X2=None):
     # _distances.py:44-52: one single-column cdist per input dimension
     X2 = X1 if X2 is None else X2
     for i in range(X1.shape[1]):
-        yield ssd.cdist(X1[:, i, None], X2[:, i, None], 'sqeuclidean')
+        if _extended(X1, X2):
+            yield (X1[:, i, None] - X2[None, :, i]) ** 2
+        else:
+            yield ssd.cdist(X1[:, i, None], X2[:, i, None], 'sqeuclidean')
+
+
+# pi and sqrt(d) at the precision of the operands (fp64 operands: the fp64 constants)
+_PI_LD = np.longdouble('3.14159265358979323846264338327950288')
+
+
+def _pi(x):
+    return _PI_LD if _extended(x) else np.pi
+
+
+def _sqrt_d(d, x):
+    return np.sqrt(np.longdouble(d)) if _extended(x) else np.sqrt(d)
 
 
 # -- kernels -----------------------------------------------------------------
@@ -204,14 +228,14 @@ def kernel_get(spec, X1, X2=None):
         return np.exp(spec['logsf'] * 2 - _sqdist(A, B) / 2)
     if kind == 'matern':
         d = spec['d']
-        A, B = _rescale(np.exp(spec['logell']) / np.sqrt(d), X1, X2)
+        A, B = _rescale(np.exp(spec['logell']) / _sqrt_d(d, spec['logell']), X1, X2)
         D = np.sqrt(_sqdist(A, B))
         return np.exp(spec['logsf'] * 2 - D) * _matern_f(d, D)
     if kind == 'periodic':
         sf2 = np.exp(spec['logsf'] * 2)
         ell = np.exp(spec['logell'])
         p = np.exp(spec['logp'])
-        D = np.sqrt(_sqdist(X1, X2)) * np.pi / p
+        D = np.sqrt(_sqdist(X1, X2)) * _pi(p) / p
         return sf2 * np.exp(-2 * (np.sin(D) / ell) ** 2)
     if kind == 'rq':                                       # rq.py:54-61
         sf2 = np.exp(spec['logsf'] * 2)
@@ -246,7 +270,7 @@ def kernel_grad(spec, X1, X2=None):
                 yield K * Dd
     elif kind == 'matern':
         d = spec['d']
-        A, B = _rescale(np.exp(spec['logell']) / np.sqrt(d), X1, X2)
+        A, B = _rescale(np.exp(spec['logell']) / _sqrt_d(d, spec['logell']), X1, X2)
         D = np.sqrt(_sqdist(A, B))
         S = np.exp(spec['logsf'] * 2 - D)
         K = S * _matern_f(d, D)
@@ -262,7 +286,7 @@ def kernel_grad(spec, X1, X2=None):
         sf2 = np.exp(spec['logsf'] * 2)
         ell = np.exp(spec['logell'])
         p = np.exp(spec['logp'])
-        D = np.sqrt(_sqdist(X1, X2)) * np.pi / p
+        D = np.sqrt(_sqdist(X1, X2)) * _pi(p) / p
         R = np.sin(D) / ell
         S = R ** 2
         E = 2 * sf2 * np.exp(-2 * S)
@@ -341,7 +365,7 @@ def kernel_gradx(spec, X1, X2=None):
         return -K[:, :, None] * D / ell
     if kind == 'matern':
         d = spec['d']
-        ell = np.exp(spec['logell']) / np.sqrt(d)
+        ell = np.exp(spec['logell']) / _sqrt_d(d, spec['logell'])
         A, B = _rescale(ell, X1, X2)
         D1 = _diff(A, B)
         D = np.sqrt(np.sum(D1 ** 2, axis=-1))
@@ -353,9 +377,9 @@ def kernel_gradx(spec, X1, X2=None):
         sf2 = np.exp(spec['logsf'] * 2)
         ell = np.exp(spec['logell'])
         p = np.exp(spec['logp'])
-        D = _diff(X1, X2) * np.pi / p
+        D = _diff(X1, X2) * _pi(p) / p
         K = sf2 * np.exp(-2 * (np.sin(D) / ell) ** 2)
-        return -2 * np.pi / ell ** 2 / p * K * np.sin(2 * D)
+        return -2 * _pi(p) / ell ** 2 / p * K * np.sin(2 * D)
     if kind == 'rq':                                       # rq.py:93-107
         sf2 = np.exp(spec['logsf'] * 2)
         ell = np.exp(spec['logell'])

@@ -82,7 +82,7 @@ struct gpx_ctx {
     int posterior_calls = 0;       // since the last factorisation (posterior_impl)
     double lZ = 0;
     // posterior / api scratch
-    DevBuf Ks, KsT, Xs, mu, s2, post_part, t0, t1, t2, split, gpart;
+    DevBuf Ks, KsT, Vc, Xs, mu, s2, post_part, t0, t1, t2, split, gpart;
     int64_t bench_n = 0;
     // results of the evaluation in flight land in pinned host memory
     double *hres = nullptr;        // [0..2] scalars, [4..] trace accumulators
@@ -631,7 +631,7 @@ int gpx_destroy(gpx_t *h)
     (void)hipStreamSynchronize(h->stream);
     DLOG("release buffers");
     DevBuf *bufs[] = {&h->X, &h->y, &h->Xf32, &h->A, &h->W, &h->Kinv, &h->r, &h->a,
-                      &h->alpha, &h->scalars, &h->partial, &h->info, &h->gv_part, &h->pctl, &h->Ks, &h->KsT,
+                      &h->alpha, &h->scalars, &h->partial, &h->info, &h->gv_part, &h->pctl, &h->Ks, &h->KsT, &h->Vc,
                       &h->Xs, &h->mu, &h->s2, &h->post_part, &h->t0, &h->t1, &h->t2, &h->split, &h->gpart};
     for (DevBuf *b : bufs) b->release();
     DLOG("events");
@@ -1511,6 +1511,21 @@ static int tri_product(gpx_ctx *h, int ta, const double *B, double *C, int mcp)
     return gpx_sum_partials(h->stream, h->split.as<double>(), nsplit, stride, stride, C);
 }
 
+// V = R^-T K (np x mcp) as V1 = W^T K with one step of refinement, V = V1 + W^T (K - R^T V1);
+// K is overwritten by the residual. The product with the explicit inverse alone has a forward
+// error that is not that of a substitution: s2 = k** - ||V||^2 cancels, and at cond(K) ~1e11
+// (sn = 1e-4) it lost up to 110x against LAPACK's dtrtrs (s2; ds2 70x, mu 40x, Sigma 20x:
+// tests/test_gpu_accuracy.py). The refinement step brings all of them within 10x.
+static int solve_rt_refined(gpx_ctx *h, double *K, double *V, int mcp)
+{
+    const DenseWs w = h->ws();
+    GPX_TRY(tri_product(h, 1, K, V, mcp));
+    GPX_TRY(gpx_rt_residual(h->stream, w.A, h->ld, h->np, V, K, mcp, mcp));
+    GPX_TRY(h->Vc.reserve((size_t)h->np * mcp * 8));
+    GPX_TRY(tri_product(h, 1, K, h->Vc.as<double>(), mcp));
+    return gpx_add_inplace(h->stream, V, h->Vc.as<double>(), (size_t)h->np * mcp);
+}
+
 static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2,
                           double *dmu, double *ds2)
 {
@@ -1528,19 +1543,14 @@ static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, dou
     const int CH = h->np <= 8192 ? 8192 : (h->np <= 16384 ? 4096 : 2048);
     const DenseWs w = h->ws();
     const bool grads = dmu && ds2;
-    // V = R^-T K* is ONE triangle-aware product with W^T once W = R^-1 is complete;
-    // with only the left-half inverses of a value-only update it is the recursive
-    // solve of chol.hip (a chain of small launches, 1.5 ms at N = 16384 even for one
-    // test point). Completing W costs a fraction of the factorisation, so do it when
-    // there are many test points or when posterior calls repeat for this
-    // factorisation (the acquisition loop of Bayesian optimisation), and always for
-    // input gradients (alpha = W a and beta = W V need it).
+    // V = R^-T K* is a triangle-aware product with W^T and one step of refinement
+    // (solve_rt_refined), so W = R^-1 is completed first if the factorisation left only
+    // the inverses of its diagonal blocks (a fraction of the factorisation's cost)
     ++h->posterior_calls;
-    if (!h->w_complete && (grads || h->posterior_calls >= 2 || m >= h->np / 4)) {
+    if (!h->w_complete) {
         GPX_TRY(gpx_trtri(h->stream, w));
         h->w_complete = true;
     }
-    const bool by_gemm = h->w_complete;
     if (grads) {
         GPX_TRY(h->alpha.reserve((size_t)h->np * 8));
         GPX_TRY(gpx_trmv_upper(h->stream, w.W, h->ld, h->np, h->a.as<double>(),
@@ -1565,14 +1575,8 @@ static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, dou
                                    mcp, false, false, 0.0));
         clk.tick(T_POST_BUILD);
         // RK = R^-T K (exact.py:88)
-        double *V = h->Ks.as<double>();
-        if (by_gemm) {
-            GPX_TRY(tri_product(h, 1, h->Ks.as<double>(), h->KsT.as<double>(), mcp));
-            V = h->KsT.as<double>();
-        } else {
-            GPX_TRY(gpx_trsm_rt(h->stream, w, h->Ks.as<double>(), h->KsT.as<double>(), mcp,
-                                mcp));
-        }
+        double *V = h->KsT.as<double>();
+        GPX_TRY(solve_rt_refined(h, h->Ks.as<double>(), V, mcp));
         GPX_TRY(gpx_posterior_reduce(h->stream, V, mcp, h->np, mcp,
                                      h->a.as<double>(), h->mean, prior,
                                      h->post_part.as<double>(), h->mu.as<double>(),
@@ -1580,8 +1584,7 @@ static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, dou
         clk.tick(T_POST_SOLVE);
         if (grads) {
             // beta = W V (V = R^-T K*): W upper -> k >= row tile
-            double *beta = (V == h->Ks.as<double>()) ? h->KsT.as<double>()
-                                                     : h->Ks.as<double>();
+            double *beta = h->Ks.as<double>();
             GPX_TRY(tri_product(h, 0, V, beta, mcp));
             GPX_TRY(h->t0.reserve((size_t)mc * h->d * 8));
             GPX_TRY(h->t1.reserve((size_t)mc * h->d * 8));
@@ -1637,8 +1640,8 @@ int gpx_exact_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, 
     GPX_TRY(gpx_kbuild<double>(h->stream, h->kp, h->X.as<double>(), h->n, h->np,
                                h->Xs.as<double>(), mc, mcp, h->d, h->Ks.as<double>(), mcp,
                                false, false, 0.0));
-    GPX_TRY(tri_product(h, 1, h->Ks.as<double>(), h->KsT.as<double>(), mcp));
     double *V = h->KsT.as<double>();
+    GPX_TRY(solve_rt_refined(h, h->Ks.as<double>(), V, mcp));
     GPX_TRY(gpx_posterior_reduce(h->stream, V, mcp, h->np, mcp, h->a.as<double>(), h->mean,
                                  0.0, h->post_part.as<double>(), h->mu.as<double>(),
                                  h->s2.as<double>()));

@@ -278,6 +278,13 @@ size_t gpx_trsv_scratch(int np);      // doubles of `partial`
 // (w.batch members: their vectors vstride, their scratch gpx_trsv_scratch(np) apart)
 int gpx_trsv_rt(hipStream_t s, const DenseWs &w, bool w_complete, double *r_scratch,
                 double *a, double *partial, long long vstride = 0);
+// B -= R^T V (np x m panels, ld ldb; m a multiple of 8): the residual of V = R^-T B, reading
+// only the upper triangle of R (batch members: R mstride, V and B pstride elements apart)
+int gpx_rt_residual(hipStream_t s, const double *R, int ld, int np, const double *V,
+                    double *B, int ldb, int m, int batch = 1, long long mstride = 0,
+                    long long pstride = 0);
+// x += d (n doubles)
+int gpx_add_inplace(hipStream_t s, double *x, const double *d, size_t n);
 // out = W v  (W upper triangular np x np)
 int gpx_trmv_upper(hipStream_t s, const double *W, int ld, int np, const double *v,
                    double *out, int batch = 1, long long mstride = 0, long long vstride = 0);

@@ -91,7 +91,7 @@ struct HostBuf {                                  // pinned
 struct Slot {                                     // one group in flight
     hipStream_t stream = nullptr;
     Buf A, W, Kinv, r, a, alpha, scalars, partial, gv_part, info, pctl, params;
-    Buf Xs, Ks, KsT, mu, s2, post_part, split, gpart, dmu, ds2;     // posteriors
+    Buf Xs, Ks, KsT, Vc, mu, s2, post_part, split, gpart, dmu, ds2; // posteriors
     HostBuf hparams, hres, hinfo;
     int cap = 0;                                  // members the buffers hold
     int np = 0, ld = 0;
@@ -239,7 +239,7 @@ void gpx_groups_destroy(GpxGroups *g)
         if (s.stream) (void)hipStreamSynchronize(s.stream);
         DLOG("slot %d buffers", si);
         Buf *bufs[] = {&s.A, &s.W, &s.Kinv, &s.r, &s.a, &s.alpha, &s.scalars, &s.partial,
-                       &s.gv_part, &s.info, &s.pctl, &s.params, &s.Xs, &s.Ks, &s.KsT, &s.mu,
+                       &s.gv_part, &s.info, &s.pctl, &s.params, &s.Xs, &s.Ks, &s.KsT, &s.Vc, &s.mu,
                        &s.s2, &s.post_part, &s.split, &s.gpart, &s.dmu, &s.ds2};
         for (Buf *b : bufs) b->release();
         DLOG("slot %d events", si);
@@ -662,14 +662,10 @@ static int group_posterior(Slot &s, const double *X, const double *y, int n, int
     hipStream_t st = s.stream;
     const int ld = s.ld;
     GPX_HIP(hipMemcpyAsync(s.hinfo.p, s.info.p, sizeof(int) * count, hipMemcpyDeviceToHost, st));
-    bool w_complete = gc.full_inverse;
-    // V = R^-T K* is one triangle-aware product with W^T once W = R^-1 is complete, the
-    // block substitution otherwise; completing W pays from np / 4 test points on (the rule
-    // of a single model's first posterior call, gpx_api.hip)
-    if (!w_complete && m >= np / 4) {
+    // V = R^-T K* is a triangle-aware product with W^T and one step of refinement, as for a
+    // single model (gpx_api.hip, solve_rt_refined): W = R^-1 is completed first
+    if (!gc.full_inverse)
         GPX_TRY(gpx_trtri(st, w));
-        w_complete = true;
-    }
     double *a = s.a.as<double>();
     if (grads) {
         GPX_TRY(s.alpha.reserve((size_t)np * 8 * s.cap));
@@ -693,18 +689,19 @@ static int group_posterior(Slot &s, const double *X, const double *y, int n, int
         mbp.mstride = pstride;
         GPX_TRY(gpx_kbuild<double>(st, kp0, X, n, np, s.Xs.as<double>(), mc, mcp, d,
                                    s.Ks.as<double>(), mcp, false, false, 0.0, nullptr, 0, -1, &mbp));
-        double *V = s.Ks.as<double>();
-        if (w_complete) {                                // RK = R^-T K (exact.py:88)
-            GPX_TRY(group_tri_product(s, w, count, 1, s.Ks.as<double>(), s.KsT.as<double>(), mcp));
-            V = s.KsT.as<double>();
-        } else {
-            GPX_TRY(gpx_trsm_rt(st, w, s.Ks.as<double>(), s.KsT.as<double>(), mcp, mcp, pstride));
-        }
+        // RK = R^-T K (exact.py:88): V1 = W^T K, V = V1 + W^T (K - R^T V1)
+        double *V = s.KsT.as<double>();
+        GPX_TRY(group_tri_product(s, w, count, 1, s.Ks.as<double>(), V, mcp));
+        GPX_TRY(gpx_rt_residual(st, w.A, ld, np, V, s.Ks.as<double>(), mcp, mcp, count,
+                                mb.mstride, pstride));
+        GPX_TRY(s.Vc.reserve((size_t)count * pstride * 8));
+        GPX_TRY(group_tri_product(s, w, count, 1, s.Ks.as<double>(), s.Vc.as<double>(), mcp));
+        GPX_TRY(gpx_add_inplace(st, V, s.Vc.as<double>(), (size_t)count * pstride));
         GPX_TRY(gpx_posterior_reduce(st, V, mcp, np, mcp, a, 0.0, 0.0, s.post_part.as<double>(),
                                      s.mu.as<double>(), s.s2.as<double>(), 1, 0, &mb, pstride));
         if (grads) {
             // beta = W V: W upper -> k >= row tile
-            double *beta = (V == s.Ks.as<double>()) ? s.KsT.as<double>() : s.Ks.as<double>();
+            double *beta = s.Ks.as<double>();
             GPX_TRY(group_tri_product(s, w, count, 0, V, beta, mcp));
             GPX_TRY(s.dmu.reserve((size_t)count * mc * d * 8));
             GPX_TRY(s.ds2.reserve((size_t)count * mc * d * 8));

@@ -149,6 +149,70 @@ int gpx_trmv_upper(hipStream_t s, const double *W, int ld, int np, const double 
     return 0;
 }
 
+// ---- one step of refinement of V = R^-T B -----------------------------------------
+// B[i, j] -= sum_{k <= i} R[k, i] V[k, j]: the residual of R^T V = B, reading only the upper
+// triangle of R (the storage below it holds the lower half of K). Threads run along i, so
+// the loads of R[k, i] are coalesced and those of V[k, j] are one address per wave; a
+// thread keeps RT_COLS columns of its row.
+#define RT_COLS 8
+__global__ __launch_bounds__(256) void rt_residual_kernel(const double *__restrict__ R,
+                                                          int ld, int np,
+                                                          const double *__restrict__ V,
+                                                          double *__restrict__ B, int ldb,
+                                                          long long sA, long long sP)
+{
+    R += (long long)blockIdx.z * sA;                      // blockIdx.z = member
+    V += (long long)blockIdx.z * sP;
+    B += (long long)blockIdx.z * sP;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int j0 = blockIdx.y * RT_COLS;
+    const int kend = min(np, blockIdx.x * 256 + 256);   // the largest row of the block + 1
+    double acc[RT_COLS];
+#pragma unroll
+    for (int c = 0; c < RT_COLS; ++c) acc[c] = 0.0;
+    const int ii = i < np ? i : np - 1;
+    for (int k = 0; k < kend; ++k) {
+        const double r = k <= i ? R[(size_t)k * ld + ii] : 0.0;
+        const double *Vk = V + (size_t)k * ldb + j0;
+#pragma unroll
+        for (int c = 0; c < RT_COLS; ++c) acc[c] = fma(r, Vk[c], acc[c]);
+    }
+    if (i >= np) return;
+    double *Bi = B + (size_t)i * ldb + j0;
+#pragma unroll
+    for (int c = 0; c < RT_COLS; ++c) Bi[c] -= acc[c];
+}
+
+__global__ __launch_bounds__(256) void add_inplace_kernel(double *__restrict__ x,
+                                                          const double *__restrict__ d,
+                                                          size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) x[i] += d[i];
+}
+
+int gpx_rt_residual(hipStream_t s, const double *R, int ld, int np, const double *V,
+                    double *B, int ldb, int m, int batch, long long mstride, long long pstride)
+{
+    if (m % RT_COLS) {
+        gpx_set_error("gpx_rt_residual: m = %d is not a multiple of %d", m, RT_COLS);
+        return -1;
+    }
+    hipLaunchKernelGGL(rt_residual_kernel, dim3((np + 255) / 256, m / RT_COLS, batch), dim3(256),
+                       0, s, R, ld, np, V, B, ldb, mstride, pstride);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+int gpx_add_inplace(hipStream_t s, double *x, const double *d, size_t n)
+{
+    if (!n) return 0;
+    hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
+                       x, d, n);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
 // ---- scalars of the log marginal likelihood ----------------------------------
 __global__ __launch_bounds__(1024) void lz_terms_kernel(const double *__restrict__ R,
                                                         int np, int n,

@@ -206,3 +206,45 @@ def test_panel_kernel_strict_handoffs():
     assert len(outs[0]) == 18 and outs[0] == outs[1]
     for n in range(3):                       # and run to run
         assert len(set(outs[0][6 * n:6 * n + 6])) == 1
+
+
+def test_whole_matrix_launch_strict_handoffs():
+    """The same for the whole-matrix panel launch that one evaluation takes up to np = 4096
+    (gpx_potrf_whole, reached by exact_eval only: la_potrf(inverse=True) never takes it),
+    value-only and with all of R^-1 assembled inside it, at N = 1300, 2048, 3001 and 4096:
+    default and GPX_PANEL_STRICT=1 give identical bits, and identical bits run to run."""
+    import os, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = (
+        "import sys, hashlib, numpy as np\n"
+        "sys.path[:0] = [%r, %r]\n"
+        "import recipes\n"
+        "import pygp_amd\n"
+        "from pygp_amd import _lib\n"
+        "dev = _lib.Handle(0)\n"
+        "D = 4\n"
+        "k = pygp_amd.kernels.SE(1.0, np.linspace(0.5, 1.5, D))\n"
+        "th = recipes.theta0(D)\n"
+        "for n in (1300, 2048, 3001, 4096):\n"
+        "    X, y, _ = recipes.synthetic(n, D)\n"
+        "    dev.set_data(X, y)\n"
+        "    for rep in range(2):\n"
+        "        print('start', n, rep, file=sys.stderr, flush=True)\n"
+        "        lv = dev.exact_eval(k._kspec(), th[0], th[-1], False)\n"
+        "        Rv, av = dev.exact_get_factor(n)\n"
+        "        lZ, dlZ = dev.exact_eval(k._kspec(), th[0], th[-1], True)\n"
+        "        R, a = dev.exact_get_factor(n)\n"
+        "        h = hashlib.sha256(np.r_[lv, lZ].tobytes() + dlZ.tobytes() + Rv.tobytes()\n"
+        "                           + av.tobytes() + R.tobytes() + a.tobytes())\n"
+        "        print(n, h.hexdigest())\n"
+        "print('done', file=sys.stderr, flush=True)\n"
+    ) % (root, os.path.join(root, 'tests'))
+    outs = []
+    for strict in ('0', '1'):
+        env = dict(os.environ, GPX_PANEL_STRICT=strict, GPX_PANEL_TIMEOUT_MS='1000')
+        out = run_child([sys.executable, '-c', code], env=env, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        outs.append(out.stdout.strip().splitlines())
+    assert len(outs[0]) == 8 and outs[0] == outs[1]
+    for n in range(4):                       # and run to run
+        assert outs[0][2 * n] == outs[0][2 * n + 1]
