@@ -49,6 +49,8 @@ _vp = C.c_void_p
 _i64 = C.c_int64
 
 # name -> (restype, argtypes); mirrors include/gpx.h one to one
+GPX_FITC, GPX_DTC = 1, 2          # enum gpx_sparse_method
+
 SIGNATURES = {
     'gpx_version': (C.c_int, []),
     'gpx_last_error': (C.c_char_p, []),
@@ -75,6 +77,13 @@ SIGNATURES = {
     'gpx_kernel_gradx': (C.c_int, [_vp, C.POINTER(_KSpec), _vp, _i64, _vp, _i64, _i64,
                                    C.c_int, _vp]),
     'gpx_exact_get_factor': (C.c_int, [_vp, _i64, _vp, _vp]),
+    'gpx_sparse_update': (C.c_int, [_vp, C.POINTER(_KSpec), C.c_int, _vp, _i64, C.c_double,
+                                    C.c_double, _ip]),
+    'gpx_sparse_loglik': (C.c_int, [_vp, _vp, _vp]),
+    'gpx_sparse_posterior': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    'gpx_sparse_posterior_full': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    'gpx_sparse_get_state': (C.c_int, [_vp, _vp, _vp, _vp]),
+    'gpx_sparse_timings': (C.c_int, [_vp, _vp]),
     'gpx_loglik_batch': (C.c_int, [_vp, C.POINTER(_KSpec), _vp, _i64, C.c_int,
                                    _vp, _vp, _vp]),
     'gpx_batch_plan': (C.c_int, [_vp, _i64, C.c_int, _ip]),
@@ -369,6 +378,47 @@ class Handle(object):
         mu, Sigma = np.empty(m), np.empty((m, m))
         check(self._L.gpx_exact_posterior_full(self._h, _ptr(Xs), m, _ptr(mu), _ptr(Sigma)))
         return mu, Sigma
+
+    # -- sparse pseudo-input models (FITC / DTC) on the resident data --
+    def sparse_update(self, spec, method, U, log_sn, mean):
+        U = _f64(U, 2)
+        info = C.c_int(0)
+        check(self._L.gpx_sparse_update(self._h, spec.ref(), int(method), _ptr(U), U.shape[0],
+                                        float(log_sn), float(mean), C.byref(info)))
+
+    def sparse_loglik(self, nhyper_kernel, grad=False):
+        lZ = C.c_double(0)
+        dlZ = np.empty(nhyper_kernel + 2) if grad else None
+        check(self._L.gpx_sparse_loglik(self._h, C.byref(lZ), _ptr(dlZ)))
+        return (lZ.value, dlZ) if grad else lZ.value
+
+    def sparse_posterior(self, Xs, grad=False):
+        Xs = _f64(Xs, 2)
+        m, d = Xs.shape
+        mu, s2 = np.empty(m), np.empty(m)
+        dmu, ds2 = (np.empty((m, d)), np.empty((m, d))) if grad else (None, None)
+        if m:
+            check(self._L.gpx_sparse_posterior(self._h, _ptr(Xs), m, _ptr(mu), _ptr(s2),
+                                               _ptr(dmu), _ptr(ds2)))
+        return (mu, s2, dmu, ds2) if grad else (mu, s2)
+
+    def sparse_posterior_full(self, Xs):
+        Xs = _f64(Xs, 2)
+        m = Xs.shape[0]
+        mu, Sigma = np.empty(m), np.empty((m, m))
+        check(self._L.gpx_sparse_posterior_full(self._h, _ptr(Xs), m, _ptr(mu), _ptr(Sigma)))
+        return mu, Sigma
+
+    def sparse_timings(self):
+        """HIP-event ms of the last [update, gradient stage, contraction pass]."""
+        ms = np.zeros(3)
+        check(self._L.gpx_sparse_timings(self._h, _ptr(ms)))
+        return ms
+
+    def sparse_get_state(self, p):
+        F1, F2, v = np.empty((p, p)), np.empty((p, p)), np.empty(p)
+        check(self._L.gpx_sparse_get_state(self._h, _ptr(F1), _ptr(F2), _ptr(v)))
+        return F1, F2, v
 
     def exact_posterior_grad(self, Xs):
         Xs = _f64(Xs, 2)

@@ -93,6 +93,10 @@ struct gpx_ctx {
     gpx_ctx *twin = nullptr;
     // member-batched evaluation of batches (group.hip), created on first use
     GpxGroups *groups = nullptr;
+    // sparse pseudo-input model (sparse.hip), created on first use; its own buffers, so the
+    // exact-GP state above stays valid beside it. Valid for the data of sparse_version only.
+    GpxSparse *sparse = nullptr;
+    long sparse_version = -1;
     // look-ahead of the factorisation (chol.hip): diagonal blocks on a high-priority
     // stream, the left half of the inverse tree on a low-priority one
     hipStream_t crit = nullptr, crit_only = nullptr, aux = nullptr, bulk = nullptr;
@@ -622,6 +626,10 @@ int gpx_destroy(gpx_t *h)
         h->twin = nullptr;
     }
     (void)hipSetDevice(h->device);
+    if (h->sparse) {
+        gpx_sparse_destroy(h->sparse);
+        h->sparse = nullptr;
+    }
     if (h->groups) {
         DLOG("groups");
         gpx_groups_destroy(h->groups);
@@ -1806,6 +1814,116 @@ int gpx_kernel_gradx(gpx_t *h, const gpx_kspec *k, const double *X1, int64_t n1,
     GPX_HIP(hipMemcpyAsync(out, h->t2.p, ob, hipMemcpyDeviceToHost, h->stream));
     GPX_HIP(hipStreamSynchronize(h->stream));
     return 0;
+}
+
+// ---- FITC / DTC (pygp/inference/fitc.py, dtc.py) -----------------------------------
+static int sparse_ready(gpx_ctx *h, const char *what)
+{
+    if (!h->sparse || h->sparse_version < 0) {
+        gpx_set_error("%s: no sparse model (call gpx_sparse_update)", what);
+        return -1;
+    }
+    if (h->sparse_version != h->data_version) {
+        gpx_set_error("%s: the data changed since gpx_sparse_update (stale model)", what);
+        return -1;
+    }
+    return 0;
+}
+
+int gpx_sparse_update(gpx_t *h, const gpx_kspec *k, int method, const double *U, int64_t p,
+                      double log_sn, double mean, int *info)
+{
+    CHECK_H(h);
+    if (info) *info = 0;
+    h->sparse_version = -1;
+    if (h->n <= 0) {
+        gpx_set_error("gpx_sparse_update: no data: call gpx_set_data first");
+        return -1;
+    }
+    if (method != GPX_FITC && method != GPX_DTC) {
+        gpx_set_error("gpx_sparse_update: method must be GPX_FITC or GPX_DTC (got %d)", method);
+        return -1;
+    }
+    if (!U || p < 1 || p > GPX_SPARSE_MAX_P) {
+        gpx_set_error("gpx_sparse_update: need 1 <= p <= %d pseudo-inputs (got %lld)",
+                      GPX_SPARSE_MAX_P, (long long)p);
+        return -1;
+    }
+    const long long pp = round_up(p, GPX_TILE), np = round_up(h->n, GPX_TILE);
+    if (pp * np >= (1LL << 31)) {
+        gpx_set_error("gpx_sparse_update: p_pad * N_pad = %lld x %lld must stay below 2^31", pp,
+                      np);
+        return -1;
+    }
+    if (!std::isfinite(log_sn) || !std::isfinite(mean)) {
+        gpx_set_error("gpx_sparse_update: non-finite hyperparameters");
+        return -1;
+    }
+    for (int64_t i = 0; i < p * h->d; ++i)
+        if (!std::isfinite(U[i])) {
+            gpx_set_error("gpx_sparse_update: non-finite pseudo-inputs");
+            return -1;
+        }
+    KParams kp;
+    GPX_TRY(gpx_flatten_kspec(k, h->d, &kp));
+    const int r = gpx_sparse_run_update(&h->sparse, h->stream, kp, method, U, (int)p, log_sn,
+                                        mean, h->X.as<double>(), h->y.as<double>(), h->n, h->d,
+                                        info);
+    if (r == 0) h->sparse_version = h->data_version;
+    return r;
+}
+
+int gpx_sparse_loglik(gpx_t *h, double *lZ, double *dlZ)
+{
+    CHECK_H(h);
+    GPX_TRY(sparse_ready(h, "gpx_sparse_loglik"));
+    if (!lZ) {
+        gpx_set_error("gpx_sparse_loglik: lZ is null");
+        return -1;
+    }
+    return gpx_sparse_run_loglik(h->sparse, h->stream, h->X.as<double>(), lZ, dlZ);
+}
+
+int gpx_sparse_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2,
+                         double *dmu, double *ds2)
+{
+    CHECK_H(h);
+    GPX_TRY(sparse_ready(h, "gpx_sparse_posterior"));
+    if (!Xs || !mu || !s2 || m < 0 || (!dmu) != (!ds2)) {
+        gpx_set_error("gpx_sparse_posterior: bad arguments");
+        return -1;
+    }
+    if (m == 0) return 0;
+    return gpx_sparse_run_posterior(h->sparse, h->stream, Xs, m, mu, s2, dmu, ds2, nullptr);
+}
+
+int gpx_sparse_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma)
+{
+    CHECK_H(h);
+    GPX_TRY(sparse_ready(h, "gpx_sparse_posterior_full"));
+    if (!Xs || !mu || !Sigma || m < 1 || m > 8192) {
+        gpx_set_error("gpx_sparse_posterior_full: bad arguments (1 <= m <= 8192)");
+        return -1;
+    }
+    return gpx_sparse_run_posterior(h->sparse, h->stream, Xs, m, mu, nullptr, nullptr, nullptr,
+                                    Sigma);
+}
+
+int gpx_sparse_get_state(gpx_t *h, double *F1, double *F2, double *v)
+{
+    CHECK_H(h);
+    GPX_TRY(sparse_ready(h, "gpx_sparse_get_state"));
+    return gpx_sparse_run_state(h->sparse, h->stream, F1, F2, v);
+}
+
+int gpx_sparse_timings(gpx_t *h, double *ms)
+{
+    CHECK_H(h);
+    if (!ms) {
+        gpx_set_error("gpx_sparse_timings: ms is null");
+        return -1;
+    }
+    return gpx_sparse_run_timings(h->sparse, ms);
 }
 
 int gpx_exact_get_factor(gpx_t *h, int64_t n, double *R, double *a)

@@ -453,6 +453,31 @@ int gpx_trace_grad(hipStream_t s, const KParams &kp, const double *X, int n,
                    double *partial, double *acc, const MemberBatch *mb = nullptr,
                    int astride = 0);
 
+// sum_{i < n1, j < n2} G[i][j] dK_h(X1_i, X2_j) for every kernel hyper h, without writing
+// the slices of dK: acc[1 + h] (acc[0] = 0), fixed-order reduction (sparse models).
+// partial: device scratch of gpx_pair_grad_scratch(n1) doubles
+#define GPX_PAIR_CHUNKS_MAX 256
+size_t gpx_pair_grad_scratch(int n1);
+int gpx_pair_grad(hipStream_t s, const KParams &kp, const double *X1, int n1,
+                  const double *X2, int n2, int d, const double *G, long long ldg,
+                  double *partial, double *acc);
+
+// ---- sparse pseudo-input models (sparse.hip) ---------------------------------------
+// FITC / DTC on the resident data X (n x d), y: the p x p factors, the lZ terms and (on
+// demand) the gradient and posteriors; *state is created on first use (per handle)
+struct GpxSparse;
+int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, int method,
+                          const double *U, int p, double log_sn, double mean,
+                          const double *X, const double *y, int n, int d, int *info);
+int gpx_sparse_run_loglik(GpxSparse *st, hipStream_t s, const double *X, double *lZ,
+                          double *dlZ);
+int gpx_sparse_run_posterior(GpxSparse *st, hipStream_t s, const double *Xs, int64_t m,
+                             double *mu, double *s2, double *dmu, double *ds2, double *Sigma);
+int gpx_sparse_run_state(GpxSparse *st, hipStream_t s, double *F1, double *F2, double *v);
+int gpx_sparse_nhyper(const GpxSparse *st);
+int gpx_sparse_run_timings(GpxSparse *st, double *ms);
+void gpx_sparse_destroy(GpxSparse *st);
+
 // d k / d x2 (sign = +1) or d k / d x1 (sign = -1): out[n1][n2][d]
 int gpx_kgrady(hipStream_t s, const KParams &kp, const double *X1, int n1, const double *X2,
                int n2, int d, double sign, double *out);

@@ -1437,6 +1437,135 @@ int gpx_trace_grad(hipStream_t s, const KParams &kp, const double *X, int n, int
     return 0;
 }
 
+// ---- weighted gradient over a rectangular pair set (sparse models, sparse.hip) -------
+// acc[1 + h] = sum_{i < n1, j < n2} G[i][j] dK_h(x1_i, x2_j). One workgroup owns a 64-row
+// block of X1 and walks the 64-column tiles bj = c0, c0 + C, ... of X2 (row-persistent, like
+// trace_grad_rows_kernel); every part's derivatives come from the same pair body as
+// trace_grad_kernel (radial_grad_t / periodic_grad / group_factor), weighted by G instead of
+// K^-1 - alpha alpha^T, and stay in registers until one block reduction per part. Nothing of
+// the nhyper slices of dK is written out. Rows and columns beyond n1 / n2 weigh exactly 0.
+template <int DMAX>
+__global__ __launch_bounds__(256) void pair_grad_kernel(
+    KParams kp, const double *__restrict__ X1, int n1, const double *__restrict__ X2, int n2,
+    int d, const double *__restrict__ G, long long ldg, double *__restrict__ partial, int nacc)
+{
+    const int C = gridDim.x;
+    const int bi = blockIdx.y, c0 = blockIdx.x;
+    const int T2 = (n2 + KT - 1) / KT;
+    double *pout = partial + ((size_t)bi * C + c0) * nacc;
+    __shared__ double xi_s[KT][DMAX + 1];
+    __shared__ double red[4][DMAX + 3];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, ig = tid >> 6;
+    const int i0 = bi * KT;
+    if (tid == 0) pout[0] = 0.0;
+    for (int p = 0; p < kp.nparts; ++p) {
+        const KPart &part = kp.part[p];
+        __syncthreads();
+        for (int e = tid; e < KT * DMAX; e += 256) {
+            const int r = e / DMAX, c = e - r * DMAX;
+            const int gi = min(i0 + r, n1 - 1);
+            xi_s[r][c] = c < d ? X1[(size_t)gi * d + c] / part.scale[c] : 0.0;
+        }
+        __syncthreads();
+        double a_sf = 0.0, a_x = 0.0, a_e[DMAX];
+#pragma unroll
+        for (int c = 0; c < DMAX; ++c) a_e[c] = 0.0;
+        for (int bj = c0; bj < T2; bj += C) {
+            const int gj = bj * KT + lane;
+            const int cj = min(gj, n2 - 1);
+            double xj[DMAX];
+#pragma unroll
+            for (int c = 0; c < DMAX; ++c)
+                xj[c] = c < d ? X2[(size_t)cj * d + c] / part.scale[c] : 0.0;
+            for (int ii = 0; ii < 16; ++ii) {
+                const int gi = i0 + ig * 16 + ii;
+                double t = gi < n1 && gj < n2 ? G[(size_t)gi * ldg + gj] : 0.0;
+                if (t == 0.0) continue;
+                if (kp.nprod != 0)
+                    t *= group_factor(kp, p, X1 + (size_t)gi * d, X2 + (size_t)cj * d, d);
+                const double *xi = xi_s[ig * 16 + ii];
+                double dd[DMAX], D2 = 0.0;
+#pragma unroll
+                for (int c = 0; c < DMAX; ++c) {
+                    const double df = xi[c] - xj[c];
+                    dd[c] = df * df;
+                    D2 += dd[c];
+                }
+                if (part.kind == GPX_PERIODIC) {
+                    const PeriodicGrad g = periodic_grad(part.sf2, part.ell, part.period, D2);
+                    a_sf += t * g.g0;
+                    a_e[0] += t * g.g1;
+                    a_e[1] += t * g.g2;
+                    continue;
+                }
+                const RadialGrad g = radial_grad_t<true>(part.kind, part.two_logsf, part.sf2,
+                                                         part.alpha, D2);
+                a_sf += t * (2 * g.K);
+                a_x += t * g.xval;
+                if (part.iso) {
+                    a_e[0] += t * g.isoval;
+                } else {
+                    const double cf = g.zero ? 0.0 : t * (g.Mv / g.rdiv);
+#pragma unroll
+                    for (int c = 0; c < DMAX; ++c) a_e[c] += cf * dd[c];
+                }
+            }
+        }
+        const int nh = part.nhyper;
+        const int ne = part.kind == GPX_RQ ? nh - 2 : nh - 1;
+        double v = wave_sum(a_sf);
+        if (lane == 0) red[ig][0] = v;
+#pragma unroll
+        for (int c = 0; c < DMAX; ++c)
+            if (c < ne) {
+                v = wave_sum(a_e[c]);
+                if (lane == 0) red[ig][1 + c] = v;
+            }
+        if (part.kind == GPX_RQ) {
+            v = wave_sum(a_x);
+            if (lane == 0) red[ig][nh - 1] = v;
+        }
+        __syncthreads();
+        if (tid < nh) {
+            const double v4 = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+            pout[1 + part.hoff + tid] = part.dup ? pout[1 + part.hoff + tid] + v4 : v4;
+        }
+    }
+}
+
+size_t gpx_pair_grad_scratch(int n1)
+{
+    return (size_t)((n1 + KT - 1) / KT) * GPX_PAIR_CHUNKS_MAX * TG_MAXACC;
+}
+
+int gpx_pair_grad(hipStream_t s, const KParams &kp, const double *X1, int n1,
+                  const double *X2, int n2, int d, const double *G, long long ldg,
+                  double *partial, double *acc)
+{
+    const int T1 = (n1 + KT - 1) / KT, T2 = (n2 + KT - 1) / KT;
+    const int nacc = 1 + kp.nhyper;
+    // about 2048 workgroups in all; the chunk count depends on the shape only, so the
+    // order of the sums (and the bits) does too
+    const int C = std::max(1, std::min(T2, std::min(GPX_PAIR_CHUNKS_MAX, 2048 / T1)));
+    dim3 grid(C, T1);
+    GPX_TRY(gpx_test_jitter(s));
+    if (d <= 8)
+        hipLaunchKernelGGL(pair_grad_kernel<8>, grid, dim3(256), 0, s, kp, X1, n1, X2, n2, d,
+                           G, ldg, partial, nacc);
+    else if (d <= 16)
+        hipLaunchKernelGGL(pair_grad_kernel<16>, grid, dim3(256), 0, s, kp, X1, n1, X2, n2, d,
+                           G, ldg, partial, nacc);
+    else
+        hipLaunchKernelGGL(pair_grad_kernel<32>, grid, dim3(256), 0, s, kp, X1, n1, X2, n2, d,
+                           G, ldg, partial, nacc);
+    GPX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(trace_reduce_kernel, dim3(nacc, 1, 1), dim3(256), 0, s, partial, T1 * C,
+                       nacc, acc, 0LL, 0);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
 // ---- input gradients -----------------------------------------------------------
 // d k(x1, x2) / d x2 ("grady"; gradx is its negative) for one part, accumulated
 // into g[0..d). SE: K (u1-u2)/ell (se.py:76-86); Matern: M (u1-u2)/ell with

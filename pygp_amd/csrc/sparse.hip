@@ -1,0 +1,886 @@
+// sparse.hip -- FITC and DTC sparse pseudo-input GPs (pygp/inference/fitc.py, dtc.py) on
+// the device. Notation of DESIGN.md section 10: L = chol(Kuu + su2 I) (upper), V0 = L^-T Kux,
+// ell_j (FITC: sqrt(kxx + sn2 - sum_i V0_ij^2), DTC: sqrt(sn2)), V = V0 / ell, rt = r / ell,
+// A = chol(I + V V^T), beta = A^-T V rt.
+//
+// Every p x p x N product runs on the fp64 tile engine (gemm_f64.hip); the products with a
+// p x p output and an inner dimension N run split-K over the CUs and their partial products
+// are summed in a fixed order here. The p x p triangular solves are products with the
+// explicit inverses the factorisation leaves behind (W = R^-1). The gradient is the
+// contraction dlZ_k = <dKuu_k, G_uu> + <dKux_k, G_ux> + <dkxx_k, g_x> (gpx_pair_grad,
+// kmat.hip); column kernels below carry the O(pN) terms. Every reduction has a fixed order:
+// the same call gives the same bits.
+#include "gpx_internal.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#define SP_T 256   // threads of the column and vector kernels
+
+namespace {
+
+struct SpBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    int reserve(size_t need)
+    {
+        if (need <= bytes) return 0;
+        if (p) GPX_HIP(hipFree(p));
+        p = nullptr;
+        bytes = 0;
+        GPX_HIP(hipMalloc(&p, need));
+        bytes = need;
+        return 0;
+    }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    double *d() const { return static_cast<double *>(p); }
+    int *as_int() const { return static_cast<int *>(p); }
+};
+
+// slots of the device scalar array
+enum {
+    S_LOGELL = 0,   // sum_j log ell_j
+    S_RT2,          // sum_j rt_j^2
+    S_V2,           // sum_ij V_ij^2
+    S_IELL2,        // sum_j 1 / ell_j^2
+    S_LOGA,         // sum_i log A_ii
+    S_AW2,          // ||A^T - A^-1||_F^2 = ||V W^T||_F^2
+    S_BETA2,        // beta^T beta
+    S_ALPHA,        // sum_j alpha_j
+    S_ALPHA2,       // sum_j alpha_j^2
+    S_B2,           // sum_ij B_ij^2
+    S_S,            // sum_j s_j = ||W||_F^2
+    S_W2,           // w^T w
+    S_C2,           // ||C||_F^2
+    S_EB2,          // sum_j (alpha_j^2 + s_j) sum_i B_ij^2
+    S_V2A,          // (V alpha)^T (V alpha)
+    S_COUNT
+};
+
+}  // namespace
+
+struct GpxSparse {
+    int method = 0, p = 0, pp = 0, ldp = 0, n = 0, np = 0, d = 0;
+    KParams kp;
+    double sn2 = 0, su2 = 0, mean = 0, prior = 0;
+    bool ready = false;
+    int gates_l[2] = {0, 0}, gates_a[2] = {0, 0};
+    SpBuf U, L, Lw, Lk, A, Aw, Ak, info, pctl;
+    // p x N panels (ld np). P2 holds V from the update to the next update: the gradient
+    // stage reads it and writes only P1 (B), P3 (W, then B diag(e)) and P4 (C W, then G_ux),
+    // so a second gradient call on the same state sees the same V
+    SpBuf P1, P2, P3, P4;
+    SpBuf ell, rt, beta, gam, u, alpha, wv, vv, bq, sq, e;
+    SpBuf part, scal, acc_uu, acc_ux, pg_part, split, Cm, CC, BEB, Guu, R2;
+    SpBuf Xs, Ks, Q1, Q2, dKc, dK, dQ1, dQ2, mu, s2, dmu, ds2, Sig;
+    double hsc[S_COUNT];
+    // HIP events around the last update, gradient stage and contraction pass (ms)
+    hipEvent_t ev[5] = {};
+    double ms[3] = {0, 0, 0};
+};
+
+static int sp_event(GpxSparse *st, hipStream_t s, int i)
+{
+    if (!st->ev[i]) GPX_HIP(hipEventCreate(&st->ev[i]));
+    GPX_HIP(hipEventRecord(st->ev[i], s));
+    return 0;
+}
+
+static double sp_elapsed(GpxSparse *st, int a, int b)
+{
+    float t = 0;
+    if (hipEventElapsedTime(&t, st->ev[a], st->ev[b]) != hipSuccess) return -1.0;
+    return t;
+}
+
+static inline int sp_round(int64_t x, int m) { return (int)((x + m - 1) / m * m); }
+
+// ---- reductions --------------------------------------------------------------------
+// fixed-order tree over the 256 threads of a block; the sum lands in thread 0
+__device__ __forceinline__ double sp_block_sum(double v, double *red)
+{
+    const int t = threadIdx.x;
+    __syncthreads();
+    red[t] = v;
+    __syncthreads();
+    for (int off = SP_T / 2; off > 0; off >>= 1) {
+        if (t < off) red[t] += red[t + off];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// out[q] = sum_b part[b * nq + q], b < nb, in a fixed order
+__global__ __launch_bounds__(SP_T) void sp_reduce_kernel(const double *__restrict__ part, int nb,
+                                                        int nq, double *__restrict__ out)
+{
+    __shared__ double red[SP_T];
+    const int q = blockIdx.x;
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nb; b += SP_T) s += part[(size_t)b * nq + q];
+    s = sp_block_sum(s, red);
+    if (threadIdx.x == 0) out[q] = s;
+}
+
+// *out = sum_i a_i b_i (b null: a_i^2), one block, fixed order
+__global__ __launch_bounds__(1024) void sp_dot_kernel(const double *__restrict__ a,
+                                                     const double *__restrict__ b, long long n,
+                                                     double *__restrict__ out)
+{
+    __shared__ double red[1024];
+    const int t = threadIdx.x;
+    double s = 0.0;
+    for (long long i = t; i < n; i += 1024) s += b ? a[i] * b[i] : a[i] * a[i];
+    red[t] = s;
+    __syncthreads();
+    for (int off = 512; off > 0; off >>= 1) {
+        if (t < off) red[t] += red[t + off];
+        __syncthreads();
+    }
+    if (t == 0) *out = red[0];
+}
+
+// ---- column kernels ----------------------------------------------------------------
+// One thread per column j of the p x N panel V0 (ld ld, pp rows): ell_j, rt_j and the
+// column scaled to V = V0 / ell in place. Columns j >= n (padding) are zero, keep
+// ell = 1, rt = 0 and add nothing to the sums. part[block][4]: sum log ell, sum rt^2,
+// sum V^2, sum 1 / ell^2.
+__global__ __launch_bounds__(SP_T) void sp_colprep_kernel(
+    double *__restrict__ V, long long ld, int pp, int n, int np, const double *__restrict__ y,
+    double mean, double kxx, double sn2, int fitc, double *__restrict__ ell,
+    double *__restrict__ rt, double *__restrict__ part)
+{
+    __shared__ double red[SP_T];
+    const int j = blockIdx.x * SP_T + threadIdx.x;
+    double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
+    if (j < n) {
+        double sq = 0.0;
+        for (int i = 0; i < pp; ++i) {
+            const double v = V[(size_t)i * ld + j];
+            sq += v * v;
+        }
+        const double l = fitc ? sqrt(kxx + sn2 - sq) : sqrt(sn2);
+        double s2 = 0.0;
+        for (int i = 0; i < pp; ++i) {
+            const double v = V[(size_t)i * ld + j] / l;
+            V[(size_t)i * ld + j] = v;
+            s2 += v * v;
+        }
+        const double r = (y[j] - mean) / l;
+        ell[j] = l;
+        rt[j] = r;
+        q0 = log(l);
+        q1 = r * r;
+        q2 = s2;
+        q3 = 1.0 / (l * l);
+    } else if (j < np) {
+        ell[j] = 1.0;
+        rt[j] = 0.0;
+    }
+    double *po = part + (size_t)blockIdx.x * 4;
+    double s = sp_block_sum(q0, red);
+    if (threadIdx.x == 0) po[0] = s;
+    s = sp_block_sum(q1, red);
+    if (threadIdx.x == 0) po[1] = s;
+    s = sp_block_sum(q2, red);
+    if (threadIdx.x == 0) po[2] = s;
+    s = sp_block_sum(q3, red);
+    if (threadIdx.x == 0) po[3] = s;
+}
+
+// out[:, j] = in[:, j] * c_j (div: / c_j; c null: 1) for j < cols, q[j] = sum_i out_ij^2
+// (q may be null); part[block] = sum_{j < cols} q_j (part may be null). rows x cols,
+// columns >= cols untouched.
+__global__ __launch_bounds__(SP_T) void sp_colscale_kernel(
+    const double *in, double *out, long long ld, int rows, int cols,
+    const double *__restrict__ c, int div, double *__restrict__ q, double *__restrict__ part)
+{
+    __shared__ double red[SP_T];
+    const int j = blockIdx.x * SP_T + threadIdx.x;
+    double s = 0.0;
+    if (j < cols) {
+        const double cj = c ? c[j] : 1.0;
+        for (int i = 0; i < rows; ++i) {
+            double v = in[(size_t)i * ld + j];
+            if (c) v = div ? v / cj : v * cj;
+            if (out != in || c) out[(size_t)i * ld + j] = v;
+            s += v * v;
+        }
+        if (q) q[j] = s;
+    }
+    if (part) {
+        s = sp_block_sum(s, red);
+        if (threadIdx.x == 0) part[blockIdx.x] = s;
+    }
+}
+
+// out_i = sum_{j < cols} M_ij x_j, one block per row, fixed order
+__global__ __launch_bounds__(SP_T) void sp_gemv_rows_kernel(const double *__restrict__ M,
+                                                           long long ld, int cols,
+                                                           const double *__restrict__ x,
+                                                           double *__restrict__ out)
+{
+    __shared__ double red[SP_T];
+    const double *row = M + (size_t)blockIdx.x * ld;
+    double s = 0.0;
+    for (int j = threadIdx.x; j < cols; j += SP_T) s += row[j] * x[j];
+    s = sp_block_sum(s, red);
+    if (threadIdx.x == 0) out[blockIdx.x] = s;
+}
+
+// out_j = sum_{i < rows} M_ij x_i for j < cols, one thread per column
+__global__ __launch_bounds__(SP_T) void sp_gemv_cols_kernel(const double *__restrict__ M,
+                                                           long long ld, int rows, int cols,
+                                                           const double *__restrict__ x,
+                                                           double *__restrict__ out)
+{
+    const int j = blockIdx.x * SP_T + threadIdx.x;
+    if (j >= cols) return;
+    double s = 0.0;
+    for (int i = 0; i < rows; ++i) s += M[(size_t)i * ld + j] * x[i];
+    out[j] = s;
+}
+
+// alpha_j = (rt_j - u_j) / ell_j (FITC) or rt_j - u_j (DTC), 0 for the padding;
+// part[block][2]: sum alpha, sum alpha^2
+__global__ __launch_bounds__(SP_T) void sp_alpha_kernel(const double *__restrict__ rt,
+                                                       const double *__restrict__ u,
+                                                       const double *__restrict__ ell, int n,
+                                                       int np, int fitc,
+                                                       double *__restrict__ alpha,
+                                                       double *__restrict__ part)
+{
+    __shared__ double red[SP_T];
+    const int j = blockIdx.x * SP_T + threadIdx.x;
+    double a = 0.0;
+    if (j < n) a = fitc ? (rt[j] - u[j]) / ell[j] : rt[j] - u[j];
+    if (j < np) alpha[j] = a;
+    double s = sp_block_sum(a, red);
+    if (threadIdx.x == 0) part[(size_t)blockIdx.x * 2] = s;
+    s = sp_block_sum(a * a, red);
+    if (threadIdx.x == 0) part[(size_t)blockIdx.x * 2 + 1] = s;
+}
+
+// FITC: e_j = alpha_j^2 + s_j (j < n, 0 beyond)
+__global__ __launch_bounds__(SP_T) void sp_evec_kernel(const double *__restrict__ alpha,
+                                                      const double *__restrict__ s, int n, int np,
+                                                      double *__restrict__ e)
+{
+    const int j = blockIdx.x * SP_T + threadIdx.x;
+    if (j < np) e[j] = j < n ? alpha[j] * alpha[j] + s[j] : 0.0;
+}
+
+// G_ux in place over CW: FITC  CW + w alpha^T - B diag(e); DTC (CW + w alpha^T - B) / ell.
+// Zero outside p x n.
+__global__ __launch_bounds__(SP_T) void sp_gux_kernel(double *__restrict__ G,
+                                                     const double *__restrict__ B, long long ld,
+                                                     int p, int n, int np,
+                                                     const double *__restrict__ w,
+                                                     const double *__restrict__ alpha,
+                                                     const double *__restrict__ e,
+                                                     const double *__restrict__ ell, int fitc)
+{
+    const int j = blockIdx.x * SP_T + threadIdx.x;
+    const int i = blockIdx.y;
+    if (j >= np) return;
+    const size_t o = (size_t)i * ld + j;
+    double g = 0.0;
+    if (i < p && j < n) {
+        if (fitc) g = G[o] + w[i] * alpha[j] - B[o] * e[j];
+        else g = (G[o] + w[i] * alpha[j] - B[o]) / ell[j];
+    }
+    G[o] = g;
+}
+
+// out[i][j] (ld ldo) = sum_s P[s * stride + i * pp + j] + (i == j ? diag : 0), s in order
+__global__ __launch_bounds__(SP_T) void sp_sum_partials_kernel(const double *__restrict__ P,
+                                                              int nsplit, long long stride,
+                                                              int pp, double *__restrict__ out,
+                                                              int ldo, double diag)
+{
+    const int j = blockIdx.x * SP_T + threadIdx.x;
+    const int i = blockIdx.y;
+    if (j >= pp) return;
+    double s = 0.0;
+    for (int k = 0; k < nsplit; ++k) s += P[(size_t)k * stride + (size_t)i * pp + j];
+    out[(size_t)i * ldo + j] = s + (i == j ? diag : 0.0);
+}
+
+// G_uu = (BEB^T - w w^T - C C^T) / 2 inside p x p, 0 outside (all ld pp)
+__global__ __launch_bounds__(SP_T) void sp_guu_kernel(const double *__restrict__ BEB,
+                                                     const double *__restrict__ CC,
+                                                     const double *__restrict__ w, int p, int pp,
+                                                     double *__restrict__ G)
+{
+    const int j = blockIdx.x * SP_T + threadIdx.x;
+    const int i = blockIdx.y;
+    if (j >= pp) return;
+    const size_t o = (size_t)i * pp + j;
+    G[o] = i < p && j < p ? 0.5 * (BEB[o] - w[i] * w[j] - CC[o]) : 0.0;
+}
+
+// strictly lower triangle of an upper factor (and its inverse) -> 0
+__global__ __launch_bounds__(SP_T) void sp_zero_lower_kernel(double *__restrict__ M, int ld,
+                                                            int pp)
+{
+    const int j = blockIdx.x * SP_T + threadIdx.x;
+    const int i = blockIdx.y;
+    if (j < i && j < pp) M[(size_t)i * ld + j] = 0.0;
+}
+
+// per row i < p of the upper factor A and its inverse Ai: part[i][0] = log A_ii,
+// part[i][1] = sum_j (A_ij - [i == j] Ai_ij)^2 + [i != j] Ai_ij^2 -- the row's share of
+// ||A^T - A^-1||_F^2
+__global__ __launch_bounds__(SP_T) void sp_factor_terms_kernel(const double *__restrict__ A,
+                                                              const double *__restrict__ Ai,
+                                                              int ld, int p,
+                                                              double *__restrict__ part)
+{
+    __shared__ double red[SP_T];
+    const int i = blockIdx.x;
+    double s = 0.0;
+    for (int j = threadIdx.x; j < p; j += SP_T) {
+        const double a = A[(size_t)i * ld + j], b = Ai[(size_t)i * ld + j];
+        s += i == j ? (a - b) * (a - b) : a * a + b * b;
+    }
+    s = sp_block_sum(s, red);
+    if (threadIdx.x == 0) {
+        part[(size_t)i * 2] = log(A[(size_t)i * ld + i]);
+        part[(size_t)i * 2 + 1] = s;
+    }
+}
+
+// posterior at test column j < m: mu = mean + Q2[:, j] . beta, s2 = kss + (|Q2_j|^2 - |Q1_j|^2)
+__global__ __launch_bounds__(SP_T) void sp_post_kernel(const double *__restrict__ Q1,
+                                                      const double *__restrict__ Q2, long long ld,
+                                                      int pp, int m, const double *__restrict__ b,
+                                                      double mean, double kss,
+                                                      double *__restrict__ mu,
+                                                      double *__restrict__ s2)
+{
+    const int j = blockIdx.x * SP_T + threadIdx.x;
+    if (j >= m) return;
+    double a = 0.0, q2 = 0.0, q1 = 0.0;
+    for (int i = 0; i < pp; ++i) {
+        const double v2 = Q2[(size_t)i * ld + j], v1 = Q1[(size_t)i * ld + j];
+        a += v2 * b[i];
+        q2 += v2 * v2;
+        q1 += v1 * v1;
+    }
+    mu[j] = mean + a;
+    s2[j] = kss + (q2 - q1);
+}
+
+// input gradients at (j, c), e = j d + c < m d: dmu = dQ2[:, e] . beta,
+// ds2 = 2 dQ2[:, e] . Q2[:, j] - 2 dQ1[:, e] . Q1[:, j]
+__global__ __launch_bounds__(SP_T) void sp_post_grad_kernel(
+    const double *__restrict__ dQ1, const double *__restrict__ dQ2, long long ldd,
+    const double *__restrict__ Q1, const double *__restrict__ Q2, long long ld, int pp, int m,
+    int d, const double *__restrict__ b, double *__restrict__ dmu, double *__restrict__ ds2)
+{
+    const int e = blockIdx.x * SP_T + threadIdx.x;
+    if (e >= m * d) return;
+    const int j = e / d;
+    double a = 0.0, t2 = 0.0, t1 = 0.0;
+    for (int i = 0; i < pp; ++i) {
+        const double g2 = dQ2[(size_t)i * ldd + e], g1 = dQ1[(size_t)i * ldd + e];
+        a += g2 * b[i];
+        t2 += g2 * Q2[(size_t)i * ld + j];
+        t1 += g1 * Q1[(size_t)i * ld + j];
+    }
+    dmu[e] = a;
+    ds2[e] = 2 * t2 - 2 * t1;
+}
+
+// ---- host helpers ----------------------------------------------------------------
+static int sp_gemm(hipStream_t s, int ta, int tb, const double *A, int lda, const double *B,
+                   int ldb, double *C, int ldc, int M, int N, int K, double alpha, double beta)
+{
+    GemmArgs g;
+    g.A = A; g.B = B; g.C = C;
+    g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+    g.M = M; g.N = N; g.K = K;
+    g.alpha = alpha; g.beta = beta;
+    g.strideA = g.strideB = g.strideC = 0;
+    g.batch = 1;
+    g.flags = 0;
+    g.tile = 0; g.order = 0; g.swizzle = 0; g.waves = 0; g.use_lists = 1;
+    g.tiles = nullptr;
+    return gpx_gemm(s, ta, tb, g);
+}
+
+// out (pp x pp, ld ldo) = A B^T + diag I for A, B: pp x K panels (ld), K = N_pad: split-K
+// over the CUs, the partial products summed in a fixed order. The split depends on the
+// shape only.
+static int sp_abt_split(GpxSparse *st, hipStream_t s, const double *A, const double *B,
+                        long long ld, int K, double *out, int ldo, double diag)
+{
+    const int pp = st->pp;
+    const long long tiles64 = (long long)(pp / 64) * (pp / 64);
+    int nsplit = (int)std::max<long long>(1, (2048 + tiles64 - 1) / tiles64);
+    nsplit = std::min(nsplit, std::max(1, K / 1024));
+    const int kc = sp_round((K + nsplit - 1) / nsplit, 128);
+    nsplit = (K + kc - 1) / kc;
+    const long long stride = (long long)pp * pp;
+    GPX_TRY(st->split.reserve((size_t)nsplit * stride * 8));
+    GemmArgs g;
+    g.A = A; g.B = B; g.C = st->split.d();
+    g.lda = (int)ld; g.ldb = (int)ld; g.ldc = pp;
+    g.M = pp; g.N = pp; g.K = K;
+    g.alpha = 1.0; g.beta = 0.0;
+    g.strideA = g.strideB = 0;
+    g.strideC = stride;
+    g.batch = nsplit;
+    g.kchunk = kc;
+    g.flags = 0;
+    g.tile = 64; g.order = 0; g.swizzle = 0; g.waves = 0; g.use_lists = 1;
+    g.tiles = nullptr;
+    GPX_TRY(gpx_gemm(s, 0, 1, g));
+    // a plain pp x pp result: the library's fixed-order sum; a factorisation's staging
+    // matrix (ld ldp, + the identity) takes the kernel above, which writes it in one pass
+    if (diag == 0.0 && ldo == pp) return gpx_sum_partials(s, st->split.d(), nsplit, stride, stride, out);
+    hipLaunchKernelGGL(sp_sum_partials_kernel, dim3((pp + SP_T - 1) / SP_T, pp), dim3(SP_T), 0,
+                       s, st->split.d(), nsplit, stride, pp, out, ldo, diag);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+static int sp_reduce(hipStream_t s, const double *part, int nb, int nq, double *out)
+{
+    hipLaunchKernelGGL(sp_reduce_kernel, dim3(nq), dim3(SP_T), 0, s, part, nb, nq, out);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+static int sp_dot(hipStream_t s, const double *a, const double *b, long long n, double *out)
+{
+    hipLaunchKernelGGL(sp_dot_kernel, dim3(1), dim3(1024), 0, s, a, b, n, out);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// upper factor of the symmetric pp x pp matrix in F (ld ldp) in place, its inverse in Fw;
+// Fk is the factorisation's scratch. Returns > 0 (pivot) when not positive definite.
+static int sp_factor(GpxSparse *st, hipStream_t s, double *F, double *Fw, double *Fk,
+                     int *gates)
+{
+    DenseWs w;
+    w.A = F;
+    w.W = Fw;
+    w.Kinv = Fk;
+    w.np = st->pp;
+    w.ld = st->ldp;
+    w.info = st->info.as_int();
+    w.pctl = static_cast<int *>(st->pctl.p);
+    w.gate_total = gates;
+    GPX_HIP(hipMemsetAsync(w.info, 0, sizeof(int), s));
+    w.whole = gpx_potrf_whole(w, GPX_POTRF_W);
+    GPX_TRY(gpx_potrf(s, w, GPX_POTRF_W, false));
+    const dim3 grid((st->pp + SP_T - 1) / SP_T, st->pp);
+    hipLaunchKernelGGL(sp_zero_lower_kernel, grid, dim3(SP_T), 0, s, F, st->ldp, st->pp);
+    hipLaunchKernelGGL(sp_zero_lower_kernel, grid, dim3(SP_T), 0, s, Fw, st->ldp, st->pp);
+    GPX_HIP(hipGetLastError());
+    int inf = 0;
+    GPX_HIP(hipMemcpyAsync(&inf, w.info, sizeof(int), hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipStreamSynchronize(s));
+    if (inf) {
+        gpx_set_error("gpx_sparse_update: matrix is not positive definite: pivot %d", inf);
+        return inf;
+    }
+    return 0;
+}
+
+// ---- entry points (called by gpx_api.hip with the handle's stream and data) ----------
+int gpx_sparse_nhyper(const GpxSparse *st) { return st ? st->kp.nhyper : -1; }
+
+void gpx_sparse_destroy(GpxSparse *st)
+{
+    if (!st) return;
+    SpBuf *bufs[] = {&st->U, &st->L, &st->Lw, &st->Lk, &st->A, &st->Aw, &st->Ak, &st->info,
+                     &st->pctl, &st->P1, &st->P2, &st->P3, &st->P4, &st->ell, &st->rt, &st->beta,
+                     &st->gam, &st->u, &st->alpha, &st->wv, &st->vv, &st->bq, &st->sq, &st->e,
+                     &st->part, &st->scal, &st->acc_uu, &st->acc_ux, &st->pg_part, &st->split,
+                     &st->Cm, &st->CC, &st->BEB, &st->Guu, &st->R2, &st->Xs, &st->Ks, &st->Q1,
+                     &st->Q2, &st->dKc, &st->dK, &st->dQ1, &st->dQ2, &st->mu, &st->s2,
+                     &st->dmu, &st->ds2, &st->Sig};
+    for (SpBuf *b : bufs) b->release();
+    for (hipEvent_t e : st->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete st;
+}
+
+int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, int method,
+                          const double *U, int p, double log_sn, double mean,
+                          const double *X, const double *y, int n, int d, int *info)
+{
+    if (!*state) *state = new GpxSparse();
+    GpxSparse *st = *state;
+    st->ready = false;
+    st->method = method;
+    st->p = p;
+    st->pp = sp_round(p, GPX_TILE);
+    st->ldp = st->pp + 32;                 // rows off one HBM channel, as ld_for does
+    st->n = n;
+    st->np = sp_round(n, GPX_TILE);
+    st->d = d;
+    st->kp = kp;
+    st->sn2 = exp(2 * log_sn);             // gaussian.py
+    // the two forms of the jitter are not bitwise equal (fitc.py, dtc.py)
+    st->su2 = method == GPX_FITC ? st->sn2 / 1e6 : st->sn2 * 1e-6;
+    st->mean = mean;
+    st->prior = gpx_kernel_prior(kp);
+    const int pp = st->pp, ldp = st->ldp, np = st->np;
+    const size_t mat = (size_t)pp * ldp * 8, panel = (size_t)pp * np * 8, vec = (size_t)np * 8;
+    GPX_TRY(st->U.reserve((size_t)p * d * 8));
+    GPX_TRY(st->L.reserve(mat));
+    GPX_TRY(st->Lw.reserve(mat));
+    GPX_TRY(st->Lk.reserve(mat));
+    GPX_TRY(st->A.reserve(mat));
+    GPX_TRY(st->Aw.reserve(mat));
+    GPX_TRY(st->Ak.reserve(mat));
+    if (!st->pctl.p) {
+        GPX_TRY(st->info.reserve(64));
+        GPX_TRY(st->pctl.reserve(gpx_panel_ctl_bytes()));
+        GPX_HIP(hipMemsetAsync(st->pctl.p, 0, gpx_panel_ctl_bytes(), s));
+    }
+    GPX_TRY(st->P1.reserve(panel));
+    GPX_TRY(st->P2.reserve(panel));
+    GPX_TRY(st->ell.reserve(vec));
+    GPX_TRY(st->rt.reserve(vec));
+    GPX_TRY(st->beta.reserve((size_t)pp * 8));
+    GPX_TRY(st->gam.reserve((size_t)pp * 8));
+    const int nbc = (np + SP_T - 1) / SP_T;
+    GPX_TRY(st->part.reserve((size_t)std::max(nbc * 4, pp * 2) * 8));
+    GPX_TRY(st->scal.reserve(S_COUNT * 8));
+    GPX_HIP(hipMemsetAsync(st->scal.p, 0, S_COUNT * 8, s));
+    GPX_HIP(hipMemcpyAsync(st->U.p, U, (size_t)p * d * 8, hipMemcpyHostToDevice, s));
+    if (info) *info = 0;
+    GPX_TRY(sp_event(st, s, 0));
+
+    // L = chol(Kuu + su2 I), identity in the padding
+    GPX_TRY(gpx_kbuild<double>(s, kp, st->U.d(), p, pp, st->U.d(), p, pp, d, st->L.d(), ldp,
+                               true, false, st->su2));
+    int r = sp_factor(st, s, st->L.d(), st->Lw.d(), st->Lk.d(), st->gates_l);
+    if (r != 0) {
+        if (r > 0 && info) *info = r;
+        return r;
+    }
+    // Kux (zero outside p x n), V0 = L^-T Kux, then ell, rt and V = V0 / ell in place
+    GPX_TRY(gpx_kbuild<double>(s, kp, st->U.d(), p, pp, X, n, np, d, st->P1.d(), np, false,
+                               false, 0.0));
+    GPX_TRY(sp_gemm(s, 1, 0, st->Lw.d(), ldp, st->P1.d(), np, st->P2.d(), np, pp, np, pp, 1.0,
+                    0.0));
+    // one step of refinement, V0 += L^-T (Kux - L^T V0): the product with the explicit
+    // inverse alone has the forward error of the inverse, and ell (FITC) takes
+    // kxx + sn2 - |V0_j|^2, which cancels (the exact path's posterior does the same,
+    // solve_rt_refined in gpx_api.hip)
+    GPX_TRY(st->P3.reserve(panel));
+    GPX_TRY(sp_gemm(s, 1, 0, st->L.d(), ldp, st->P2.d(), np, st->P1.d(), np, pp, np, pp, -1.0,
+                    1.0));
+    GPX_TRY(sp_gemm(s, 1, 0, st->Lw.d(), ldp, st->P1.d(), np, st->P3.d(), np, pp, np, pp, 1.0,
+                    0.0));
+    GPX_TRY(gpx_add_inplace(s, st->P2.d(), st->P3.d(), (size_t)pp * np));
+    hipLaunchKernelGGL(sp_colprep_kernel, dim3(nbc), dim3(SP_T), 0, s, st->P2.d(), (long long)np,
+                       pp, n, np, y, mean, st->prior, st->sn2, method == GPX_FITC ? 1 : 0,
+                       st->ell.d(), st->rt.d(), st->part.d());
+    GPX_HIP(hipGetLastError());
+    GPX_TRY(sp_reduce(s, st->part.d(), nbc, 4, st->scal.d() + S_LOGELL));
+    // A = chol(I + V V^T)
+    GPX_TRY(sp_abt_split(st, s, st->P2.d(), st->P2.d(), np, np, st->A.d(), ldp, 1.0));
+    r = sp_factor(st, s, st->A.d(), st->Aw.d(), st->Ak.d(), st->gates_a);
+    if (r != 0) {
+        if (r > 0 && info) *info = r;
+        return r;
+    }
+    // beta = A^-T (V rt)
+    hipLaunchKernelGGL(sp_gemv_rows_kernel, dim3(pp), dim3(SP_T), 0, s, st->P2.d(),
+                       (long long)np, n, st->rt.d(), st->gam.d());
+    hipLaunchKernelGGL(sp_gemv_cols_kernel, dim3((pp + SP_T - 1) / SP_T), dim3(SP_T), 0, s,
+                       st->Aw.d(), (long long)ldp, pp, pp, st->gam.d(), st->beta.d());
+    GPX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(sp_factor_terms_kernel, dim3(p), dim3(SP_T), 0, s, st->A.d(), st->Aw.d(),
+                       ldp, p, st->part.d());
+    GPX_HIP(hipGetLastError());
+    GPX_TRY(sp_reduce(s, st->part.d(), p, 2, st->scal.d() + S_LOGA));
+    GPX_TRY(sp_dot(s, st->beta.d(), nullptr, pp, st->scal.d() + S_BETA2));
+    GPX_HIP(hipMemcpyAsync(st->hsc, st->scal.p, S_COUNT * 8, hipMemcpyDeviceToHost, s));
+    GPX_TRY(sp_event(st, s, 1));
+    GPX_HIP(hipStreamSynchronize(s));
+    st->ms[0] = sp_elapsed(st, 0, 1);
+    st->ms[1] = st->ms[2] = 0.0;
+    st->ready = true;
+    return 0;
+}
+
+int gpx_sparse_run_loglik(GpxSparse *st, hipStream_t s, const double *X, double *lZ,
+                          double *dlZ)
+{
+    if (!st || !st->ready) {
+        gpx_set_error("gpx_sparse_loglik: no sparse model (call gpx_sparse_update)");
+        return -1;
+    }
+    const double *sc = st->hsc;
+    // lZ = -sum log A_ii - sum log ell - (rt^T rt - beta^T beta) / 2 - N log(2 pi) / 2
+    *lZ = -sc[S_LOGA] - sc[S_LOGELL] - 0.5 * (sc[S_RT2] - sc[S_BETA2]) -
+          0.5 * st->n * log(2 * M_PI);
+    if (!dlZ) return 0;
+
+    const bool fitc = st->method == GPX_FITC;
+    const int p = st->p, pp = st->pp, ldp = st->ldp, n = st->n, np = st->np, d = st->d;
+    const long long ld = np;
+    const size_t panel = (size_t)pp * np * 8, vec = (size_t)np * 8;
+    GPX_TRY(st->P3.reserve(panel));
+    GPX_TRY(st->u.reserve(vec));
+    GPX_TRY(st->alpha.reserve(vec));
+    GPX_TRY(st->bq.reserve(vec));
+    GPX_TRY(st->sq.reserve(vec));
+    GPX_TRY(st->e.reserve(vec));
+    GPX_TRY(st->wv.reserve((size_t)pp * 8));
+    GPX_TRY(st->vv.reserve((size_t)pp * 8));
+    GPX_TRY(st->Cm.reserve((size_t)pp * pp * 8));
+    GPX_TRY(st->CC.reserve((size_t)pp * pp * 8));
+    GPX_TRY(st->BEB.reserve((size_t)pp * pp * 8));
+    GPX_TRY(st->Guu.reserve((size_t)pp * pp * 8));
+    const int nacc = 1 + st->kp.nhyper;
+    GPX_TRY(st->acc_uu.reserve((size_t)nacc * 8));
+    GPX_TRY(st->acc_ux.reserve((size_t)nacc * 8));
+    GPX_TRY(st->pg_part.reserve(gpx_pair_grad_scratch(pp) * 8));
+    const int nbc = (np + SP_T - 1) / SP_T;
+    const dim3 cgrid(nbc);
+    GPX_TRY(st->P4.reserve(panel));
+    double *P1 = st->P1.d(), *P2 = st->P2.d(), *P3 = st->P3.d(), *P4 = st->P4.d();
+    double *scal = st->scal.d();
+    GPX_TRY(sp_event(st, s, 2));
+
+    // gamma = A^-1 beta, u = V^T gamma, alpha
+    hipLaunchKernelGGL(sp_gemv_rows_kernel, dim3(pp), dim3(SP_T), 0, s, st->Aw.d(),
+                       (long long)ldp, pp, st->beta.d(), st->gam.d());
+    hipLaunchKernelGGL(sp_gemv_cols_kernel, cgrid, dim3(SP_T), 0, s, P2, ld, pp, np,
+                       st->gam.d(), st->u.d());
+    hipLaunchKernelGGL(sp_alpha_kernel, cgrid, dim3(SP_T), 0, s, st->rt.d(), st->u.d(),
+                       st->ell.d(), n, np, fitc ? 1 : 0, st->alpha.d(), st->part.d());
+    GPX_HIP(hipGetLastError());
+    GPX_TRY(sp_reduce(s, st->part.d(), nbc, 2, scal + S_ALPHA));
+    // B = L^-1 V0 (FITC) = L^-1 V diag(ell), or L^-1 V (DTC); q: column sums of B^2
+    GPX_TRY(sp_gemm(s, 0, 0, st->Lw.d(), ldp, P2, np, P1, np, pp, np, pp, 1.0, 0.0));
+    hipLaunchKernelGGL(sp_colscale_kernel, cgrid, dim3(SP_T), 0, s, P1, P1, ld, pp, n,
+                       fitc ? st->ell.d() : nullptr, 0, st->bq.d(), st->part.d());
+    GPX_HIP(hipGetLastError());
+    GPX_TRY(sp_reduce(s, st->part.d(), nbc, 1, scal + S_B2));
+    // W = A^-T V / ell (FITC) or A^-T V (DTC); s_j = sum_i W_ij^2
+    GPX_TRY(sp_gemm(s, 1, 0, st->Aw.d(), ldp, P2, np, P3, np, pp, np, pp, 1.0, 0.0));
+    hipLaunchKernelGGL(sp_colscale_kernel, cgrid, dim3(SP_T), 0, s, P3, P3, ld, pp, n,
+                       fitc ? st->ell.d() : nullptr, 1, st->sq.d(), st->part.d());
+    GPX_HIP(hipGetLastError());
+    GPX_TRY(sp_reduce(s, st->part.d(), nbc, 1, scal + S_S));
+    // w = B alpha, (V alpha) for DTC's noise term
+    hipLaunchKernelGGL(sp_gemv_rows_kernel, dim3(pp), dim3(SP_T), 0, s, P1, ld, n,
+                       st->alpha.d(), st->wv.d());
+    hipLaunchKernelGGL(sp_gemv_rows_kernel, dim3(pp), dim3(SP_T), 0, s, P2, ld, n,
+                       st->alpha.d(), st->vv.d());
+    GPX_HIP(hipGetLastError());
+    GPX_TRY(sp_dot(s, st->wv.d(), nullptr, pp, scal + S_W2));
+    GPX_TRY(sp_dot(s, st->vv.d(), nullptr, pp, scal + S_V2A));
+    // C = B W^T (pp x pp), ||C||^2 by columns, CW = C W into the fourth panel
+    GPX_TRY(sp_abt_split(st, s, P1, P3, ld, np, st->Cm.d(), pp, 0.0));
+    hipLaunchKernelGGL(sp_colscale_kernel, dim3((pp + SP_T - 1) / SP_T), dim3(SP_T), 0, s,
+                       st->Cm.d(), st->Cm.d(), (long long)pp, pp, pp, nullptr, 0, nullptr,
+                       st->part.d());
+    GPX_HIP(hipGetLastError());
+    GPX_TRY(sp_reduce(s, st->part.d(), (pp + SP_T - 1) / SP_T, 1, scal + S_C2));
+    GPX_TRY(sp_gemm(s, 0, 0, st->Cm.d(), pp, P3, np, P4, np, pp, np, pp, 1.0, 0.0));
+    // FITC: e = alpha^2 + s and sum_j e_j sum_i B_ij^2
+    if (fitc) {
+        hipLaunchKernelGGL(sp_evec_kernel, cgrid, dim3(SP_T), 0, s, st->alpha.d(), st->sq.d(), n,
+                           np, st->e.d());
+        GPX_HIP(hipGetLastError());
+        GPX_TRY(sp_dot(s, st->e.d(), st->bq.d(), n, scal + S_EB2));   // (bq: j < n only)
+    }
+    // G_ux in place over CW
+    hipLaunchKernelGGL(sp_gux_kernel, dim3(nbc, pp), dim3(SP_T), 0, s, P4, P1, ld, p, n, np,
+                       st->wv.d(), st->alpha.d(), st->e.d(), st->ell.d(), fitc ? 1 : 0);
+    GPX_HIP(hipGetLastError());
+    // B diag(e) B^T (FITC) or B B^T (DTC), C C^T, G_uu
+    const double *BE = P1;
+    if (fitc) {
+        hipLaunchKernelGGL(sp_colscale_kernel, cgrid, dim3(SP_T), 0, s, P1, P3, ld, pp, np,
+                           st->e.d(), 0, nullptr, nullptr);
+        GPX_HIP(hipGetLastError());
+        BE = P3;
+    }
+    GPX_TRY(sp_abt_split(st, s, BE, P1, ld, np, st->BEB.d(), pp, 0.0));
+    GPX_TRY(sp_gemm(s, 0, 1, st->Cm.d(), pp, st->Cm.d(), pp, st->CC.d(), pp, pp, pp, pp, 1.0,
+                    0.0));
+    hipLaunchKernelGGL(sp_guu_kernel, dim3((pp + SP_T - 1) / SP_T, pp), dim3(SP_T), 0, s,
+                       st->BEB.d(), st->CC.d(), st->wv.d(), p, pp, st->Guu.d());
+    GPX_HIP(hipGetLastError());
+    // the contractions with the kernel derivatives
+    GPX_TRY(sp_event(st, s, 3));
+    GPX_TRY(gpx_pair_grad(s, st->kp, st->U.d(), p, st->U.d(), p, d, st->Guu.d(), pp,
+                          st->pg_part.d(), st->acc_uu.d()));
+    GPX_TRY(gpx_pair_grad(s, st->kp, st->U.d(), p, X, n, d, P4, ld, st->pg_part.d(),
+                          st->acc_ux.d()));
+    std::vector<double> auu(nacc), aux(nacc);
+    GPX_HIP(hipMemcpyAsync(auu.data(), st->acc_uu.p, nacc * 8, hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipMemcpyAsync(aux.data(), st->acc_ux.p, nacc * 8, hipMemcpyDeviceToHost, s));
+    double h[S_COUNT];
+    GPX_HIP(hipMemcpyAsync(h, st->scal.p, S_COUNT * 8, hipMemcpyDeviceToHost, s));
+    GPX_TRY(sp_event(st, s, 4));
+    GPX_HIP(hipStreamSynchronize(s));
+    st->ms[1] = sp_elapsed(st, 2, 4);
+    st->ms[2] = sp_elapsed(st, 3, 4);
+
+    const double sn2 = st->sn2, su2 = st->su2;
+    const int nh = st->kp.nhyper;
+    // d kxx / d theta: k(x, x) = sum over groups of the product of sf^2, so only the log sf
+    // slots move (2 x the group's product per occurrence of a part)
+    std::vector<double> dprior(nh, 0.0);
+    for (int q = 0; q < st->kp.nparts; ++q) {
+        double g = 1.0;
+        for (int t = 0; t < st->kp.nparts; ++t)
+            if (st->kp.part[t].group == st->kp.part[q].group) g *= st->kp.part[t].sf2;
+        dprior[st->kp.part[q].hoff] += 2 * g;
+    }
+    if (fitc) {
+        const double gx = 0.5 * (h[S_ALPHA2] + h[S_S] - h[S_IELL2]);
+        dlZ[0] = -sn2 * (h[S_IELL2] - h[S_S] - h[S_ALPHA2]) - su2 * (h[S_W2] + h[S_C2]) +
+                 su2 * h[S_EB2];
+        for (int k = 0; k < nh; ++k) dlZ[1 + k] = auu[1 + k] + aux[1 + k] + dprior[k] * gx;
+        dlZ[1 + nh] = h[S_ALPHA];
+    } else {
+        dlZ[0] = -(-h[S_RT2] + h[S_BETA2] + h[S_V2A] + su2 * h[S_W2] + n - h[S_V2] + h[S_AW2] -
+                   su2 * (h[S_B2] - h[S_C2]));
+        for (int k = 0; k < nh; ++k) dlZ[1 + k] = auu[1 + k] + aux[1 + k];
+        dlZ[1 + nh] = h[S_ALPHA] / sqrt(sn2);
+    }
+    return 0;
+}
+
+// mu, s2 (and dmu, ds2: m x d, or Sigma: m x m) at the m test points Xs (host)
+int gpx_sparse_run_posterior(GpxSparse *st, hipStream_t s, const double *Xs, int64_t m,
+                             double *mu, double *s2, double *dmu, double *ds2, double *Sigma)
+{
+    if (!st || !st->ready) {
+        gpx_set_error("gpx_sparse_posterior: no sparse model (call gpx_sparse_update)");
+        return -1;
+    }
+    const int p = st->p, pp = st->pp, ldp = st->ldp, d = st->d;
+    const bool grads = dmu && ds2;
+    const int CH = Sigma ? 8192 : 4096;
+    for (int64_t c0 = 0; c0 < m; c0 += CH) {
+        const int mc = (int)std::min<int64_t>(CH, m - c0);
+        const int mcp = sp_round(mc, GPX_TILE);
+        GPX_TRY(st->Xs.reserve((size_t)mc * d * 8));
+        GPX_TRY(st->Ks.reserve((size_t)pp * mcp * 8));
+        GPX_TRY(st->Q1.reserve((size_t)pp * mcp * 8));
+        GPX_TRY(st->Q2.reserve((size_t)pp * mcp * 8));
+        GPX_TRY(st->mu.reserve((size_t)mcp * 8));
+        GPX_TRY(st->s2.reserve((size_t)mcp * 8));
+        GPX_HIP(hipMemcpyAsync(st->Xs.p, Xs + c0 * d, (size_t)mc * d * 8, hipMemcpyHostToDevice,
+                               s));
+        // K(U, X*), Q1 = L^-T K, Q2 = A^-T Q1 = (A L)^-T K
+        GPX_TRY(gpx_kbuild<double>(s, st->kp, st->U.d(), p, pp, st->Xs.d(), mc, mcp, d,
+                                   st->Ks.d(), mcp, false, false, 0.0));
+        GPX_TRY(sp_gemm(s, 1, 0, st->Lw.d(), ldp, st->Ks.d(), mcp, st->Q1.d(), mcp, pp, mcp, pp,
+                        1.0, 0.0));
+        GPX_TRY(st->Q2.reserve((size_t)pp * mcp * 8));
+        GPX_TRY(sp_gemm(s, 1, 0, st->L.d(), ldp, st->Q1.d(), mcp, st->Ks.d(), mcp, pp, mcp, pp,
+                        -1.0, 1.0));                       // (refined as V0 above)
+        GPX_TRY(sp_gemm(s, 1, 0, st->Lw.d(), ldp, st->Ks.d(), mcp, st->Q2.d(), mcp, pp, mcp, pp,
+                        1.0, 0.0));
+        GPX_TRY(gpx_add_inplace(s, st->Q1.d(), st->Q2.d(), (size_t)pp * mcp));
+        GPX_TRY(sp_gemm(s, 1, 0, st->Aw.d(), ldp, st->Q1.d(), mcp, st->Q2.d(), mcp, pp, mcp, pp,
+                        1.0, 0.0));
+        hipLaunchKernelGGL(sp_post_kernel, dim3((mc + SP_T - 1) / SP_T), dim3(SP_T), 0, s,
+                           st->Q1.d(), st->Q2.d(), (long long)mcp, pp, mc, st->beta.d(),
+                           st->mean, st->prior, st->mu.d(), st->s2.d());
+        GPX_HIP(hipGetLastError());
+        GPX_HIP(hipMemcpyAsync(mu + c0, st->mu.p, (size_t)mc * 8, hipMemcpyDeviceToHost, s));
+        if (s2)
+            GPX_HIP(hipMemcpyAsync(s2 + c0, st->s2.p, (size_t)mc * 8, hipMemcpyDeviceToHost, s));
+        if (Sigma) {
+            // K(X*, X*) + Q2^T Q2 - Q1^T Q1 (fitc.py / dtc.py _full_posterior)
+            GPX_TRY(st->Sig.reserve((size_t)mcp * mcp * 8));
+            GPX_TRY(gpx_kbuild<double>(s, st->kp, st->Xs.d(), mc, mcp, st->Xs.d(), mc, mcp, d,
+                                       st->Sig.d(), mcp, false, false, 0.0));
+            GPX_TRY(sp_gemm(s, 1, 0, st->Q2.d(), mcp, st->Q2.d(), mcp, st->Sig.d(), mcp, mcp,
+                            mcp, pp, 1.0, 1.0));
+            GPX_TRY(sp_gemm(s, 1, 0, st->Q1.d(), mcp, st->Q1.d(), mcp, st->Sig.d(), mcp, mcp,
+                            mcp, pp, -1.0, 1.0));
+            GPX_HIP(hipMemcpy2DAsync(Sigma, (size_t)m * 8, st->Sig.p, (size_t)mcp * 8,
+                                     (size_t)mc * 8, mc, hipMemcpyDeviceToHost, s));
+        }
+        if (grads) {
+            // dK = grady(U, X*): p x (m d), padded to pp x ldd; dQ1 = L^-T dK, dQ2 = A^-T dQ1
+            const int md = mc * d, ldd = sp_round(md, GPX_TILE);
+            GPX_TRY(st->dKc.reserve((size_t)p * md * 8));
+            GPX_TRY(st->dK.reserve((size_t)pp * ldd * 8));
+            GPX_TRY(st->dQ1.reserve((size_t)pp * ldd * 8));
+            GPX_TRY(st->dQ2.reserve((size_t)pp * ldd * 8));
+            GPX_TRY(st->dmu.reserve((size_t)md * 8));
+            GPX_TRY(st->ds2.reserve((size_t)md * 8));
+            GPX_TRY(gpx_kgrady(s, st->kp, st->U.d(), p, st->Xs.d(), mc, d, 1.0, st->dKc.d()));
+            GPX_HIP(hipMemsetAsync(st->dK.p, 0, (size_t)pp * ldd * 8, s));
+            GPX_HIP(hipMemcpy2DAsync(st->dK.p, (size_t)ldd * 8, st->dKc.p, (size_t)md * 8,
+                                     (size_t)md * 8, p, hipMemcpyDeviceToDevice, s));
+            GPX_TRY(sp_gemm(s, 1, 0, st->Lw.d(), ldp, st->dK.d(), ldd, st->dQ1.d(), ldd, pp, ldd,
+                            pp, 1.0, 0.0));
+            GPX_TRY(sp_gemm(s, 1, 0, st->Aw.d(), ldp, st->dQ1.d(), ldd, st->dQ2.d(), ldd, pp,
+                            ldd, pp, 1.0, 0.0));
+            hipLaunchKernelGGL(sp_post_grad_kernel, dim3((md + SP_T - 1) / SP_T), dim3(SP_T), 0,
+                               s, st->dQ1.d(), st->dQ2.d(), (long long)ldd, st->Q1.d(),
+                               st->Q2.d(), (long long)mcp, pp, mc, d, st->beta.d(), st->dmu.d(),
+                               st->ds2.d());
+            GPX_HIP(hipGetLastError());
+            GPX_HIP(hipMemcpyAsync(dmu + c0 * d, st->dmu.p, (size_t)md * 8,
+                                   hipMemcpyDeviceToHost, s));
+            GPX_HIP(hipMemcpyAsync(ds2 + c0 * d, st->ds2.p, (size_t)md * 8,
+                                   hipMemcpyDeviceToHost, s));
+        }
+        GPX_HIP(hipStreamSynchronize(s));
+        if (Sigma) break;                   // (one pass: the caller limits m)
+    }
+    return 0;
+}
+
+// host copies of the stored factors: F1 = L (FITC) / Ruu (DTC), F2 = A L (FITC R, DTC Rux),
+// v = beta (FITC b) / sn2 beta (DTC a); p x p row-major upper, any may be null
+int gpx_sparse_run_state(GpxSparse *st, hipStream_t s, double *F1, double *F2, double *v)
+{
+    if (!st || !st->ready) {
+        gpx_set_error("gpx_sparse_get_state: no sparse model (call gpx_sparse_update)");
+        return -1;
+    }
+    const int p = st->p, pp = st->pp, ldp = st->ldp;
+    if (F1)
+        GPX_HIP(hipMemcpy2DAsync(F1, (size_t)p * 8, st->L.p, (size_t)ldp * 8, (size_t)p * 8, p,
+                                 hipMemcpyDeviceToHost, s));
+    if (F2) {
+        GPX_TRY(st->R2.reserve((size_t)pp * pp * 8));
+        GPX_TRY(sp_gemm(s, 0, 0, st->A.d(), ldp, st->L.d(), ldp, st->R2.d(), pp, pp, pp, pp, 1.0,
+                        0.0));
+        GPX_HIP(hipMemcpy2DAsync(F2, (size_t)p * 8, st->R2.p, (size_t)pp * 8, (size_t)p * 8, p,
+                                 hipMemcpyDeviceToHost, s));
+    }
+    std::vector<double> b(p);
+    if (v) GPX_HIP(hipMemcpyAsync(b.data(), st->beta.p, (size_t)p * 8, hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipStreamSynchronize(s));
+    if (v)
+        for (int i = 0; i < p; ++i) v[i] = st->method == GPX_FITC ? b[i] : st->sn2 * b[i];
+    return 0;
+}
+
+int gpx_sparse_run_timings(GpxSparse *st, double *ms)
+{
+    if (!st) {
+        gpx_set_error("gpx_sparse_timings: no sparse model");
+        return -1;
+    }
+    for (int i = 0; i < 3; ++i) ms[i] = st->ms[i];
+    return 0;
+}

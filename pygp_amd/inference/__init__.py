@@ -1,4 +1,6 @@
 from .exact import GP, ExactGP
 from .basic import BasicGP
+from .fitc import FITC
+from .dtc import DTC
 
-__all__ = ['GP', 'ExactGP', 'BasicGP']
+__all__ = ['GP', 'ExactGP', 'BasicGP', 'FITC', 'DTC']

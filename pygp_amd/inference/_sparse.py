@@ -1,0 +1,137 @@
+"""
+Shared state machine of the sparse pseudo-input models FITC and DTC
+(pygp/inference/fitc.py, dtc.py).
+
+The numerical work -- Kuu, Kux, the two p x p Cholesky factors, the lZ terms, the
+gradient contraction and the posteriors -- runs in libgpx.so (sparse.hip). The model owns
+a device handle with X and y resident after add_data; set_hyper / add_data refactor on
+the device (no incremental update: the reference refactors on add_data too).
+"""
+
+import numpy as np
+
+from ..likelihoods import Gaussian
+from .. import _lib
+from .exact import GP
+
+__all__ = ['SparseGP']
+
+
+class SparseGP(GP):
+    """Base of FITC and DTC: a Gaussian likelihood and p pseudo-inputs U."""
+
+    _method = None          # _lib.GPX_FITC / GPX_DTC
+
+    def __init__(self, likelihood, kernel, mean, U):
+        if not isinstance(likelihood, Gaussian):
+            raise ValueError('sparse inference requires a Gaussian likelihood')
+        super(SparseGP, self).__init__(likelihood, kernel, mean)
+        self._U = np.array(U, ndmin=2, dtype=float, copy=True)
+        self._dev_ = None
+        self._resident = False
+        self._factored = False
+
+    # -- device state -------------------------------------------------------
+    def _dev(self):
+        if self._dev_ is None:
+            self._dev_ = _lib.Handle()
+            self._resident = False
+        return self._dev_
+
+    def _data_changed(self):
+        self._resident = False
+        self._factored = False
+
+    def __deepcopy__(self, memo):
+        """A copy gets hypers, pseudo-inputs and host data, never the device handle; it
+        uploads and refactors lazily (as ExactGP.__deepcopy__)."""
+        import copy
+        clone = type(self).__new__(type(self))
+        memo[id(self)] = clone
+        for key, val in self.__dict__.items():
+            if key not in ('_dev_', '_resident', '_factored'):
+                setattr(clone, key, copy.deepcopy(val, memo))
+        clone._dev_, clone._resident, clone._factored = None, False, False
+        return clone
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state['_dev_'], state['_resident'], state['_factored'] = None, False, False
+        return state
+
+    @property
+    def pseudoinputs(self):
+        """The pseudo-input points."""
+        return self._U
+
+    @classmethod
+    def from_gp(cls, gp, U=None):
+        if U is None:
+            if hasattr(gp, 'pseudoinputs'):
+                U = gp.pseudoinputs.copy()
+            else:
+                raise ValueError('gp has no pseudoinputs and none are given')
+        new = cls(gp._likelihood.copy(), gp._kernel.copy(), gp._mean, U)
+        if gp.ndata > 0:
+            new.add_data(*gp.data)
+        return new
+
+    def reset(self):
+        super(SparseGP, self).reset()
+        self._data_changed()
+
+    # -- the hot path -------------------------------------------------------
+    def _update(self):
+        if not (np.all(np.isfinite(self.get_hyper())) and
+                (self._resident or (np.all(np.isfinite(self._X)) and
+                                    np.all(np.isfinite(self._y))))):
+            self._factored = False
+            raise ValueError('array must not contain infs or NaNs')
+        if self._U.shape[1] != self._X.shape[1]:
+            raise ValueError('pseudo-inputs have the wrong dimension')
+        dev = self._dev()
+        if not self._resident:
+            dev.set_data(self._X, self._y)
+            self._resident = True
+        self._factored = False
+        dev.sparse_update(self._kernel._kspec(), self._method, self._U,
+                          self._likelihood.get_hyper()[0], self._mean)
+        self._factored = True
+
+    def _ensure(self):
+        if self.ndata > 0 and not self._factored:
+            self._update()
+
+    def loglikelihood(self, grad=False):
+        if self.ndata == 0:
+            raise ValueError('no data')
+        self._ensure()
+        return self._dev().sparse_loglik(self._kernel.nhyper, grad)
+
+    def _marg_posterior(self, X, grad=False):
+        if self._X is None:
+            prior = (np.full(X.shape[0], self._mean), self._kernel.dget(X))
+            # constant mean, stationary kernel: flat prior gradients
+            return prior + (np.zeros_like(X), np.zeros_like(X)) if grad else prior
+        self._ensure()
+        if X.shape[1] != self._X.shape[1]:
+            raise ValueError('test inputs have the wrong dimension')
+        return self._dev().sparse_posterior(X, grad)
+
+    def _full_posterior(self, X):
+        if X.shape[0] > 8192:
+            # (the m x m covariance of one device pass; GP.sample draws from it)
+            raise ValueError('the full posterior covers at most 8192 points (got %d)'
+                             % X.shape[0])
+        if self._X is None:
+            return np.full(X.shape[0], self._mean), self._kernel.get(X)
+        self._ensure()
+        if X.shape[1] != self._X.shape[1]:
+            raise ValueError('test inputs have the wrong dimension')
+        return self._dev().sparse_posterior_full(X)
+
+    def _state(self, i):
+        if self.ndata == 0:
+            return None
+        self._ensure()
+        return self._dev().sparse_get_state(self._U.shape[0])[i]

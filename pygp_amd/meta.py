@@ -38,6 +38,12 @@ class HyperEnsemble(object):
         (gpx_loglik_batch_multi / gpx_posterior_batch_multi: a host thread and handle per
         device inside the library, one RCCL all-gather, no torch.distributed); None: this
         process's device, or the ranks of `group` when torch.distributed is initialised."""
+        from .inference._sparse import SparseGP
+        if isinstance(model, SparseGP):
+            # the batch entry points evaluate EXACT GPs: their numbers would not be the
+            # sparse model's
+            raise TypeError('HyperEnsemble runs exact GPs only; %s is a sparse model'
+                            % type(model).__name__)
         self._model = model.copy()
         self._hypers = np.array(hypers, dtype=float, ndmin=2)
         if self._hypers.shape[1] != self._model.nhyper:
