@@ -260,6 +260,12 @@ int gpx_sparse_get_state(gpx_t *h, double *F1, double *F2, double *v);
  * ms[1] the gradient stage of the last gpx_sparse_loglik with dlZ (0 if none since the
  * update), ms[2] the contraction pass inside it */
 int gpx_sparse_timings(gpx_t *h, double *ms);
+/* lZ, dlZ as gpx_sparse_loglik(h, lZ, dlZ) (same bits), plus dU[p*d] row-major =
+ * d lZ / d U at the pseudo-inputs of the last gpx_sparse_update */
+int gpx_sparse_loglik_pseudo(gpx_t *h, double *lZ, double *dlZ, double *dU);
+/* HIP-event ms of the dU pass of the last gpx_sparse_loglik_pseudo (0 if none since the
+ * update) */
+int gpx_sparse_pseudo_timing(gpx_t *h, double *ms);
 
 /* ---- instrumentation ---------------------------------------------------- */
 /* per-stage GPU times (ms) of the last gpx_exact_eval / update+loglik measured

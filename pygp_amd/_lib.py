@@ -84,6 +84,8 @@ SIGNATURES = {
     'gpx_sparse_posterior_full': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     'gpx_sparse_get_state': (C.c_int, [_vp, _vp, _vp, _vp]),
     'gpx_sparse_timings': (C.c_int, [_vp, _vp]),
+    'gpx_sparse_loglik_pseudo': (C.c_int, [_vp, _vp, _vp, _vp]),
+    'gpx_sparse_pseudo_timing': (C.c_int, [_vp, _vp]),
     'gpx_loglik_batch': (C.c_int, [_vp, C.POINTER(_KSpec), _vp, _i64, C.c_int,
                                    _vp, _vp, _vp]),
     'gpx_batch_plan': (C.c_int, [_vp, _i64, C.c_int, _ip]),
@@ -414,6 +416,19 @@ class Handle(object):
         ms = np.zeros(3)
         check(self._L.gpx_sparse_timings(self._h, _ptr(ms)))
         return ms
+
+    def sparse_loglik_pseudo(self, nhyper_kernel, p, d):
+        """lZ, dlZ (as sparse_loglik with grad) and dU = d lZ / d U (p x d)."""
+        lZ = C.c_double(0)
+        dlZ, dU = np.empty(nhyper_kernel + 2), np.empty((p, d))
+        check(self._L.gpx_sparse_loglik_pseudo(self._h, C.byref(lZ), _ptr(dlZ), _ptr(dU)))
+        return lZ.value, dlZ, dU
+
+    def sparse_pseudo_timing(self):
+        """HIP-event ms of the dU pass of the last sparse_loglik_pseudo."""
+        ms = np.zeros(1)
+        check(self._L.gpx_sparse_pseudo_timing(self._h, _ptr(ms)))
+        return float(ms[0])
 
     def sparse_get_state(self, p):
         F1, F2, v = np.empty((p, p)), np.empty((p, p)), np.empty(p)

@@ -1926,6 +1926,27 @@ int gpx_sparse_timings(gpx_t *h, double *ms)
     return gpx_sparse_run_timings(h->sparse, ms);
 }
 
+int gpx_sparse_loglik_pseudo(gpx_t *h, double *lZ, double *dlZ, double *dU)
+{
+    CHECK_H(h);
+    GPX_TRY(sparse_ready(h, "gpx_sparse_loglik_pseudo"));
+    if (!lZ || !dlZ || !dU) {
+        gpx_set_error("gpx_sparse_loglik_pseudo: lZ, dlZ and dU must not be null");
+        return -1;
+    }
+    return gpx_sparse_run_loglik_pseudo(h->sparse, h->stream, h->X.as<double>(), lZ, dlZ, dU);
+}
+
+int gpx_sparse_pseudo_timing(gpx_t *h, double *ms)
+{
+    CHECK_H(h);
+    if (!ms) {
+        gpx_set_error("gpx_sparse_pseudo_timing: ms is null");
+        return -1;
+    }
+    return gpx_sparse_run_pseudo_timing(h->sparse, ms);
+}
+
 int gpx_exact_get_factor(gpx_t *h, int64_t n, double *R, double *a)
 {
     CHECK_H(h);

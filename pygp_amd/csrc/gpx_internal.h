@@ -461,6 +461,14 @@ size_t gpx_pair_grad_scratch(int n1);
 int gpx_pair_grad(hipStream_t s, const KParams &kp, const double *X1, int n1,
                   const double *X2, int n2, int d, const double *G, long long ldg,
                   double *partial, double *acc);
+// out[i][c] (+= with accumulate) sum_{j < n2} Gs_ij d k(X1_i, X2_j) / d X1_ic for i < n1,
+// c < d, Gs = G (+ G^T with sym, n1 == n2): the input gradient of the same contraction
+// (pseudo-inputs), out n1 x d row-major, fixed-order reduction over the column chunks.
+// partial: device scratch of gpx_pair_gradx_scratch(n1, n2, d) doubles
+size_t gpx_pair_gradx_scratch(int n1, int n2, int d);
+int gpx_pair_gradx(hipStream_t s, const KParams &kp, const double *X1, int n1,
+                   const double *X2, int n2, int d, const double *G, long long ldg, bool sym,
+                   double *partial, double *out, bool accumulate);
 
 // ---- sparse pseudo-input models (sparse.hip) ---------------------------------------
 // FITC / DTC on the resident data X (n x d), y: the p x p factors, the lZ terms and (on
@@ -471,6 +479,10 @@ int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, i
                           const double *X, const double *y, int n, int d, int *info);
 int gpx_sparse_run_loglik(GpxSparse *st, hipStream_t s, const double *X, double *lZ,
                           double *dlZ);
+// gpx_sparse_run_loglik with dlZ, then dU[p * d] = d lZ / d U from its adjoints
+int gpx_sparse_run_loglik_pseudo(GpxSparse *st, hipStream_t s, const double *X, double *lZ,
+                                 double *dlZ, double *dU);
+int gpx_sparse_run_pseudo_timing(GpxSparse *st, double *ms);
 int gpx_sparse_run_posterior(GpxSparse *st, hipStream_t s, const double *Xs, int64_t m,
                              double *mu, double *s2, double *dmu, double *ds2, double *Sigma);
 int gpx_sparse_run_state(GpxSparse *st, hipStream_t s, double *F1, double *F2, double *v);

@@ -1566,6 +1566,174 @@ int gpx_pair_grad(hipStream_t s, const KParams &kp, const double *X1, int n1,
     return 0;
 }
 
+// ---- weighted input gradient over a rectangular pair set (pseudo-inputs, sparse.hip) --
+// part[c0][i][c] = sum_{j in chunk c0} Gs_ij d k(x1_i, x2_j) / d x1_ic, Gs_ij = G[i][j]
+// (+ G[j][i] with sym: the (U, U) set, where x1_i sits in both arguments of k). The grid,
+// the chunks and the column walk are those of pair_grad_kernel; each wave owns 16 rows of
+// the 64-row block but carries R = 32 / DMAX of them at a time (R * DMAX = 32 accumulators,
+// the same at every DMAX), re-walking the chunk's columns for the next R. Every part adds
+// into the same accumulators: fac * dk_p / dx1 = fac * cf (x2 - x1) / scale^2 from direct
+// differences (part_grady with the sign of x1), the product rule through group_factor.
+// Rows and columns beyond n1 / n2 weigh exactly 0; one wave reduction per row and chunk.
+template <int DMAX>
+__global__ __launch_bounds__(256) void pair_gradx_kernel(
+    KParams kp, const double *__restrict__ X1, int n1, const double *__restrict__ X2, int n2,
+    int d, const double *__restrict__ G, long long ldg, int sym, double *__restrict__ partial,
+    int rows)
+{
+    constexpr int R = 32 / DMAX;
+    const int C = gridDim.x;
+    const int bi = blockIdx.y, c0 = blockIdx.x;
+    const int T2 = (n2 + KT - 1) / KT;
+    __shared__ double xi_s[KT][DMAX + 1];
+    __shared__ double is_s[GPX_MAX_PARTS][DMAX];     // 1 / scale, 0 beyond d
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, ig = tid >> 6;
+    const int i0 = bi * KT;
+    for (int e = tid; e < KT * DMAX; e += 256) {
+        const int r = e / DMAX, c = e - r * DMAX;
+        const int gi = min(i0 + r, n1 - 1);
+        xi_s[r][c] = c < d ? X1[(size_t)gi * d + c] : 0.0;
+    }
+    for (int e = tid; e < kp.nparts * DMAX; e += 256) {
+        const int q = e / DMAX, c = e - q * DMAX;
+        is_s[q][c] = c < d ? 1.0 / kp.part[q].scale[c] : 0.0;
+    }
+    __syncthreads();
+    for (int r0 = 0; r0 < 16; r0 += R) {
+        double acc[R][DMAX];
+#pragma unroll
+        for (int rr = 0; rr < R; ++rr)
+#pragma unroll
+            for (int c = 0; c < DMAX; ++c) acc[rr][c] = 0.0;
+        for (int bj = c0; bj < T2; bj += C) {
+            const int gj = bj * KT + lane;
+            const int cj = min(gj, n2 - 1);
+            double xj[DMAX];
+#pragma unroll
+            for (int c = 0; c < DMAX; ++c) xj[c] = c < d ? X2[(size_t)cj * d + c] : 0.0;
+#pragma unroll
+            for (int rr = 0; rr < R; ++rr) {
+                const int li = ig * 16 + r0 + rr;
+                const int gi = i0 + li;
+                double t = 0.0;
+                if (gi < n1 && gj < n2) {
+                    t = G[(size_t)gi * ldg + gj];
+                    if (sym) t += G[(size_t)gj * ldg + gi];
+                }
+                if (t == 0.0) continue;
+                const double *xi = xi_s[li];
+                for (int p = 0; p < kp.nparts; ++p) {
+                    const KPart &part = kp.part[p];
+                    double tp = t;
+                    if (kp.nprod != 0)
+                        tp *= group_factor(kp, p, X1 + (size_t)gi * d, X2 + (size_t)cj * d, d);
+                    if (part.kind == GPX_PERIODIC) {             // d == 1 (periodic.py:84-97)
+                        const double D = (xj[0] - xi[0]) * M_PI / part.period;
+                        const double sn = sin(D) / part.ell;
+                        const double K = part.sf2 * exp(-2 * (sn * sn));
+                        acc[rr][0] += tp * (2 * M_PI / (part.ell * part.ell) / part.period * K *
+                                            sin(2 * D));
+                        continue;
+                    }
+                    const double *is = is_s[p];
+                    double u[DMAX], D2 = 0.0;
+#pragma unroll
+                    for (int c = 0; c < DMAX; ++c) {
+                        u[c] = (xj[c] - xi[c]) * is[c];
+                        D2 += u[c] * u[c];
+                    }
+                    double cf;
+                    if (part.kind == GPX_SE) {
+                        cf = exp(part.two_logsf - D2 / 2);
+                    } else if (part.kind == GPX_RQ) {
+                        const double E = 1 + 0.5 * D2 / part.alpha;
+                        cf = part.sf2 * pow(E, -part.alpha) / E;
+                    } else {
+                        const double r = sqrt(D2);
+                        const double S = exp(part.two_logsf - r);
+                        const double df = part.kind == GPX_MATERN1 ? 1.0
+                                          : (part.kind == GPX_MATERN3 ? r : r * (1 + r) / 3.);
+                        cf = r < 1e-12 ? 0.0 : S * df / r;
+                    }
+                    const double w = tp * cf;
+#pragma unroll
+                    for (int c = 0; c < DMAX; ++c) acc[rr][c] += w * (u[c] * is[c]);
+                }
+            }
+        }
+        // one wave reduction per row of the group; lane 0 writes the chunk's partial sums
+#pragma unroll
+        for (int rr = 0; rr < R; ++rr) {
+            double *po = partial + ((size_t)c0 * rows + i0 + ig * 16 + r0 + rr) * d;
+#pragma unroll
+            for (int c = 0; c < DMAX; ++c)
+                if (c < d) {
+                    const double v = wave_sum(acc[rr][c]);
+                    if (lane == 0) po[c] = v;
+                }
+        }
+    }
+}
+
+// out[i][c] (+)= sum_{k < C} part[k][i][c], k ascending: the chunks' order fixes the bits
+__global__ __launch_bounds__(256) void pair_gradx_reduce_kernel(
+    const double *__restrict__ partial, int C, int rows, int n1, int d, int accumulate,
+    double *__restrict__ out)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n1 * d) return;
+    double v = 0.0;
+    for (int k = 0; k < C; ++k) v += partial[(size_t)k * rows * d + e];
+    out[e] = accumulate ? out[e] + v : v;
+}
+
+// chunks of gpx_pair_gradx: the rule of gpx_pair_grad (a function of the shape only)
+static int pair_chunks(int n1, int n2)
+{
+    const int T1 = (n1 + KT - 1) / KT, T2 = (n2 + KT - 1) / KT;
+    return std::max(1, std::min(T2, std::min(GPX_PAIR_CHUNKS_MAX, 2048 / T1)));
+}
+
+size_t gpx_pair_gradx_scratch(int n1, int n2, int d)
+{
+    return (size_t)pair_chunks(n1, n2) * ((n1 + KT - 1) / KT * KT) * d;
+}
+
+int gpx_pair_gradx(hipStream_t s, const KParams &kp, const double *X1, int n1,
+                   const double *X2, int n2, int d, const double *G, long long ldg, bool sym,
+                   double *partial, double *out, bool accumulate)
+{
+    for (int p = 0; p < kp.nparts; ++p)
+        if (kp.part[p].kind == GPX_PERIODIC && d != 1) {
+            gpx_set_error("input gradients of the periodic kernel need ndim == 1");
+            return -1;
+        }
+    if (d < 1 || d > GPX_MAX_DIM || n1 < 1 || n2 < 1 || (sym && n1 != n2)) {
+        gpx_set_error("pair_gradx: bad shape n1=%d n2=%d d=%d", n1, n2, d);
+        return -1;
+    }
+    const int T1 = (n1 + KT - 1) / KT;
+    const int C = pair_chunks(n1, n2);
+    const int rows = T1 * KT;
+    dim3 grid(C, T1);
+    GPX_TRY(gpx_test_jitter(s));
+    if (d <= 8)
+        hipLaunchKernelGGL(pair_gradx_kernel<8>, grid, dim3(256), 0, s, kp, X1, n1, X2, n2, d,
+                           G, ldg, sym ? 1 : 0, partial, rows);
+    else if (d <= 16)
+        hipLaunchKernelGGL(pair_gradx_kernel<16>, grid, dim3(256), 0, s, kp, X1, n1, X2, n2, d,
+                           G, ldg, sym ? 1 : 0, partial, rows);
+    else
+        hipLaunchKernelGGL(pair_gradx_kernel<32>, grid, dim3(256), 0, s, kp, X1, n1, X2, n2, d,
+                           G, ldg, sym ? 1 : 0, partial, rows);
+    GPX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(pair_gradx_reduce_kernel, dim3((n1 * d + 255) / 256), dim3(256), 0, s,
+                       partial, C, rows, n1, d, accumulate ? 1 : 0, out);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
 // ---- input gradients -----------------------------------------------------------
 // d k(x1, x2) / d x2 ("grady"; gradx is its negative) for one part, accumulated
 // into g[0..d). SE: K (u1-u2)/ell (se.py:76-86); Matern: M (u1-u2)/ell with

@@ -78,10 +78,14 @@ struct GpxSparse {
     SpBuf ell, rt, beta, gam, u, alpha, wv, vv, bq, sq, e;
     SpBuf part, scal, acc_uu, acc_ux, pg_part, split, Cm, CC, BEB, Guu, R2;
     SpBuf Xs, Ks, Q1, Q2, dKc, dK, dQ1, dQ2, mu, s2, dmu, ds2, Sig;
+    // the pseudo-input gradient (gpx_sparse_run_loglik_pseudo only): chunk partials, dU
+    SpBuf px_part, dU;
     double hsc[S_COUNT];
-    // HIP events around the last update, gradient stage and contraction pass (ms)
-    hipEvent_t ev[5] = {};
+    // HIP events around the last update, gradient stage and contraction pass, then the dU
+    // pass (ms)
+    hipEvent_t ev[7] = {};
     double ms[3] = {0, 0, 0};
+    double ms_pseudo = 0;
 };
 
 static int sp_event(GpxSparse *st, hipStream_t s, int i)
@@ -507,7 +511,7 @@ void gpx_sparse_destroy(GpxSparse *st)
                      &st->part, &st->scal, &st->acc_uu, &st->acc_ux, &st->pg_part, &st->split,
                      &st->Cm, &st->CC, &st->BEB, &st->Guu, &st->R2, &st->Xs, &st->Ks, &st->Q1,
                      &st->Q2, &st->dKc, &st->dK, &st->dQ1, &st->dQ2, &st->mu, &st->s2,
-                     &st->dmu, &st->ds2, &st->Sig};
+                     &st->dmu, &st->ds2, &st->Sig, &st->px_part, &st->dU};
     for (SpBuf *b : bufs) b->release();
     for (hipEvent_t e : st->ev)
         if (e) (void)hipEventDestroy(e);
@@ -613,6 +617,7 @@ int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, i
     GPX_HIP(hipStreamSynchronize(s));
     st->ms[0] = sp_elapsed(st, 0, 1);
     st->ms[1] = st->ms[2] = 0.0;
+    st->ms_pseudo = 0.0;
     st->ready = true;
     return 0;
 }
@@ -758,6 +763,40 @@ int gpx_sparse_run_loglik(GpxSparse *st, hipStream_t s, const double *X, double 
         for (int k = 0; k < nh; ++k) dlZ[1 + k] = auu[1 + k] + aux[1 + k];
         dlZ[1 + nh] = h[S_ALPHA] / sqrt(sn2);
     }
+    return 0;
+}
+
+// The gradient stage above leaves G_uu (Guu, ld pp) and G_ux (P4, ld np) behind; neither kxx
+// nor su2 depends on U, so dlZ/dU_ic = sum_j (G_uu[i][j] + G_uu[j][i]) dk(u_i, u_j)/du_ic
+// + sum_j G_ux[i][j] dk(u_i, x_j)/du_ic: two more contractions of the same adjoints
+// (gpx_pair_gradx), on the same stream. Scratch is reserved here, on first use.
+int gpx_sparse_run_loglik_pseudo(GpxSparse *st, hipStream_t s, const double *X, double *lZ,
+                                 double *dlZ, double *dU)
+{
+    GPX_TRY(gpx_sparse_run_loglik(st, s, X, lZ, dlZ));
+    const int p = st->p, pp = st->pp, n = st->n, d = st->d;
+    GPX_TRY(st->px_part.reserve(std::max(gpx_pair_gradx_scratch(p, p, d),
+                                         gpx_pair_gradx_scratch(p, n, d)) * 8));
+    GPX_TRY(st->dU.reserve((size_t)p * d * 8));
+    GPX_TRY(sp_event(st, s, 5));
+    GPX_TRY(gpx_pair_gradx(s, st->kp, st->U.d(), p, st->U.d(), p, d, st->Guu.d(), pp, true,
+                           st->px_part.d(), st->dU.d(), false));
+    GPX_TRY(gpx_pair_gradx(s, st->kp, st->U.d(), p, X, n, d, st->P4.d(), (long long)st->np,
+                           false, st->px_part.d(), st->dU.d(), true));
+    GPX_TRY(sp_event(st, s, 6));
+    GPX_HIP(hipMemcpyAsync(dU, st->dU.p, (size_t)p * d * 8, hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipStreamSynchronize(s));
+    st->ms_pseudo = sp_elapsed(st, 5, 6);
+    return 0;
+}
+
+int gpx_sparse_run_pseudo_timing(GpxSparse *st, double *ms)
+{
+    if (!st) {
+        gpx_set_error("gpx_sparse_pseudo_timing: no sparse model");
+        return -1;
+    }
+    *ms = st->ms_pseudo;
     return 0;
 }
 

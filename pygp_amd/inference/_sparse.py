@@ -64,6 +64,18 @@ class SparseGP(GP):
         """The pseudo-input points."""
         return self._U
 
+    def set_pseudoinputs(self, U):
+        """Move the pseudo-inputs to U (p x d; p may change). The resident data stays on
+        the device; the model refactors on its next use."""
+        U = np.array(U, ndmin=2, dtype=float, copy=True)
+        ndim = self._U.shape[1] if self._X is None else self._X.shape[1]
+        if U.ndim != 2 or U.shape[0] < 1 or U.shape[1] != ndim:
+            raise ValueError('pseudo-inputs have the wrong dimension')
+        if not np.all(np.isfinite(U)):
+            raise ValueError('array must not contain infs or NaNs')
+        self._U = U
+        self._factored = False
+
     @classmethod
     def from_gp(cls, gp, U=None):
         if U is None:
@@ -102,10 +114,14 @@ class SparseGP(GP):
         if self.ndata > 0 and not self._factored:
             self._update()
 
-    def loglikelihood(self, grad=False):
+    def loglikelihood(self, grad=False, pseudoinputs=False):
+        """lZ (and dlZ with grad); with pseudoinputs, (lZ, dlZ, dU) where dU = d lZ / d U
+        has the shape of the pseudo-inputs."""
         if self.ndata == 0:
             raise ValueError('no data')
         self._ensure()
+        if pseudoinputs:
+            return self._dev().sparse_loglik_pseudo(self._kernel.nhyper, *self._U.shape)
         return self._dev().sparse_loglik(self._kernel.nhyper, grad)
 
     def _marg_posterior(self, X, grad=False):

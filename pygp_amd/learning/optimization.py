@@ -16,10 +16,13 @@ from ..utils.models import get_params
 __all__ = ['optimize']
 
 
-def optimize(gp, priors=None):
+def optimize(gp, priors=None, pseudoinputs=False):
     """Maximise the marginal likelihood over the hypers of `gp` in place.
     priors: {name: None} freezes the named block (the only prior form the
-    reference supports, optimization.py:47-52)."""
+    reference supports, optimization.py:47-52). pseudoinputs: also move the
+    pseudo-inputs of a sparse model (FITC, DTC), jointly with the free hypers."""
+    if pseudoinputs:
+        return _optimize_pseudo(gp, priors)
     start = gp.get_hyper()
     free = np.ones(gp.nhyper, dtype=bool)
     blocks = dict((name, block) for name, block, _ in get_params(gp))
@@ -39,3 +42,36 @@ def optimize(gp, priors=None):
     final = start.copy()
     final[free] = x
     gp.set_hyper(final)
+
+
+def _optimize_pseudo(gp, priors):
+    """L-BFGS over [free hypers, U.ravel()]; one loglikelihood(True, pseudoinputs=True)
+    per objective call."""
+    if not hasattr(gp, 'set_pseudoinputs'):
+        raise ValueError('pseudo-input optimisation needs a sparse model (FITC, DTC)')
+    start = gp.get_hyper()
+    free = np.ones(gp.nhyper, dtype=bool)
+    blocks = dict((name, block) for name, block, _ in get_params(gp))
+    for name, prior in (priors or {}).items():
+        if prior is not None:
+            raise NotImplementedError('only fixing priors (None) are supported')
+        free[blocks[name]] = False
+    shape = gp.pseudoinputs.shape
+    nfree = int(free.sum())
+
+    def unpack(x):
+        hyper = start.copy()
+        hyper[free] = x[:nfree]
+        return hyper, x[nfree:].reshape(shape)
+
+    def negative_loglik(x):
+        hyper, U = unpack(x)
+        gp.set_pseudoinputs(U)           # first: set_hyper then factors once, with this U
+        gp.set_hyper(hyper)
+        lZ, dlZ, dU = gp.loglikelihood(True, pseudoinputs=True)
+        return -lZ, -np.r_[dlZ[free], dU.ravel()]
+
+    x, _, _ = so.fmin_l_bfgs_b(negative_loglik, np.r_[start[free], gp.pseudoinputs.ravel()])
+    hyper, U = unpack(x)
+    gp.set_pseudoinputs(U)
+    gp.set_hyper(hyper)

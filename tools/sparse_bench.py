@@ -15,7 +15,11 @@ The contraction pass's GB/s is the 8 p N bytes of G_ux it reads once, over its m
 time (its X reads are 8 N d bytes per 64-row block of U, mostly from cache). At p = 2048
 N is 2^20 - 128: p_pad N_pad must stay below 2^31. A host NumPy fp64 evaluation
 (tests/sparse_ref.py) at N = 16384, p = 256 is timed with perf_counter for context.
-usage: sparse_bench.py [--reps R] [--warmup W] [--quick]"""
+
+--pseudo also times the pseudo-input gradient pass (gpx_sparse_pseudo_timing: the two
+contractions of G_uu and G_ux with dk/du, median of 3 after a warm-up) and adds pseudo_ms,
+its pairs/s over the p N + p^2 pairs and its GB/s over the 8 p N bytes of G_ux it reads.
+usage: sparse_bench.py [--reps R] [--warmup W] [--quick] [--pseudo]"""
 import argparse
 import json
 import os
@@ -37,6 +41,7 @@ def main():
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--quick', action='store_true', help='N = 2^17 (a smoke run)')
+    ap.add_argument('--pseudo', action='store_true', help='also time the dU pass')
     a = ap.parse_args()
     import pygp_amd
     from pygp_amd import _lib
@@ -85,6 +90,15 @@ def main():
             grad_stage_tflops_model=f_grad / (t_g - t_c) * 1e-12,
             grad_stage_frac_peak_model=f_grad / (t_g - t_c) * 1e-12 / PEAK_TFLOPS,
             contraction_ms=t_c * 1e3, contraction_gbs=g_bytes / t_c * 1e-9))
+        if a.pseudo:
+            def pseudo():
+                dev.sparse_loglik_pseudo(kern.nhyper, p, D)
+                return dev.sparse_pseudo_timing()
+
+            pseudo()
+            t_p = statistics.median(pseudo() for _ in range(3)) * 1e-3
+            points[-1].update(pseudo_ms=t_p * 1e3, pseudo_pairs_per_s=(p * N + p * p) / t_p,
+                              pseudo_gbs=g_bytes / t_p * 1e-9)
     # host fp64 context
     import sparse_ref as sr
     from oracle import gp_oracle as orc
