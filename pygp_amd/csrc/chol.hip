@@ -11,10 +11,8 @@
 //          first and F_k+1 starts on a high-priority stream while `bulk` is still
 //          busy with the rest of step k: the latency-bound chain of diagonal blocks
 //          hides under the MFMA-bound products of ONE evaluation (the optimize()
-//          pattern). Default: every stream over every CU, the two small products
-//          between F_k and F_k+1 on the high-priority stream itself (fast chain);
-//          GPX_RESERVE_CUS=32: the CU partition of the first half of round 2
-//          (products on CU-masked streams, diagonal blocks on the reserved CUs).
+//          pattern). Every stream runs over every CU; the two small products
+//          between F_k and F_k+1 run on the high-priority stream itself (fast chain).
 //          With GPX_POTRF_W / _KINV the sweep also builds R^-1 and (R^T R)^-1 block
 //          column by block column (inverse_column, on a third stream): the
 //          shrinking trailing update and the growing inverse work add up to about
@@ -179,11 +177,10 @@ static GemmArgs mk(const double *A, int lda, const double *B, int ldb, double *C
 // C -= P^T P on the upper tiles of the n x n block C, P = k x n (the engine runs whole
 // rounds of 128-tiles and the remainder as 64-tiles)
 static int syrk_upper(hipStream_t s, const double *P, int ldp, double *C, int ldc, int n,
-                      int k, double *C2, int slots = 0)
+                      int k, double *C2)
 {
     GemmArgs g = mk(P, ldp, P, ldp, C, ldc, n, n, k, -1.0, 1.0, GEMM_UPPER_ONLY);
     g.C2 = C2;
-    g.slots = slots;
     return gpx_gemm(s, 1, 0, g);
 }
 
@@ -651,18 +648,12 @@ int gpx_potrf(hipStream_t s, const DenseWs &w, int mode, bool offdiag_staged)
     // look-ahead needs the extra streams and two events per block
     const bool ahead = w.crit && w.bulk && w.aux && w.events && nb <= GPX_MAX_BLOCKS &&
                        w.batch <= 1;
-    // Only with a CU partition (GPX_RESERVE_CUS > 0; w.crit_only is null otherwise):
-    // with the inverse in the same sweep every diagonal block above np = 8192 hides
-    // completely under the products of its step and gets the reserved CUs and nothing
-    // else (strict partition, 1.7 ms faster at N = 16384 than "anywhere, first in
-    // line"). Otherwise the diagonal blocks may run anywhere.
-    const bool strict = ahead && w.crit_only && mode != GPX_POTRF_R && w.np > 8192;
     static const int overlap_env = env_int("GPX_OVERLAP_NOSPLIT", 1);
     struct OverlapScope {
         explicit OverlapScope(int v) { tl_overlap = v; }
         ~OverlapScope() { tl_overlap = 0; }
     } overlap_scope(ahead && overlap_env ? 1 : 0);
-    hipStream_t crit = ahead ? (strict ? w.crit_only : w.crit) : s;
+    hipStream_t crit = ahead ? w.crit : s;
     hipStream_t bulk = ahead ? w.bulk : s;
     // The inverse columns run on a third stream (same CUs as `bulk`, low priority) beside the
     // trailing updates of their step: the two launch sequences fill each other's
@@ -671,7 +662,6 @@ int gpx_potrf(hipStream_t s, const DenseWs &w, int mode, bool offdiag_staged)
     // backlog ending up serial). GPX_AUX=0: they follow the trailing update on `bulk`.
     static const int aux_on = env_int("GPX_AUX", 1);
     hipStream_t aux = ahead && aux_on ? w.aux : bulk;
-    const int slots = ahead ? w.bulk_slots : 0;
     hipEvent_t *F = w.events, *D = w.events + GPX_MAX_BLOCKS;
     hipEvent_t evJoin = ahead ? w.events[4 * GPX_MAX_BLOCKS] : nullptr;
     hipEvent_t evAux = ahead ? w.events[4 * GPX_MAX_BLOCKS + 1] : nullptr;
@@ -679,15 +669,15 @@ int gpx_potrf(hipStream_t s, const DenseWs &w, int mode, bool offdiag_staged)
     // the caller goes on (vector kernels that need R and R^-1 only) while the last K^-1
     // update is still running
     const bool defer = ahead && w.defer_kinv && mode == GPX_POTRF_KINV && aux != bulk;
-    // Without the strict partition the diagonal blocks are (part of) the critical path,
-    // and on `bulk` the two small products between F_k and F_k+1 -- the block column of
-    // the row panel that the next diagonal block needs and that block's update -- queued
-    // behind the far trailing update of step k-1 (N = 8192: 0.5-0.8 ms between two 0.45-ms
-    // diagonal blocks). Fast chain: they run on `crit` itself, right behind F_k (high
-    // priority, every CU), the far update of a step hands over its first diagonal block
-    // (event TD) before it goes on, and `bulk` keeps the rest.
+    // The diagonal blocks are (part of) the critical path, and on `bulk` the two small
+    // products between F_k and F_k+1 -- the block column of the row panel that the next
+    // diagonal block needs and that block's update -- queued behind the far trailing update
+    // of step k-1 (N = 8192: 0.5-0.8 ms between two 0.45-ms diagonal blocks). Fast chain:
+    // they run on `crit` itself, right behind F_k (high priority, every CU), the far update
+    // of a step hands over its first diagonal block (event TD) before it goes on, and
+    // `bulk` keeps the rest.
     static const int fast_env = env_int("GPX_FASTCHAIN", 1);
-    const bool fast = ahead && !strict && fast_env != 0;
+    const bool fast = ahead && fast_env != 0;
     hipEvent_t *G = w.events + 2 * GPX_MAX_BLOCKS;       // row k+1 carries update k
     hipEvent_t *TD = w.events + 3 * GPX_MAX_BLOCKS;      // block (k+2,k+2) carries update k
     bool lead = false;
@@ -747,7 +737,6 @@ int gpx_potrf(hipStream_t s, const DenseWs &w, int mode, bool offdiag_staged)
                 GemmArgs g = mk(w.W + okk, ld, w.Kinv + ok1 + n1, ld, w.A + ok1 + n1, ld, nk,
                                 rest - n1, nk, 1.0, 0.0, GEMM_KHI_M);
                 g.order = env_int("GPX_ORD_R12", 1);
-                g.slots = slots;
                 GPX_TRY(gpx_gemm(bulk, 1, 0, g));
             }
             GPX_EV(hipStreamWaitEvent(bulk, D[k + 1], 0));       // R[k,k+1] is in A
@@ -759,14 +748,12 @@ int gpx_potrf(hipStream_t s, const DenseWs &w, int mode, bool offdiag_staged)
                 {
                     GemmArgs g = mk(w.A + ok1, ld, w.A + ok2, ld, w.Kinv + o12, ld, n1, rest2,
                                     nk, -1.0, 1.0, 0);
-                    g.slots = slots;
                     GPX_TRY(gpx_gemm(bulk, 1, 0, g));
                 }
                 GPX_TRY(gate_bump(bulk, w, 0));                  // row k+1 carries update k
                 GPX_EV(hipEventRecord(G[k], bulk));
                 // ... and the trailing blocks, the diagonal block of step k+2 first
-                GPX_TRY(syrk_upper(bulk, w.A + ok2, ld, w.A + o22, ld, n2, nk, w.Kinv + o22,
-                                   slots));
+                GPX_TRY(syrk_upper(bulk, w.A + ok2, ld, w.A + o22, ld, n2, nk, w.Kinv + o22));
                 GPX_TRY(gate_bump(bulk, w, 1));                  // block (k+2, k+2) too
                 GPX_EV(hipEventRecord(TD[k], bulk));
                 if (k + 3 < nb) {
@@ -775,10 +762,9 @@ int gpx_potrf(hipStream_t s, const DenseWs &w, int mode, bool offdiag_staged)
                                  o33 = (size_t)o3 * ld + o3;
                     GemmArgs g = mk(w.A + ok2, ld, w.A + ok3, ld, w.Kinv + o23, ld, n2, rest3, nk,
                                     -1.0, 1.0, 0);
-                    g.slots = slots;
                     GPX_TRY(gpx_gemm(bulk, 1, 0, g));
                     GPX_TRY(syrk_upper(bulk, w.A + ok3, ld, w.A + o33, ld, rest3, nk,
-                                       w.Kinv + o33, slots));
+                                       w.Kinv + o33));
                 }
             }
         } else if (k + 1 < nb) {
@@ -793,14 +779,12 @@ int gpx_potrf(hipStream_t s, const DenseWs &w, int mode, bool offdiag_staged)
                 GemmArgs g = mk(w.W + okk, ld, w.Kinv + ok1 + skip, ld, w.A + ok1 + skip, ld, nk,
                                 rest - skip, nk, 1.0, 0.0, GEMM_KHI_M);
                 g.order = env_int("GPX_ORD_R12", 1);
-                g.slots = slots;
                 GPX_TRY(gpx_gemm(bulk, 1, 0, g));
             }
             // update k of the next diagonal block first: F_k+1 can start
             const size_t o11 = (size_t)o1 * ld + o1;
             if (!wide)
-                GPX_TRY(syrk_upper(bulk, w.A + ok1, ld, w.A + o11, ld, n1, nk, w.Kinv + o11,
-                                   slots));
+                GPX_TRY(syrk_upper(bulk, w.A + ok1, ld, w.A + o11, ld, n1, nk, w.Kinv + o11));
             if (ahead) GPX_EV(hipEventRecord(D[k + 1], bulk));
             if (k + 2 < nb) {
                 const int o2 = bl.off(k + 2), rest2 = w.np - o2;
@@ -811,13 +795,11 @@ int gpx_potrf(hipStream_t s, const DenseWs &w, int mode, bool offdiag_staged)
                 {
                     GemmArgs g = mk(w.A + ok1, ld, w.A + ok2, ld, w.Kinv + o12, ld, n1, rest2,
                                     nk, -1.0, 1.0, 0);
-                    g.slots = slots;
                     GPX_TRY(gpx_gemm(bulk, 1, 0, g));
                 }
                 GPX_TRY(gate_bump(bulk, w, 0));
                 // ... and the trailing blocks: diagonal tiles in A, the others in Kinv
-                GPX_TRY(syrk_upper(bulk, w.A + ok2, ld, w.A + o22, ld, rest2, nk, w.Kinv + o22,
-                                   slots));
+                GPX_TRY(syrk_upper(bulk, w.A + ok2, ld, w.A + o22, ld, rest2, nk, w.Kinv + o22));
                 GPX_TRY(gate_bump(bulk, w, 1));
             }
         }

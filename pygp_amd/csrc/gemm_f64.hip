@@ -290,6 +290,10 @@ static int tile_order(int device)
     return xcd_env >= 0 ? xcd_env : (gpx_gemm_concurrent(device) > 0 ? 0 : 1);
 }
 
+// workgroup slots of the GPU (2 per CU): equal-k launches run whole rounds of 128-tiles
+// and the rest as 64-tiles
+#define GEMM_SLOTS 512
+
 // part 0: every live tile. Equal-k launches that do not fill whole rounds of `slots`
 // workgroups are cut in two: part 1 = the first floor(L / slots) * slots 128-tiles,
 // part 2 = the remaining 128-tiles as 64-tiles (tile must be 64 then; a quarter of the
@@ -450,7 +454,7 @@ static int launch(hipStream_t s, const GemmArgs &g0, const LaunchCtx &lc, int pa
     if (part) {
         TileList tl;
         GPX_TRY(tile_list(lc.device, lc.xcd_order, G::TILE, g.M / 128, g.N / 128, g.K, g.flags,
-                          &tl, part, g.slots > 0 ? g.slots : 512));
+                          &tl, part, GEMM_SLOTS));
         if (tl.count == 0) return 0;
         g.tiles = tl.dev;
         grid = dim3(tl.count, 1, 1);
@@ -586,7 +590,7 @@ int gpx_gemm(hipStream_t s, int ta, int tb, const GemmArgs &g)
                 work += len;
                 longest = std::max(longest, len);
             }
-        const double S = g.slots > 0 ? g.slots : 512;
+        const double S = GEMM_SLOTS;
         const double t128 = std::max((double)longest, work / S);
         const double t64 = std::max(longest / 4.0, 1.08 * work / S);
         if (t64 < 0.9 * t128) tile = 64;
@@ -598,7 +602,7 @@ int gpx_gemm(hipStream_t s, int ta, int tb, const GemmArgs &g)
     const int kstruct = g.flags & (GEMM_KLO_M | GEMM_KHI_M | GEMM_KLO_N | GEMM_KHI_N);
     if (split_on && !g.overlap && g.tile == 0 && tile == 128 && !kstruct && g.use_lists &&
         g.batch <= 1 && g.kchunk == 0 && !g.waves && !big_cfg && !small_cfg) {
-        const long long S = g.slots > 0 ? g.slots : 512;
+        const long long S = GEMM_SLOTS;
         long long L = (long long)(g.M / 128) * (g.N / 128);
         if (g.flags & GEMM_UPPER_ONLY) {
             L = 0;

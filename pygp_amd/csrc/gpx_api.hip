@@ -99,8 +99,7 @@ struct gpx_ctx {
     long sparse_version = -1;
     // look-ahead of the factorisation (chol.hip): diagonal blocks on a high-priority
     // stream, the left half of the inverse tree on a low-priority one
-    hipStream_t crit = nullptr, crit_only = nullptr, aux = nullptr, bulk = nullptr;
-    int bulk_slots = 0;
+    hipStream_t crit = nullptr, aux = nullptr, bulk = nullptr;
     bool stream_borrowed = false;  // batch context: `stream` belongs to the device's pool
     bool bulk_borrowed = false;    // ... and `bulk` is that stream
     std::vector<hipStream_t> chain_streams;   // ... and the streams of the contexts before it
@@ -136,10 +135,8 @@ struct gpx_ctx {
         // found by tools/soak_threads.py big)
         if (crit && (!in_batch || batch_la)) {
             w.crit = crit;
-            w.crit_only = crit_only;
             w.aux = aux;
             w.bulk = bulk;
-            w.bulk_slots = bulk_slots;
             w.events = const_cast<hipEvent_t *>(la_events);
         }
         return w;
@@ -242,91 +239,27 @@ __global__ void hold_kernel(long long ticks)
 // by side if those streams sit on different hardware queues: the runtime hands a stream
 // the least-used of its few queues when the stream is first needed, kernels of two
 // streams that share a queue run one after the other, and which streams share depends on
-// everything the process created and used before. Round 2 met this as "194 or 240
-// evals/s for 64 thetas at N = 8192, depending on whether an unused CU-masked queue had
-// been created in front of a twin's stream"; round 3 first fixed the creation order of a
-// per-device pool and still found 188 instead of 250 evals/s whenever single evaluations
-// (which use the look-ahead streams) had run on the handle before its first batch
-// (tools/r03_exp38.sh): the second member then shared the first member's queue.
-// Now the layout is MEASURED instead of arranged: the twin streams of a device still come
-// from one pool, created once, and a context takes the first pool stream that does not
-// share a queue with any stream of the contexts before it in its chain. The probe: a
-// kernel that spins for 0.3 ms on one stream, an empty kernel on the other -- the empty
-// one ends first unless it had to queue behind the spinner. A few probes of 0.3 ms, once
-// per batch context. (Two handles batching on one device from two threads at the same
-// time may pick the same pool streams: correct, their members then queue behind each
+// everything the process created and used before (round 3: 188 instead of 250 evals/s for
+// 64 thetas at N = 8192 whenever single evaluations, which use the look-ahead streams, had
+// run on the handle before its first batch: the second member then shared the first
+// member's queue). So the layout is MEASURED instead of arranged: the twin streams of a
+// device come from one pool, created once, and a context takes the first pool stream that
+// does not share a queue with any stream of the contexts before it in its chain. The
+// probe: a kernel that spins for 0.3 ms on one stream, an empty kernel on the other -- the
+// empty one ends first unless it had to queue behind the spinner. A few probes of 0.3 ms,
+// once per batch context. (Two handles batching on one device from two threads at the
+// same time may pick the same pool streams: correct, their members then queue behind each
 // other.) A second probe (stream_pair_cost below) finds the pairs of queues that are not
-// shared but run badly side by side (GPX_TWIN_LOG=1 prints the costs seen), and the pool's
-// streams have hardware queues of their own (twin_pool_make), so that a good one exists
-// whatever the process did before. Measured and dropped: making every queue up front, in one order, at handle
-// creation (this stream, the pool, each touched once): uniform -- and uniformly worse, the
-// streams made later then share queues with the touched ones (64 thetas 202-207 evals/s
-// in every order, one evaluation at N = 4096 2.42 -> 2.82 ms, the metric batch 14.4 ->
-// 11.8 evals/s).
-// ---- CU-masked streams are never destroyed ------------------------------------------
-// hipStreamDestroy of a stream made with hipExtStreamCreateWithCUMask did not return in 3 of
-// about 90 teardowns at the end of round 4 (always in the teardown of a handle, never in a
-// kernel). Every masked stream the library makes -- the opt-in CU
-// partition GPX_RESERVE_CUS, the opt-in pool GPX_TWIN_MASKED -- therefore comes from a
-// per-device cache that lives as long as the process: a handle that goes away hands its
-// masked streams back (synchronised, idle), the next handle that asks for the same mask takes
-// them over, and nothing ever calls hipStreamDestroy on one. The runtime reclaims the queues
-// at process exit.
-struct MaskedStream {
-    hipStream_t s;
-    uint32_t mask[32];
-    bool busy;
-};
-static std::mutex g_masked_mu;
-static std::vector<MaskedStream> g_masked[64];
-
-static int masked_stream_acquire(int device, int ncu, const uint32_t *mask, hipStream_t *out)
-{
-    if (device < 0 || device >= 64) {
-        gpx_set_error("masked stream: device %d", device);
-        return -1;
-    }
-    std::lock_guard<std::mutex> lock(g_masked_mu);
-    for (MaskedStream &m : g_masked[device])
-        if (!m.busy && memcmp(m.mask, mask, sizeof m.mask) == 0) {
-            m.busy = true;
-            *out = m.s;
-            return 0;
-        }
-    MaskedStream m;
-    memcpy(m.mask, mask, sizeof m.mask);
-    m.busy = true;
-    GPX_HIP(hipExtStreamCreateWithCUMask(&m.s, (uint32_t)((ncu + 31) / 32), mask));
-    g_masked[device].push_back(m);
-    *out = m.s;
-    return 0;
-}
-
-// back to the cache (true), or not one of the cached streams (false: the caller destroys it)
-static bool masked_stream_release(int device, hipStream_t s)
-{
-    if (device < 0 || device >= 64 || !s) return false;
-    std::lock_guard<std::mutex> lock(g_masked_mu);
-    for (MaskedStream &m : g_masked[device])
-        if (m.s == s) {
-            (void)hipStreamSynchronize(s);
-            m.busy = false;
-            return true;
-        }
-    return false;
-}
-
-static void stream_retire(int device, hipStream_t s)
-{
-    if (s && !masked_stream_release(device, s)) (void)hipStreamDestroy(s);
-}
-
+// shared but run badly side by side (GPX_TWIN_LOG=1 prints the costs seen). Measured and
+// dropped: making every queue up front, in one order, at handle creation (this stream,
+// the pool, each touched once): uniform -- and uniformly worse, the streams made later
+// then share queues with the touched ones (64 thetas 202-207 evals/s in every order, one
+// evaluation at N = 4096 2.42 -> 2.82 ms, the metric batch 14.4 -> 11.8 evals/s).
 #define GPX_TWIN_POOL 7
 struct TwinPool {
     std::mutex mu;
     bool made = false;
     int users = 0;                 // batch contexts that hold one of the streams
-    hipStream_t spacer[GPX_TWIN_POOL] = {};
     hipStream_t stream[GPX_TWIN_POOL] = {};
 };
 static TwinPool g_twin_pool[64];
@@ -389,41 +322,19 @@ static double stream_pair_cost(hipStream_t a, hipStream_t b, double *alone_us)
 }
 
 // the pool's streams, once, in one order (caller holds the pool's mutex)
-static int twin_pool_make(TwinPool &p, int device, int ncu)
+static int twin_pool_make(TwinPool &p)
 {
     if (p.made) return 0;
-    // Plain streams (round 4). Rounds 3-4 made every pool stream a full-mask CU-masked stream,
-    // because the runtime gives such a stream a hardware queue of its own (plain streams share
-    // four) and a context could then always find one that runs well beside the streams before
-    // it (64 value-only thetas at N = 8192 through three contexts: 250 evals/s in every order
-    // against 200-215 on a handle that had done single evaluations). Batches of that kind run
-    // in groups now (group.hip) and no longer come here, and DESTROYING masked streams turned
-    // out not to be safe: hipStreamDestroy of a pool stream did not return in 3 of about 90
-    // pool teardowns at the end of round 4 (tests that open and close a handle per case;
-    // DESIGN.md section 4), always inside twin_pool_release. GPX_TWIN_MASKED=1 brings the
-    // masked queues back (=2: plain streams, each behind an unused masked queue, the
-    // arrangement of the first half of round 3); since round 5 they come from the
-    // process-lifetime cache above and are never destroyed.
-    static const int masked_env = getenv("GPX_TWIN_MASKED") ? atoi(getenv("GPX_TWIN_MASKED")) : 0;
-    const bool masked = masked_env > 0 && ncu >= 1 && ncu <= 1024;
-    uint32_t mask[32] = {};
-    for (int i = 0; masked && i < ncu; ++i) mask[i / 32] |= 1u << (i % 32);
-    for (int i = 0; i < GPX_TWIN_POOL; ++i) {
-        if (masked && masked_env == 1) {
-            GPX_TRY(masked_stream_acquire(device, ncu, mask, &p.stream[i]));
-            continue;
-        }
-        if (masked) GPX_TRY(masked_stream_acquire(device, ncu, mask, &p.spacer[i]));
+    for (int i = 0; i < GPX_TWIN_POOL; ++i)
         GPX_HIP(hipStreamCreateWithFlags(&p.stream[i], hipStreamNonBlocking));
-    }
     p.made = true;
     return 0;
 }
 
 // stream of the index-th (1-based) batch context of a chain on `device` (current device):
 // the first pool stream from position index - 1 on that shares no queue with `avoid`
-static int twin_pool_stream(int device, int index, int ncu,
-                            const std::vector<hipStream_t> &avoid, hipStream_t *out)
+static int twin_pool_stream(int device, int index, const std::vector<hipStream_t> &avoid,
+                            hipStream_t *out)
 {
     if (device < 0 || device >= 64 || index < 1) {
         gpx_set_error("twin stream: device %d index %d", device, index);
@@ -431,7 +342,7 @@ static int twin_pool_stream(int device, int index, int ncu,
     }
     TwinPool &p = g_twin_pool[device];
     std::lock_guard<std::mutex> lock(p.mu);
-    GPX_TRY(twin_pool_make(p, device, ncu));
+    GPX_TRY(twin_pool_make(p));
     ++p.users;
     // the first pool stream from position index - 1 on that runs well beside every stream
     // earlier in the chain: not on the same queue, not one of the bad pairs (cost 3.5+
@@ -462,8 +373,7 @@ static int twin_pool_stream(int device, int index, int ncu,
     return 0;
 }
 
-// a batch context goes away; the pool goes with the last one (live CU-masked queues at
-// process exit crashed the profiler's teardown) and is rebuilt on the next use
+// a batch context goes away; the pool goes with the last one and is rebuilt on the next use
 static void twin_pool_release(int device)
 {
     if (device < 0 || device >= 64) return;
@@ -476,9 +386,8 @@ static void twin_pool_release(int device)
                 fprintf(stderr, "twin_pool_release: stream %d\n", i);
                 fflush(stderr);
             }
-            stream_retire(device, p.stream[i]);        // (masked ones go back to the cache)
-            stream_retire(device, p.spacer[i]);
-            p.stream[i] = p.spacer[i] = nullptr;
+            if (p.stream[i]) (void)hipStreamDestroy(p.stream[i]);
+            p.stream[i] = nullptr;
         }
         p.made = false;
     }
@@ -496,57 +405,24 @@ static bool lookahead_enabled()
 static int create_lookahead_streams(gpx_ctx *h)
 {
     if (h->crit) return 0;
-    hipDeviceProp_t prop;
-    GPX_HIP(hipGetDeviceProperties(&prop, h->device));
     int lo = 0, hi = 0;                        // numerically lower = higher priority
     GPX_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
     GPX_HIP(hipStreamCreateWithPriority(&h->crit, hipStreamNonBlocking, hi));
-    // trailing updates (bulk) and the inverse columns (aux) run on every CU but
-    // GPX_RESERVE_CUS (default 32, four per XCD; the products are power-bound
-    // rather than CU-bound: with 224 CUs they lose nothing measurable): a 128-KB
-    // leaf workgroup of the next diagonal
-    // block never finds room on a CU that holds two 72-KB GEMM workgroups. Mask
-    // bit i is a CU of XCD i % 8 (the driver deals the bits round-robin to the
-    // XCDs), so the low bits take the same number of CUs from every XCD.
-    // Default 0 since late in round 2: no CU masks. A masked kernel runs at the pace
-    // of its CUs (224 of 256: a 7260-workgroup K^-1 update takes 6.93 ms against
-    // 6.02), a mask that takes CUs from some shader engines only at the pace of the
-    // emptiest one (240 or 248 CUs are no faster than 224), and since the diagonal
-    // blocks became one panel launch each they lose less by waiting for the tail of a
-    // product launch than the products lose to the mask: one evaluation at
-    // N = 16384 75.9 -> 71.6 ms, 2-4 % at N = 2048 ... 8192, value-only 29.2 -> 28.1.
-    // GPX_RESERVE_CUS=32 restores the partition (strict above np = 8192).
-    static const int reserve = getenv("GPX_RESERVE_CUS") ? atoi(getenv("GPX_RESERVE_CUS")) : 0;
-    const int ncu = prop.multiProcessorCount;
-    if (reserve > 0 && reserve < ncu && ncu <= 1024) {
-        uint32_t mask[32] = {};
-        for (int i = reserve; i < ncu; ++i) mask[i / 32] |= 1u << (i % 32);
-        GPX_TRY(masked_stream_acquire(h->device, ncu, mask, &h->bulk));
-        GPX_TRY(masked_stream_acquire(h->device, ncu, mask, &h->aux));
-        h->bulk_slots = 2 * (ncu - reserve);
-        static const int crit_mask = getenv("GPX_CRIT_MASK") ? atoi(getenv("GPX_CRIT_MASK")) : 1;
-        if (crit_mask) {
-            uint32_t cm[32] = {};
-            for (int i = 0; i < reserve; ++i) cm[i / 32] |= 1u << (i % 32);
-            GPX_TRY(masked_stream_acquire(h->device, ncu, cm, &h->crit_only));
-        }
+    // A batch context that runs the look-ahead (large batch members) takes its own stream
+    // for the trailing updates too: that stream was picked on a queue that runs well beside
+    // the other members' (twin_pool_stream), a fresh stream would land on whichever of the
+    // four plain queues is least used -- possibly another member's -- and build / vector
+    // kernels and trailing updates of ONE member have nothing to run side by side for (the
+    // updates wait for the build, the vector kernels for them). GPX_TWIN_OWN_BULK=0: a
+    // stream of its own, as before.
+    static const bool own_bulk = !(getenv("GPX_TWIN_OWN_BULK") && !atoi(getenv("GPX_TWIN_OWN_BULK")));
+    if (h->stream_borrowed && own_bulk) {
+        h->bulk = h->stream;
+        h->bulk_borrowed = true;
     } else {
-        // A batch context that runs the look-ahead (large batch members) takes its own
-        // stream for the trailing updates too: that stream was picked on a queue that runs
-        // well beside the other members' (twin_pool_stream), a fresh stream would land on
-        // whichever of the four plain queues is least used -- possibly another member's --
-        // and build / vector kernels and trailing updates of ONE member have nothing to
-        // run side by side for (the updates wait for the build, the vector kernels for
-        // them). GPX_TWIN_OWN_BULK=0: a stream of its own, as before.
-        static const bool own_bulk = !(getenv("GPX_TWIN_OWN_BULK") && !atoi(getenv("GPX_TWIN_OWN_BULK")));
-        if (h->stream_borrowed && own_bulk) {
-            h->bulk = h->stream;
-            h->bulk_borrowed = true;
-        } else {
-            GPX_HIP(hipStreamCreateWithFlags(&h->bulk, hipStreamNonBlocking));
-        }
-        GPX_HIP(hipStreamCreateWithPriority(&h->aux, hipStreamNonBlocking, lo));
+        GPX_HIP(hipStreamCreateWithFlags(&h->bulk, hipStreamNonBlocking));
     }
+    GPX_HIP(hipStreamCreateWithPriority(&h->aux, hipStreamNonBlocking, lo));
     for (hipEvent_t &e : h->la_events)
         GPX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     return 0;
@@ -582,8 +458,7 @@ int gpx_create(int device, gpx_t **out)
     if (g_creating_twin == 2) {
         // batch context: its stream comes from the device's pool (see above); it never
         // runs the look-ahead, so it needs no other stream
-        GPX_TRY(twin_pool_stream(device, g_twin_index, prop.multiProcessorCount, g_twin_avoid,
-                                 &h->stream));
+        GPX_TRY(twin_pool_stream(device, g_twin_index, g_twin_avoid, &h->stream));
         h->stream_borrowed = true;
         h->twin_index = g_twin_index;
         h->chain_streams = g_twin_avoid;
@@ -653,12 +528,10 @@ int gpx_destroy(gpx_t *h)
         if (e) (void)hipEventDestroy(e);
     DLOG("stream crit");
     if (h->crit) (void)hipStreamDestroy(h->crit);
-    DLOG("stream crit_only");
-    stream_retire(h->device, h->crit_only);            // (masked streams: back to the cache,
-    DLOG("stream bulk");                               //  never destroyed)
-    if (!h->bulk_borrowed) stream_retire(h->device, h->bulk);
+    DLOG("stream bulk");
+    if (h->bulk && !h->bulk_borrowed) (void)hipStreamDestroy(h->bulk);
     DLOG("stream aux");
-    stream_retire(h->device, h->aux);
+    if (h->aux) (void)hipStreamDestroy(h->aux);
     DLOG("stream main");
     if (h->stream && !h->stream_borrowed) (void)hipStreamDestroy(h->stream);
     DLOG("pool");

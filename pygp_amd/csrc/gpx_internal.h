@@ -115,9 +115,6 @@ struct GemmArgs {
     const int *tiles;      // set by the launcher
     double *C2 = nullptr;  // C is a diagonal block of a matrix: its off-diagonal 128-tiles
                            // are read and written at C2 (same ldc) instead of C
-    int slots = 0;         // workgroup slots of the stream the launch goes to (2 per CU
-                           // the stream may use; 0 = the whole GPU): equal-k launches
-                           // run whole rounds of 128-tiles and the rest as 64-tiles
     int kshift = 0;        // GEMM_KLO_*: the zero structure starts kshift columns in,
                            // op(A)[m][k] == 0 for k < m0 - kshift (a block column of a
                            // triangular matrix whose diagonal block sits kshift rows down)
@@ -174,16 +171,9 @@ struct DenseWs {           // device buffers of one factorisation, all np x np
     int *gate_total = nullptr;   // host: how often each of the two gate counters behind the
                                  // control block has been moved by launches enqueued so far
     // look-ahead of gpx_potrf (all null: everything on the caller's stream): a
-    // high-priority stream for the diagonal blocks, a low-priority one for the left
-    // half of the inverse tree, and GPX_LA_EVENTS events
-    hipStream_t crit = nullptr, aux = nullptr;
-    hipStream_t crit_only = nullptr;   // the reserved CUs and nothing else
-    // the trailing updates run on `bulk`, a stream whose CU mask leaves a few CUs
-    // (one or two per XCD) free: a 128-KB leaf workgroup of the next diagonal block
-    // never finds room on a CU that holds two 72-KB GEMM workgroups, and would
-    // otherwise wait for the whole update launch to drain
-    hipStream_t bulk = nullptr;
-    int bulk_slots = 0;    // workgroup slots of `bulk` (2 per unmasked CU)
+    // high-priority stream for the diagonal blocks, `bulk` for the trailing updates, a
+    // low-priority one for the left half of the inverse tree, and GPX_LA_EVENTS events
+    hipStream_t crit = nullptr, aux = nullptr, bulk = nullptr;
     hipEvent_t *events = nullptr;
     // set by the caller of gpx_potrf (look-ahead only):
     // lead: event after which the first lead_rows rows of the input are in place (the
@@ -216,8 +206,8 @@ struct DenseWs {           // device buffers of one factorisation, all np x np
 // default that a value-only factorisation and its later trtri / lauum must share: with
 // GPX_SPLIT_LAST=1, for 4096 <= np < 8192 the last 1024-block is cut in two. The inverse
 // column and K^-1 share of the last block are what nothing hides (a quarter of an
-// evaluation at N = 4096). Worth 3 % there while the products ran on CU-masked streams;
-// nothing since they run on every CU (2.72 ms either way), so off by default.
+// evaluation at N = 4096). Worth nothing now that the products run on every CU (2.72 ms
+// either way; 3 % under round 2's CU partition), so off by default.
 int gpx_block_layout(int np, int *offs, bool full_inverse = false);
 struct GpxBlocks {
     int np, count;

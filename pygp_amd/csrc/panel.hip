@@ -3055,8 +3055,7 @@ int gpx_panel(hipStream_t s, const DenseWs &w, int off, int n, int extra, int ga
     // same evaluation and every workgroup here holds a whole CU (157 KB of LDS) that the
     // products cannot use while it polls: 32 (round 3, N = 16384: 8 / 16 / 24 / 32 / 48 /
     // 64 workers 72.8 / 71.5 / 70.8 / 71.0 / 71.5 / 71.8 ms per evaluation, N = 8192:
-    // 32 / 64 / 128 workers 11.29 / 11.48 / 11.79 ms); on the 32 reserved CUs 29, so
-    // that the whole grid is resident whatever order the workgroups are dispatched in
+    // 32 / 64 / 128 workers 11.29 / 11.48 / 11.79 ms)
     static const int workers_env = [] {
         const int v = env_once("GPX_PANEL_WG", -1);
         return v < 1 || v > 256 ? -1 : v;
@@ -3081,7 +3080,6 @@ int gpx_panel(hipStream_t s, const DenseWs &w, int off, int n, int extra, int ga
     int workers = whole ? (whole_env > 0 ? whole_env : (T <= 16 ? 160 : 250))
                   : E > 0 ? (wide_env > 0 ? wide_env : (w.np <= 4096 ? 96 : 64))
                   : workers_env > 0 ? workers_env
-                  : (w.crit_only && s == w.crit_only) ? 29      // + 3 spine = the 32 CUs
                   : w.np <= 4096 ? 128 : 32;
     // Member-batched launch: the same graph for every member of the workspace. The chain of
     // a member keeps 1-3 spine workgroups busy and its products a handful of workers, so the

@@ -797,14 +797,13 @@ def test_multi_device_entry_on_one_gpu():
 
 
 @pytest.mark.gpu
-def test_cu_partition_switch_gives_the_same_bits():
-    """The look-ahead driver has two arrangements: products on every CU with the two small
-    products between diagonal blocks on the critical stream (default), and the round-2
-    partition -- 32 CUs kept for the diagonal blocks, products on CU-masked streams,
-    strict above np = 8192 (GPX_RESERVE_CUS=32). Both cut the same tile products, so one
-    evaluation just above np = 8192 must give the same bits either way, and so must a
-    small one. The child makes and closes two handles: the second takes the first one's
-    masked streams over from the cache, and the teardown runs to the end."""
+def test_retired_cu_partition_switch_is_ignored():
+    """GPX_RESERVE_CUS=32 once selected the round-2 partition of the look-ahead driver (32 CUs
+    kept for the diagonal blocks, products on CU-masked streams). That mode is retired and
+    the library creates no CU-masked streams, so the variable must be ignored: one
+    evaluation just above np = 8192 gives the same bits with it as without, and so does a
+    small one. The child makes and closes two handles, and the teardown runs to the end
+    (ADVICE r4)."""
     import json
     import os
     import sys
@@ -824,9 +823,8 @@ def test_cu_partition_switch_gives_the_same_bits():
         "    lZ, dlZ = dev.exact_eval(k.copy(th[1:-1])._kspec(), th[0], th[-1], True)\n"
         "    out[str(N)] = [float(lZ).hex()] + [float(v).hex() for v in dlZ]\n"
         "print(json.dumps(out), flush=True)\n"
-        "dev.close()    # normal teardown: CU-masked streams go back to the library's\n"
-        "               # process-lifetime cache and are never destroyed (round 5; round 4\n"
-        "               # skipped the teardown here because hipStreamDestroy of one could hang)\n"
+        "dev.close()    # normal teardown: the library creates no CU-masked streams, whose\n"
+        "               # hipStreamDestroy could hang (round 4 skipped the teardown here)\n"
     ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
          os.path.dirname(os.path.abspath(__file__)))
     got = []
@@ -842,10 +840,11 @@ def test_cu_partition_switch_gives_the_same_bits():
 def test_queue_probe_switch_gives_the_same_bits():
     """Where batches still run one context and stream per member (above np = 32768; everything
     with GPX_GROUP_MAX_NP=0) a context picks its stream by measuring how
-    it runs beside the streams before it. Whatever it picks -- the probe on, off
-    (pool order), full-mask streams with queues of their own instead of plain ones (round 3's
-    pool) -- is an arrangement of streams, not of arithmetic: the same bits, and the bits of
-    the groups."""
+    it runs beside the streams before it. Whatever it picks -- the probe on or
+    off (pool order) -- is an arrangement of streams, not of arithmetic: the same bits, and
+    the bits of the groups. GPX_TWIN_MASKED=1, which once selected round
+    3's pool of CU-masked streams, is retired and must be ignored (the depth-3 child of
+    tools/bench_configs.py still sets it)."""
     import json
     import os
     import sys
@@ -866,9 +865,8 @@ def test_queue_probe_switch_gives_the_same_bits():
         "    lZv = dev.loglik_batch(k._kspec(), th, grad=False)\n"
         "    out[str(N)] = [float(v).hex() for v in np.r_[lZ, dlZ.ravel(), lZv]]\n"
         "print(json.dumps(out), flush=True)\n"
-        "dev.close()    # normal teardown: CU-masked streams go back to the library's\n"
-        "               # process-lifetime cache and are never destroyed (round 5; round 4\n"
-        "               # skipped the teardown here because hipStreamDestroy of one could hang)\n"
+        "dev.close()    # normal teardown: the library creates no CU-masked streams, whose\n"
+        "               # hipStreamDestroy could hang (round 4 skipped the teardown here)\n"
     ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
          os.path.dirname(os.path.abspath(__file__)))
     got = []
