@@ -235,14 +235,15 @@ int gpx_posterior_batch(gpx_t *h, const gpx_kspec *k, const double *thetas, int6
                         double *ds2, int *info);
 
 /* ---- sparse pseudo-input models (pygp/inference/fitc.py, dtc.py) -------- */
-/* FITC and DTC on the handle's resident data (gpx_set_data): p pseudo-inputs U[p*d] and the
- * hypers [log sn | kernel | mean] as for ExactGP. Limits: 1 <= p <= GPX_SPARSE_MAX_P and
+/* FITC, DTC and VFE (the variational bound: DTC's lZ minus tr(K - Q) / (2 sn2), DTC's
+ * posterior and stored statistics) on the handle's resident data (gpx_set_data): p
+ * pseudo-inputs U[p*d] and the hypers [log sn | kernel | mean] as for ExactGP. Limits: 1 <= p <= GPX_SPARSE_MAX_P and
  * round_up(p, 128) * round_up(N, 128) < 2^31. The model has buffers of its own: an exact
  * factorisation of the same handle stays valid beside it. gpx_set_data makes the sparse
  * model stale (its calls fail until the next gpx_sparse_update). A non-positive-definite
  * Kuu + su2 I returns its pivot (> 0, also in *info). */
 #define GPX_SPARSE_MAX_P 4096
-enum gpx_sparse_method { GPX_FITC = 1, GPX_DTC = 2 };
+enum gpx_sparse_method { GPX_FITC = 1, GPX_DTC = 2, GPX_VFE = 3 };
 int gpx_sparse_update(gpx_t *h, const gpx_kspec *k, int method, const double *U, int64_t p,
                       double log_sn, double mean, int *info);
 /* loglikelihood of the last update; dlZ == NULL: value only, else dlZ[1 + nhyper + 1] in
@@ -254,7 +255,7 @@ int gpx_sparse_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, doub
 /* _full_posterior: mu[m], Sigma[m][m], 1 <= m <= 8192 */
 int gpx_sparse_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma);
 /* the stored statistics, p x p row-major upper factors and a p-vector (any may be NULL):
- * FITC _L, _R, _b; DTC _Ruu, _Rux, _a */
+ * FITC _L, _R, _b; DTC and VFE _Ruu, _Rux, _a */
 int gpx_sparse_get_state(gpx_t *h, double *F1, double *F2, double *v);
 /* HIP-event times (ms) of the last sparse calls on this handle: ms[0] the update,
  * ms[1] the gradient stage of the last gpx_sparse_loglik with dlZ (0 if none since the

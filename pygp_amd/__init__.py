@@ -3,7 +3,7 @@ pygp_amd -- MI355X-native exact-GP hot path behind pygp's Kernel / GP interface.
 
 Only the path named in BASELINE.json is here: pairwise kernel evaluation
 (SE / Matern / Periodic / RQ, sums of products), ExactGP update /
-log-likelihood (+gradient) / posterior and the sparse FITC / DTC models, executed by
+log-likelihood (+gradient) / posterior and the sparse FITC / DTC / VFE models, executed by
 hand-written HIP kernels in libgpx.so; `batch` and `meta` route the
 per-sample loops of the reference's meta-models through the batched entry points.
 """
@@ -14,8 +14,8 @@ from . import inference
 from . import learning
 from . import batch
 from . import meta
-from .inference import BasicGP, ExactGP, FITC, DTC
+from .inference import BasicGP, ExactGP, FITC, DTC, VFE
 from .learning import optimize
 
-__all__ = ['BasicGP', 'ExactGP', 'FITC', 'DTC', 'optimize', 'kernels', 'likelihoods',
+__all__ = ['BasicGP', 'ExactGP', 'FITC', 'DTC', 'VFE', 'optimize', 'kernels', 'likelihoods',
            'inference', 'learning', 'batch', 'meta']

@@ -49,7 +49,7 @@ _vp = C.c_void_p
 _i64 = C.c_int64
 
 # name -> (restype, argtypes); mirrors include/gpx.h one to one
-GPX_FITC, GPX_DTC = 1, 2          # enum gpx_sparse_method
+GPX_FITC, GPX_DTC, GPX_VFE = 1, 2, 3          # enum gpx_sparse_method
 
 SIGNATURES = {
     'gpx_version': (C.c_int, []),
@@ -381,7 +381,7 @@ class Handle(object):
         check(self._L.gpx_exact_posterior_full(self._h, _ptr(Xs), m, _ptr(mu), _ptr(Sigma)))
         return mu, Sigma
 
-    # -- sparse pseudo-input models (FITC / DTC) on the resident data --
+    # -- sparse pseudo-input models (FITC / DTC / VFE) on the resident data --
     def sparse_update(self, spec, method, U, log_sn, mean):
         U = _f64(U, 2)
         info = C.c_int(0)

@@ -1689,7 +1689,7 @@ int gpx_kernel_gradx(gpx_t *h, const gpx_kspec *k, const double *X1, int64_t n1,
     return 0;
 }
 
-// ---- FITC / DTC (pygp/inference/fitc.py, dtc.py) -----------------------------------
+// ---- FITC / DTC (pygp/inference/fitc.py, dtc.py) and VFE -----------------------------
 static int sparse_ready(gpx_ctx *h, const char *what)
 {
     if (!h->sparse || h->sparse_version < 0) {
@@ -1713,8 +1713,9 @@ int gpx_sparse_update(gpx_t *h, const gpx_kspec *k, int method, const double *U,
         gpx_set_error("gpx_sparse_update: no data: call gpx_set_data first");
         return -1;
     }
-    if (method != GPX_FITC && method != GPX_DTC) {
-        gpx_set_error("gpx_sparse_update: method must be GPX_FITC or GPX_DTC (got %d)", method);
+    if (method != GPX_FITC && method != GPX_DTC && method != GPX_VFE) {
+        gpx_set_error("gpx_sparse_update: method must be GPX_FITC, GPX_DTC or GPX_VFE (got %d)",
+                      method);
         return -1;
     }
     if (!U || p < 1 || p > GPX_SPARSE_MAX_P) {

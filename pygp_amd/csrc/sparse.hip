@@ -1,7 +1,9 @@
-// sparse.hip -- FITC and DTC sparse pseudo-input GPs (pygp/inference/fitc.py, dtc.py) on
-// the device. Notation of DESIGN.md section 10: L = chol(Kuu + su2 I) (upper), V0 = L^-T Kux,
+// sparse.hip -- FITC and DTC sparse pseudo-input GPs (pygp/inference/fitc.py, dtc.py) and the
+// variational bound VFE on the device. Notation of DESIGN.md section 10:
+// L = chol(Kuu + su2 I) (upper), V0 = L^-T Kux,
 // ell_j (FITC: sqrt(kxx + sn2 - sum_i V0_ij^2), DTC: sqrt(sn2)), V = V0 / ell, rt = r / ell,
-// A = chol(I + V V^T), beta = A^-T V rt.
+// A = chol(I + V V^T), beta = A^-T V rt. VFE is DTC with lZ - t / (2 sn2),
+// t = sum_j (kxx - sum_i V0_ij^2), and the adjoints of that term in the gradient.
 //
 // Every p x p x N product runs on the fp64 tile engine (gemm_f64.hip); the products with a
 // p x p output and an inner dimension N run split-K over the CUs and their partial products
@@ -59,6 +61,7 @@ enum {
     S_C2,           // ||C||_F^2
     S_EB2,          // sum_j (alpha_j^2 + s_j) sum_i B_ij^2
     S_V2A,          // (V alpha)^T (V alpha)
+    S_T,            // VFE: sum_j (kxx - sum_i V0_ij^2); 0 for the other methods
     S_COUNT
 };
 
@@ -72,8 +75,8 @@ struct GpxSparse {
     int gates_l[2] = {0, 0}, gates_a[2] = {0, 0};
     SpBuf U, L, Lw, Lk, A, Aw, Ak, info, pctl;
     // p x N panels (ld np). P2 holds V from the update to the next update: the gradient
-    // stage reads it and writes only P1 (B), P3 (W, then B diag(e)) and P4 (C W, then G_ux),
-    // so a second gradient call on the same state sees the same V
+    // stage reads it and writes only P1 (B), P3 (W, then FITC's B diag(e)) and P4 (C W, then
+    // G_ux), so a second gradient call on the same state sees the same V
     SpBuf P1, P2, P3, P4;
     SpBuf ell, rt, beta, gam, u, alpha, wv, vv, bq, sq, e;
     SpBuf part, scal, acc_uu, acc_ux, pg_part, split, Cm, CC, BEB, Guu, R2;
@@ -197,6 +200,28 @@ __global__ __launch_bounds__(SP_T) void sp_colprep_kernel(
     if (threadIdx.x == 0) po[3] = s;
 }
 
+// VFE: part[block] = sum over the block's columns j < n of kxx - sum_i V0_ij^2, from the
+// refined V0 before sp_colprep_kernel scales it. The difference cancels (it is FITC's ell^2
+// without sn2), so it is formed per column and the differences are summed.
+__global__ __launch_bounds__(SP_T) void sp_coltrace_kernel(const double *__restrict__ V0,
+                                                          long long ld, int pp, int n,
+                                                          double kxx, double *__restrict__ part)
+{
+    __shared__ double red[SP_T];
+    const int j = blockIdx.x * SP_T + threadIdx.x;
+    double q = 0.0;
+    if (j < n) {
+        double sq = 0.0;
+        for (int i = 0; i < pp; ++i) {
+            const double v = V0[(size_t)i * ld + j];
+            sq += v * v;
+        }
+        q = kxx - sq;
+    }
+    q = sp_block_sum(q, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = q;
+}
+
 // out[:, j] = in[:, j] * c_j (div: / c_j; c null: 1) for j < cols, q[j] = sum_i out_ij^2
 // (q may be null); part[block] = sum_{j < cols} q_j (part may be null). rows x cols,
 // columns >= cols untouched.
@@ -301,6 +326,23 @@ __global__ __launch_bounds__(SP_T) void sp_gux_kernel(double *__restrict__ G,
     G[o] = g;
 }
 
+// VFE: G_ux = (CW + w alpha^T) / ell in place over CW -- the trace term's B0 / sn2 is DTC's
+// B / ell, so the two cancel and B is not read. Zero outside p x n.
+__global__ __launch_bounds__(SP_T) void sp_gux_vfe_kernel(double *__restrict__ G, long long ld,
+                                                         int p, int n, int np,
+                                                         const double *__restrict__ w,
+                                                         const double *__restrict__ alpha,
+                                                         const double *__restrict__ ell)
+{
+    const int j = blockIdx.x * SP_T + threadIdx.x;
+    const int i = blockIdx.y;
+    if (j >= np) return;
+    const size_t o = (size_t)i * ld + j;
+    double g = 0.0;
+    if (i < p && j < n) g = (G[o] + w[i] * alpha[j]) / ell[j];
+    G[o] = g;
+}
+
 // out[i][j] (ld ldo) = sum_s P[s * stride + i * pp + j] + (i == j ? diag : 0), s in order
 __global__ __launch_bounds__(SP_T) void sp_sum_partials_kernel(const double *__restrict__ P,
                                                               int nsplit, long long stride,
@@ -326,6 +368,19 @@ __global__ __launch_bounds__(SP_T) void sp_guu_kernel(const double *__restrict__
     if (j >= pp) return;
     const size_t o = (size_t)i * pp + j;
     G[o] = i < p && j < p ? 0.5 * (BEB[o] - w[i] * w[j] - CC[o]) : 0.0;
+}
+
+// VFE: G_uu = -(w w^T + C C^T) / 2 inside p x p, 0 outside -- the trace term's
+// -B0 B0^T / (2 sn2) is -B B^T / 2 and cancels DTC's B B^T / 2, so that product is not formed
+__global__ __launch_bounds__(SP_T) void sp_guu_vfe_kernel(const double *__restrict__ CC,
+                                                         const double *__restrict__ w, int p,
+                                                         int pp, double *__restrict__ G)
+{
+    const int j = blockIdx.x * SP_T + threadIdx.x;
+    const int i = blockIdx.y;
+    if (j >= pp) return;
+    const size_t o = (size_t)i * pp + j;
+    G[o] = i < p && j < p ? -0.5 * (w[i] * w[j] + CC[o]) : 0.0;
 }
 
 // strictly lower triangle of an upper factor (and its inverse) -> 0
@@ -589,6 +644,13 @@ int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, i
     GPX_TRY(sp_gemm(s, 1, 0, st->Lw.d(), ldp, st->P1.d(), np, st->P3.d(), np, pp, np, pp, 1.0,
                     0.0));
     GPX_TRY(gpx_add_inplace(s, st->P2.d(), st->P3.d(), (size_t)pp * np));
+    if (method == GPX_VFE) {
+        // t from the refined V0, one more read of the panel before it is scaled
+        hipLaunchKernelGGL(sp_coltrace_kernel, dim3(nbc), dim3(SP_T), 0, s, st->P2.d(),
+                           (long long)np, pp, n, st->prior, st->part.d());
+        GPX_HIP(hipGetLastError());
+        GPX_TRY(sp_reduce(s, st->part.d(), nbc, 1, st->scal.d() + S_T));
+    }
     hipLaunchKernelGGL(sp_colprep_kernel, dim3(nbc), dim3(SP_T), 0, s, st->P2.d(), (long long)np,
                        pp, n, np, y, mean, st->prior, st->sn2, method == GPX_FITC ? 1 : 0,
                        st->ell.d(), st->rt.d(), st->part.d());
@@ -633,9 +695,10 @@ int gpx_sparse_run_loglik(GpxSparse *st, hipStream_t s, const double *X, double 
     // lZ = -sum log A_ii - sum log ell - (rt^T rt - beta^T beta) / 2 - N log(2 pi) / 2
     *lZ = -sc[S_LOGA] - sc[S_LOGELL] - 0.5 * (sc[S_RT2] - sc[S_BETA2]) -
           0.5 * st->n * log(2 * M_PI);
+    const bool fitc = st->method == GPX_FITC, vfe = st->method == GPX_VFE;
+    if (vfe) *lZ -= sc[S_T] / (2 * st->sn2);
     if (!dlZ) return 0;
 
-    const bool fitc = st->method == GPX_FITC;
     const int p = st->p, pp = st->pp, ldp = st->ldp, n = st->n, np = st->np, d = st->d;
     const long long ld = np;
     const size_t panel = (size_t)pp * np * 8, vec = (size_t)np * 8;
@@ -649,7 +712,7 @@ int gpx_sparse_run_loglik(GpxSparse *st, hipStream_t s, const double *X, double 
     GPX_TRY(st->vv.reserve((size_t)pp * 8));
     GPX_TRY(st->Cm.reserve((size_t)pp * pp * 8));
     GPX_TRY(st->CC.reserve((size_t)pp * pp * 8));
-    GPX_TRY(st->BEB.reserve((size_t)pp * pp * 8));
+    if (!vfe) GPX_TRY(st->BEB.reserve((size_t)pp * pp * 8));
     GPX_TRY(st->Guu.reserve((size_t)pp * pp * 8));
     const int nacc = 1 + st->kp.nhyper;
     GPX_TRY(st->acc_uu.reserve((size_t)nacc * 8));
@@ -673,6 +736,9 @@ int gpx_sparse_run_loglik(GpxSparse *st, hipStream_t s, const double *X, double 
     GPX_TRY(sp_reduce(s, st->part.d(), nbc, 2, scal + S_ALPHA));
     // B = L^-1 V0 (FITC) = L^-1 V diag(ell), or L^-1 V (DTC); q: column sums of B^2
     GPX_TRY(sp_gemm(s, 0, 0, st->Lw.d(), ldp, P2, np, P1, np, pp, np, pp, 1.0, 0.0));
+    // (VFE reads neither q nor S_B2 -- its su2 ||B||^2 cancelled; for it this is one read of
+    // B that writes nothing to the panel, kept so that its stage is DTC's launch sequence up
+    // to G_ux)
     hipLaunchKernelGGL(sp_colscale_kernel, cgrid, dim3(SP_T), 0, s, P1, P1, ld, pp, n,
                        fitc ? st->ell.d() : nullptr, 0, st->bq.d(), st->part.d());
     GPX_HIP(hipGetLastError());
@@ -707,22 +773,32 @@ int gpx_sparse_run_loglik(GpxSparse *st, hipStream_t s, const double *X, double 
         GPX_TRY(sp_dot(s, st->e.d(), st->bq.d(), n, scal + S_EB2));   // (bq: j < n only)
     }
     // G_ux in place over CW
-    hipLaunchKernelGGL(sp_gux_kernel, dim3(nbc, pp), dim3(SP_T), 0, s, P4, P1, ld, p, n, np,
-                       st->wv.d(), st->alpha.d(), st->e.d(), st->ell.d(), fitc ? 1 : 0);
+    if (vfe)
+        hipLaunchKernelGGL(sp_gux_vfe_kernel, dim3(nbc, pp), dim3(SP_T), 0, s, P4, ld, p, n, np,
+                           st->wv.d(), st->alpha.d(), st->ell.d());
+    else
+        hipLaunchKernelGGL(sp_gux_kernel, dim3(nbc, pp), dim3(SP_T), 0, s, P4, P1, ld, p, n, np,
+                           st->wv.d(), st->alpha.d(), st->e.d(), st->ell.d(), fitc ? 1 : 0);
     GPX_HIP(hipGetLastError());
-    // B diag(e) B^T (FITC) or B B^T (DTC), C C^T, G_uu
-    const double *BE = P1;
-    if (fitc) {
-        hipLaunchKernelGGL(sp_colscale_kernel, cgrid, dim3(SP_T), 0, s, P1, P3, ld, pp, np,
-                           st->e.d(), 0, nullptr, nullptr);
-        GPX_HIP(hipGetLastError());
-        BE = P3;
+    // B diag(e) B^T (FITC) or B B^T (DTC; VFE: cancelled, not formed), C C^T, G_uu
+    if (!vfe) {
+        const double *BE = P1;
+        if (fitc) {
+            hipLaunchKernelGGL(sp_colscale_kernel, cgrid, dim3(SP_T), 0, s, P1, P3, ld, pp, np,
+                               st->e.d(), 0, nullptr, nullptr);
+            GPX_HIP(hipGetLastError());
+            BE = P3;
+        }
+        GPX_TRY(sp_abt_split(st, s, BE, P1, ld, np, st->BEB.d(), pp, 0.0));
     }
-    GPX_TRY(sp_abt_split(st, s, BE, P1, ld, np, st->BEB.d(), pp, 0.0));
     GPX_TRY(sp_gemm(s, 0, 1, st->Cm.d(), pp, st->Cm.d(), pp, st->CC.d(), pp, pp, pp, pp, 1.0,
                     0.0));
-    hipLaunchKernelGGL(sp_guu_kernel, dim3((pp + SP_T - 1) / SP_T, pp), dim3(SP_T), 0, s,
-                       st->BEB.d(), st->CC.d(), st->wv.d(), p, pp, st->Guu.d());
+    if (vfe)
+        hipLaunchKernelGGL(sp_guu_vfe_kernel, dim3((pp + SP_T - 1) / SP_T, pp), dim3(SP_T), 0, s,
+                           st->CC.d(), st->wv.d(), p, pp, st->Guu.d());
+    else
+        hipLaunchKernelGGL(sp_guu_kernel, dim3((pp + SP_T - 1) / SP_T, pp), dim3(SP_T), 0, s,
+                           st->BEB.d(), st->CC.d(), st->wv.d(), p, pp, st->Guu.d());
     GPX_HIP(hipGetLastError());
     // the contractions with the kernel derivatives
     GPX_TRY(sp_event(st, s, 3));
@@ -757,6 +833,15 @@ int gpx_sparse_run_loglik(GpxSparse *st, hipStream_t s, const double *X, double 
                  su2 * h[S_EB2];
         for (int k = 0; k < nh; ++k) dlZ[1 + k] = auu[1 + k] + aux[1 + k] + dprior[k] * gx;
         dlZ[1 + nh] = h[S_ALPHA];
+    } else if (vfe) {
+        // DTC's terms without the su2 ||B||^2 the trace term's share of the jitter path
+        // cancels, + d/dlog sn of -t / (2 sn2); g_x = -1 / (2 sn2) on every column, and as
+        // kxx is the same on all of them the contraction <dkxx, g_x> needs only their sum
+        const double gx_sum = -0.5 * n / sn2;
+        dlZ[0] = -(-h[S_RT2] + h[S_BETA2] + h[S_V2A] + su2 * h[S_W2] + n - h[S_V2] + h[S_AW2] +
+                   su2 * h[S_C2]) + h[S_T] / sn2;
+        for (int k = 0; k < nh; ++k) dlZ[1 + k] = auu[1 + k] + aux[1 + k] + dprior[k] * gx_sum;
+        dlZ[1 + nh] = h[S_ALPHA] / sqrt(sn2);
     } else {
         dlZ[0] = -(-h[S_RT2] + h[S_BETA2] + h[S_V2A] + su2 * h[S_W2] + n - h[S_V2] + h[S_AW2] -
                    su2 * (h[S_B2] - h[S_C2]));

@@ -2,5 +2,6 @@ from .exact import GP, ExactGP
 from .basic import BasicGP
 from .fitc import FITC
 from .dtc import DTC
+from .vfe import VFE
 
-__all__ = ['GP', 'ExactGP', 'BasicGP', 'FITC', 'DTC']
+__all__ = ['GP', 'ExactGP', 'BasicGP', 'FITC', 'DTC', 'VFE']

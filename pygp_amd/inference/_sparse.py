@@ -1,6 +1,6 @@
 """
 Shared state machine of the sparse pseudo-input models FITC and DTC
-(pygp/inference/fitc.py, dtc.py).
+(pygp/inference/fitc.py, dtc.py) and the variational bound VFE.
 
 The numerical work -- Kuu, Kux, the two p x p Cholesky factors, the lZ terms, the
 gradient contraction and the posteriors -- runs in libgpx.so (sparse.hip). The model owns
@@ -18,9 +18,9 @@ __all__ = ['SparseGP']
 
 
 class SparseGP(GP):
-    """Base of FITC and DTC: a Gaussian likelihood and p pseudo-inputs U."""
+    """Base of FITC, DTC and VFE: a Gaussian likelihood and p pseudo-inputs U."""
 
-    _method = None          # _lib.GPX_FITC / GPX_DTC
+    _method = None          # _lib.GPX_FITC / GPX_DTC / GPX_VFE
 
     def __init__(self, likelihood, kernel, mean, U):
         if not isinstance(likelihood, Gaussian):

@@ -20,7 +20,7 @@ def optimize(gp, priors=None, pseudoinputs=False):
     """Maximise the marginal likelihood over the hypers of `gp` in place.
     priors: {name: None} freezes the named block (the only prior form the
     reference supports, optimization.py:47-52). pseudoinputs: also move the
-    pseudo-inputs of a sparse model (FITC, DTC), jointly with the free hypers."""
+    pseudo-inputs of a sparse model (FITC, DTC, VFE), jointly with the free hypers."""
     if pseudoinputs:
         return _optimize_pseudo(gp, priors)
     start = gp.get_hyper()
@@ -48,7 +48,7 @@ def _optimize_pseudo(gp, priors):
     """L-BFGS over [free hypers, U.ravel()]; one loglikelihood(True, pseudoinputs=True)
     per objective call."""
     if not hasattr(gp, 'set_pseudoinputs'):
-        raise ValueError('pseudo-input optimisation needs a sparse model (FITC, DTC)')
+        raise ValueError('pseudo-input optimisation needs a sparse model (FITC, DTC, VFE)')
     start = gp.get_hyper()
     free = np.ones(gp.nhyper, dtype=bool)
     blocks = dict((name, block) for name, block, _ in get_params(gp))

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Sparse pseudo-input models on one GPU: FITC value-only and with gradients at N = 2^20,
-D = 8, SE-ARD, p in {512, 1024, 2048}. Prints ONE JSON line.
+"""Sparse pseudo-input models on one GPU: value-only and with gradients at N = 2^20,
+D = 8, SE-ARD, p in {512, 1024, 2048}; --method picks FITC (the default), DTC or VFE, and
+several may be given to time them on the same shapes in one run. Prints ONE JSON line per
+method.
 
 Times are HIP events the library records on its stream (gpx_sparse_timings): the update
 (value-only: Kuu, Kux, the two factorisations and the lZ terms), the gradient stage on top
@@ -9,7 +11,7 @@ The dense-stage rate against the fp64 peak uses the flop model of DESIGN.md sect
 a model count, not a measured one:
 
   value-only   6 p^2 N   (L^-T Kux with one refinement step: 3 products; V V^T: 1)
-  gradient     10 p^2 N  (B, W, C = B W^T, C W, B E B^T)
+  gradient     10 p^2 N  (B, W, C = B W^T, C W, B E B^T; VFE forms no B E B^T: 8 p^2 N)
 
 The contraction pass's GB/s is the 8 p N bytes of G_ux it reads once, over its measured
 time (its X reads are 8 N d bytes per 64-row block of U, mostly from cache). At p = 2048
@@ -19,7 +21,8 @@ N is 2^20 - 128: p_pad N_pad must stay below 2^31. A host NumPy fp64 evaluation
 --pseudo also times the pseudo-input gradient pass (gpx_sparse_pseudo_timing: the two
 contractions of G_uu and G_ux with dk/du, median of 3 after a warm-up) and adds pseudo_ms,
 its pairs/s over the p N + p^2 pairs and its GB/s over the 8 p N bytes of G_ux it reads.
-usage: sparse_bench.py [--reps R] [--warmup W] [--quick] [--pseudo]"""
+usage: sparse_bench.py [--reps R] [--warmup W] [--quick] [--pseudo]
+                       [--method {fitc,dtc,vfe} ...]"""
 import argparse
 import json
 import os
@@ -42,10 +45,20 @@ def main():
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--quick', action='store_true', help='N = 2^17 (a smoke run)')
     ap.add_argument('--pseudo', action='store_true', help='also time the dU pass')
+    ap.add_argument('--method', nargs='+', choices=['fitc', 'dtc', 'vfe'], default=['fitc'],
+                    help='the sparse method(s) to time, one JSON line each')
     a = ap.parse_args()
+    for name in a.method:
+        run(a, name)
+
+
+def run(a, name):
     import pygp_amd
     from pygp_amd import _lib
+    import sparse_ref as sr
 
+    method = dict(fitc=_lib.GPX_FITC, dtc=_lib.GPX_DTC, vfe=_lib.GPX_VFE)[name]
+    grad_products = 8.0 if name == 'vfe' else 10.0
     D = 8
     N0 = 1 << 17 if a.quick else 1 << 20
     rng = np.random.RandomState(0)
@@ -62,7 +75,7 @@ def main():
         U = X[rng.choice(N, p, replace=False)]
 
         def upd():
-            dev.sparse_update(spec, _lib.GPX_FITC, U, log_sn, mean)
+            dev.sparse_update(spec, method, U, log_sn, mean)
             return dev.sparse_timings()[0]
 
         def grad():
@@ -81,7 +94,7 @@ def main():
         t_val = statistics.median(t_upd) * 1e-3
         t_g = statistics.median(t_grad) * 1e-3
         t_c = statistics.median(t_pass) * 1e-3
-        f_val, f_grad = 6.0 * p * p * N, 10.0 * p * p * N
+        f_val, f_grad = 6.0 * p * p * N, grad_products * p * p * N
         g_bytes = 8.0 * p * N          # G_ux, read once by the contraction pass
         points.append(dict(
             p=p, N=N, update_ms=t_val * 1e3, grad_stage_ms=t_g * 1e3,
@@ -99,23 +112,34 @@ def main():
             t_p = statistics.median(pseudo() for _ in range(3)) * 1e-3
             points[-1].update(pseudo_ms=t_p * 1e3, pseudo_pairs_per_s=(p * N + p * p) / t_p,
                               pseudo_gbs=g_bytes / t_p * 1e-9)
-    # host fp64 context
-    import sparse_ref as sr
+    # host fp64 context: the method's own restatement
+    if name == 'vfe':
+        import sparse_vfe_ref as svr
+        host_name = 'tests/sparse_vfe_ref.py vfe_eval'
+
+        def host_eval(*args, **kw):
+            return svr.vfe_eval(*args, **kw)
+    else:
+        host_method = sr.FITC if name == 'fitc' else sr.DTC
+        host_name = 'tests/sparse_ref.py sparse_eval (%s)' % name.upper()
+
+        def host_eval(spec_, *args, **kw):
+            return sr.sparse_eval(spec_, host_method, *args, **kw)
     from oracle import gp_oracle as orc
     Nh, ph = 16384, 256
     sp = orc.se_spec(1.0, np.linspace(1.0, 3.0, D))
     th = np.r_[log_sn, orc.spec_get_hyper(sp), mean]
     Uh = X[:ph]
     t0 = time.perf_counter()
-    sr.sparse_eval(sp, sr.FITC, th, Uh, X[:Nh], y[:Nh], grad=False)
+    host_eval(sp, th, Uh, X[:Nh], y[:Nh], grad=False)
     t1 = time.perf_counter()
-    sr.sparse_eval(sp, sr.FITC, th, Uh, X[:Nh], y[:Nh], grad=True)
+    host_eval(sp, th, Uh, X[:Nh], y[:Nh], grad=True)
     t2 = time.perf_counter()
     print(json.dumps(dict(
-        tool='sparse_bench', method='FITC', kernel='SE-ARD', D=D, peak_tflops=PEAK_TFLOPS,
+        tool='sparse_bench', method=name.upper(), kernel='SE-ARD', D=D, peak_tflops=PEAK_TFLOPS,
         flops_are_model_counts=True, timing='HIP events (gpx_sparse_timings), median',
         reps=a.reps, warmup=a.warmup, points=points,
-        host_numpy=dict(N=Nh, p=ph, value_ms=(t1 - t0) * 1e3, grad_ms=(t2 - t1) * 1e3))))
+        host_numpy=dict(restatement=host_name, N=Nh, p=ph, value_ms=(t1 - t0) * 1e3, grad_ms=(t2 - t1) * 1e3))))
 
 
 if __name__ == '__main__':
