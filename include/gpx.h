@@ -312,11 +312,14 @@ int gpx_la_potrf_bench(gpx_t *h, int64_t n, int with_inverse, int reps,
  * topological order of the counter dependencies, final counters, spine order; stream = 1
  * the round-2 graph, 0 the round-1 graph. No GPU. */
 int gpx_panel_graph_check(int T, int workers, int stream, int *ntasks);
-/* co-residency of a panel launch over nmem members on a device of ncu CUs (host only): every
- * workgroup of the launch holds a whole CU, and all spine workgroups plus at least one worker
- * must be resident together for the launch to make progress. *nspwg = spine workgroups per
- * member the launch would use (3 / 2 / 1 by members, fewer if they would not fit), *workers =
- * the shared pool; < 0: even one spine workgroup per member does not fit. */
+/* the sizing rule of a MEMBER-BATCHED panel launch over nmem members on a device of ncu CUs
+ * (host only; the function the launch itself calls): every workgroup of the launch holds a
+ * whole CU, and all spine workgroups plus at least one worker must be resident together for
+ * the launch to make progress. *nspwg = spine workgroups per member (3 / 2 / 1 by members, or
+ * GPX_PANEL_MSPINE; fewer if they would not fit), *workers = the shared pool (250 workgroups in
+ * all, or GPX_PANEL_MWG); < 0: even one spine workgroup per member does not fit. A launch
+ * over a single matrix sizes itself separately (9 / 5 / 3 spine workgroups by split and fold,
+ * workers by the size of the matrix). */
 int gpx_panel_grid_check(int nmem, int ncu, int *nspwg, int *workers);
 /* the same for a wide panel launch: the block's T tiles plus E (0..8) tile columns to its
  * right, whose row-panel tiles and whose E x E diagonal block's update run inside the launch */

@@ -19,8 +19,8 @@ OBJ = os.path.join(CSRC, '_obj')
 LIB = os.path.join(HERE, 'libgpx.so')
 SOURCES = ['gpx_api.hip', 'kmat.hip', 'gemm_f64.hip', 'chol.hip', 'leaf.hip', 'panel.hip', 'vec.hip',
            'multi.hip', 'group.hip', 'sparse.hip']
-HEADERS = [os.path.join(CSRC, 'gpx_internal.h'), os.path.join(CSRC, 'gemm_tile.h'),
-           os.path.join(CSRC, 'leaf_dev.h'),
+HEADERS = [os.path.join(CSRC, 'gpx_internal.h'), os.path.join(CSRC, 'gpx_env.h'),
+           os.path.join(CSRC, 'gemm_tile.h'), os.path.join(CSRC, 'leaf_dev.h'),
            os.path.join(HERE, '..', 'include', 'gpx.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall',
          '-Wno-unused-function']

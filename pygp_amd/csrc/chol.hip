@@ -33,27 +33,8 @@
 
 #define LB GPX_TILE                    // leaf order
 
-// ---- environment knobs (developer experiments) --------------------------------
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
-#include <map>
 #include <vector>
-#include <mutex>
-#include <string>
-static int env_int(const char *name, int dflt)
-{
-    static std::map<std::string, int> cache;
-    static std::mutex mu;                       // handles may live on several threads
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find(name);
-    if (it != cache.end()) return it->second;
-    const char *e = getenv(name);
-    const int v = e ? atoi(e) : dflt;
-    cache[name] = v;
-    return v;
-}
-
 
 // ---- block copy (row panel -> scratch before its out-of-place multiply) ------
 __global__ __launch_bounds__(256) void copy_block_kernel(const double *__restrict__ src,
@@ -115,9 +96,7 @@ static int gate_bump(hipStream_t s, const DenseWs &w, int which)
 
 static int wide_level()
 {
-    static const int v = env_int("GPX_PANEL_WIDE", 0);
-    static const int graph = env_int("GPX_PANEL_STREAM", 1);   // the round-1 graph has no XS tasks
-    return graph ? v : 0;
+    return gpx_panel_streaming() ? gpx_env().panel_wide : 0;   // the round-1 graph has no XS tasks
 }
 
 // block (off, n) followed by `next` rows: can one wide launch take both?
@@ -167,9 +146,9 @@ static GemmArgs mk(const double *A, int lda, const double *B, int ldb, double *C
     g.flags = flags;
     g.tile = 0;
     g.order = 0;
-    g.swizzle = env_int("GPX_SWIZZLE", 0);
+    g.swizzle = gpx_env().swizzle;
     g.waves = 0;
-    g.use_lists = env_int("GPX_TILE_LISTS", 1);
+    g.use_lists = gpx_env().tile_lists;
     g.tiles = nullptr;
     return g;
 }
@@ -196,13 +175,13 @@ static int extend_inverse(hipStream_t s, const DenseWs &w, int off, int n, int n
     {
         GemmArgs g = mk(w.A + o12, ld, w.W + o22, ld, w.Kinv + o12, ld, n1, n2, n2, 1.0,
                         0.0, GEMM_KHI_N);
-        g.order = env_int("GPX_ORD_T", 2);
+        g.order = gpx_env().ord_t;
         GPX_TRY(gpx_gemm(s, 0, 0, g));
     }
     // W12 = -W11 T : op(A) = W11 upper -> k >= row tile
     return gpx_gemm(s, 0, 0,
                     mk(w.W + o11, ld, w.Kinv + o12, ld, w.W + o12, ld, n1, n2, n1, -1.0,
-                       0.0, GEMM_KLO_M | (env_int("GPX_KREV", 0) ? GEMM_KREV : 0)));
+                       0.0, GEMM_KLO_M | (gpx_env().krev ? GEMM_KREV : 0)));
 }
 
 // ---- lock-step sweep of a block of tiles over all members of a batched workspace ------
@@ -228,13 +207,8 @@ static int extend_inverse(hipStream_t s, const DenseWs &w, int off, int n, int n
 //   for s:  T = W[i0:s, i0:s] R[i0:s, s];  W[i0:s, s] = -T W_ss
 static bool sweep_on(const DenseWs &w)
 {
-    // members from which a workspace is swept in lock-step instead of by one panel launch
-    // with the members' task graphs interleaved (fewer members: the chain of one member is
-    // what takes the time, and the panel launch overlaps its steps)
-    static const int min_members = env_int("GPX_SWEEP_MIN_MEMBERS", 16);
     // (many members at a small order: one workgroup per member instead, gpx_panel_solo)
-    return w.batch > 1 && min_members > 0 && w.batch >= min_members && gpx_panel_streaming() &&
-           !gpx_panel_solo(w);
+    return gpx_sweep_members(w.batch) && gpx_panel_streaming() && !gpx_panel_solo(w);
 }
 
 static int sweep_block(hipStream_t s, const DenseWs &w, int off, int n, bool aug, bool inverse)
@@ -258,7 +232,7 @@ static int sweep_block(hipStream_t s, const DenseWs &w, int off, int n, bool aug
     // leaf: two launches a tile row instead of four.
     const bool lite = gpx_sweep_lite();
     const int depth = gpx_sweep_fold_depth(T);
-    const int ig = w.full_w && off == 0 && n == w.np && T > 8 ? T : 8;
+    const int ig = gpx_inverse_group(w.full_w, off, n, w.np);
     auto inverse_column = [&](hipStream_t st, int q) -> int {
         const int i0 = q / ig * ig;                        // inside the 1024-block of tile q (or all)
         if (q == i0) return 0;
@@ -276,7 +250,7 @@ static int sweep_block(hipStream_t s, const DenseWs &w, int off, int n, bool aug
         if (lite) {
             // first tile column the dense launch solves: (q, q+1) too (GPX_SWEEP_PRE=0: that one
             // stays with the fused task, which then solves it as well)
-            static const int pre = env_int("GPX_SWEEP_PRE", 1);
+            const int pre = gpx_env().sweep_pre;
             const int t0 = q + 1 < T && !pre ? q + 2 : q + 1;
             // Small matrices (up to GPX_SWEEP_RIGHT tiles): RIGHT-looking -- the dense launch of
             // row q applies step q-1 to every tile from row q down (the same order per tile),
@@ -292,8 +266,7 @@ static int sweep_block(hipStream_t s, const DenseWs &w, int off, int n, bool aug
             // (the right-hand-side tile stays out of the products: narrow, it takes ALL its
             // steps in the dense launch at an eighth of the cost -- as one of TW - q - 1 full
             // tile columns of these products it was a quarter of their work at 16 tiles)
-            static const int rhs_env = env_int("GPX_SWEEP_RHS_DENSE", 1);
-            const bool rhs_dense = aug && rhs_env && gpx_sweep_narrow();
+            const bool rhs_dense = aug && gpx_env().sweep_rhs_dense && gpx_sweep_narrow();
             const int ncols = TW - q - 1 - (rhs_dense ? 1 : 0);
             if (kf > 0) {                                  // the steps before kf: the tile engine
                 if (ncols > 0)
@@ -332,8 +305,7 @@ static int sweep_block(hipStream_t s, const DenseWs &w, int off, int n, bool aug
     // is ONE product nb tiles wide; each column then continues ITS sum over the rows of the
     // block (beta = 1: the accumulator starts from the stored partial sum, k still ascending --
     // the chain of the one-product form, the same bits) and takes its product with W_qq.
-    static const int nbenv = env_int("GPX_SWEEP_INVBLOCK", 4);
-    const int nb = std::max(1, std::min(nbenv, 8));
+    const int nb = gpx_env().sweep_invblock;                   // (1 .. 8)
     for (int b = 1; b < T;) {
         const int i0 = b / ig * ig;
         if (b == i0) {                                     // first tile of an inverse group: the leaf's
@@ -402,7 +374,7 @@ static int potrf_rec(hipStream_t s, const DenseWs &w, int off, int n, bool inver
         {
             GemmArgs g = mk(w.W + o11, ld, w.Kinv + o12, ld, w.A + o12, ld, n1, n2, n1, 1.0,
                             0.0, GEMM_KHI_M);
-            g.order = env_int("GPX_ORD_R12", 1);
+            g.order = gpx_env().ord_r12;
             GPX_TRY(gpx_gemm(s, 1, 0, g));
         }
         // A22 -= R12^T R12, upper tiles only: diagonal tiles in A, the others in Kinv
@@ -416,19 +388,9 @@ static int potrf_rec(hipStream_t s, const DenseWs &w, int off, int n, bool inver
 // ---- diagonal blocks of the right-looking driver ---------------------------------
 int gpx_block_layout(int np, int *offs, bool full_inverse)
 {
-    static const int split_last = env_int("GPX_SPLIT_LAST", 0);
-    static const int env0 = env_int("GPX_NB0", 0), env = env_int("GPX_NB", 0);
-    static std::vector<int> list;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        const char *e = getenv("GPX_BLOCKS");
-        while (e && *e) {
-            const int v = atoi(e);
-            if (v >= LB && v % LB == 0) list.push_back(v);
-            e = strchr(e, ',');
-            if (e) ++e;
-        }
-    });
+    const int split_last = gpx_env().split_last;
+    const int env0 = gpx_env().nb0, env = gpx_env().nb;
+    const std::vector<int> &list = gpx_env().blocks;
     int count = 0, at = 0;
     offs[0] = 0;
     if (!list.empty()) {
@@ -493,7 +455,7 @@ static int inverse_column(hipStream_t s, const DenseWs &w, const Blocks &bl, int
     // default: up to np = 8192, where the chain of diagonal blocks is the critical path
     // (N = 2048 1.13 -> 1.09 ms, 4096 2.64 -> 2.55, 8192 10.90 -> 10.87); above, the large
     // product beside the diagonal block only takes CUs from it (N = 16384 69.3 -> 69.8 ms)
-    static const int early_env = env_int("GPX_INVCOL_EARLY", -1);
+    const int early_env = gpx_env().invcol_early;
     const bool early_on = early_env >= 0 ? early_env != 0 : w.np <= 8192;
     const int ld = w.ld, ok = bl.off(k), nk = bl.len(k);
     const size_t okk = (size_t)ok * ld + ok;
@@ -501,11 +463,11 @@ static int inverse_column(hipStream_t s, const DenseWs &w, const Blocks &bl, int
         if (early) GPX_EV(hipStreamWaitEvent(s, early, 0));
         GPX_TRY(gpx_gemm(s, 0, 0,
                          mk(w.W, ld, w.A + ok, ld, w.Kinv + ok, ld, ok, nk, ok, 1.0, 0.0,
-                            GEMM_KLO_M | (env_int("GPX_KREV_INVCOL", 0) ? GEMM_KREV : 0))));
+                            GEMM_KLO_M | (gpx_env().krev_invcol ? GEMM_KREV : 0))));
         if (late) GPX_EV(hipStreamWaitEvent(s, late, 0));
         GemmArgs g = mk(w.Kinv + ok, ld, w.W + okk, ld, w.W + ok, ld, ok, nk, nk, -1.0, 0.0,
                         GEMM_KHI_N);
-        g.order = env_int("GPX_ORD_T", 2);
+        g.order = gpx_env().ord_t;
         GPX_TRY(gpx_gemm(s, 0, 0, g));
     } else {
         if (late) GPX_EV(hipStreamWaitEvent(s, late, 0));
@@ -513,12 +475,12 @@ static int inverse_column(hipStream_t s, const DenseWs &w, const Blocks &bl, int
             {
                 GemmArgs g = mk(w.A + ok, ld, w.W + okk, ld, w.Kinv + ok, ld, ok, nk, nk, 1.0, 0.0,
                                 GEMM_KHI_N);
-                g.order = env_int("GPX_ORD_T", 2);
+                g.order = gpx_env().ord_t;
                 GPX_TRY(gpx_gemm(s, 0, 0, g));
             }
             GPX_TRY(gpx_gemm(s, 0, 0,
                              mk(w.W, ld, w.Kinv + ok, ld, w.W + ok, ld, ok, nk, ok, -1.0, 0.0,
-                                GEMM_KLO_M | (env_int("GPX_KREV_INVCOL", 0) ? GEMM_KREV : 0))));
+                                GEMM_KLO_M | (gpx_env().krev_invcol ? GEMM_KREV : 0))));
         }
     }
     if (after_w) GPX_HIP(hipEventRecord(after_w, s));        // block column k of R^-1 is in
@@ -544,10 +506,7 @@ static int inverse_column(hipStream_t s, const DenseWs &w, const Blocks &bl, int
 // up to 253 CUs. GPX_PANEL_WHOLE=<largest order> (0: off).
 bool gpx_potrf_whole(const DenseWs &w, int mode)
 {
-    static const int whole_max = [] {
-        const int v = env_int("GPX_PANEL_WHOLE", GPX_PANEL_WHOLE_DEFAULT);
-        return v < 0 ? 0 : (v > GPX_PANEL_WHOLE_MAX ? GPX_PANEL_WHOLE_MAX : v);
-    }();
+    const int whole_max = gpx_env().panel_whole;           // (0 .. GPX_PANEL_WHOLE_MAX)
     if (mode != GPX_POTRF_R || w.np > whole_max || w.np <= GPX_PANEL_MAX || !w.pctl) return false;
     const Blocks bl(w.np, false);
     bool regular = true;                               // blocks of 1024, the last one any
@@ -569,8 +528,7 @@ bool gpx_potrf_whole(const DenseWs &w, int mode)
 // the bits of its single evaluation. GPX_GRAD_WHOLE = largest padded order (0: never).
 int gpx_grad_mode(const DenseWs &w)
 {
-    static const int grad_whole = env_int("GPX_GRAD_WHOLE", 4096);
-    if (w.np <= grad_whole && gpx_potrf_whole(w, GPX_POTRF_R)) return GPX_POTRF_R;
+    if (w.np <= gpx_env().grad_whole && gpx_potrf_whole(w, GPX_POTRF_R)) return GPX_POTRF_R;
     return GPX_POTRF_KINV;
 }
 
@@ -586,15 +544,13 @@ int gpx_grad_mode(const DenseWs &w)
 // primary pattern (optimize()). profiles/r05_full_w_ab.txt.
 bool gpx_grad_full_w(const DenseWs &w, int mode)
 {
-    static const int full_max = env_int("GPX_GRAD_FULL_W", 4096);
-    return w.np <= full_max && mode == GPX_POTRF_R && Blocks(w.np).count > 1 &&
+    return w.np <= gpx_env().grad_full_w && mode == GPX_POTRF_R && Blocks(w.np).count > 1 &&
            gpx_potrf_whole(w, mode);
 }
 
 bool gpx_potrf_rhs_ok(const DenseWs &w, int mode)
 {
-    static const bool on = !(getenv("GPX_PANEL_RHS") && !atoi(getenv("GPX_PANEL_RHS")));
-    if (!on || w.ld < w.np + LB || !w.pctl) return false;
+    if (!gpx_env().panel_rhs || w.ld < w.np + LB || !w.pctl) return false;
     if (gpx_potrf_whole(w, mode)) return true;
     // one block that is one panel launch (or one sweep) of at least two tiles
     return Blocks(w.np, mode == GPX_POTRF_KINV).count == 1 && w.np >= 2 * LB &&
@@ -648,7 +604,7 @@ int gpx_potrf(hipStream_t s, const DenseWs &w, int mode, bool offdiag_staged)
     // look-ahead needs the extra streams and two events per block
     const bool ahead = w.crit && w.bulk && w.aux && w.events && nb <= GPX_MAX_BLOCKS &&
                        w.batch <= 1;
-    static const int overlap_env = env_int("GPX_OVERLAP_NOSPLIT", 1);
+    const int overlap_env = gpx_env().overlap_nosplit;
     struct OverlapScope {
         explicit OverlapScope(int v) { tl_overlap = v; }
         ~OverlapScope() { tl_overlap = 0; }
@@ -660,7 +616,7 @@ int gpx_potrf(hipStream_t s, const DenseWs &w, int mode, bool offdiag_staged)
     // drain tails (75.9 against 76.8 ms per evaluation at N = 16384; with 248 instead
     // of 224 CUs for the products it was the other way round, the third stream's
     // backlog ending up serial). GPX_AUX=0: they follow the trailing update on `bulk`.
-    static const int aux_on = env_int("GPX_AUX", 1);
+    const int aux_on = gpx_env().aux;
     hipStream_t aux = ahead && aux_on ? w.aux : bulk;
     hipEvent_t *F = w.events, *D = w.events + GPX_MAX_BLOCKS;
     hipEvent_t evJoin = ahead ? w.events[4 * GPX_MAX_BLOCKS] : nullptr;
@@ -676,7 +632,7 @@ int gpx_potrf(hipStream_t s, const DenseWs &w, int mode, bool offdiag_staged)
     // they run on `crit` itself, right behind F_k (high priority, every CU), the far update
     // of a step hands over its first diagonal block (event TD) before it goes on, and
     // `bulk` keeps the rest.
-    static const int fast_env = env_int("GPX_FASTCHAIN", 1);
+    const int fast_env = gpx_env().fastchain;
     const bool fast = ahead && fast_env != 0;
     hipEvent_t *G = w.events + 2 * GPX_MAX_BLOCKS;       // row k+1 carries update k
     hipEvent_t *TD = w.events + 3 * GPX_MAX_BLOCKS;      // block (k+2,k+2) carries update k
@@ -725,7 +681,7 @@ int gpx_potrf(hipStream_t s, const DenseWs &w, int mode, bool offdiag_staged)
                 {
                     GemmArgs g = mk(w.W + okk, ld, w.Kinv + ok1, ld, w.A + ok1, ld, nk, n1, nk,
                                     1.0, 0.0, GEMM_KHI_M);
-                    g.order = env_int("GPX_ORD_R12", 1);
+                    g.order = gpx_env().ord_r12;
                     GPX_TRY(gpx_gemm(crit, 1, 0, g));
                 }
                 if (k >= 1) GPX_EV(hipStreamWaitEvent(crit, TD[k - 1], 0));
@@ -736,7 +692,7 @@ int gpx_potrf(hipStream_t s, const DenseWs &w, int mode, bool offdiag_staged)
             if (rest > n1) {
                 GemmArgs g = mk(w.W + okk, ld, w.Kinv + ok1 + n1, ld, w.A + ok1 + n1, ld, nk,
                                 rest - n1, nk, 1.0, 0.0, GEMM_KHI_M);
-                g.order = env_int("GPX_ORD_R12", 1);
+                g.order = gpx_env().ord_r12;
                 GPX_TRY(gpx_gemm(bulk, 1, 0, g));
             }
             GPX_EV(hipStreamWaitEvent(bulk, D[k + 1], 0));       // R[k,k+1] is in A
@@ -778,7 +734,7 @@ int gpx_potrf(hipStream_t s, const DenseWs &w, int mode, bool offdiag_staged)
             if (rest > skip) {
                 GemmArgs g = mk(w.W + okk, ld, w.Kinv + ok1 + skip, ld, w.A + ok1 + skip, ld, nk,
                                 rest - skip, nk, 1.0, 0.0, GEMM_KHI_M);
-                g.order = env_int("GPX_ORD_R12", 1);
+                g.order = gpx_env().ord_r12;
                 GPX_TRY(gpx_gemm(bulk, 1, 0, g));
             }
             // update k of the next diagonal block first: F_k+1 can start
@@ -894,7 +850,7 @@ int gpx_lauum(hipStream_t s, const DenseWs &w)
     const int n = w.np, ld = w.ld;
     GemmArgs g = mk(w.W, ld, w.W, ld, w.Kinv, ld, n, n, n, 1.0, 0.0,
                     GEMM_UPPER_ONLY | GEMM_KLO_M | GEMM_KLO_N |
-                        (env_int("GPX_KREV", 0) ? GEMM_KREV : 0));
-    g.order = env_int("GPX_ORD_LAUUM", 0);
+                        (gpx_env().krev ? GEMM_KREV : 0));
+    g.order = gpx_env().ord_lauum;
     return gpx_gemm(s, 0, 1, g);
 }

@@ -286,7 +286,7 @@ int gpx_gemm_concurrent(int device)
 // must cut the same list, whatever another thread does to the count in between.
 static int tile_order(int device)
 {
-    static const int xcd_env = getenv("GPX_TILE_XCD") ? atoi(getenv("GPX_TILE_XCD")) : -1;
+    const int xcd_env = gpx_env().tile_xcd;
     return xcd_env >= 0 ? xcd_env : (gpx_gemm_concurrent(device) > 0 ? 0 : 1);
 }
 
@@ -428,7 +428,7 @@ static void log_launch(hipStream_t s, int ta, int tb, int tile, const GemmArgs &
     std::lock_guard<std::mutex> lock(mu);
     if (!init) {
         init = true;
-        const char *e = getenv("GPX_GEMM_LOG");
+        const char *e = gpx_env().gemm_log;
         if (e && *e) f = fopen(e, "w");
     }
     if (!f) return;
@@ -512,12 +512,6 @@ static int dispatch(hipStream_t s, int ta, int tb, const GemmArgs &g, const Laun
     return launch<1, 1, G>(s, g, lc, part);
 }
 
-static int env_choice(const char *name)
-{
-    const char *e = getenv(name);
-    return e ? atoi(e) : 0;
-}
-
 __global__ void gpx_jitter_kernel(long long ticks)
 {
     const long long t0 = wall_clock64();
@@ -526,17 +520,12 @@ __global__ void gpx_jitter_kernel(long long ticks)
 
 int gpx_test_jitter(hipStream_t s)
 {
-    static const char *env = getenv("GPX_TEST_JITTER");
-    if (!env) return 0;
+    if (!gpx_env().test_jitter) return 0;
     static std::mutex mu;
     static unsigned long long state = 0;
-    static int max_us = 300;
+    const int max_us = gpx_env().test_jitter_max_us;
     std::lock_guard<std::mutex> lock(mu);
-    if (state == 0) {
-        state = 0x9E3779B97F4A7C15ull ^ (unsigned long long)atoll(env);
-        const char *c = strchr(env, ':');
-        if (c) max_us = atoi(c + 1);
-    }
+    if (state == 0) state = 0x9E3779B97F4A7C15ull ^ (unsigned long long)gpx_env().test_jitter_seed;
     state = state * 6364136223846793005ull + 1442695040888963407ull;
     const unsigned r = (unsigned)(state >> 33);
     if (r & 1) return 0;
@@ -562,9 +551,9 @@ int gpx_gemm(hipStream_t s, int ta, int tb, const GemmArgs &g)
     // quarter the serial K-loop latency of each workgroup
     long long tiles = (long long)(g.M / 128) * (g.N / 128) * (g.batch > 0 ? g.batch : 1);
     if (g.flags & GEMM_UPPER_ONLY) tiles = tiles / 2 + g.M / 256;
-    static const int big_cfg = env_choice("GPX_GEMM_BIG");       // 4 or 8 (waves)
-    static const int small_cfg = env_choice("GPX_GEMM_SMALL");
-    static const int small_below = env_choice("GPX_GEMM_SMALL_BELOW");
+    const int big_cfg = gpx_env().gemm_big;                     // 4 or 8 (waves)
+    const int small_cfg = gpx_env().gemm_small;
+    const int small_below = gpx_env().gemm_small_below;
     const int threshold = small_below > 0 ? small_below : 400;
     int tile = g.tile;
     if (tile == 0) tile = tiles < threshold ? 64 : 128;
@@ -573,7 +562,7 @@ int gpx_gemm(hipStream_t s, int ta, int tb, const GemmArgs &g)
     // on 512 slots -- the launch took as long as its longest tile, 1.24 ms for 0.75 ms of
     // work): 64-tiles quarter the longest one. Estimated from the k-ranges, in units of
     // one 128-tile k-step; 64-tiles are charged 8 % for their lower efficiency.
-    static const int balance_on = env_choice("GPX_GEMM_NOBALANCE") ? 0 : 1;
+    const int balance_on = gpx_env().gemm_nobalance ? 0 : 1;
     const int kstruct_ = g.flags & (GEMM_KLO_M | GEMM_KHI_M | GEMM_KLO_N | GEMM_KHI_N);
     if (balance_on && g.tile == 0 && tile == 128 && kstruct_ && g.use_lists && g.batch <= 1 &&
         g.kchunk == 0) {
@@ -598,7 +587,7 @@ int gpx_gemm(hipStream_t s, int ta, int tb, const GemmArgs &g)
     // equal-k launches (rank-k updates, rectangular products): whole rounds of 128-tiles,
     // the rest as 64-tiles, when that is cheaper than a last round that is mostly empty
     // (a row panel of 896 tiles on 512 slots: 1.75 instead of 2 tile times)
-    static const int split_on = env_choice("GPX_GEMM_NOSPLIT") ? 0 : 1;
+    const int split_on = gpx_env().gemm_nosplit ? 0 : 1;
     const int kstruct = g.flags & (GEMM_KLO_M | GEMM_KHI_M | GEMM_KLO_N | GEMM_KHI_N);
     if (split_on && !g.overlap && g.tile == 0 && tile == 128 && !kstruct && g.use_lists &&
         g.batch <= 1 && g.kchunk == 0 && !g.waves && !big_cfg && !small_cfg) {

@@ -150,12 +150,7 @@ static inline int round_up(int64_t x, int m) { return (int)((x + m - 1) / m * m)
 // 256 B) rotate consecutive rows over the channels.
 static int ld_for(int np)
 {
-    static const int pad = [] {
-        const char *e = getenv("GPX_LDPAD");
-        const int v = e ? atoi(e) : 32;
-        return v < 0 || v % 2 ? 32 : v;
-    }();
-    return np + pad;
+    return np + gpx_env().ldpad;                    // (even, at least 0)
 }
 
 #define CHECK_H(h)                                                             \
@@ -348,7 +343,7 @@ static int twin_pool_stream(int device, int index, const std::vector<hipStream_t
     // earlier in the chain: not on the same queue, not one of the bad pairs (cost 3.5+
     // against 1.6-1.7; the threshold sits well above what host-side timing adds); failing
     // that, the best of the ones on queues of their own
-    static const bool probe = !(getenv("GPX_TWIN_PROBE") && !atoi(getenv("GPX_TWIN_PROBE")));
+    const bool probe = gpx_env().twin_probe != 0;
     int pick = (index - 1) % GPX_TWIN_POOL;
     double best = 1e30, alone = 0.0;
     for (int k = 0; probe && k < GPX_TWIN_POOL; ++k) {
@@ -361,8 +356,7 @@ static int twin_pool_stream(int device, int index, const std::vector<hipStream_t
             }
             worst = std::max(worst, stream_pair_cost(a, p.stream[c], &alone));
         }
-        static const bool log = getenv("GPX_TWIN_LOG") != nullptr;
-        if (log) fprintf(stderr, "gpx: batch context %d, pool stream %d: cost %.2f\n", index, c, worst);
+        if (gpx_env().twin_log) fprintf(stderr, "gpx: batch context %d, pool stream %d: cost %.2f\n", index, c, worst);
         if (worst < best) {
             best = worst;
             pick = c;
@@ -380,7 +374,7 @@ static void twin_pool_release(int device)
     TwinPool &p = g_twin_pool[device];
     std::lock_guard<std::mutex> lock(p.mu);
     if (p.users > 0 && --p.users == 0 && p.made) {
-        static const bool dlog = getenv("GPX_DESTROY_LOG") != nullptr;
+        const bool dlog = gpx_env().destroy_log;
         for (int i = 0; i < GPX_TWIN_POOL; ++i) {
             if (dlog) {
                 fprintf(stderr, "twin_pool_release: stream %d\n", i);
@@ -395,8 +389,7 @@ static void twin_pool_release(int device)
 
 static bool lookahead_enabled()
 {
-    static const bool on = !(getenv("GPX_LOOKAHEAD") && !atoi(getenv("GPX_LOOKAHEAD")));
-    return on;
+    return gpx_env().lookahead != 0;
 }
 
 // streams and events of the look-ahead (chol.hip) for context h on the current device. A
@@ -415,8 +408,7 @@ static int create_lookahead_streams(gpx_ctx *h)
     // kernels and trailing updates of ONE member have nothing to run side by side for (the
     // updates wait for the build, the vector kernels for them). GPX_TWIN_OWN_BULK=0: a
     // stream of its own, as before.
-    static const bool own_bulk = !(getenv("GPX_TWIN_OWN_BULK") && !atoi(getenv("GPX_TWIN_OWN_BULK")));
-    if (h->stream_borrowed && own_bulk) {
+    if (h->stream_borrowed && gpx_env().twin_own_bulk) {
         h->bulk = h->stream;
         h->bulk_borrowed = true;
     } else {
@@ -493,7 +485,7 @@ int gpx_create(int device, gpx_t **out)
 int gpx_destroy(gpx_t *h)
 {
     if (!h) return 0;
-    static const bool dlog = getenv("GPX_DESTROY_LOG") != nullptr;
+    const bool dlog = gpx_env().destroy_log;
 #define DLOG(msg) do { if (dlog) { fprintf(stderr, "gpx_destroy %p: %s\n", (void *)h, msg); fflush(stderr); } } while (0)
     DLOG("enter");
     if (h->twin) {
@@ -812,7 +804,7 @@ static int enqueue_update(gpx_ctx *h, StageClock &clk, int mode, bool grad_follo
     // from which the factorisation's panel products read them. With look-ahead the
     // rows of the first diagonal block are built first and that block is factored
     // while the rest of the matrix is still being built.
-    static const int lead_on = getenv("GPX_LEAD_BUILD") ? atoi(getenv("GPX_LEAD_BUILD")) : 1;
+    const int lead_on = gpx_env().lead_build;
     // (two blocks when the first launch may be a wide panel, chol.hip)
     const GpxBlocks lb(h->np, mode == GPX_POTRF_KINV);
     const int lead_rows = lb.count >= 2 && lb.len(1) <= GPX_PANEL_MAX ? lb.off(2) : lb.len(0);
@@ -826,8 +818,7 @@ static int enqueue_update(gpx_ctx *h, StageClock &clk, int mode, bool grad_follo
         // test hook (tests/test_gpu_la.py): hold the rest of the build back, so that an
         // ordering bug between it and what follows the first diagonal block shows every
         // time instead of once in a busy batch
-        static const int hold_us = getenv("GPX_TEST_HOLD_BUILD_US")
-                                       ? atoi(getenv("GPX_TEST_HOLD_BUILD_US")) : 0;
+        const int hold_us = gpx_env().test_hold_build_us;
         if (hold_us > 0)
             hipLaunchKernelGGL(hold_kernel, dim3(1), dim3(64), 0, h->stream,
                                (long long)hold_us * 100);
@@ -843,7 +834,7 @@ static int enqueue_update(gpx_ctx *h, StageClock &clk, int mode, bool grad_follo
     }
     clk.tick(T_BUILD);
     // with the gradient in view, R^-1 and (R^T R)^-1 are built beside the factorisation
-    static const int defer_on = getenv("GPX_DEFER_KINV") ? atoi(getenv("GPX_DEFER_KINV")) : 1;
+    const int defer_on = gpx_env().defer_kinv;
     w.defer_kinv = grad_follows && defer_on && mode == GPX_POTRF_KINV;
     h->kinv_pending = w.defer_kinv;
     h->lz_enqueued = false;              // (a failed evaluation may have left it set)
@@ -1280,11 +1271,7 @@ int gpx_loglik_batch(gpx_t *h, const gpx_kspec *k, const double *thetas, int64_t
     // Independent evaluations: keep a few in flight (own stream + workspace each) so
     // that the latency-bound diagonal-block chain of one overlaps the MFMA-bound
     // trailing updates of the other. GPX_BATCH_INFLIGHT=1 restores one at a time.
-    static const int inflight = [] {
-        const char *e = getenv("GPX_BATCH_INFLIGHT");
-        const int v = e ? atoi(e) : 3;    // measured best at N = 4096 .. 16384
-        return v < 1 || v > 8 ? 3 : v;
-    }();
+    const int inflight = gpx_env().batch_inflight;   // (1 .. 8; 3 measured best at N = 4096 .. 16384)
     int depth = (int)std::min<int64_t>(B > 1 ? inflight : 1, B > 0 ? B : 1);
     // every context holds three np x ld matrices: stay well inside 288 GB of HBM
     const double ws_bytes = 3.0 * h->np * (double)h->ld * 8;
@@ -1301,7 +1288,7 @@ int gpx_loglik_batch(gpx_t *h, const gpx_kspec *k, const double *thetas, int64_t
     // 82.8 -> 81.4; N = 10240 54.8 -> 55.3 / 137 -> 128; N = 8192 (64 thetas) 103 -> 104 /
     // 251 -> 217: on from np = 12288 with gradients, from 16384 without
     // (GPX_BATCH_LOOKAHEAD=0 / 1 forces). Four members in flight this way collapse.
-    static const int batch_la_env = getenv("GPX_BATCH_LOOKAHEAD") ? atoi(getenv("GPX_BATCH_LOOKAHEAD")) : -1;
+    const int batch_la_env = gpx_env().batch_lookahead;
     const bool batch_la = depth > 1 && depth <= 3 && lookahead_enabled() &&
                           (batch_la_env >= 0 ? batch_la_env != 0
                                              : (h->np >= 16384 || (grad && h->np >= 12288)));
@@ -1973,11 +1960,7 @@ int gpx_la_gemm_bench_ex(gpx_t *h, int ta, int tb, int64_t n, int flags, int ord
         return -1;
     }
     // GPX_BENCH_LDPAD: row stride n + pad, as the factorisation workspaces have
-    static const int ldpad = [] {
-        const char *e = getenv("GPX_BENCH_LDPAD");
-        const int v = e ? atoi(e) : 0;
-        return v < 0 || v % 2 ? 0 : v;
-    }();
+    const int ldpad = gpx_env().bench_ldpad;        // (even, at least 0)
     const size_t ldn = (size_t)n + ldpad;
     const size_t cnt = (size_t)n * ldn;
     const bool fresh = h->t0.bytes < cnt * 8 || h->t1.bytes < cnt * 8 ||

@@ -15,6 +15,10 @@
 #define GPX_PANEL_MAX 1024    // largest diagonal block factored by one panel launch
 #define GPX_PANEL_WHOLE_MAX 4096   // largest whole matrix factored by one panel launch
 #define GPX_PANEL_WHOLE_DEFAULT 4096   // ... by default (GPX_PANEL_WHOLE)
+#define PANEL_IG 8             // tiles per inverse group: W is assembled inside the 1024-blocks
+                               // of the blocked driver only, whatever the launch covers
+
+#include "gpx_env.h"           // the developer switches (environment), read once
 
 // ---- error plumbing --------------------------------------------------------
 void gpx_set_error(const char *fmt, ...);
@@ -340,6 +344,21 @@ int *gpx_panel_gates(const DenseWs &w);
 // that runs the member's whole task graph (panel.hip) instead of the lock-step sweep
 bool gpx_panel_solo(const DenseWs &w);
 bool gpx_panel_solo_np(int np, int members);
+// members from which a workspace is swept in lock-step instead of by one panel launch with
+// the members' task graphs interleaved (fewer members: the chain of one member is what takes
+// the time, and the panel launch overlaps its steps); GPX_SWEEP_MIN_MEMBERS, 0: never
+static inline bool gpx_sweep_members(int members)
+{
+    const int min_members = gpx_env().sweep_min_members;
+    return members > 1 && min_members > 0 && members >= min_members;
+}
+// tiles per inverse group of a launch or sweep over the block (off, n) of a matrix of padded
+// order np: a launch over the WHOLE matrix with full_w leaves all of R^-1 behind
+static inline int gpx_inverse_group(bool full_w, int off, int n, int np)
+{
+    const int T = n / GPX_TILE;
+    return full_w && off == 0 && n == np && T > PANEL_IG ? T : PANEL_IG;
+}
 int gpx_sweep_phase(hipStream_t s, const DenseWs &w, int off, int T, bool aug, int phase,
                     bool no_inverse, bool fused_only = false, bool presolved = false);
 // the row-panel tiles (s, t >= t0) of every member as one dense launch: each tile takes its

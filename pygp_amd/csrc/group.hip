@@ -122,12 +122,6 @@ struct GpxGroups {
 
 namespace {
 
-int env_int(const char *name, int dflt)
-{
-    const char *e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
 int ld_for_group(int np)
 {
     // room for the right-hand-side tile column of a whole-matrix launch, plus the padding
@@ -177,8 +171,7 @@ int slot_reserve(Slot &s, int cap, int np, bool inverse)
 // panel keeps a few CUs busy), few enough that two groups fit into HBM many times over
 int members_per_group(int np, bool grad)
 {
-    static const int forced = env_int("GPX_GROUP_MEMBERS", 0);
-    if (forced > 0) return std::min(forced, 256);
+    if (gpx_env().group_members > 0) return gpx_env().group_members;   // (at most 256)
     (void)grad;
     // (64 thetas at N = 8192, value-only / with gradients: 4 members per group 255 / 102
     // evals/s, 8: 276 / 106, 16: 306 / 110, 32: 320 / 113 -- from 16 on swept in lock-step)
@@ -206,31 +199,17 @@ int members_per_group(int np, bool grad)
 // (tools/attic/r04_exp12.py, contexts -> group, evals/s: N = 9000 B = 2 120 -> 150 value-only,
 // 61 -> 68 with gradients; B = 3 113 -> 167, 59 -> 72; N = 12000 B = 3 62 -> 84, 29 -> 33;
 // N = 16384 B = 2 35.0 -> 36.8, 14.20 -> 14.02; B = 3 34.6 -> 38.7, 14.19 -> 14.33): 2.
-int gpx_groups_min_big()
-{
-    static const int v = [] {
-        const int e = env_int("GPX_GROUP_MIN_BIG", 2);
-        return e < 2 ? 2 : e;
-    }();
-    return v;
-}
+int gpx_groups_min_big() { return gpx_env().group_min_big; }   // (at least 2)
 
-int gpx_groups_max_np()
-{
-    static const int v = [] {
-        // (32768 since the end of round 4: N = 20000 / 24000 / 32768, two or three thetas,
-        // 1-8 % faster than the contexts and bit-equal to single evaluations,
-        // tools/attic/r04_exp13.py, r04_exp14.py; 26 GB of workspaces per member at the top)
-        const int e = env_int("GPX_GROUP_MAX_NP", 32768);
-        return e < 0 ? 0 : e;
-    }();
-    return v;
-}
+// (32768 since the end of round 4: N = 20000 / 24000 / 32768, two or three thetas, 1-8 % faster
+// than the contexts and bit-equal to single evaluations, tools/attic/r04_exp13.py,
+// r04_exp14.py; 26 GB of workspaces per member at the top)
+int gpx_groups_max_np() { return gpx_env().group_max_np; }     // (at least 0)
 
 void gpx_groups_destroy(GpxGroups *g)
 {
     if (!g) return;
-    static const bool dlog = getenv("GPX_DESTROY_LOG") != nullptr;
+    const bool dlog = gpx_env().destroy_log;
 #define DLOG(...) do { if (dlog) { fprintf(stderr, "groups_destroy: " __VA_ARGS__); fputc('\n', stderr); fflush(stderr); } } while (0)
     (void)hipSetDevice(g->device);
     int si = 0;
@@ -459,10 +438,7 @@ static int group_harvest(GpxGroups *g, Slot &s, int n, int nth, double *lZ, doub
 static int groups_plan(const GpxGroups *g, int np, int64_t B, bool grad, int *m_out,
                        int *nslots_out)
 {
-    static const int inflight_env = [] {
-        const int v = env_int("GPX_GROUP_INFLIGHT", 0);
-        return v < 1 || v > 4 ? 0 : v;
-    }();
+    const int inflight_env = gpx_env().group_inflight;       // (1 .. 4, or 0: by size)
     // two groups in flight up to np = 8192; above, one (see members_per_group)
     const int inflight = inflight_env > 0 ? inflight_env : (np <= 8192 ? 2 : 1);
     int m = (int)std::min<int64_t>(members_per_group(np, grad), std::max<int64_t>(B, 1));
@@ -547,9 +523,7 @@ int gpx_groups_plan(const GpxGroups *g, int np, int64_t B, bool grad, int *membe
                     int *lockstep)
 {
     GPX_TRY(groups_plan(g, np, B, grad, members, inflight));
-    // (chol.hip: sweep_on)
-    const int min_members = env_int("GPX_SWEEP_MIN_MEMBERS", 16);
-    *lockstep = *members > 1 && min_members > 0 && *members >= min_members ? 1 : 0;
+    *lockstep = gpx_sweep_members(*members) ? 1 : 0;
     // (panel.hip: one workgroup per member instead of the sweep, unless the handle is in safe mode)
     if (*lockstep && !(g && g->no_panel) && gpx_panel_solo_np(np, *members)) *lockstep = 2;
     return 0;

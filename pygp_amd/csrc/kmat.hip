@@ -689,7 +689,7 @@ static int kbuild_launch(hipStream_t s, const KParams &kp, const T *X1, int n1, 
                          int ntj, int tile_rows, bool triangular,
                          const MemberBatch *mb = nullptr)
 {
-    static const int forced = getenv("GPX_KBUILD_W") ? atoi(getenv("GPX_KBUILD_W")) : 0;
+    const int forced = gpx_env().kbuild_w;
     const bool together = kp.nparts * d <= GPX_MAX_DIM;
     const int rows = together ? kp.nparts * d : d;
     int W = together ? 4 : 1;
@@ -1357,7 +1357,7 @@ int gpx_trace_grad(hipStream_t s, const KParams &kp, const double *X, int n, int
     for (int p = 0; p < kp.nparts; ++p)
         simple = simple && (kp.part[p].kind == GPX_SE || kp.part[p].kind == GPX_MATERN1 ||
                             kp.part[p].kind == GPX_MATERN3 || kp.part[p].kind == GPX_MATERN5);
-    static const int rows_env = getenv("GPX_TRACE_ROWS") ? atoi(getenv("GPX_TRACE_ROWS")) : 16;
+    const int rows_env = gpx_env().trace_rows;
     if (simple && rows_env > 0) {
         // row-persistent kernel: C column chunks per 64-row block
         const int C = std::min(T, rows_env);

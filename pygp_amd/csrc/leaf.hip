@@ -48,11 +48,8 @@ int gpx_leaf2_init()
 int gpx_potrf_leaf2(hipStream_t s, double *Ablk, int lda, double *Wblk, int ldw, int *info,
                     int goff, int batch, long long mstride)
 {
-    static const int skip = [] {
-        const char *e = getenv("GPX_LEAF_SKIP");
-        const char *m = getenv("GPX_LEAF_MFMA");           // 0: register factorisation of the
-        return (e ? atoi(e) : 0) | (m && !atoi(m) ? 32 : 0);   // 16 x 16 blocks (rounds 1-2)
-    }();
+    // (GPX_LEAF_MFMA=0: register factorisation of the 16 x 16 blocks, rounds 1-2)
+    const int skip = gpx_env().leaf_skip | (gpx_env().leaf_mfma ? 0 : 32);
     hipLaunchKernelGGL(potrf_leaf2_kernel, dim3(batch > 1 ? batch : 1), dim3(256), LEAF2_LDS, s,
                        Ablk, lda, Wblk, ldw, info, goff, skip, mstride);
     GPX_HIP(hipGetLastError());

@@ -213,7 +213,7 @@ static int multi_run(const char *what, int ndev, int64_t B, int width, const dou
     // partition, packing and scatter -- and the ONE collective is replaced by the
     // concatenation ncclAllGather would deliver (RCCL refuses a communicator with one GPU
     // twice). Everything but the wire is exercised; never set in production.
-    static const bool fake = getenv("GPX_MULTI_FAKE") && atoi(getenv("GPX_MULTI_FAKE"));
+    const bool fake = gpx_env().multi_fake != 0;
     if (have < 1 || (ndev > have && !fake)) {
         gpx_set_error("%s: %d devices asked for, %d present", what, ndev, have);
         return -1;
@@ -231,7 +231,7 @@ static int multi_run(const char *what, int ndev, int64_t B, int width, const dou
 
     // GPX_MULTI_FORCE_RCCL=1 sends a one-device call through the collective too (the
     // rehearsal of the gather on a one-GPU box)
-    static const bool force = getenv("GPX_MULTI_FORCE_RCCL") && atoi(getenv("GPX_MULTI_FORCE_RCCL"));
+    const bool force = gpx_env().multi_force_rccl != 0;
     const bool gather = ndev > 1 || force;
     const int64_t slot = gpx_multi_slot(B, ndev);            // members per device slot
     std::vector<std::vector<double>> loc(ndev);

@@ -93,8 +93,6 @@
 // fewer) and are never cleared
 #define PCTL_TMAX (GPX_PANEL_WHOLE_MAX / 128)
 #define PCTL_GATES (PCTL_HEAD + (PCTL_TMAX + 1) * (PCTL_TMAX + 1) + 2 * PCTL_TMAX * PCTL_TMAX + PCTL_TMAX)
-#define PANEL_IG 8          // tiles per inverse group: W is assembled inside the 1024-blocks
-                            // of the blocked driver only, whatever the launch covers
 #define SUB 64              // edge of a product task
 
 // Task offsets are stored for a SYMBOLIC row stride of PT_LD elements (row * PT_LD + column,
@@ -1751,8 +1749,7 @@ struct Graph {
     // / 2.15 / 2.155 / 2.165 / 2.27 / 2.26; N <= 3072 within noise.
     static double chain_us(double us)
     {
-        static const double f = getenv("GPX_PANEL_CHAIN_SCALE") ? atof(getenv("GPX_PANEL_CHAIN_SCALE")) : 0.75;
-        return us * f;
+        return us * gpx_env().panel_chain_scale;
     }
     int inv_chunks(int i, int s) const             // stages of the scratch tile (i, s)
     {
@@ -1875,7 +1872,7 @@ struct Graph {
                     const int nb = inv_chunks(i, s) - 1;              // bulk chunks
                     // (from 17 tiles on: up to 16 the workers have time to spare and the
                     // shorter tasks win, N = 2048 0.83 against 0.87 ms)
-                    static const int big_env = getenv("GPX_PANEL_I128") ? atoi(getenv("GPX_PANEL_I128")) : -1;
+                    const int big_env = gpx_env().panel_i128;
                     const bool big = big_env >= 0 ? big_env != 0 : T > 16;
                     for (int c = 0; c < nb; ++c) {
                         const int l = std::min(i + 4 * c + 3, s - 2);     // last tile row of the chunk
@@ -2105,7 +2102,7 @@ struct Graph {
                         if (s % kbatch != kbatch - 1 && s != q - 3) continue;
                         s0 = s - s % kbatch;
                     }
-                    static const int u128 = getenv("GPX_PANEL_U128") ? atoi(getenv("GPX_PANEL_U128")) : 6;
+                    const int u128 = gpx_env().panel_u128;
                     const bool one = u128 >= 0 && kbatch > 1 && s - s0 + 1 >= 4 && q >= s + 3 + u128;
                     // the tile the next spine task solves (its X) in 32 x 32 tasks
                     const int fine = one ? 128 : (q == s + 1 && q < T && t == s + 1 + (stream ? 1 : 0)) ? 32 : SUB,
@@ -2259,12 +2256,6 @@ struct Graph {
     }
 };
 
-int env_once(const char *name, int dflt)
-{
-    const char *e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
 // whole-matrix launches batch the early updates of far tiles (GPX_PANEL_KBATCH, default 4)
 int panel_kbatch(int T, int E)
 {
@@ -2273,10 +2264,7 @@ int panel_kbatch(int T, int E)
     // 1.80 / 1.77 / 1.79 / 1.78 / 1.83 ms, N = 3072 1.31 / 1.30 / 1.28 / 1.24 / 1.23 / 1.26 /
     // 1.26 / 1.31, N = 2048 0.78 / 0.77 / 0.79 / 0.77 / 0.77 / 0.79 / 0.81 / 0.82; 0.79 / 1.58 /
     // 2.69 without batching)
-    static const int kb = [] {
-        const int v = env_once("GPX_PANEL_KBATCH", -1);
-        return v < 1 ? -1 : (v > 16 ? 16 : v);
-    }();
+    const int kb = gpx_env().panel_kbatch;               // (1 .. 16, or -1)
     if (T <= GPX_PANEL_MAX / 128 || E > 1) return 1;
     return kb > 0 ? kb : 8;
 }
@@ -2286,17 +2274,12 @@ int panel_kbatch(int T, int E)
 // panels and not for the round-1 graph.
 bool panel_split(bool stream, int E, bool aug)
 {
-    static const int on = env_once("GPX_PANEL_SPLIT", 1);
-    return on && stream && (E == 0 || aug);
+    return gpx_env().panel_split && stream && (E == 0 || aug);
 }
 
 // (with the split spine) the spine's solves fold the last update of their tile in themselves
 // (GPX_PANEL_FOLD=0: sixteen worker products apply it)
-bool panel_fold()
-{
-    static const int on = env_once("GPX_PANEL_FOLD", 1);
-    return on != 0;
-}
+bool panel_fold() { return gpx_env().panel_fold != 0; }
 
 struct PanelList {
     PTask *dev = nullptr;                    // [ntasks] general tasks, then [nspine] leaves
@@ -2315,7 +2298,7 @@ int panel_list(int T, int E, int workers, bool aug, int ig, PanelList *out, int 
     static std::mutex mu;
     int device = 0;
     GPX_HIP(hipGetDevice(&device));
-    static const int stream = env_once("GPX_PANEL_STREAM", 1);
+    const bool stream = gpx_panel_streaming();
     const Key key(device, T, aug ? -1 : E, solo ? 0 : workers, ig, solo);   // (aug: E = 1, a right-hand side)
     std::lock_guard<std::mutex> lock(mu);
     auto it = cache.find(key);
@@ -2329,10 +2312,10 @@ int panel_list(int T, int E, int workers, bool aug, int ig, PanelList *out, int 
     g.T = T;
     g.E = E;
     g.ld = PT_LD;
-    g.stream = stream != 0;
+    g.stream = stream;
     g.kbatch = panel_kbatch(T, E);
     g.aug = aug;
-    g.split = panel_split(stream != 0, E, aug);
+    g.split = panel_split(stream, E, aug);
     g.fold = panel_fold();
     g.ig = ig;
     g.build();
@@ -2393,22 +2376,71 @@ static bool gpx_panel_grid_fits(int nmem, int nspwg, int ncu)
 {
     return nmem >= 1 && nspwg >= 1 && (long long)nmem * nspwg + 1 <= ncu;
 }
-// spine workgroups per member by the default rule of gpx_panel (3 up to 16 members, 2 up to
-// 40, 1 beyond), reduced until the launch fits a device of ncu CUs; -1: it cannot fit
+// Member-batched launch: the same graph for every member of the workspace. The chain of
+// a member keeps 1-3 spine workgroups busy and its products a handful of workers, so the
+// members share one pool of workers (the interleaved queue) and the launch is sized to
+// the GPU: about 250 workgroups in all -- each holds a whole CU -- of which the spines
+// take 3 per member up to 16 members, 2 up to 40, 1 beyond (the chain of a member then
+// runs solve, diagonal update and leaf one after the other on one CU: 70 instead of 42 us
+// per tile, for a third of the CUs), fewer until the launch fits a device of ncu CUs.
+// GPX_PANEL_MSPINE / GPX_PANEL_MWG override. false: it cannot fit.
+static bool panel_grid_members(int nmem, int ncu, int *nspwg, int *workers)
+{
+    const int mspine = gpx_env().panel_mspine, mwg = gpx_env().panel_mwg;   // (-1: the rule)
+    int sp = mspine > 0 ? mspine : (nmem <= 16 ? 3 : (nmem <= 40 ? 2 : 1));
+    while (sp > 1 && !gpx_panel_grid_fits(nmem, sp, ncu)) --sp;
+    if (!gpx_panel_grid_fits(nmem, sp, ncu)) return false;
+    *nspwg = sp;
+    *workers = std::max(8, (mwg > 0 ? mwg : 250) - nmem * sp);
+    return true;
+}
+// A single-matrix launch sizes itself by the matrix: spine workgroups by the graph (round 5,
+// split spine: per tile a solving and a following task -- nine spine workgroups, five without
+// the fold, so that solve, follower + leaf and the leaf's inverse tail of neighbouring tiles
+// never wait for each other's workgroup; three for the fused spine task), fewer if the
+// device is smaller than that, and workers beside them: the row-panel tasks hold up to
+// seven of them for the length of a leaf and a workgroup that has claimed a task waits for
+// it, whatever else is ready (32 -> 64 -> 128: 450 / 412 / 370 us per 1024-block; N = 4096
+// evaluation 3.08 -> 2.96 ms with 128); above N = 4096 the chain hides under the products of
+// the same evaluation and every workgroup here holds a whole CU (157 KB of LDS) that the
+// products cannot use while it polls: 32 (round 3, N = 16384: 8 / 16 / 24 / 32 / 48 / 64
+// workers 72.8 / 71.5 / 70.8 / 71.0 / 71.5 / 71.8 ms per evaluation, N = 8192: 32 / 64 / 128
+// workers 11.29 / 11.48 / 11.79 ms). Wide panels (E > 0) carry three times the product tasks
+// and up to 15 row-panel tasks per leaf: 96 / 64 workers (never more than 96: their tasks may
+// wait for another stream's launches, which need CUs of their own). A whole matrix: the
+// trailing updates of all steps are tasks of this launch (21 800 of them at n = 4096, ~9 us
+// each) and have to keep up with a chain of 41 us per tile. GPX_PANEL_NSPINE, GPX_PANEL_WG,
+// GPX_PANEL_WG_WIDE, GPX_PANEL_WG_WHOLE override.
+static bool panel_grid_single(int np, int T, int E, bool whole, bool split, int ncu, int *nspwg,
+                              int *workers)
+{
+    const GpxEnv &e = gpx_env();                       // (-1: the rule)
+    int sp = e.panel_nspine > 0 ? e.panel_nspine : (split ? (panel_fold() ? 9 : 5) : 3);
+    while (sp > 1 && !gpx_panel_grid_fits(1, sp, ncu)) --sp;
+    if (!gpx_panel_grid_fits(1, sp, ncu)) return false;
+    *nspwg = sp;
+    *workers = whole ? (e.panel_wg_whole > 0 ? e.panel_wg_whole : (T <= 16 ? 160 : 250))
+               : E > 0 ? (e.panel_wg_wide > 0 ? e.panel_wg_wide : (np <= 4096 ? 96 : 64))
+               : e.panel_wg > 0 ? e.panel_wg
+               : np <= 4096 ? 128 : 32;
+    return true;
+}
+// the rule of a MEMBER-BATCHED launch (panel_grid_members, which gpx_panel applies) as a
+// host check: spine workgroups per member and workers for nmem members on ncu CUs; -1: the
+// launch cannot fit. (A single-matrix launch sizes itself separately: panel_grid_single.)
 extern "C" int gpx_panel_grid_check(int nmem, int ncu, int *nspwg, int *workers)
 {
     if (nmem < 1 || ncu < 1) {
         gpx_set_error("panel grid check: bad arguments");
         return -1;
     }
-    int sp = nmem == 1 ? 3 : (nmem <= 16 ? 3 : (nmem <= 40 ? 2 : 1));
-    while (sp > 1 && !gpx_panel_grid_fits(nmem, sp, ncu)) --sp;
-    if (!gpx_panel_grid_fits(nmem, sp, ncu)) {
+    int sp = 0, wk = 0;
+    if (!panel_grid_members(nmem, ncu, &sp, &wk)) {
         gpx_set_error("panel grid check: %d members do not fit %d CUs", nmem, ncu);
         return -1;
     }
     if (nspwg) *nspwg = sp;
-    if (workers) *workers = std::max(8, 250 - nmem * sp);
+    if (workers) *workers = wk;
     return 0;
 }
 extern "C" int gpx_panel_graph_check(int T, int workers, int stream, int *ntasks)
@@ -2449,7 +2481,7 @@ extern "C" int gpx_panel_solo_check(int T, int aug, int full, int value_only, in
     g.aug = aug != 0;
     g.split = panel_split(true, g.E, g.aug);
     g.fold = panel_fold();
-    g.ig = full && T > PANEL_IG ? T : PANEL_IG;
+    g.ig = gpx_inverse_group(full != 0, 0, 128 * T, 128 * T);
     g.build();
     if (!g.solo_order_ok()) {
         gpx_set_error("panel solo check: generation order is not sequential (T = %d)", T);
@@ -2507,7 +2539,7 @@ static int panel_graph_check(int T, int E, int workers, int stream, int *ntasks,
     g.aug = aug;
     g.split = panel_split(stream != 0, E, aug);
     g.fold = panel_fold();
-    g.ig = full_w && T > PANEL_IG ? T : PANEL_IG;
+    g.ig = gpx_inverse_group(full_w, 0, 128 * T, 128 * T);
     g.build();
     const int n = (int)g.tasks.size();
     if (ntasks) *ntasks = n;
@@ -2643,6 +2675,26 @@ int sweep_list(int T, int E, SweepList **out)
 
 }  // namespace
 
+// What every task-queue launch is told about its hand-offs: the wait bound in 100-MHz ticks
+// (GPX_PANEL_TIMEOUT_MS; us_hook: GPX_PANEL_TIMEOUT_US, a test hook -- a bound of a few
+// microseconds makes every panel launch of two or more tiles end in "timed out waiting",
+// deterministically; tools/check_safe_mode.py), fences on every hand-off (GPX_PANEL_STRICT)
+// and the leaf's skip mask (GPX_PANEL_LEAF_SKIP; 32: GPX_LEAF_MFMA=0).
+struct Handoff {
+    long long timeout;
+    int strict, leafskip;
+};
+static Handoff panel_handoff(bool us_hook)
+{
+    const GpxEnv &e = gpx_env();
+    Handoff h;
+    h.timeout = us_hook && e.panel_timeout_us > 0 ? (long long)e.panel_timeout_us * 100LL
+                                                  : (long long)e.panel_timeout_ms * 100000LL;
+    h.strict = e.panel_strict;
+    h.leafskip = e.panel_leaf_skip | (e.leaf_mfma ? 0 : 32);
+    return h;
+}
+
 // phase 0: the leaf of tile (0,0); phase 1 + s: the row panel of tile row s -- XS(s,t) for
 // every tile right of the diagonal, the one next to it fused with the update and the leaf
 // of tile (s+1,s+1) -- for the block (off, 128 T) [+ `aug` right-hand-side column] of every
@@ -2661,13 +2713,7 @@ int gpx_sweep_phase(hipStream_t s, const DenseWs &w, int off, int T, bool aug, i
     const int ntask = fused_only ? (phase >= 1 && phase < T ? 1 : 0) : sl->count[phase];
     if (ntask == 0) return 0;
     GPX_TRY(gpx_test_jitter(s));
-    static const int timeout_ms = [] {
-        const int v = env_once("GPX_PANEL_TIMEOUT_MS", 2000);
-        return v < 1 ? 2000 : v;
-    }();
-    static const int strict = env_once("GPX_PANEL_STRICT", 0);
-    static const int leafskip = env_once("GPX_PANEL_LEAF_SKIP", 0) |
-                                (env_once("GPX_LEAF_MFMA", 1) ? 0 : 32);
+    const Handoff ho = panel_handoff(false);
     const size_t o = (size_t)off * w.ld + off;
     const int nmem = w.batch > 1 ? w.batch : 1;
     SweepArgs p;
@@ -2682,10 +2728,10 @@ int gpx_sweep_phase(hipStream_t s, const DenseWs &w, int off, int T, bool aug, i
     p.ctl = sl->ctl;
     p.info = w.info;
     p.goff = off;
-    p.timeout = (long long)timeout_ms * 100000LL;
-    p.strict = strict;
+    p.timeout = ho.timeout;
+    p.strict = ho.strict;
     // no_inverse: nothing will read W beyond the diagonal 16-blocks the solves use
-    p.leafskip = leafskip | (no_inverse ? 8 : 0);
+    p.leafskip = ho.leafskip | (no_inverse ? 8 : 0);
     p.presolved = fused_only && presolved ? 1 : 0;
     hipLaunchKernelGGL(sweep_kernel, dim3(p.ntasks * nmem), dim3(256), LEAF2_LDS, s, p);
     GPX_HIP(hipGetLastError());
@@ -2731,14 +2777,13 @@ int gpx_sweep_xs(hipStream_t st, const DenseWs &w, int off, int T, bool aug, int
     p.nsolve = TW - t0;
     p.TW = TW;
     // (GPX_SWEEP_NARROW=0: the right-hand-side tiles as full tiles)
-    static const int narrow_on = env_once("GPX_SWEEP_NARROW", 1);
-    p.narrow_col = aug && narrow_on ? T : -1;
+    p.narrow_col = aug && gpx_sweep_narrow() ? T : -1;
     // (the narrow tiles may fold from an earlier step on than the others: their updates cost an
     // eighth, and the products of the tile engine that would apply them run full tiles)
     p.kfirst_narrow = p.narrow_col >= 0 && kfirst_rhs >= 0 && kfirst_rhs <= kfirst ? kfirst_rhs : kfirst;
     p.right = upd == 3 ? 1 : 0;
     p.trace = nullptr;
-    static const int debug = env_once("GPX_XS_DEBUG", 0);    // developer aid: stamps of workgroup 0
+    const int debug = gpx_env().xs_debug;                    // developer aid: stamps of workgroup 0
     static long long *trace_dev = nullptr;
     if (debug) {
         if (!trace_dev) GPX_HIP(hipMalloc((void **)&trace_dev, 32 * sizeof(long long)));
@@ -2778,14 +2823,10 @@ int gpx_sweep_xs(hipStream_t st, const DenseWs &w, int off, int T, bool aug, int
 // 2.20k / 2.24k / 2.29k evals/s; N = 3072 level from 16 on). GPX_SWEEP_FOLD overrides.
 int gpx_sweep_fold_depth(int T)
 {
-    static const int depth_env = env_once("GPX_SWEEP_FOLD", -1);
+    const int depth_env = gpx_env().sweep_fold;
     return depth_env >= 0 ? depth_env : T;
 }
-bool gpx_sweep_lite()
-{
-    static const int lite = env_once("GPX_SWEEP_LITE", 1);
-    return lite != 0;
-}
+bool gpx_sweep_lite() { return gpx_env().sweep_lite != 0; }
 
 static int sweep_check_impl(int T, int aug, bool lite, int depth, bool right = false)
 {
@@ -2948,17 +2989,9 @@ extern "C" int gpx_sweep_check_lite(int T, int aug, int depth)
 }
 // the right-hand-side tiles of a sweep are narrow (sweep_xs_kernel): the caller may leave ALL
 // their updates to the dense tasks
-bool gpx_sweep_narrow()
-{
-    static const int narrow_on = env_once("GPX_SWEEP_NARROW", 1);
-    return narrow_on != 0;
-}
+bool gpx_sweep_narrow() { return gpx_env().sweep_narrow != 0; }
 // tiles up to which the sweep is right-looking (GPX_SWEEP_RIGHT; 0: never)
-int gpx_sweep_right_max()
-{
-    static const int v = env_once("GPX_SWEEP_RIGHT", 4);
-    return v;
-}
+int gpx_sweep_right_max() { return gpx_env().sweep_right; }
 
 int gpx_panel_init()
 {
@@ -2979,22 +3012,12 @@ int gpx_panel_init()
 // overrides.
 int gpx_panel_max(int np)
 {
-    // magic statics: the host threads of the multi-device path reach this together
-    static const int forced = [] {
-        const char *e = getenv("GPX_PANEL");
-        int f = e ? atoi(e) : -1;
-        if (f > 0 && (f < 256 || f > GPX_PANEL_MAX || f % 128)) f = GPX_PANEL_MAX;
-        return f;
-    }();
+    const int forced = gpx_env().panel;      // (0, a multiple of 128 in 256 .. GPX_PANEL_MAX, or -1)
     (void)np;
     return forced >= 0 ? forced : GPX_PANEL_MAX;
 }
 
-bool gpx_panel_streaming()
-{
-    static const int stream = env_once("GPX_PANEL_STREAM", 1);
-    return stream != 0;
-}
+bool gpx_panel_streaming() { return gpx_env().panel_stream != 0; }
 
 // Solo launches (round 5): the diagonal blocks of a group of MANY members at a SMALL order as
 // one launch with one workgroup per member that runs the member's whole task graph, task after
@@ -3010,8 +3033,7 @@ bool gpx_panel_streaming()
 // and of the sweep. GPX_SOLO_MAX_NP (largest padded order, 0: never), GPX_SOLO_MIN_MEMBERS.
 bool gpx_panel_solo_np(int np, int members)
 {
-    static const int max_np = env_once("GPX_SOLO_MAX_NP", 0);
-    static const int min_members = env_once("GPX_SOLO_MIN_MEMBERS", 16);
+    const int max_np = gpx_env().solo_max_np, min_members = gpx_env().solo_min_members;
     return min_members > 0 && members >= min_members && np >= 256 && np <= max_np &&
            gpx_panel_streaming();
 }
@@ -3023,6 +3045,86 @@ size_t gpx_panel_ctl_bytes()
 }
 
 int *gpx_panel_gates(const DenseWs &w) { return w.pctl ? w.pctl + PCTL_GATES : nullptr; }
+
+// GPX_PANEL_DEBUG: wait for the launch; >= 2: print the per-task trace; dump the progress log
+// and leave the process if it stalls
+static int panel_watch(hipStream_t s, const PanelArgs &p, const PanelList &pl, int T, int grid,
+                       int debug, const int *dbg_host, const long long *trace_dev)
+{
+    for (int ms = 0; ms < 3000; ++ms) {
+        if (hipStreamQuery(s) == hipSuccess) {
+            if (debug >= 2 && p.trace) {
+                const int nall = pl.ntasks + pl.nspine;
+                std::vector<long long> tr(32 * nall);
+                std::vector<PTask> tk(nall);
+                GPX_HIP(hipMemcpy(tr.data(), trace_dev, tr.size() * 8, hipMemcpyDeviceToHost));
+                GPX_HIP(hipMemcpy(tk.data(), pl.dev, tk.size() * sizeof(PTask),
+                                  hipMemcpyDeviceToHost));
+                long long base = tr[0];
+                for (int i = 0; i < nall; ++i) base = std::min(base, tr[32 * i]);
+                fprintf(stderr, "panel trace T=%d tasks=%d (us: claim start end | wg op k sig)\n",
+                        T, nall);
+                for (int i = 0; i < nall; ++i)
+                    fprintf(stderr, "  %4d %8.2f %8.2f %8.2f | %2lld %d %4d %3d | %.2f %.2f %.2f %.2f\n",
+                            i, (tr[32 * i] - base) * 0.01, (tr[32 * i + 1] - base) * 0.01,
+                            (tr[32 * i + 2] - base) * 0.01, tr[32 * i + 3], tk[i].op,
+                            tk[i].khi - tk[i].klo, (int)tk[i].sig,
+                            tr[32 * i + 4] ? (tr[32 * i + 4] - base) * 0.01 : 0.0,
+                            tr[32 * i + 5] ? (tr[32 * i + 5] - base) * 0.01 : 0.0,
+                            tr[32 * i + 6] ? (tr[32 * i + 6] - base) * 0.01 : 0.0,
+                            tr[32 * i + 7] ? (tr[32 * i + 7] - base) * 0.01 : 0.0);
+                {   // in-kernel clock: shader cycles (s_memtime) per 100-MHz tick
+                    double cyc = 0.0, ticks = 0.0;
+                    for (int i = 0; i < nall; ++i) {
+                        cyc += (double)(tr[32 * i + 13] - tr[32 * i + 12]);
+                        ticks += (double)(tr[32 * i + 2] - tr[32 * i + 1]);
+                    }
+                    fprintf(stderr, "  in-kernel clock %.0f MHz\n", cyc / ticks * 100.0);
+                }
+                for (int i = 0; i < nall; ++i)
+                    if (tr[32 * i + 16]) {
+                        fprintf(stderr, "  leaf %4d", i);
+                        for (int q = 16; q < 31; ++q)
+                            fprintf(stderr, " %.2f", tr[32 * i + q] ? (tr[32 * i + q] - base) * 0.01 : 0.0);
+                        fprintf(stderr, "\n");
+                    }
+                for (int i = 0; i < nall; ++i)
+                    if (tr[32 * i + 8])
+                        fprintf(stderr, "  sub %4d %.2f %.2f %.2f %.2f\n", i,
+                                (tr[32 * i + 8] - base) * 0.01, (tr[32 * i + 9] - base) * 0.01,
+                                (tr[32 * i + 10] - base) * 0.01, (tr[32 * i + 11] - base) * 0.01);
+            }
+            return 0;
+        }
+        usleep(1000);
+    }
+    fprintf(stderr, "panel stalled: T=%d tasks=%d grid=%d\n", T, pl.ntasks, grid);
+    for (int g = 0; g < grid; ++g)
+        fprintf(stderr, "  wg %2d task %4d state %d dep %d need %d\n", g, dbg_host[8 * g],
+                dbg_host[8 * g + 1], dbg_host[8 * g + 2], dbg_host[8 * g + 3]);
+    fflush(stderr);
+    _exit(3);
+    return 0;
+}
+
+// CUs of the current device
+static int device_cus(int *out)
+{
+    static int ncu_of[64] = {};
+    int device = 0;
+    GPX_HIP(hipGetDevice(&device));
+    int ncu = 256;
+    if (device >= 0 && device < 64) {
+        if (!ncu_of[device]) {
+            hipDeviceProp_t prop;
+            GPX_HIP(hipGetDeviceProperties(&prop, device));
+            ncu_of[device] = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+        }
+        ncu = ncu_of[device];
+    }
+    *out = ncu;
+    return 0;
+}
 
 int gpx_panel(hipStream_t s, const DenseWs &w, int off, int n, int extra, int gate_need0,
               int gate_need1, bool rhs)
@@ -3048,71 +3150,28 @@ int gpx_panel(hipStream_t s, const DenseWs &w, int off, int n, int extra, int ga
         return -1;
     }
     GPX_TRY(gpx_test_jitter(s));
-    // workgroups beside the spine: the row-panel tasks hold up to seven of them for the
-    // length of a leaf and a workgroup that has claimed a task waits for it, whatever else
-    // is ready (32 -> 64 -> 128: 450 / 412 / 370 us per 1024-block; N = 4096 evaluation
-    // 3.08 -> 2.96 ms with 128); above N = 4096 the chain hides under the products of the
-    // same evaluation and every workgroup here holds a whole CU (157 KB of LDS) that the
-    // products cannot use while it polls: 32 (round 3, N = 16384: 8 / 16 / 24 / 32 / 48 /
-    // 64 workers 72.8 / 71.5 / 70.8 / 71.0 / 71.5 / 71.8 ms per evaluation, N = 8192:
-    // 32 / 64 / 128 workers 11.29 / 11.48 / 11.79 ms)
-    static const int workers_env = [] {
-        const int v = env_once("GPX_PANEL_WG", -1);
-        return v < 1 || v > 256 ? -1 : v;
-    }();
-    static const int timeout_ms = [] {
-        const int v = env_once("GPX_PANEL_TIMEOUT_MS", 2000);
-        return v < 1 ? 2000 : v;
-    }();
-    // wide panels (E > 0) carry three times the product tasks and up to 15 row-panel
-    // tasks per leaf: 96 / 64 workers (never more than 96: their tasks may wait for
-    // another stream's launches, which need CUs of their own)
-    static const int wide_env = [] {
-        const int v = env_once("GPX_PANEL_WG_WIDE", -1);
-        return v < 1 || v > 96 ? -1 : v;
-    }();
-    // a whole matrix: the trailing updates of all steps are tasks of this launch (21 800 of
-    // them at n = 4096, ~9 us each) and have to keep up with a chain of 41 us per tile
-    static const int whole_env = [] {
-        const int v = env_once("GPX_PANEL_WG_WHOLE", -1);
-        return v < 1 || v > 250 ? -1 : v;
-    }();
-    int workers = whole ? (whole_env > 0 ? whole_env : (T <= 16 ? 160 : 250))
-                  : E > 0 ? (wide_env > 0 ? wide_env : (w.np <= 4096 ? 96 : 64))
-                  : workers_env > 0 ? workers_env
-                  : w.np <= 4096 ? 128 : 32;
-    // Member-batched launch: the same graph for every member of the workspace. The chain of
-    // a member keeps 1-3 spine workgroups busy and its products a handful of workers, so the
-    // members share one pool of workers (the interleaved queue) and the launch is sized to
-    // the GPU: about 250 workgroups in all -- each holds a whole CU -- of which the spines
-    // take 3 per member up to 16 members, 2 up to 40, 1 beyond (the chain of a member then
-    // runs solve, diagonal update and leaf one after the other on one CU: 70 instead of 42 us
-    // per tile, for a third of the CUs). GPX_PANEL_MSPINE / GPX_PANEL_MWG override.
     const int nmem = w.batch > 1 ? w.batch : 1;
-    // (round 5, split spine: per tile a solving and a following task -- five spine workgroups
-    // for one matrix, so that solve, follower + leaf and the leaf's inverse tail of
-    // neighbouring tiles never wait for each other's workgroup)
-    static const int nspine_env = [] {
-        const int v = env_once("GPX_PANEL_NSPINE", -1);
-        return v < 1 || v > 8 ? -1 : v;
-    }();
-    static const int stream_env = env_once("GPX_PANEL_STREAM", 1);
-    const bool split = panel_split(stream_env != 0, E, aug);
-    int nspwg_want = nspine_env > 0 ? nspine_env : (split ? (panel_fold() ? 9 : 5) : 3);
-    if (nmem > 1) {
-        static const int mspine_env = [] {
-            const int v = env_once("GPX_PANEL_MSPINE", -1);
-            return v < 1 || v > 9 ? -1 : v;
-        }();
-        static const int mwg_env = [] {
-            const int v = env_once("GPX_PANEL_MWG", -1);
-            return v < 8 || v > 1024 ? -1 : v;
-        }();
-        nspwg_want = mspine_env > 0 ? mspine_env : (nmem <= 16 ? 3 : (nmem <= 40 ? 2 : 1));
-        const int total = mwg_env > 0 ? mwg_env : 250;
-        workers = std::max(8, total - nmem * nspwg_want);
-        if (E > 0 && !aug) {
-            gpx_set_error("panel: wide panels are not member-batched");
+    if (nmem > 1 && E > 0 && !aug) {
+        gpx_set_error("panel: wide panels are not member-batched");
+        return -1;
+    }
+    const bool split = panel_split(gpx_panel_streaming(), E, aug);
+    // one workgroup per member, the member's whole graph on it (gpx_panel_solo)
+    const bool solo = nmem > 1 && off == 0 && n == w.np && (E == 0 || aug) && gpx_panel_solo(w);
+    // spine workgroups per member and workers of the launch (solo: the member's workgroup)
+    int nspwg = 1, workers = 0;
+    if (!solo) {      // (a solo workgroup waits for nobody: any residency makes progress)
+        // Co-residency (the progress argument of this launch): every spine workgroup -- they
+        // come first in the grid -- and at least one worker must be resident at the same time,
+        // and each holds a whole CU. Reachable only through the environment switches today
+        // (GPX_GROUP_MEMBERS up to 256 with the sweep off): fewer spines per member, or an
+        // error instead of a launch that would wait out its 2-s bound.
+        int ncu = 0;
+        GPX_TRY(device_cus(&ncu));
+        if (!(nmem > 1 ? panel_grid_members(nmem, ncu, &nspwg, &workers)
+                       : panel_grid_single(w.np, T, E, whole, split, ncu, &nspwg, &workers))) {
+            gpx_set_error("panel: %d members need %d spine workgroups, the device has %d CUs "
+                          "(run such groups through the lock-step sweep)", nmem, nmem, ncu);
             return -1;
         }
     }
@@ -3120,14 +3179,8 @@ int gpx_panel(hipStream_t s, const DenseWs &w, int off, int n, int extra, int ga
     const int sched_workers = nmem > 1 ? std::min(128, std::max(4, workers / nmem)) : workers;
     PanelList pl;
     // (full_w: a launch over a whole matrix that leaves ALL of R^-1 behind)
-    const int ig = w.full_w && off == 0 && n == w.np && T > PANEL_IG ? T : PANEL_IG;
-    // one workgroup per member, the member's whole graph on it (gpx_panel_solo)
-    const bool solo = nmem > 1 && off == 0 && n == w.np && (E == 0 || aug) && gpx_panel_solo(w);
+    const int ig = gpx_inverse_group(w.full_w, off, n, w.np);
     GPX_TRY(panel_list(T, E, sched_workers, aug, ig, &pl, solo ? (w.no_inverse ? 2 : 1) : 0));
-    if (solo) {
-        nspwg_want = 1;
-        workers = 0;
-    }
     const size_t o = (size_t)off * w.ld + off;
     PanelArgs p;
     p.bA = w.A + o;
@@ -3138,32 +3191,7 @@ int gpx_panel(hipStream_t s, const DenseWs &w, int off, int n, int extra, int ga
     p.spine = pl.dev + pl.ntasks;
     p.ntasks = pl.ntasks;
     p.nspine = pl.nspine;
-    p.nspwg = std::min(nspwg_want, pl.nspine);
-    if (!solo) {      // (a solo workgroup waits for nobody: any residency makes progress)
-        // Co-residency (the progress argument of this launch): every spine workgroup -- they
-        // come first in the grid -- and at least one worker must be resident at the same time,
-        // and each holds a whole CU. Reachable only through the environment switches today
-        // (GPX_GROUP_MEMBERS up to 256 with the sweep off): fewer spines per member, or an
-        // error instead of a launch that would wait out its 2-s bound.
-        static int ncu_of[64] = {};
-        int device = 0;
-        GPX_HIP(hipGetDevice(&device));
-        int ncu = 256;
-        if (device >= 0 && device < 64) {
-            if (!ncu_of[device]) {
-                hipDeviceProp_t prop;
-                GPX_HIP(hipGetDeviceProperties(&prop, device));
-                ncu_of[device] = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-            }
-            ncu = ncu_of[device];
-        }
-        while (p.nspwg > 1 && !gpx_panel_grid_fits(nmem, p.nspwg, ncu)) --p.nspwg;
-        if (!gpx_panel_grid_fits(nmem, p.nspwg, ncu)) {
-            gpx_set_error("panel: %d members need %d spine workgroups, the device has %d CUs "
-                          "(run such groups through the lock-step sweep)", nmem, nmem * p.nspwg, ncu);
-            return -1;
-        }
-    }
+    p.nspwg = std::min(nspwg, pl.nspine);
     p.nctr = pl.nctr;
     p.nmem = nmem;
     p.mstride = nmem > 1 ? w.mstride : 0;
@@ -3178,19 +3206,14 @@ int gpx_panel(hipStream_t s, const DenseWs &w, int off, int n, int extra, int ga
     p.ctl = w.pctl;
     p.info = w.info;
     p.goff = off;
-    // (GPX_PANEL_TIMEOUT_US: test hook -- a bound of a few microseconds makes every launch of
-    // two or more tiles end in "timed out waiting", deterministically; tools/check_safe_mode.py)
-    static const int timeout_us = env_once("GPX_PANEL_TIMEOUT_US", 0);
-    p.timeout = timeout_us > 0 ? (long long)timeout_us * 100LL : (long long)timeout_ms * 100000LL;
-    static const int strict = env_once("GPX_PANEL_STRICT", 0);
-    p.strict = strict;
-    static const int leafskip = env_once("GPX_PANEL_LEAF_SKIP", 0) |
-                                (env_once("GPX_LEAF_MFMA", 1) ? 0 : 32);
+    const Handoff ho = panel_handoff(true);
+    p.timeout = ho.timeout;
+    p.strict = ho.strict;
     // (solo, value-only members: nothing reads W beyond the diagonal 16-blocks of the solves)
-    p.leafskip = leafskip | (solo && w.no_inverse ? 8 : 0);
+    p.leafskip = ho.leafskip | (solo && w.no_inverse ? 8 : 0);
     p.dbg = nullptr;
     p.trace = nullptr;
-    static const int debug = env_once("GPX_PANEL_DEBUG", 0);
+    const int debug = gpx_env().panel_debug;
     static int *dbg_host = nullptr;          // developer runs are single-threaded
     static long long *trace_dev = nullptr;
     // + the spine workgroups
@@ -3217,7 +3240,7 @@ int gpx_panel(hipStream_t s, const DenseWs &w, int off, int n, int extra, int ga
     // one stream -- an evaluation's look-ahead, a group -- follow each other anyway.
     // Processes are not ordered against each other: one process per GPU.
     // GPX_PANEL_SERIAL=0: no ordering (rounds 1-3).
-    if (stream_env != 0 && T >= 2) {
+    if (gpx_panel_streaming() && T >= 2) {
         // the tiles that are polled as data: the mailboxes of the diagonal tiles (diagonal
         // tiles of the staging matrix: unused -- the first K^-1 update that writes them comes
         // after this block's factorisation) and, with the split spine, the tiles (s, s+1) the
@@ -3229,7 +3252,7 @@ int gpx_panel(hipStream_t s, const DenseWs &w, int off, int n, int extra, int ga
         GPX_HIP(hipGetLastError());
     }
     {
-        static const int serial = env_once("GPX_PANEL_SERIAL", 1);
+        const int serial = gpx_env().panel_serial;
         struct Last { hipEvent_t ev = nullptr; hipStream_t stream = nullptr; };
         static Last last[64];
         static std::mutex mu;
@@ -3250,60 +3273,8 @@ int gpx_panel(hipStream_t s, const DenseWs &w, int off, int n, int extra, int ga
             GPX_HIP(hipGetLastError());
         }
     }
-    if (debug && (nmem == 1 || solo)) {     // developer aid: watch the launch, dump the progress log if it stalls
-        for (int ms = 0; ms < 3000; ++ms) {
-            if (hipStreamQuery(s) == hipSuccess) {
-                if (debug >= 2 && p.trace) {
-                    const int nall = pl.ntasks + pl.nspine;
-                    std::vector<long long> tr(32 * nall);
-                    std::vector<PTask> tk(nall);
-                    GPX_HIP(hipMemcpy(tr.data(), trace_dev, tr.size() * 8, hipMemcpyDeviceToHost));
-                    GPX_HIP(hipMemcpy(tk.data(), pl.dev, tk.size() * sizeof(PTask),
-                                      hipMemcpyDeviceToHost));
-                    long long base = tr[0];
-                    for (int i = 0; i < nall; ++i) base = std::min(base, tr[32 * i]);
-                    fprintf(stderr, "panel trace T=%d tasks=%d (us: claim start end | wg op k sig)\n",
-                            T, nall);
-                    for (int i = 0; i < nall; ++i)
-                        fprintf(stderr, "  %4d %8.2f %8.2f %8.2f | %2lld %d %4d %3d | %.2f %.2f %.2f %.2f\n",
-                                i, (tr[32 * i] - base) * 0.01, (tr[32 * i + 1] - base) * 0.01,
-                                (tr[32 * i + 2] - base) * 0.01, tr[32 * i + 3], tk[i].op,
-                                tk[i].khi - tk[i].klo, (int)tk[i].sig,
-                                tr[32 * i + 4] ? (tr[32 * i + 4] - base) * 0.01 : 0.0,
-                                tr[32 * i + 5] ? (tr[32 * i + 5] - base) * 0.01 : 0.0,
-                                tr[32 * i + 6] ? (tr[32 * i + 6] - base) * 0.01 : 0.0,
-                                tr[32 * i + 7] ? (tr[32 * i + 7] - base) * 0.01 : 0.0);
-                    {   // in-kernel clock: shader cycles (s_memtime) per 100-MHz tick
-                        double cyc = 0.0, ticks = 0.0;
-                        for (int i = 0; i < nall; ++i) {
-                            cyc += (double)(tr[32 * i + 13] - tr[32 * i + 12]);
-                            ticks += (double)(tr[32 * i + 2] - tr[32 * i + 1]);
-                        }
-                        fprintf(stderr, "  in-kernel clock %.0f MHz\n", cyc / ticks * 100.0);
-                    }
-                    for (int i = 0; i < nall; ++i)
-                        if (tr[32 * i + 16]) {
-                            fprintf(stderr, "  leaf %4d", i);
-                            for (int q = 16; q < 31; ++q)
-                                fprintf(stderr, " %.2f", tr[32 * i + q] ? (tr[32 * i + q] - base) * 0.01 : 0.0);
-                            fprintf(stderr, "\n");
-                        }
-                    for (int i = 0; i < nall; ++i)
-                        if (tr[32 * i + 8])
-                            fprintf(stderr, "  sub %4d %.2f %.2f %.2f %.2f\n", i,
-                                    (tr[32 * i + 8] - base) * 0.01, (tr[32 * i + 9] - base) * 0.01,
-                                    (tr[32 * i + 10] - base) * 0.01, (tr[32 * i + 11] - base) * 0.01);
-                }
-                return 0;
-            }
-            usleep(1000);
-        }
-        fprintf(stderr, "panel stalled: T=%d tasks=%d grid=%d\n", T, pl.ntasks, grid);
-        for (int g = 0; g < grid; ++g)
-            fprintf(stderr, "  wg %2d task %4d state %d dep %d need %d\n", g, dbg_host[8 * g],
-                    dbg_host[8 * g + 1], dbg_host[8 * g + 2], dbg_host[8 * g + 3]);
-        fflush(stderr);
-        _exit(3);
-    }
+    // developer aid: watch the launch, dump the progress log if it stalls
+    if (debug && (nmem == 1 || solo))
+        return panel_watch(s, p, pl, T, grid, debug, dbg_host, trace_dev);
     return 0;
 }

@@ -288,3 +288,32 @@ def test_panel_launch_co_residency_rule(libpath):
     # a smaller part: the spines give way first
     assert _lib.panel_grid_check(16, 40) == (2, 218)
     assert _lib.panel_grid_check(16, 20)[0] == 1
+
+
+CSRC = os.path.join(ROOT, 'pygp_amd', 'csrc')
+
+
+def test_switches_are_read_in_one_place():
+    """Every developer switch of the library is read in gpx_env.h (one table, filled once per
+    process): no other source under pygp_amd/csrc/ talks to the environment."""
+    readers = [f for f in sorted(os.listdir(CSRC)) if f.endswith(('.hip', '.h'))
+               and 'getenv' in open(os.path.join(CSRC, f)).read()]
+    assert readers == ['gpx_env.h']
+
+
+def test_design_lists_every_switch_of_the_table():
+    """DESIGN section 9 and the table of gpx_env.h name the same switches. Section 9 also lists
+    the switches of the Python layer and of bench.py, which the library never sees."""
+    elsewhere = {'GPX_DEVICE', 'GPX_AUTO_SAFE_MODE',                               # pygp_amd/*.py
+                 'GPX_BENCH_BACKEND', 'GPX_BENCH_FORCE_DIST', 'GPX_CPU_CORES'}     # bench.py
+    table = re.findall(r'^\s*X\([^,]+, \w+, "(GPX_[A-Z0-9_]+)",',
+                       open(os.path.join(CSRC, 'gpx_env.h')).read(), re.M)
+    assert len(table) > 80 and len(set(table)) == len(table)
+    design = open(os.path.join(ROOT, 'DESIGN.md')).read()
+    section = design[design.index('\n## 9. '):design.index('\n## 10. ')]
+    rows = [line for line in section.splitlines() if line.startswith('| `GPX_')]
+    documented = set()
+    for row in rows:
+        documented.update(re.findall(r'`(GPX_[A-Z0-9_]+)`', row.split('|')[1]))
+    assert elsewhere <= documented
+    assert documented - elsewhere == set(table)
