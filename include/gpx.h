@@ -141,6 +141,14 @@ int gpx_exact_append(gpx_t *h, const double *Xnew, const double *ynew, int64_t m
 /* ExactGP.loglikelihood (exact.py:118-143) for the last update. dlZ == NULL ->
  * value only; else dlZ[1 + nhyper_kernel + 1] in order [sn, kernel..., mean]. */
 int gpx_exact_loglik(gpx_t *h, double *lZ, double *dlZ);
+/* Leave-one-out cross-validation of the last update (own design; GPML section 5.4.2): *L the
+ * sum over the points of the log predictive density of y_i given the other points; dL[1 +
+ * nhyper_kernel + 1] its gradient in the order and sign convention of gpx_exact_loglik; mu[n],
+ * s2[n] the leave-one-out predictive means and (noisy) variances in the order of the data. Any
+ * output may be NULL. Completes R^-1 and K^-1 exactly as gpx_exact_loglik with dlZ does and only
+ * reads them: later calls on the handle return the bits they return without this one. The
+ * gradient takes two more n x n device matrices, allocated by the first call that asks for it. */
+int gpx_exact_loo(gpx_t *h, double *L, double *dL, double *mu, double *s2);
 /* One optimiser objective = set_hyper + loglikelihood(grad)
  * (pygp/learning/optimization.py:54-59) in a single call. */
 int gpx_exact_eval(gpx_t *h, const gpx_kspec *k, double log_sn, double mean,

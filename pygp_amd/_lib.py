@@ -69,6 +69,7 @@ SIGNATURES = {
                                    C.c_double, _ip]),
     'gpx_exact_append': (C.c_int, [_vp, _vp, _vp, _i64, _ip]),
     'gpx_exact_loglik': (C.c_int, [_vp, _dp, _vp]),
+    'gpx_exact_loo': (C.c_int, [_vp, _dp, _vp, _vp, _vp]),
     'gpx_exact_eval': (C.c_int, [_vp, C.POINTER(_KSpec), C.c_double, C.c_double,
                                  C.c_int, _dp, _vp, _ip]),
     'gpx_exact_posterior': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
@@ -357,6 +358,18 @@ class Handle(object):
         dlZ = np.empty(nhyper_kernel + 2) if grad else None
         check(self._L.gpx_exact_loglik(self._h, C.byref(lZ), _ptr(dlZ)))
         return (lZ.value, dlZ) if grad else lZ.value
+
+    def exact_loo(self, nhyper_kernel, n, grad=False, points=False):
+        """Leave-one-out log predictive probability L of the last update; grad: (L, dL);
+        points: (mu, s2), the n leave-one-out predictive means and variances, instead."""
+        if points:
+            mu, s2 = np.empty(n), np.empty(n)
+            check(self._L.gpx_exact_loo(self._h, None, None, _ptr(mu), _ptr(s2)))
+            return mu, s2
+        L = C.c_double(0)
+        dL = np.empty(nhyper_kernel + 2) if grad else None
+        check(self._L.gpx_exact_loo(self._h, C.byref(L), _ptr(dL), None, None))
+        return (L.value, dL) if grad else L.value
 
     def exact_eval(self, spec, log_sn, mean, grad=True):
         lZ, info = C.c_double(0), C.c_int(0)

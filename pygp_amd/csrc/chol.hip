@@ -854,3 +854,11 @@ int gpx_lauum(hipStream_t s, const DenseWs &w)
     g.order = gpx_env().ord_lauum;
     return gpx_gemm(s, 0, 1, g);
 }
+
+int gpx_aat_upper(hipStream_t s, const DenseWs &w, const double *S, double *C)
+{
+    // C[i][j] = sum_k S[i][k] S[j][k] over every k, tiles with j >= i
+    const BatchScope batch_scope(w);
+    const int n = w.np, ld = w.ld;
+    return gpx_gemm(s, 0, 1, mk(S, ld, S, ld, C, ld, n, n, n, 1.0, 0.0, GEMM_UPPER_ONLY));
+}

@@ -83,6 +83,9 @@ struct gpx_ctx {
     double lZ = 0;
     // posterior / api scratch
     DevBuf Ks, KsT, Vc, Xs, mu, s2, post_part, t0, t1, t2, split, gpart;
+    // leave-one-out cross-validation (gpx_exact_loo), allocated on first use: the scaled full
+    // copy of K^-1 and its product (np x ld each, gradient only), vectors, result doubles
+    DevBuf loo_S, loo_M, loo_vec, loo_out;
     int64_t bench_n = 0;
     // results of the evaluation in flight land in pinned host memory
     double *hres = nullptr;        // [0..2] scalars, [4..] trace accumulators
@@ -507,7 +510,8 @@ int gpx_destroy(gpx_t *h)
     DLOG("release buffers");
     DevBuf *bufs[] = {&h->X, &h->y, &h->Xf32, &h->A, &h->W, &h->Kinv, &h->r, &h->a,
                       &h->alpha, &h->scalars, &h->partial, &h->info, &h->gv_part, &h->pctl, &h->Ks, &h->KsT, &h->Vc,
-                      &h->Xs, &h->mu, &h->s2, &h->post_part, &h->t0, &h->t1, &h->t2, &h->split, &h->gpart};
+                      &h->Xs, &h->mu, &h->s2, &h->post_part, &h->t0, &h->t1, &h->t2, &h->split, &h->gpart,
+                      &h->loo_S, &h->loo_M, &h->loo_vec, &h->loo_out};
     for (DevBuf *b : bufs) b->release();
     DLOG("events");
     for (int i = 0; i <= GPX_NTIMERS; ++i)
@@ -874,8 +878,9 @@ static int enqueue_update(gpx_ctx *h, StageClock &clk, int mode, bool grad_follo
     return 0;
 }
 
-// enqueue K^-1, alpha and the trace terms; no host sync
-static int enqueue_grad(gpx_ctx *h, StageClock &clk)
+// enqueue the rest of R^-1, alpha and K^-1: what the trace terms and the leave-one-out
+// terms read; no host sync
+static int enqueue_inverse(gpx_ctx *h, StageClock &clk)
 {
     DenseWs w = h->ws();
     if (!h->w_complete) {
@@ -905,6 +910,14 @@ static int enqueue_grad(gpx_ctx *h, StageClock &clk)
         h->kinv_ready = true;
         clk.tick(T_LAUUM);
     }
+    return 0;
+}
+
+// enqueue K^-1, alpha and the trace terms; no host sync
+static int enqueue_grad(gpx_ctx *h, StageClock &clk)
+{
+    GPX_TRY(enqueue_inverse(h, clk));
+    const DenseWs w = h->ws();
     GPX_TRY(gpx_trace_grad(h->stream, h->kp, h->X.as<double>(), h->n, h->np, h->d, w.Kinv,
                            h->ld, h->alpha.as<double>(), h->partial.as<double>(),
                            h->acc.as<double>()));
@@ -1010,6 +1023,60 @@ int gpx_exact_loglik(gpx_t *h, double *lZ, double *dlZ)
     int r = finish(h, clk, true, lZ, dlZ, nullptr);
     if (r == 0) h->have_inverse = true;
     return r;
+}
+
+// the buffers of gpx_exact_loo, sized like those of reserve_factor (for the capacity, so
+// that appended observations find them in place)
+static int reserve_loo(gpx_ctx *h, bool grad)
+{
+    const size_t mat = (size_t)h->cap * h->ld * 8;
+    GPX_TRY(h->loo_vec.reserve(gpx_loo_scratch(h->cap) * 8));
+    GPX_TRY(h->loo_out.reserve((4 + 1 + GPX_MAX_HYPER) * sizeof(double)));
+    if (grad) {
+        GPX_TRY(h->loo_S.reserve(mat));
+        GPX_TRY(h->loo_M.reserve(mat));
+    }
+    return 0;
+}
+
+int gpx_exact_loo(gpx_t *h, double *L, double *dL, double *mu, double *s2)
+{
+    CHECK_H(h);
+    if (!h->have_factor) {
+        gpx_set_error("gpx_exact_loo: no factorisation (call gpx_exact_update)");
+        return -1;
+    }
+    const bool grad = dL != nullptr;
+    GPX_TRY(reserve_factor(h, true));
+    GPX_TRY(reserve_loo(h, grad));
+    StageClock clk(h);
+    // R^-1, alpha and K^-1 by the steps of an evaluation with gradients: whatever follows on
+    // this handle finds the state, and returns the bits, it would after gpx_exact_loglik
+    GPX_TRY(enqueue_inverse(h, clk));
+    double *vec = h->loo_vec.as<double>();
+    GPX_TRY(gpx_loo(h->stream, h->ws(), h->kp, h->X.as<double>(), h->y.as<double>(), h->n, h->d,
+                    h->alpha.as<double>(), grad, h->loo_S.as<double>(), h->loo_M.as<double>(),
+                    vec, h->partial.as<double>(), h->loo_out.as<double>()));
+    const int nres = grad ? 4 + 1 + h->kp.nhyper : 1;
+    GPX_HIP(hipMemcpyAsync(h->hres, h->loo_out.p, nres * sizeof(double), hipMemcpyDeviceToHost,
+                           h->stream));
+    if (mu)
+        GPX_HIP(hipMemcpyAsync(mu, vec, (size_t)h->n * 8, hipMemcpyDeviceToHost, h->stream));
+    if (s2)
+        GPX_HIP(hipMemcpyAsync(s2, vec + h->np, (size_t)h->n * 8, hipMemcpyDeviceToHost,
+                               h->stream));
+    GPX_HIP(hipStreamSynchronize(h->stream));          // the one host sync of the call
+    clk.collect();
+    h->have_inverse = true;
+    const double *res = h->hres, *acc = h->hres + 4;
+    if (L) *L = res[0] - 0.5 * log(2 * M_PI) * h->n;
+    if (grad) {
+        const int nh = h->kp.nhyper;
+        dL[0] = -2.0 * exp(h->log_sn * 2) * acc[0];      // 2 sn^2 tr(G)
+        for (int i = 0; i < nh; ++i) dL[1 + i] = -acc[1 + i];
+        dL[1 + nh] = res[1];
+    }
+    return 0;
 }
 
 int gpx_exact_eval(gpx_t *h, const gpx_kspec *k, double log_sn, double mean,

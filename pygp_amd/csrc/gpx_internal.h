@@ -259,6 +259,8 @@ hipEvent_t gpx_potrf_lead_event(const DenseWs &w);
 // complete W = R^-1 after a gpx_potrf(..., false)
 int gpx_trtri(hipStream_t s, const DenseWs &w);
 int gpx_lauum(hipStream_t s, const DenseWs &w);            // Kinv = W W^T
+// C = S S^T on the tiles with column >= row, S a full np x np matrix (ld w.ld, like C)
+int gpx_aat_upper(hipStream_t s, const DenseWs &w, const double *S, double *C);
 // X = R^-T B for B (np x m, ld ldb) in place, m multiple of GPX_TILE; T is a
 // scratch of the same shape as B
 // (w.batch members: their panels B and T lie pstride elements apart)
@@ -461,6 +463,17 @@ int gpx_trace_grad(hipStream_t s, const KParams &kp, const double *X, int n,
                    int np, int d, const double *Kinv, int ld, const double *alpha,
                    double *partial, double *acc, const MemberBatch *mb = nullptr,
                    int astride = 0);
+
+// ---- leave-one-out cross-validation (loo.hip) ----------------------------------------
+// From w.Kinv (upper) and alpha = K^-1 (y - m): out[0] = sum_i [1/2 log q_i - 1/2 alpha_i^2 /
+// q_i], q = diag K^-1; the LOO means and variances into vec[0 .. np) and vec[np .. 2 np).
+// grad: also out[1] = dL/dmean, out[4] = -tr(G), out[5 + h] = -<G, dK_h> (the accumulators of
+// gpx_trace_grad on -G). S, M: np x ld matrices (grad only); vec: gpx_loo_scratch(np) doubles;
+// trace_partial: gpx_trace_scratch(np) doubles. W, Kinv, alpha and the factor are only read.
+size_t gpx_loo_scratch(int np);
+int gpx_loo(hipStream_t s, const DenseWs &w, const KParams &kp, const double *X,
+            const double *y, int n, int d, const double *alpha, bool grad, double *S, double *M,
+            double *vec, double *trace_partial, double *out);
 
 // sum_{i < n1, j < n2} G[i][j] dK_h(X1_i, X2_j) for every kernel hyper h, without writing
 // the slices of dK: acc[1 + h] (acc[0] = 0), fixed-order reduction (sparse models).

@@ -231,6 +231,23 @@ class ExactGP(GP):
         self._ensure()
         return self._dev().exact_loglik(self._kernel.nhyper, grad)
 
+    def loo(self, grad=False):
+        """Leave-one-out log predictive probability, sum_i log p(y_i | X, y_-i) (GPML
+        eq. 5.10-5.11), and with grad its derivatives in the hyper layout and sign
+        convention of loglikelihood. No counterpart in the reference."""
+        if self.ndata == 0:
+            raise ValueError('no data')
+        self._ensure()
+        return self._dev().exact_loo(self._kernel.nhyper, self.ndata, grad)
+
+    def loo_posterior(self):
+        """(mu, s2): for every observation, in the data's order, the predictive mean and
+        variance of y_i given all the other observations (GPML eq. 5.12)."""
+        if self.ndata == 0:
+            raise ValueError('no data')
+        self._ensure()
+        return self._dev().exact_loo(self._kernel.nhyper, self.ndata, points=True)
+
     def _marg_posterior(self, X, grad=False):
         """Predictive mean and variance (exact.py:81-97)."""
         if self._X is None:

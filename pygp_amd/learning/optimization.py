@@ -5,7 +5,8 @@ The reference's optimize() (/root/reference/pygp/learning/optimization.py:21-67)
 is pure control flow over get_hyper / set_hyper / loglikelihood(True); it is
 restated here only so that the drop-in can be exercised end to end
 (tests/test_gpu_gp.py reproduces /root/reference/tests/test_learning.py). Each
-objective call is one gpx_exact_update + one gpx_exact_loglik on the device.
+objective call is one gpx_exact_update + one gpx_exact_loglik on the device
+(objective='loo': one gpx_exact_loo, the leave-one-out log predictive probability).
 """
 
 import numpy as np
@@ -16,11 +17,20 @@ from ..utils.models import get_params
 __all__ = ['optimize']
 
 
-def optimize(gp, priors=None, pseudoinputs=False):
+def optimize(gp, priors=None, pseudoinputs=False, objective='lik'):
     """Maximise the marginal likelihood over the hypers of `gp` in place.
     priors: {name: None} freezes the named block (the only prior form the
     reference supports, optimization.py:47-52). pseudoinputs: also move the
-    pseudo-inputs of a sparse model (FITC, DTC, VFE), jointly with the free hypers."""
+    pseudo-inputs of a sparse model (FITC, DTC, VFE), jointly with the free hypers.
+    objective: 'lik' the marginal likelihood, 'loo' the leave-one-out log predictive
+    probability (gp.loo, exact models only)."""
+    if objective not in ('lik', 'loo'):
+        raise ValueError("objective must be 'lik' or 'loo'")
+    if objective == 'loo':
+        if pseudoinputs:
+            raise ValueError('the leave-one-out objective does not move pseudo-inputs')
+        if not hasattr(gp, 'loo'):
+            raise ValueError('the leave-one-out objective needs an exact model')
     if pseudoinputs:
         return _optimize_pseudo(gp, priors)
     start = gp.get_hyper()
@@ -35,7 +45,7 @@ def optimize(gp, priors=None, pseudoinputs=False):
         hyper = start.copy()
         hyper[free] = x
         gp.set_hyper(hyper)
-        lZ, dlZ = gp.loglikelihood(True)
+        lZ, dlZ = gp.loo(True) if objective == 'loo' else gp.loglikelihood(True)
         return -lZ, -dlZ[free]
 
     x, _, _ = so.fmin_l_bfgs_b(negative_loglik, start[free])
