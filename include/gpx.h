@@ -276,6 +276,23 @@ int gpx_sparse_loglik_pseudo(gpx_t *h, double *lZ, double *dlZ, double *dU);
  * update) */
 int gpx_sparse_pseudo_timing(gpx_t *h, double *ms);
 
+/* ---- greedy pseudo-input selection --------------------------------------- */
+/* Greedy conditional-variance selection = pivoted partial Cholesky of K(X,X) (own design).
+ * X == NULL: the handle's resident data (gpx_set_data); else X[n*d] is copied to buffers of
+ * the call's own. Never touches the resident data, an exact factorisation or a sparse model
+ * of the handle. idx[p], piv[p], trace[p] (piv, trace may be NULL); *count <= p.
+ * Step j takes the point i_j with the largest residual prior variance d given the points
+ * chosen so far (on exact ties the lowest index) and stops when d <= tol * k(x, x) or d <= 0
+ * (tol >= 0): idx[j] = i_j, piv[j] = that d, trace[j] = tr(K - Q) after the step, k the
+ * noise-free kernel. Slots beyond *count are not written. Limits as gpx_sparse_update:
+ * d <= GPX_MAX_DIM, 1 <= n <= 2^20, 1 <= p <= min(n, GPX_SPARSE_MAX_P),
+ * round_up(p, 128) * round_up(n, 128) < 2^31. */
+int gpx_select_pivots(gpx_t *h, const gpx_kspec *k, const double *X, int64_t n, int64_t d,
+                      int64_t p, double tol, int64_t *idx, double *piv, double *trace,
+                      int64_t *count);
+/* HIP-event ms around the launches of the last gpx_select_pivots on this handle (0: none) */
+int gpx_select_timing(gpx_t *h, double *ms);
+
 /* ---- instrumentation ---------------------------------------------------- */
 /* per-stage GPU times (ms) of the last gpx_exact_eval / update+loglik measured
  * with HIP events on the handle's stream. names via gpx_timing_name(i). */

@@ -50,6 +50,7 @@ _i64 = C.c_int64
 
 # name -> (restype, argtypes); mirrors include/gpx.h one to one
 GPX_FITC, GPX_DTC, GPX_VFE = 1, 2, 3          # enum gpx_sparse_method
+GPX_SPARSE_MAX_P = 4096
 
 SIGNATURES = {
     'gpx_version': (C.c_int, []),
@@ -87,6 +88,9 @@ SIGNATURES = {
     'gpx_sparse_timings': (C.c_int, [_vp, _vp]),
     'gpx_sparse_loglik_pseudo': (C.c_int, [_vp, _vp, _vp, _vp]),
     'gpx_sparse_pseudo_timing': (C.c_int, [_vp, _vp]),
+    'gpx_select_pivots': (C.c_int, [_vp, C.POINTER(_KSpec), _vp, _i64, _i64, _i64, C.c_double,
+                                    _vp, _vp, _vp, C.POINTER(_i64)]),
+    'gpx_select_timing': (C.c_int, [_vp, _vp]),
     'gpx_loglik_batch': (C.c_int, [_vp, C.POINTER(_KSpec), _vp, _i64, C.c_int,
                                    _vp, _vp, _vp]),
     'gpx_batch_plan': (C.c_int, [_vp, _i64, C.c_int, _ip]),
@@ -441,6 +445,31 @@ class Handle(object):
         """HIP-event ms of the dU pass of the last sparse_loglik_pseudo."""
         ms = np.zeros(1)
         check(self._L.gpx_sparse_pseudo_timing(self._h, _ptr(ms)))
+        return float(ms[0])
+
+    def select_pivots(self, spec, X, p, tol=0.0):
+        """Greedy conditional-variance selection (pivoted partial Cholesky of K(X, X)) of at
+        most p rows of X (n x d, host), or of the handle's resident data when X is None:
+        (idx, piv, trace), each of length count <= p."""
+        p = int(p)
+        if X is None:
+            n = d = 0
+        else:
+            X = _f64(X, 2)
+            n, d = X.shape
+        size = max(p, 0)
+        idx = np.empty(size, dtype=np.int64)
+        piv, trace = np.empty(size), np.empty(size)
+        count = _i64(0)
+        check(self._L.gpx_select_pivots(self._h, spec.ref(), _ptr(X), n, d, p, float(tol),
+                                        _ptr(idx), _ptr(piv), _ptr(trace), C.byref(count)))
+        c = count.value
+        return idx[:c].copy(), piv[:c].copy(), trace[:c].copy()
+
+    def select_timing(self):
+        """HIP-event ms around the launches of the last select_pivots."""
+        ms = np.zeros(1)
+        check(self._L.gpx_select_timing(self._h, _ptr(ms)))
         return float(ms[0])
 
     def sparse_get_state(self, p):

@@ -100,6 +100,8 @@ struct gpx_ctx {
     // exact-GP state above stays valid beside it. Valid for the data of sparse_version only.
     GpxSparse *sparse = nullptr;
     long sparse_version = -1;
+    // greedy pseudo-input selection (select.hip), created on first use; buffers of its own
+    GpxSelect *select = nullptr;
     // look-ahead of the factorisation (chol.hip): diagonal blocks on a high-priority
     // stream, the left half of the inverse tree on a low-priority one
     hipStream_t crit = nullptr, aux = nullptr, bulk = nullptr;
@@ -499,6 +501,10 @@ int gpx_destroy(gpx_t *h)
     if (h->sparse) {
         gpx_sparse_destroy(h->sparse);
         h->sparse = nullptr;
+    }
+    if (h->select) {
+        gpx_select_destroy(h->select);
+        h->select = nullptr;
     }
     if (h->groups) {
         DLOG("groups");
@@ -1873,6 +1879,68 @@ int gpx_sparse_pseudo_timing(gpx_t *h, double *ms)
         return -1;
     }
     return gpx_sparse_run_pseudo_timing(h->sparse, ms);
+}
+
+// ---- greedy pseudo-input selection (select.hip) ---------------------------------------
+int gpx_select_pivots(gpx_t *h, const gpx_kspec *k, const double *X, int64_t n, int64_t d,
+                      int64_t p, double tol, int64_t *idx, double *piv, double *trace,
+                      int64_t *count)
+{
+    CHECK_H(h);
+    if (!k || !idx || !count) {
+        gpx_set_error("gpx_select_pivots: k, idx and count must not be null");
+        return -1;
+    }
+    if (!X) {
+        if (h->n <= 0) {
+            gpx_set_error("gpx_select_pivots: X is null and the handle has no data "
+                          "(gpx_set_data)");
+            return -1;
+        }
+        n = h->n;
+        d = h->d;
+    }
+    if (n < 1 || n > (1 << 20) || d < 1 || d > GPX_MAX_DIM) {
+        gpx_set_error("gpx_select_pivots: bad shape n=%lld d=%lld (1 <= n <= 2^20, d <= %d)",
+                      (long long)n, (long long)d, GPX_MAX_DIM);
+        return -1;
+    }
+    if (p < 1 || p > n || p > GPX_SPARSE_MAX_P) {
+        gpx_set_error("gpx_select_pivots: need 1 <= p <= min(n, %d) (got p=%lld, n=%lld)",
+                      GPX_SPARSE_MAX_P, (long long)p, (long long)n);
+        return -1;
+    }
+    const long long pp = round_up(p, GPX_TILE), np = round_up(n, GPX_TILE);
+    if (pp * np >= (1LL << 31)) {
+        gpx_set_error("gpx_select_pivots: p_pad * N_pad = %lld x %lld must stay below 2^31", pp,
+                      np);
+        return -1;
+    }
+    if (!(tol >= 0.0) || !std::isfinite(tol)) {
+        gpx_set_error("gpx_select_pivots: tol must be finite and >= 0");
+        return -1;
+    }
+    if (X)
+        for (int64_t i = 0; i < n * d; ++i)
+            if (!std::isfinite(X[i])) {
+                gpx_set_error("gpx_select_pivots: non-finite X");
+                return -1;
+            }
+    KParams kp;
+    GPX_TRY(gpx_flatten_kspec(k, d, &kp));
+    return gpx_select_run(&h->select, h->stream, kp, X ? nullptr : h->X.as<double>(), X, (int)n,
+                          (int)d, (int)p, tol, idx, piv, trace, count);
+}
+
+int gpx_select_timing(gpx_t *h, double *ms)
+{
+    CHECK_H(h);
+    if (!ms) {
+        gpx_set_error("gpx_select_timing: ms is null");
+        return -1;
+    }
+    *ms = gpx_select_ms(h->select);
+    return 0;
 }
 
 int gpx_exact_get_factor(gpx_t *h, int64_t n, double *R, double *a)

@@ -512,6 +512,21 @@ int gpx_sparse_nhyper(const GpxSparse *st);
 int gpx_sparse_run_timings(GpxSparse *st, double *ms);
 void gpx_sparse_destroy(GpxSparse *st);
 
+// ---- greedy pseudo-input selection (select.hip) ----------------------------------------
+// out[j] = k(x_j, x*) for j < n, 0 for n <= j < np; x* = xs[0 .. d) on the device, written by
+// an earlier launch of the stream. *stop (device) != 0: the launch returns at once (kmat.hip)
+int gpx_kcolumn(hipStream_t s, const KParams &kp, const double *X, int n, int np, int d,
+                const double *xs, const int *stop, double *out);
+// the pivoted partial Cholesky factorisation of K(X, X) on Xdev (n x d, device) or, Xdev null,
+// on a copy of Xhost in the state's own buffer: idx[p], piv[p], trace[p] (either may be null),
+// *count <= p. One host synchronisation. *state is created on first use (per handle)
+struct GpxSelect;
+int gpx_select_run(GpxSelect **state, hipStream_t s, const KParams &kp, const double *Xdev,
+                   const double *Xhost, int n, int d, int p, double tol, int64_t *idx,
+                   double *piv, double *trace, int64_t *count);
+double gpx_select_ms(const GpxSelect *st);   // HIP-event ms of the last run's launches
+void gpx_select_destroy(GpxSelect *st);
+
 // d k / d x2 (sign = +1) or d k / d x1 (sign = -1): out[n1][n2][d]
 int gpx_kgrady(hipStream_t s, const KParams &kp, const double *X1, int n1, const double *X2,
                int n2, int d, double sign, double *out);

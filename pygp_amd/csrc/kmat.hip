@@ -1566,6 +1566,40 @@ int gpx_pair_grad(hipStream_t s, const KParams &kp, const double *X1, int n1,
     return 0;
 }
 
+// ---- one kernel column against a point staged on the device (select.hip) ----------------
+// out[j] = k(x_j, x*) for j < n and 0 for n <= j < np, the noise-free kernel: the sum over the
+// groups of the product of their parts, each group entered at its first part (part_value_pair
+// times group_factor, the per-pair code of the gradients above). x* = xs[0 .. d) was written by
+// an earlier launch on the stream; *stop != 0: nothing to do (the selection has ended).
+__global__ __launch_bounds__(256) void kcolumn_kernel(KParams kp, const double *__restrict__ X,
+                                                     int n, int np, int d,
+                                                     const double *__restrict__ xs,
+                                                     const int *__restrict__ stop,
+                                                     double *__restrict__ out)
+{
+    if (*stop) return;
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= np) return;
+    double v = 0.0;
+    if (j < n) {
+        const double *xj = X + (size_t)j * d;
+        for (int p = 0; p < kp.nparts; ++p) {
+            if (p > 0 && kp.part[p].group == kp.part[p - 1].group) continue;
+            v += part_value_pair(kp.part[p], xj, xs, d) * group_factor(kp, p, xj, xs, d);
+        }
+    }
+    out[j] = v;
+}
+
+int gpx_kcolumn(hipStream_t s, const KParams &kp, const double *X, int n, int np, int d,
+                const double *xs, const int *stop, double *out)
+{
+    hipLaunchKernelGGL(kcolumn_kernel, dim3((np + 255) / 256), dim3(256), 0, s, kp, X, n, np, d,
+                       xs, stop, out);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
 // ---- weighted input gradient over a rectangular pair set (pseudo-inputs, sparse.hip) --
 // part[c0][i][c] = sum_{j in chunk c0} Gs_ij d k(x1_i, x2_j) / d x1_ic, Gs_ij = G[i][j]
 // (+ G[j][i] with sym: the (U, U) set, where x1_i sits in both arguments of k). The grid,

@@ -3,5 +3,6 @@ from .basic import BasicGP
 from .fitc import FITC
 from .dtc import DTC
 from .vfe import VFE
+from .select import select_pseudoinputs
 
-__all__ = ['GP', 'ExactGP', 'BasicGP', 'FITC', 'DTC', 'VFE']
+__all__ = ['GP', 'ExactGP', 'BasicGP', 'FITC', 'DTC', 'VFE', 'select_pseudoinputs']

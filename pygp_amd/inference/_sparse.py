@@ -13,6 +13,7 @@ import numpy as np
 from ..likelihoods import Gaussian
 from .. import _lib
 from .exact import GP
+from .select import select_pseudoinputs, _check as select_check
 
 __all__ = ['SparseGP']
 
@@ -77,8 +78,17 @@ class SparseGP(GP):
         self._factored = False
 
     @classmethod
-    def from_gp(cls, gp, U=None):
-        if U is None:
+    def from_gp(cls, gp, U=None, p=None, tol=0.0):
+        """A sparse model with gp's likelihood, kernel, mean and data. U: the pseudo-inputs;
+        or p: choose at most p of gp's inputs greedily under a copy of gp's kernel
+        (select_pseudoinputs); neither: gp's own pseudo-inputs."""
+        if U is not None and p is not None:
+            raise ValueError('give the pseudo-inputs U or their number p, not both')
+        if p is not None:
+            if gp.ndata == 0:
+                raise ValueError('gp has no data to select pseudo-inputs from')
+            U = select_pseudoinputs(gp._kernel.copy(), gp.data[0], p, tol)[0]
+        elif U is None:
             if hasattr(gp, 'pseudoinputs'):
                 U = gp.pseudoinputs.copy()
             else:
@@ -87,6 +97,28 @@ class SparseGP(GP):
         if gp.ndata > 0:
             new.add_data(*gp.data)
         return new
+
+    def reselect(self, p=None, tol=0.0):
+        """Select the pseudo-inputs again at the current hypers, on the resident data of the
+        model's own handle (p: at most that many, default the current number), and move to
+        them (set_pseudoinputs): the natural alternation with optimize. Returns
+        (idx, trace) of the selection."""
+        if self.ndata == 0:
+            raise ValueError('no data')
+        p = self._U.shape[0] if p is None else p
+        select_check(self._X.shape[0], self._X.shape[1], p, tol)
+        if not np.all(np.isfinite(self._kernel.get_hyper())):
+            raise ValueError('array must not contain infs or NaNs')
+        dev = self._dev()
+        if not self._resident:
+            if not (np.all(np.isfinite(self._X)) and np.all(np.isfinite(self._y))):
+                raise ValueError('array must not contain infs or NaNs')
+            dev.set_data(self._X, self._y)
+            self._resident = True
+            self._factored = False
+        idx, _, trace = dev.select_pivots(self._kernel._kspec(), None, int(p), tol)
+        self.set_pseudoinputs(self._X[idx])
+        return idx, trace
 
     def reset(self):
         super(SparseGP, self).reset()
