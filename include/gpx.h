@@ -254,6 +254,20 @@ int gpx_posterior_batch(gpx_t *h, const gpx_kspec *k, const double *thetas, int6
 enum gpx_sparse_method { GPX_FITC = 1, GPX_DTC = 2, GPX_VFE = 3 };
 int gpx_sparse_update(gpx_t *h, const gpx_kspec *k, int method, const double *U, int64_t p,
                       double log_sn, double mean, int *info);
+/* m new observations Xnew[m*d], ynew[m] behind the resident data and into the current sparse
+ * model, in place: O(p^2 m + p^3) and one upload of m rows whatever N is (the model keeps
+ * I + V V^T, V rt and its scalar sums on the device; the new columns add to them in a fixed
+ * order and the p x p matrix is factorised again). Results agree with a gpx_sparse_update on
+ * the grown data to rounding, not bit for bit, and the same sequence of calls gives the same
+ * bits. On success the handle holds n + m observations, the sparse model is current for them,
+ * and an exact factorisation of the handle is stale as after gpx_set_data. Returns -3, with no
+ * error text and nothing touched, when that is not possible: no current sparse model, n + m
+ * beyond the capacity gpx_set_data reserved (at least 256 rows), or a model whose panels could
+ * not take the capacity as leading dimension within the limits above; the caller then calls
+ * gpx_set_data + gpx_sparse_update. Any other nonzero result (a device error, or the pivot > 0
+ * of a sum that is not positive definite, also in *info) leaves the handle on its old n and
+ * the sparse model not ready: its calls fail until the next gpx_sparse_update. */
+int gpx_sparse_append(gpx_t *h, const double *Xnew, const double *ynew, int64_t m, int *info);
 /* loglikelihood of the last update; dlZ == NULL: value only, else dlZ[1 + nhyper + 1] in
  * order [sn, kernel..., mean] (fitc.py / dtc.py loglikelihood) */
 int gpx_sparse_loglik(gpx_t *h, double *lZ, double *dlZ);
@@ -265,7 +279,8 @@ int gpx_sparse_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu,
 /* the stored statistics, p x p row-major upper factors and a p-vector (any may be NULL):
  * FITC _L, _R, _b; DTC and VFE _Ruu, _Rux, _a */
 int gpx_sparse_get_state(gpx_t *h, double *F1, double *F2, double *v);
-/* HIP-event times (ms) of the last sparse calls on this handle: ms[0] the update,
+/* HIP-event times (ms) of the last sparse calls on this handle: ms[0] the update (or the
+ * append, when a gpx_sparse_append was the last change of the model),
  * ms[1] the gradient stage of the last gpx_sparse_loglik with dlZ (0 if none since the
  * update), ms[2] the contraction pass inside it */
 int gpx_sparse_timings(gpx_t *h, double *ms);

@@ -81,6 +81,7 @@ SIGNATURES = {
     'gpx_exact_get_factor': (C.c_int, [_vp, _i64, _vp, _vp]),
     'gpx_sparse_update': (C.c_int, [_vp, C.POINTER(_KSpec), C.c_int, _vp, _i64, C.c_double,
                                     C.c_double, _ip]),
+    'gpx_sparse_append': (C.c_int, [_vp, _vp, _vp, _i64, _ip]),
     'gpx_sparse_loglik': (C.c_int, [_vp, _vp, _vp]),
     'gpx_sparse_posterior': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     'gpx_sparse_posterior_full': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
@@ -404,6 +405,20 @@ class Handle(object):
         info = C.c_int(0)
         check(self._L.gpx_sparse_update(self._h, spec.ref(), int(method), _ptr(U), U.shape[0],
                                         float(log_sn), float(mean), C.byref(info)))
+
+    def sparse_append(self, Xnew, ynew):
+        """True if the sparse model took the new observations in place, False if the caller
+        has to upload everything and refactor (no current model / they do not fit)."""
+        Xnew, ynew = _f64(Xnew, 2), _f64(ynew, 1)
+        if Xnew.shape[0] != ynew.shape[0]:
+            raise ValueError('X and y disagree')
+        info = C.c_int(0)
+        code = self._L.gpx_sparse_append(self._h, _ptr(Xnew), _ptr(ynew), Xnew.shape[0],
+                                         C.byref(info))
+        if code == -3:
+            return False
+        check(code)
+        return True
 
     def sparse_loglik(self, nhyper_kernel, grad=False):
         lZ = C.c_double(0)

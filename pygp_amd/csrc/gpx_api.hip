@@ -1802,9 +1802,50 @@ int gpx_sparse_update(gpx_t *h, const gpx_kspec *k, int method, const double *U,
     GPX_TRY(gpx_flatten_kspec(k, h->d, &kp));
     const int r = gpx_sparse_run_update(&h->sparse, h->stream, kp, method, U, (int)p, log_sn,
                                         mean, h->X.as<double>(), h->y.as<double>(), h->n, h->d,
-                                        info);
+                                        h->cap, info);
     if (r == 0) h->sparse_version = h->data_version;
     return r;
+}
+
+// m observations behind the resident data and into the current sparse model, in
+// O(p^2 m + p^3) whatever N is (sparse.hip, gpx_sparse_run_append). -3 (no error text) when
+// that is not possible; nothing has been touched then.
+int gpx_sparse_append(gpx_t *h, const double *Xnew, const double *ynew, int64_t m, int *info)
+{
+    CHECK_H(h);
+    if (info) *info = 0;
+    if (!Xnew || !ynew || m < 1) {
+        gpx_set_error("gpx_sparse_append: bad arguments");
+        return -1;
+    }
+    if (!h->sparse || h->sparse_version < 0 || h->sparse_version != h->data_version ||
+        h->n <= 0 || h->n + m > h->cap)
+        return -3;
+    const int n_old = h->n;
+    const size_t xrow = (size_t)h->d * 8;
+    if (h->X.bytes < (size_t)(n_old + m) * xrow || h->y.bytes < (size_t)(n_old + m) * 8 ||
+        !gpx_sparse_can_append(h->sparse, n_old, (int)m))
+        return -3;
+    double *Xd = h->X.as<double>() + (size_t)n_old * h->d, *yd = h->y.as<double>() + n_old;
+    GPX_HIP(hipMemcpyAsync(Xd, Xnew, (size_t)m * xrow, hipMemcpyHostToDevice, h->stream));
+    GPX_HIP(hipMemcpyAsync(yd, ynew, (size_t)m * 8, hipMemcpyHostToDevice, h->stream));
+    const int r = gpx_sparse_run_append(h->sparse, h->stream, Xd, yd, n_old, (int)m, info);
+    if (r != 0) {
+        // the rows behind n are never read and the old data stand (h->n, h->np), but the
+        // model's sums and factor are gone: every sparse call fails until gpx_sparse_update
+        (void)hipStreamSynchronize(h->stream);
+        h->sparse_version = -1;
+        return r;
+    }
+    // the data changed: an exact factorisation of this handle is stale as after gpx_set_data
+    h->n = n_old + (int)m;
+    h->np = round_up(h->n, GPX_TILE);
+    h->data_version++;
+    h->sparse_version = h->data_version;
+    h->have_factor = h->have_inverse = false;
+    h->kinv_ready = false;
+    h->posterior_calls = 0;
+    return 0;
 }
 
 int gpx_sparse_loglik(gpx_t *h, double *lZ, double *dlZ)

@@ -498,7 +498,15 @@ int gpx_pair_gradx(hipStream_t s, const KParams &kp, const double *X1, int n1,
 struct GpxSparse;
 int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, int method,
                           const double *U, int p, double log_sn, double mean,
-                          const double *X, const double *y, int n, int d, int *info);
+                          const double *X, const double *y, int n, int d, int cap, int *info);
+// m new observations behind the n_old of the last update or append, in place: Xnew (m x d) and
+// ynew are the rows on the device, behind the resident ones. cap above: the rows the
+// handle's data buffers hold, the leading dimension of the model's p x N panels where the
+// limits allow it. -3: the model cannot take them and nothing was touched; any other nonzero
+// result leaves the model not ready
+bool gpx_sparse_can_append(const GpxSparse *st, int n_old, int m);
+int gpx_sparse_run_append(GpxSparse *st, hipStream_t s, const double *Xnew, const double *ynew,
+                          int n_old, int m, int *info);
 int gpx_sparse_run_loglik(GpxSparse *st, hipStream_t s, const double *X, double *lZ,
                           double *dlZ);
 // gpx_sparse_run_loglik with dlZ, then dU[p * d] = d lZ / d U from its adjoints

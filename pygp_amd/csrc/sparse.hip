@@ -12,6 +12,12 @@
 // contraction dlZ_k = <dKuu_k, G_uu> + <dKux_k, G_ux> + <dkxx_k, g_x> (gpx_pair_grad,
 // kmat.hip); column kernels below carry the O(pN) terms. Every reduction has a fixed order:
 // the same call gives the same bits.
+//
+// gpx_sparse_run_append grows a model in place: L does not depend on
+// the data and everything else is a sum over columns, so the update keeps I + V V^T (before
+// its factorisation) and V rt on the device, and m new observations cost the strip of their
+// columns plus the p x p re-factorisation. The panels have a leading dimension of their own
+// (ldn, the handle's data capacity) so that the columns have somewhere to go.
 #include "gpx_internal.h"
 #include <algorithm>
 #include <cmath>
@@ -69,12 +75,16 @@ enum {
 
 struct GpxSparse {
     int method = 0, p = 0, pp = 0, ldp = 0, n = 0, np = 0, d = 0;
+    // leading dimension of the p x N panels and length of the N-vectors: the handle's data
+    // capacity, or np where pp * capacity would pass the 2^31 limit of the tile engine (such
+    // a model cannot open a new 128-block). n and np stay the logical sizes.
+    int ldn = 0;
     KParams kp;
     double sn2 = 0, su2 = 0, mean = 0, prior = 0;
     bool ready = false;
     int gates_l[2] = {0, 0}, gates_a[2] = {0, 0};
     SpBuf U, L, Lw, Lk, A, Aw, Ak, info, pctl;
-    // p x N panels (ld np). P2 holds V from the update to the next update: the gradient
+    // p x N panels (ld ldn). P2 holds V from the update to the next update: the gradient
     // stage reads it and writes only P1 (B), P3 (W, then FITC's B diag(e)) and P4 (C W, then
     // G_ux), so a second gradient call on the same state sees the same V
     SpBuf P1, P2, P3, P4;
@@ -83,6 +93,12 @@ struct GpxSparse {
     SpBuf Xs, Ks, Q1, Q2, dKc, dK, dQ1, dQ2, mu, s2, dmu, ds2, Sig;
     // the pseudo-input gradient (gpx_sparse_run_loglik_pseudo only): chunk partials, dU
     SpBuf px_part, dU;
+    // kept from one update or append to the next: I + V V^T before its factorisation (pp x pp,
+    // ld ldp, as A receives it) and V rt (pp)
+    SpBuf VV, vrt;
+    // gpx_sparse_run_append: three pp x round_up(m, 128) strips, the strip's share of V rt,
+    // block partials and sums of its column kernel
+    SpBuf S1, S2, S3, svrt, spart, sscal;
     double hsc[S_COUNT];
     // HIP events around the last update, gradient stage and contraction pass, then the dU
     // pass (ms)
@@ -220,6 +236,87 @@ __global__ __launch_bounds__(SP_T) void sp_coltrace_kernel(const double *__restr
     }
     q = sp_block_sum(q, red);
     if (threadIdx.x == 0) part[blockIdx.x] = q;
+}
+
+// x[i][j] += d[i][j] for i < rows, j < cols (both ld)
+__global__ __launch_bounds__(SP_T) void sp_add_panel_kernel(double *__restrict__ x,
+                                                           const double *__restrict__ d,
+                                                           long long ld, int cols)
+{
+    const int j = blockIdx.x * SP_T + threadIdx.x;
+    if (j >= cols) return;
+    const size_t o = (size_t)blockIdx.y * ld + j;
+    x[o] += d[o];
+}
+
+// The column kernel of an append, one thread per column c of [n_old, np_new): c < m is a new
+// observation whose refined V0 column sits in the strip S (pp rows, ld lds): ell, rt (and
+// VFE's kxx - |V0|^2 from the unscaled column), the column scaled to V in place in the strip
+// and copied to column n_old + c of the panel V (ld ld); the columns behind the new n up to
+// np_new are the padding of a block the append may have opened: zero, ell = 1, rt = 0.
+// part[block][5]: sum log ell, sum rt^2, sum V^2, sum 1 / ell^2, sum (kxx - |V0|^2).
+__global__ __launch_bounds__(SP_T) void sp_colappend_kernel(
+    double *__restrict__ S, long long lds, double *__restrict__ V, long long ld, int pp,
+    int n_old, int m, int np_new, const double *__restrict__ ynew, double mean, double kxx,
+    double sn2, int fitc, double *__restrict__ ell, double *__restrict__ rt,
+    double *__restrict__ part)
+{
+    __shared__ double red[SP_T];
+    const int c = blockIdx.x * SP_T + threadIdx.x;
+    const int j = n_old + c;
+    double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0, q4 = 0.0;
+    if (c < m) {
+        double sq = 0.0;
+        for (int i = 0; i < pp; ++i) {
+            const double v = S[(size_t)i * lds + c];
+            sq += v * v;
+        }
+        const double l = fitc ? sqrt(kxx + sn2 - sq) : sqrt(sn2);
+        double s2 = 0.0;
+        for (int i = 0; i < pp; ++i) {
+            const double v = S[(size_t)i * lds + c] / l;
+            S[(size_t)i * lds + c] = v;
+            V[(size_t)i * ld + j] = v;
+            s2 += v * v;
+        }
+        const double r = (ynew[c] - mean) / l;
+        ell[j] = l;
+        rt[j] = r;
+        q0 = log(l);
+        q1 = r * r;
+        q2 = s2;
+        q3 = 1.0 / (l * l);
+        q4 = kxx - sq;
+    } else if (j < np_new) {
+        for (int i = 0; i < pp; ++i) V[(size_t)i * ld + j] = 0.0;
+        ell[j] = 1.0;
+        rt[j] = 0.0;
+    }
+    double *po = part + (size_t)blockIdx.x * 5;
+    double s = sp_block_sum(q0, red);
+    if (threadIdx.x == 0) po[0] = s;
+    s = sp_block_sum(q1, red);
+    if (threadIdx.x == 0) po[1] = s;
+    s = sp_block_sum(q2, red);
+    if (threadIdx.x == 0) po[2] = s;
+    s = sp_block_sum(q3, red);
+    if (threadIdx.x == 0) po[3] = s;
+    s = sp_block_sum(q4, red);
+    if (threadIdx.x == 0) po[4] = s;
+}
+
+// the kept sums take a strip's share, old + strip: scal[S_LOGELL .. S_IELL2] += sums[0 .. 3],
+// scal[S_T] += sums[4] (VFE only), vrt[i] += svrt[i] for i < pp
+__global__ __launch_bounds__(SP_T) void sp_accumulate_kernel(double *__restrict__ scal,
+                                                            const double *__restrict__ sums,
+                                                            int vfe, double *__restrict__ vrt,
+                                                            const double *__restrict__ svrt,
+                                                            int pp)
+{
+    const int i = blockIdx.x * SP_T + threadIdx.x;
+    if (i < pp) vrt[i] = vrt[i] + svrt[i];
+    if (i < 4) scal[S_LOGELL + i] = scal[S_LOGELL + i] + sums[i];
+    if (i == 4 && vfe) scal[S_T] = scal[S_T] + sums[4];
 }
 
 // out[:, j] = in[:, j] * c_j (div: / c_j; c null: 1) for j < cols, q[j] = sum_i out_ij^2
@@ -566,16 +663,47 @@ void gpx_sparse_destroy(GpxSparse *st)
                      &st->part, &st->scal, &st->acc_uu, &st->acc_ux, &st->pg_part, &st->split,
                      &st->Cm, &st->CC, &st->BEB, &st->Guu, &st->R2, &st->Xs, &st->Ks, &st->Q1,
                      &st->Q2, &st->dKc, &st->dK, &st->dQ1, &st->dQ2, &st->mu, &st->s2,
-                     &st->dmu, &st->ds2, &st->Sig, &st->px_part, &st->dU};
+                     &st->dmu, &st->ds2, &st->Sig, &st->px_part, &st->dU, &st->VV, &st->vrt,
+                     &st->S1, &st->S2, &st->S3, &st->svrt, &st->spart, &st->sscal};
     for (SpBuf *b : bufs) b->release();
     for (hipEvent_t e : st->ev)
         if (e) (void)hipEventDestroy(e);
     delete st;
 }
 
+// The tail of an update and of an append: A = chol(VV) from the kept sum I + V V^T,
+// beta = A^-T (V rt) from the kept vector, the factor's scalars, and the scalars to the host.
+// Returns the pivot (> 0, also in *info) when the sum is not positive definite.
+static int sp_finish(GpxSparse *st, hipStream_t s, int *info)
+{
+    const int p = st->p, pp = st->pp, ldp = st->ldp;
+    GPX_HIP(hipMemcpyAsync(st->A.p, st->VV.p, (size_t)pp * ldp * 8, hipMemcpyDeviceToDevice, s));
+    const int r = sp_factor(st, s, st->A.d(), st->Aw.d(), st->Ak.d(), st->gates_a);
+    if (r != 0) {
+        if (r > 0 && info) *info = r;
+        return r;
+    }
+    hipLaunchKernelGGL(sp_gemv_cols_kernel, dim3((pp + SP_T - 1) / SP_T), dim3(SP_T), 0, s,
+                       st->Aw.d(), (long long)ldp, pp, pp, st->vrt.d(), st->beta.d());
+    GPX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(sp_factor_terms_kernel, dim3(p), dim3(SP_T), 0, s, st->A.d(), st->Aw.d(),
+                       ldp, p, st->part.d());
+    GPX_HIP(hipGetLastError());
+    GPX_TRY(sp_reduce(s, st->part.d(), p, 2, st->scal.d() + S_LOGA));
+    GPX_TRY(sp_dot(s, st->beta.d(), nullptr, pp, st->scal.d() + S_BETA2));
+    GPX_HIP(hipMemcpyAsync(st->hsc, st->scal.p, S_COUNT * 8, hipMemcpyDeviceToHost, s));
+    GPX_TRY(sp_event(st, s, 1));
+    GPX_HIP(hipStreamSynchronize(s));
+    st->ms[0] = sp_elapsed(st, 0, 1);
+    st->ms[1] = st->ms[2] = 0.0;
+    st->ms_pseudo = 0.0;
+    st->ready = true;
+    return 0;
+}
+
 int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, int method,
                           const double *U, int p, double log_sn, double mean,
-                          const double *X, const double *y, int n, int d, int *info)
+                          const double *X, const double *y, int n, int d, int cap, int *info)
 {
     if (!*state) *state = new GpxSparse();
     GpxSparse *st = *state;
@@ -586,6 +714,8 @@ int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, i
     st->ldp = st->pp + 32;                 // rows off one HBM channel, as ld_for does
     st->n = n;
     st->np = sp_round(n, GPX_TILE);
+    st->ldn = cap > st->np && cap % 2 == 0 && (long long)st->pp * cap < (1LL << 31) ? cap
+                                                                                      : st->np;
     st->d = d;
     st->kp = kp;
     st->sn2 = exp(2 * log_sn);             // gaussian.py
@@ -593,8 +723,8 @@ int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, i
     st->su2 = method == GPX_FITC ? st->sn2 / 1e6 : st->sn2 * 1e-6;
     st->mean = mean;
     st->prior = gpx_kernel_prior(kp);
-    const int pp = st->pp, ldp = st->ldp, np = st->np;
-    const size_t mat = (size_t)pp * ldp * 8, panel = (size_t)pp * np * 8, vec = (size_t)np * 8;
+    const int pp = st->pp, ldp = st->ldp, np = st->np, ldn = st->ldn;
+    const size_t mat = (size_t)pp * ldp * 8, panel = (size_t)pp * ldn * 8, vec = (size_t)ldn * 8;
     GPX_TRY(st->U.reserve((size_t)p * d * 8));
     GPX_TRY(st->L.reserve(mat));
     GPX_TRY(st->Lw.reserve(mat));
@@ -602,6 +732,7 @@ int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, i
     GPX_TRY(st->A.reserve(mat));
     GPX_TRY(st->Aw.reserve(mat));
     GPX_TRY(st->Ak.reserve(mat));
+    GPX_TRY(st->VV.reserve(mat));
     if (!st->pctl.p) {
         GPX_TRY(st->info.reserve(64));
         GPX_TRY(st->pctl.reserve(gpx_panel_ctl_bytes()));
@@ -613,8 +744,10 @@ int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, i
     GPX_TRY(st->rt.reserve(vec));
     GPX_TRY(st->beta.reserve((size_t)pp * 8));
     GPX_TRY(st->gam.reserve((size_t)pp * 8));
+    GPX_TRY(st->vrt.reserve((size_t)pp * 8));
     const int nbc = (np + SP_T - 1) / SP_T;
-    GPX_TRY(st->part.reserve((size_t)std::max(nbc * 4, pp * 2) * 8));
+    // (the block partials of the column kernels: for every n an append can reach)
+    GPX_TRY(st->part.reserve((size_t)std::max((ldn + SP_T - 1) / SP_T * 4, pp * 2) * 8));
     GPX_TRY(st->scal.reserve(S_COUNT * 8));
     GPX_HIP(hipMemsetAsync(st->scal.p, 0, S_COUNT * 8, s));
     GPX_HIP(hipMemcpyAsync(st->U.p, U, (size_t)p * d * 8, hipMemcpyHostToDevice, s));
@@ -630,58 +763,98 @@ int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, i
         return r;
     }
     // Kux (zero outside p x n), V0 = L^-T Kux, then ell, rt and V = V0 / ell in place
-    GPX_TRY(gpx_kbuild<double>(s, kp, st->U.d(), p, pp, X, n, np, d, st->P1.d(), np, false,
+    GPX_TRY(gpx_kbuild<double>(s, kp, st->U.d(), p, pp, X, n, np, d, st->P1.d(), ldn, false,
                                false, 0.0));
-    GPX_TRY(sp_gemm(s, 1, 0, st->Lw.d(), ldp, st->P1.d(), np, st->P2.d(), np, pp, np, pp, 1.0,
+    GPX_TRY(sp_gemm(s, 1, 0, st->Lw.d(), ldp, st->P1.d(), ldn, st->P2.d(), ldn, pp, np, pp, 1.0,
                     0.0));
     // one step of refinement, V0 += L^-T (Kux - L^T V0): the product with the explicit
     // inverse alone has the forward error of the inverse, and ell (FITC) takes
     // kxx + sn2 - |V0_j|^2, which cancels (the exact path's posterior does the same,
     // solve_rt_refined in gpx_api.hip)
     GPX_TRY(st->P3.reserve(panel));
-    GPX_TRY(sp_gemm(s, 1, 0, st->L.d(), ldp, st->P2.d(), np, st->P1.d(), np, pp, np, pp, -1.0,
+    GPX_TRY(sp_gemm(s, 1, 0, st->L.d(), ldp, st->P2.d(), ldn, st->P1.d(), ldn, pp, np, pp, -1.0,
                     1.0));
-    GPX_TRY(sp_gemm(s, 1, 0, st->Lw.d(), ldp, st->P1.d(), np, st->P3.d(), np, pp, np, pp, 1.0,
+    GPX_TRY(sp_gemm(s, 1, 0, st->Lw.d(), ldp, st->P1.d(), ldn, st->P3.d(), ldn, pp, np, pp, 1.0,
                     0.0));
-    GPX_TRY(gpx_add_inplace(s, st->P2.d(), st->P3.d(), (size_t)pp * np));
+    hipLaunchKernelGGL(sp_add_panel_kernel, dim3((np + SP_T - 1) / SP_T, pp), dim3(SP_T), 0, s,
+                       st->P2.d(), st->P3.d(), (long long)ldn, np);
+    GPX_HIP(hipGetLastError());
     if (method == GPX_VFE) {
         // t from the refined V0, one more read of the panel before it is scaled
         hipLaunchKernelGGL(sp_coltrace_kernel, dim3(nbc), dim3(SP_T), 0, s, st->P2.d(),
-                           (long long)np, pp, n, st->prior, st->part.d());
+                           (long long)ldn, pp, n, st->prior, st->part.d());
         GPX_HIP(hipGetLastError());
         GPX_TRY(sp_reduce(s, st->part.d(), nbc, 1, st->scal.d() + S_T));
     }
-    hipLaunchKernelGGL(sp_colprep_kernel, dim3(nbc), dim3(SP_T), 0, s, st->P2.d(), (long long)np,
-                       pp, n, np, y, mean, st->prior, st->sn2, method == GPX_FITC ? 1 : 0,
-                       st->ell.d(), st->rt.d(), st->part.d());
+    hipLaunchKernelGGL(sp_colprep_kernel, dim3(nbc), dim3(SP_T), 0, s, st->P2.d(),
+                       (long long)ldn, pp, n, np, y, mean, st->prior, st->sn2,
+                       method == GPX_FITC ? 1 : 0, st->ell.d(), st->rt.d(), st->part.d());
     GPX_HIP(hipGetLastError());
     GPX_TRY(sp_reduce(s, st->part.d(), nbc, 4, st->scal.d() + S_LOGELL));
-    // A = chol(I + V V^T)
-    GPX_TRY(sp_abt_split(st, s, st->P2.d(), st->P2.d(), np, np, st->A.d(), ldp, 1.0));
-    r = sp_factor(st, s, st->A.d(), st->Aw.d(), st->Ak.d(), st->gates_a);
-    if (r != 0) {
-        if (r > 0 && info) *info = r;
-        return r;
-    }
-    // beta = A^-T (V rt)
+    // the kept sums I + V V^T and V rt, then A = chol(I + V V^T) and beta = A^-T (V rt)
+    GPX_TRY(sp_abt_split(st, s, st->P2.d(), st->P2.d(), ldn, np, st->VV.d(), ldp, 1.0));
     hipLaunchKernelGGL(sp_gemv_rows_kernel, dim3(pp), dim3(SP_T), 0, s, st->P2.d(),
-                       (long long)np, n, st->rt.d(), st->gam.d());
-    hipLaunchKernelGGL(sp_gemv_cols_kernel, dim3((pp + SP_T - 1) / SP_T), dim3(SP_T), 0, s,
-                       st->Aw.d(), (long long)ldp, pp, pp, st->gam.d(), st->beta.d());
+                       (long long)ldn, n, st->rt.d(), st->vrt.d());
     GPX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(sp_factor_terms_kernel, dim3(p), dim3(SP_T), 0, s, st->A.d(), st->Aw.d(),
-                       ldp, p, st->part.d());
+    return sp_finish(st, s, info);
+}
+
+// does the model hold exactly n_old observations and have room for m more columns?
+bool gpx_sparse_can_append(const GpxSparse *st, int n_old, int m)
+{
+    return st && st->ready && st->n == n_old && m >= 1 &&
+           sp_round((int64_t)n_old + m, GPX_TILE) <= st->ldn;
+}
+
+// m new observations (rows Xnew, ynew on the device) behind the n_old the model holds: the
+// strip of their columns, the kept sums, the p x p re-factorisation (section 13 of
+// DESIGN.md). Returns -3 without having touched anything when the model cannot take them
+// (not ready, another n, no room in the panels); on any other failure the model is not ready.
+int gpx_sparse_run_append(GpxSparse *st, hipStream_t s, const double *Xnew, const double *ynew,
+                          int n_old, int m, int *info)
+{
+    if (!gpx_sparse_can_append(st, n_old, m)) return -3;
+    const int n_new = n_old + m, np_new = sp_round(n_new, GPX_TILE);
+    st->ready = false;
+    const int p = st->p, pp = st->pp, ldp = st->ldp, ldn = st->ldn, d = st->d;
+    const int mp = sp_round(m, GPX_TILE);
+    const bool fitc = st->method == GPX_FITC, vfe = st->method == GPX_VFE;
+    const size_t strip = (size_t)pp * mp * 8;
+    const int width = np_new - n_old, nbs = (width + SP_T - 1) / SP_T;
+    GPX_TRY(st->S1.reserve(strip));
+    GPX_TRY(st->S2.reserve(strip));
+    GPX_TRY(st->S3.reserve(strip));
+    GPX_TRY(st->svrt.reserve((size_t)pp * 8));
+    GPX_TRY(st->spart.reserve((size_t)nbs * 5 * 8));
+    GPX_TRY(st->sscal.reserve(5 * 8));
+    double *S1 = st->S1.d(), *S2 = st->S2.d(), *S3 = st->S3.d();
+    if (info) *info = 0;
+    GPX_TRY(sp_event(st, s, 0));
+    // Kux on the strip (zero outside p x m), V0 = L^-T Kux and its refinement as the update's
+    GPX_TRY(gpx_kbuild<double>(s, st->kp, st->U.d(), p, pp, Xnew, m, mp, d, S1, mp, false, false,
+                               0.0));
+    GPX_TRY(sp_gemm(s, 1, 0, st->Lw.d(), ldp, S1, mp, S2, mp, pp, mp, pp, 1.0, 0.0));
+    GPX_TRY(sp_gemm(s, 1, 0, st->L.d(), ldp, S2, mp, S1, mp, pp, mp, pp, -1.0, 1.0));
+    GPX_TRY(sp_gemm(s, 1, 0, st->Lw.d(), ldp, S1, mp, S3, mp, pp, mp, pp, 1.0, 0.0));
+    GPX_TRY(gpx_add_inplace(s, S2, S3, (size_t)pp * mp));
+    // ell, rt, V on the strip and into the panel behind column n_old; the strip's sums
+    hipLaunchKernelGGL(sp_colappend_kernel, dim3(nbs), dim3(SP_T), 0, s, S2, (long long)mp,
+                       st->P2.d(), (long long)ldn, pp, n_old, m, np_new, ynew, st->mean,
+                       st->prior, st->sn2, fitc ? 1 : 0, st->ell.d(), st->rt.d(),
+                       st->spart.d());
     GPX_HIP(hipGetLastError());
-    GPX_TRY(sp_reduce(s, st->part.d(), p, 2, st->scal.d() + S_LOGA));
-    GPX_TRY(sp_dot(s, st->beta.d(), nullptr, pp, st->scal.d() + S_BETA2));
-    GPX_HIP(hipMemcpyAsync(st->hsc, st->scal.p, S_COUNT * 8, hipMemcpyDeviceToHost, s));
-    GPX_TRY(sp_event(st, s, 1));
-    GPX_HIP(hipStreamSynchronize(s));
-    st->ms[0] = sp_elapsed(st, 0, 1);
-    st->ms[1] = st->ms[2] = 0.0;
-    st->ms_pseudo = 0.0;
-    st->ready = true;
-    return 0;
+    GPX_TRY(sp_reduce(s, st->spart.d(), nbs, 5, st->sscal.d()));
+    // kept sums: old + strip
+    hipLaunchKernelGGL(sp_gemv_rows_kernel, dim3(pp), dim3(SP_T), 0, s, S2, (long long)mp, m,
+                       st->rt.d() + n_old, st->svrt.d());
+    hipLaunchKernelGGL(sp_accumulate_kernel, dim3((std::max(pp, 5) + SP_T - 1) / SP_T),
+                       dim3(SP_T), 0, s, st->scal.d(), st->sscal.d(), vfe ? 1 : 0, st->vrt.d(),
+                       st->svrt.d(), pp);
+    GPX_HIP(hipGetLastError());
+    GPX_TRY(sp_gemm(s, 0, 1, S2, mp, S2, mp, st->VV.d(), ldp, pp, pp, mp, 1.0, 1.0));
+    st->n = n_new;
+    st->np = np_new;
+    return sp_finish(st, s, info);
 }
 
 int gpx_sparse_run_loglik(GpxSparse *st, hipStream_t s, const double *X, double *lZ,
@@ -700,8 +873,9 @@ int gpx_sparse_run_loglik(GpxSparse *st, hipStream_t s, const double *X, double 
     if (!dlZ) return 0;
 
     const int p = st->p, pp = st->pp, ldp = st->ldp, n = st->n, np = st->np, d = st->d;
-    const long long ld = np;
-    const size_t panel = (size_t)pp * np * 8, vec = (size_t)np * 8;
+    const int ldn = st->ldn;
+    const long long ld = ldn;
+    const size_t panel = (size_t)pp * ldn * 8, vec = (size_t)ldn * 8;
     GPX_TRY(st->P3.reserve(panel));
     GPX_TRY(st->u.reserve(vec));
     GPX_TRY(st->alpha.reserve(vec));
@@ -735,7 +909,7 @@ int gpx_sparse_run_loglik(GpxSparse *st, hipStream_t s, const double *X, double 
     GPX_HIP(hipGetLastError());
     GPX_TRY(sp_reduce(s, st->part.d(), nbc, 2, scal + S_ALPHA));
     // B = L^-1 V0 (FITC) = L^-1 V diag(ell), or L^-1 V (DTC); q: column sums of B^2
-    GPX_TRY(sp_gemm(s, 0, 0, st->Lw.d(), ldp, P2, np, P1, np, pp, np, pp, 1.0, 0.0));
+    GPX_TRY(sp_gemm(s, 0, 0, st->Lw.d(), ldp, P2, ldn, P1, ldn, pp, np, pp, 1.0, 0.0));
     // (VFE reads neither q nor S_B2 -- its su2 ||B||^2 cancelled; for it this is one read of
     // B that writes nothing to the panel, kept so that its stage is DTC's launch sequence up
     // to G_ux)
@@ -744,7 +918,7 @@ int gpx_sparse_run_loglik(GpxSparse *st, hipStream_t s, const double *X, double 
     GPX_HIP(hipGetLastError());
     GPX_TRY(sp_reduce(s, st->part.d(), nbc, 1, scal + S_B2));
     // W = A^-T V / ell (FITC) or A^-T V (DTC); s_j = sum_i W_ij^2
-    GPX_TRY(sp_gemm(s, 1, 0, st->Aw.d(), ldp, P2, np, P3, np, pp, np, pp, 1.0, 0.0));
+    GPX_TRY(sp_gemm(s, 1, 0, st->Aw.d(), ldp, P2, ldn, P3, ldn, pp, np, pp, 1.0, 0.0));
     hipLaunchKernelGGL(sp_colscale_kernel, cgrid, dim3(SP_T), 0, s, P3, P3, ld, pp, n,
                        fitc ? st->ell.d() : nullptr, 1, st->sq.d(), st->part.d());
     GPX_HIP(hipGetLastError());
@@ -764,7 +938,7 @@ int gpx_sparse_run_loglik(GpxSparse *st, hipStream_t s, const double *X, double 
                        st->part.d());
     GPX_HIP(hipGetLastError());
     GPX_TRY(sp_reduce(s, st->part.d(), (pp + SP_T - 1) / SP_T, 1, scal + S_C2));
-    GPX_TRY(sp_gemm(s, 0, 0, st->Cm.d(), pp, P3, np, P4, np, pp, np, pp, 1.0, 0.0));
+    GPX_TRY(sp_gemm(s, 0, 0, st->Cm.d(), pp, P3, ldn, P4, ldn, pp, np, pp, 1.0, 0.0));
     // FITC: e = alpha^2 + s and sum_j e_j sum_i B_ij^2
     if (fitc) {
         hipLaunchKernelGGL(sp_evec_kernel, cgrid, dim3(SP_T), 0, s, st->alpha.d(), st->sq.d(), n,
@@ -851,7 +1025,7 @@ int gpx_sparse_run_loglik(GpxSparse *st, hipStream_t s, const double *X, double 
     return 0;
 }
 
-// The gradient stage above leaves G_uu (Guu, ld pp) and G_ux (P4, ld np) behind; neither kxx
+// The gradient stage above leaves G_uu (Guu, ld pp) and G_ux (P4, ld ldn) behind; neither kxx
 // nor su2 depends on U, so dlZ/dU_ic = sum_j (G_uu[i][j] + G_uu[j][i]) dk(u_i, u_j)/du_ic
 // + sum_j G_ux[i][j] dk(u_i, x_j)/du_ic: two more contractions of the same adjoints
 // (gpx_pair_gradx), on the same stream. Scratch is reserved here, on first use.
@@ -866,7 +1040,7 @@ int gpx_sparse_run_loglik_pseudo(GpxSparse *st, hipStream_t s, const double *X, 
     GPX_TRY(sp_event(st, s, 5));
     GPX_TRY(gpx_pair_gradx(s, st->kp, st->U.d(), p, st->U.d(), p, d, st->Guu.d(), pp, true,
                            st->px_part.d(), st->dU.d(), false));
-    GPX_TRY(gpx_pair_gradx(s, st->kp, st->U.d(), p, X, n, d, st->P4.d(), (long long)st->np,
+    GPX_TRY(gpx_pair_gradx(s, st->kp, st->U.d(), p, X, n, d, st->P4.d(), (long long)st->ldn,
                            false, st->px_part.d(), st->dU.d(), true));
     GPX_TRY(sp_event(st, s, 6));
     GPX_HIP(hipMemcpyAsync(dU, st->dU.p, (size_t)p * d * 8, hipMemcpyDeviceToHost, s));

@@ -5,7 +5,10 @@ Shared state machine of the sparse pseudo-input models FITC and DTC
 The numerical work -- Kuu, Kux, the two p x p Cholesky factors, the lZ terms, the
 gradient contraction and the posteriors -- runs in libgpx.so (sparse.hip). The model owns
 a device handle with X and y resident after add_data; set_hyper / add_data refactor on
-the device (no incremental update: the reference refactors on add_data too).
+the device, as the reference does on add_data too. append_data is the incremental route:
+the device keeps the sums over columns the model is made of, so a few new observations cost
+their own columns and one p x p factorisation. Its results agree with
+add_data's to rounding, not bit for bit, which is why it is a method of its own.
 """
 
 import numpy as np
@@ -31,6 +34,7 @@ class SparseGP(GP):
         self._dev_ = None
         self._resident = False
         self._factored = False
+        self._appends_in_place = 0  # append_data calls served by gpx_sparse_append
 
     # -- device state -------------------------------------------------------
     def _dev(self):
@@ -50,14 +54,16 @@ class SparseGP(GP):
         clone = type(self).__new__(type(self))
         memo[id(self)] = clone
         for key, val in self.__dict__.items():
-            if key not in ('_dev_', '_resident', '_factored'):
+            if key not in ('_dev_', '_resident', '_factored', '_appends_in_place'):
                 setattr(clone, key, copy.deepcopy(val, memo))
         clone._dev_, clone._resident, clone._factored = None, False, False
+        clone._appends_in_place = 0
         return clone
 
     def __getstate__(self):
         state = dict(self.__dict__)
         state['_dev_'], state['_resident'], state['_factored'] = None, False, False
+        state['_appends_in_place'] = 0
         return state
 
     @property
@@ -141,6 +147,38 @@ class SparseGP(GP):
         dev.sparse_update(self._kernel._kspec(), self._method, self._U,
                           self._likelihood.get_hyper()[0], self._mean)
         self._factored = True
+
+    def append_data(self, X, y):
+        """Add observations to the current model in place: one upload of the new rows and
+        O(p^2 m + p^3) work on the device whatever N is. Without data or a current
+        factorisation, or when the rows do not fit the capacity the device reserved, this is
+        add_data. Results agree with add_data's to rounding, not bit for bit."""
+        X = self._kernel.transform(X)
+        y = self._likelihood.transform(y)
+        if X.shape[0] != y.shape[0]:
+            raise ValueError('X and y disagree')
+        ndim = self._U.shape[1] if self._X is None else self._X.shape[1]
+        if X.ndim != 2 or X.shape[1] != ndim:
+            raise ValueError('new inputs have the wrong dimension')
+        if not (np.all(np.isfinite(X)) and np.all(np.isfinite(y))):
+            raise ValueError('array must not contain infs or NaNs')
+        if X.shape[0] == 0:
+            return
+        if self._X is None or not (self._factored and self._resident):
+            return self.add_data(X, y)
+        try:
+            extended = self._dev().sparse_append(X, y)
+        except Exception:
+            # a failed append has spent the kept sums; the model stays on its old data and
+            # the next use uploads and refactors from the host copy (as ExactGP._updateinc)
+            self._resident = False
+            self._factored = False
+            raise
+        if not extended:
+            return self.add_data(X, y)
+        self._X = np.r_[self._X, X]
+        self._y = np.r_[self._y, y]
+        self._appends_in_place += 1
 
     def _ensure(self):
         if self.ndata > 0 and not self._factored:
