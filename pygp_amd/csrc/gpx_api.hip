@@ -33,28 +33,6 @@ static const char *kTimerNames[GPX_NTIMERS] = {
     "kernel_build", "potrf", "trsv", "trtri", "trmv", "lauum", "trace_grad",
     "scalars", "posterior_build", "posterior_solve"};
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    int reserve(size_t need)
-    {
-        if (need <= bytes) return 0;
-        if (p) GPX_HIP(hipFree(p));
-        p = nullptr;
-        bytes = 0;
-        GPX_HIP(hipMalloc(&p, need));
-        bytes = need;
-        return 0;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-    template <typename T> T *as() const { return static_cast<T *>(p); }
-};
-
 struct gpx_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -65,7 +43,8 @@ struct gpx_ctx {
     long data_version = 0;         // bumped by gpx_set_data (twin refresh)
     DevBuf X, y, Xf32;
     // factorisation state
-    DevBuf A, W, Kinv, r, a, alpha, scalars, acc, partial, info, gv_part, pctl;
+    DevBuf A, W, Kinv, r, a, alpha, scalars, partial, info, gv_part, pctl;
+    double *acc = nullptr;         // the trace accumulators: a view of scalars
     KParams kp;
     double log_sn = 0, mean = 0;
     bool have_factor = false, have_inverse = false;
@@ -147,8 +126,6 @@ struct gpx_ctx {
         return w;
     }
 };
-
-static inline int round_up(int64_t x, int m) { return (int)((x + m - 1) / m * m); }
 
 // Row stride of the np x np device matrices. A power-of-two stride puts the
 // same column of every row on one HBM channel; GPX_LDPAD doubles (default 32 =
@@ -479,8 +456,7 @@ int gpx_create(int device, gpx_t **out)
     GPX_HIP(hipStreamSynchronize(h->stream));
     // [0..2] scalar terms, [3] status word, [4..] trace accumulators: one result copy
     GPX_TRY(h->scalars.reserve((4 + GPX_MAX_HYPER + 2) * sizeof(double)));
-    h->acc.p = h->scalars.as<double>() + 4;             // a view, never released on its own
-    h->acc.bytes = 0;
+    h->acc = h->scalars.as<double>() + 4;
     GPX_HIP(hipHostMalloc((void **)&h->hres, (GPX_MAX_HYPER + 8) * sizeof(double)));
     GPX_HIP(hipHostMalloc((void **)&h->hinfo, 64));
     *out = h;
@@ -514,6 +490,8 @@ int gpx_destroy(gpx_t *h)
     DLOG("sync stream");
     (void)hipStreamSynchronize(h->stream);
     DLOG("release buffers");
+    // (the destructors would free these with the handle below; here they go before the
+    // streams do, as they always have. A buffer missing from the list is freed by `delete`.)
     DevBuf *bufs[] = {&h->X, &h->y, &h->Xf32, &h->A, &h->W, &h->Kinv, &h->r, &h->a,
                       &h->alpha, &h->scalars, &h->partial, &h->info, &h->gv_part, &h->pctl, &h->Ks, &h->KsT, &h->Vc,
                       &h->Xs, &h->mu, &h->s2, &h->post_part, &h->t0, &h->t1, &h->t2, &h->split, &h->gpart,
@@ -926,7 +904,7 @@ static int enqueue_grad(gpx_ctx *h, StageClock &clk)
     const DenseWs w = h->ws();
     GPX_TRY(gpx_trace_grad(h->stream, h->kp, h->X.as<double>(), h->n, h->np, h->d, w.Kinv,
                            h->ld, h->alpha.as<double>(), h->partial.as<double>(),
-                           h->acc.as<double>()));
+                           h->acc));
     clk.tick(T_TRACE);
     return 0;
 }
@@ -1176,12 +1154,9 @@ static int append_block(gpx_ctx *h, int j0)
         g.A = A; g.B = B; g.C = C;
         g.lda = g.ldb = g.ldc = ld;
         g.M = M; g.N = GPX_TILE; g.K = K;
-        g.alpha = alpha; g.beta = 0.0;
-        g.strideA = g.strideB = g.strideC = 0;
-        g.batch = 1;
+        g.alpha = alpha;
         g.flags = flags;
-        g.tile = 64; g.order = 0; g.swizzle = 0; g.waves = 0; g.use_lists = 1;
-        g.tiles = nullptr;
+        g.tile = 64;
         return gpx_gemm(s, ta, 0, g);
     };
     if (j0 > 0) {
@@ -1197,12 +1172,9 @@ static int append_block(gpx_ctx *h, int j0)
         g.A = Xst; g.B = Xst; g.C = h->split.as<double>();
         g.lda = g.ldb = ld; g.ldc = GPX_TILE;
         g.M = g.N = GPX_TILE; g.K = j0;
-        g.alpha = 1.0; g.beta = 0.0;
-        g.strideA = g.strideB = 0; g.strideC = stride;
+        g.strideC = stride;
         g.batch = nsplit; g.kchunk = kc;
-        g.flags = 0;
-        g.tile = 64; g.order = 0; g.swizzle = 0; g.waves = 0; g.use_lists = 1;
-        g.tiles = nullptr;
+        g.tile = 64;
         GPX_TRY(gpx_gemm(s, 1, 0, g));
         GPX_TRY(gpx_sub_partials(s, h->split.as<double>(), nsplit, stride, GPX_TILE, GPX_TILE,
                                  Sdiag, ld));
@@ -1431,12 +1403,8 @@ static int tri_product(gpx_ctx *h, int ta, const double *B, double *C, int mcp)
     g.A = w.W; g.B = B; g.C = C;
     g.lda = h->ld; g.ldb = mcp; g.ldc = mcp;
     g.M = h->np; g.N = mcp; g.K = h->np;
-    g.alpha = 1.0; g.beta = 0.0;
-    g.strideA = g.strideB = g.strideC = 0;
-    g.batch = 1;
     g.flags = ta ? GEMM_KHI_M : GEMM_KLO_M;
-    g.tile = 0; g.order = ta ? 1 : 0; g.swizzle = 0; g.waves = 0; g.use_lists = 1;
-    g.tiles = nullptr;
+    g.order = ta ? 1 : 0;
     const long long tiles64 = (long long)(h->np / 64) * (mcp / 64);
     if (tiles64 > 1024 || h->np < 2048) return gpx_gemm(h->stream, ta, 0, g);
     const int kc = h->np >= 8192 ? 2048 : 1024;
@@ -1595,11 +1563,6 @@ int gpx_exact_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, 
     g.lda = mcp; g.ldb = mcp; g.ldc = mcp;
     g.M = mcp; g.N = mcp; g.K = h->np;
     g.alpha = -1.0; g.beta = 1.0;
-    g.strideA = g.strideB = g.strideC = 0;
-    g.batch = 1;
-    g.flags = 0;
-    g.tile = 0; g.order = 0; g.swizzle = 0; g.waves = 0; g.use_lists = 1;
-    g.tiles = nullptr;
     GPX_TRY(gpx_gemm(h->stream, 1, 0, g));
     GPX_HIP(hipMemcpyAsync(mu, h->mu.p, (size_t)mc * 8, hipMemcpyDeviceToHost, h->stream));
     GPX_HIP(hipMemcpy2DAsync(Sigma, (size_t)mc * 8, h->t2.p, (size_t)mcp * 8, (size_t)mc * 8, mc,
@@ -2043,15 +2006,6 @@ int gpx_la_gemm(gpx_t *h, int ta, int tb, int64_t M, int64_t N, int64_t K, doubl
     g.lda = ac; g.ldb = bc; g.ldc = Np;
     g.M = Mp; g.N = Np; g.K = Kp;
     g.alpha = alpha; g.beta = beta;
-    g.strideA = g.strideB = g.strideC = 0;
-    g.batch = 1;
-    g.flags = 0;
-    g.tile = 0;
-    g.order = 0;
-    g.swizzle = 0;
-    g.waves = 0;
-    g.use_lists = 1;
-    g.tiles = nullptr;
     GPX_TRY(gpx_gemm(h->stream, ta, tb, g));
     GPX_HIP(hipMemcpy2DAsync(C, (size_t)ldc * 8, h->t2.p, (size_t)Np * 8, (size_t)N * 8, M,
                              hipMemcpyDeviceToHost, h->stream));
@@ -2157,16 +2111,12 @@ int gpx_la_gemm_bench_ex(gpx_t *h, int ta, int tb, int64_t n, int flags, int ord
     if (same_ab) g.B = g.A;
     g.lda = g.ldb = g.ldc = (int)ldn;
     g.M = g.N = g.K = (int)n;
-    g.alpha = 1.0; g.beta = 0.0;
-    g.strideA = g.strideB = g.strideC = 0;
-    g.batch = 1;
     g.flags = flags;
     g.tile = tile;
     g.order = order;
     g.swizzle = swizzle & 1;
     g.waves = waves;
     g.use_lists = (swizzle & 2) ? 0 : 1;      // bit 1 of swizzle: plain 2-D grid
-    g.tiles = nullptr;
     if (reps < 1) reps = 1;
     hipEvent_t e0 = h->ev[GPX_NTIMERS], e1 = h->ev[0];
     GPX_HIP(hipEventRecord(e0, h->stream));
@@ -2208,15 +2158,8 @@ int gpx_la_gemm_bench_mnk(gpx_t *h, int ta, int tb, int64_t M, int64_t N, int64_
     g.lda = g.ldb = g.ldc = (int)ldn;
     g.M = (int)M; g.N = (int)N; g.K = (int)K;
     g.alpha = beta != 0.0 ? -1e-6 : 1.0; g.beta = beta;
-    g.strideA = g.strideB = g.strideC = 0;
-    g.batch = 1;
     g.flags = flags;
     g.tile = tile;
-    g.order = 0;
-    g.swizzle = 0;
-    g.waves = 0;
-    g.use_lists = 1;
-    g.tiles = nullptr;
     if (reps < 1) reps = 1;
     hipEvent_t e0 = h->ev[GPX_NTIMERS], e1 = h->ev[0];
     GPX_TRY(gpx_gemm(h->stream, ta, tb, g));                 // warm-up (tile lists)

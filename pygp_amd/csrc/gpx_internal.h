@@ -37,6 +37,39 @@ void gpx_set_error(const char *fmt, ...);
         if (r_ < 0) return r_;                                                 \
     } while (0)
 
+static inline int round_up(int64_t x, int m) { return (int)((x + m - 1) / m * m); }
+
+// ---- device memory -----------------------------------------------------------
+// A device allocation that only grows and frees itself with its owner. Every owner (the
+// handle, a slot of the groups, the sparse and selection states) lives on the heap and dies
+// in its destroy call, before the runtime shuts down; none has static storage duration.
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    int reserve(size_t need)
+    {
+        if (need <= bytes) return 0;
+        if (p) GPX_HIP(hipFree(p));
+        p = nullptr;
+        bytes = 0;
+        GPX_HIP(hipMalloc(&p, need));
+        bytes = need;
+        return 0;
+    }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    template <typename T> T *as() const { return static_cast<T *>(p); }
+    double *d() const { return as<double>(); }
+};
+
 // ---- flattened kernel parameters (passed to kernels by value) -------------
 // One primitive part of a (sum) kernel. scale[d] is the per-dimension divisor
 // applied to the inputs exactly as the reference does (x / ell for SE,
@@ -99,24 +132,24 @@ enum {
     GEMM_KREV = 32,        // walk k from the top of the range downwards
 };
 struct GemmArgs {
-    const double *A;
-    const double *B;
-    double *C;
-    int lda, ldb, ldc;
-    int M, N, K;           // multiples of GPX_TILE (K: multiple of GPX_BK)
-    double alpha, beta;
-    long long strideA, strideB, strideC;   // batch strides (elements)
-    int batch;
-    int flags;
-    int tile;              // 0 = choose by grid size, 64 or 128 = force
-    int order;             // tile walk, so that the longest k-ranges start first:
+    const double *A = nullptr;
+    const double *B = nullptr;
+    double *C = nullptr;
+    int lda = 0, ldb = 0, ldc = 0;
+    int M = 0, N = 0, K = 0;   // multiples of GPX_TILE (K: multiple of GPX_BK)
+    double alpha = 1.0, beta = 0.0;
+    long long strideA = 0, strideB = 0, strideC = 0;   // batch strides (elements)
+    int batch = 1;
+    int flags = 0;
+    int tile = 0;          // 0 = choose by grid size, 64 or 128 = force
+    int order = 0;         // tile walk, so that the longest k-ranges start first:
                            // 0 row-major, 1 row-major from the last tile row,
                            // 2 column-major from the last tile column,
                            // 3 column-major from the first tile column
-    int swizzle;           // 1: XCD-aware 8x8 macro-tile walk when the grid allows
-    int waves;             // 0 = default wave geometry, 4 or 8 = force
-    int use_lists;         // 1: structured launches walk a sorted live-tile list
-    const int *tiles;      // set by the launcher
+    int swizzle = 0;       // 1: XCD-aware 8x8 macro-tile walk when the grid allows
+    int waves = 0;         // 0 = default wave geometry, 4 or 8 = force
+    int use_lists = 1;     // 1: structured launches walk a sorted live-tile list
+    const int *tiles = nullptr;   // set by the launcher
     double *C2 = nullptr;  // C is a diagonal block of a matrix: its off-diagonal 128-tiles
                            // are read and written at C2 (same ldc) instead of C
     int kshift = 0;        // GEMM_KLO_*: the zero structure starts kshift columns in,

@@ -42,28 +42,6 @@
 
 namespace {
 
-struct Buf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    int reserve(size_t need)
-    {
-        if (need <= bytes) return 0;
-        if (p) GPX_HIP(hipFree(p));
-        p = nullptr;
-        bytes = 0;
-        GPX_HIP(hipMalloc(&p, need));
-        bytes = need;
-        return 0;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-    template <typename T> T *as() const { return static_cast<T *>(p); }
-};
-
 struct HostBuf {                                  // pinned
     void *p = nullptr;
     size_t bytes = 0;
@@ -77,6 +55,10 @@ struct HostBuf {                                  // pinned
         bytes = need;
         return 0;
     }
+    HostBuf() = default;
+    HostBuf(const HostBuf &) = delete;
+    HostBuf &operator=(const HostBuf &) = delete;
+    ~HostBuf() { release(); }
     void release()
     {
         if (p) (void)hipHostFree(p);
@@ -90,8 +72,8 @@ struct HostBuf {                                  // pinned
 
 struct Slot {                                     // one group in flight
     hipStream_t stream = nullptr;
-    Buf A, W, Kinv, r, a, alpha, scalars, partial, gv_part, info, pctl, params;
-    Buf Xs, Ks, KsT, Vc, mu, s2, post_part, split, gpart, dmu, ds2; // posteriors
+    DevBuf A, W, Kinv, r, a, alpha, scalars, partial, gv_part, info, pctl, params;
+    DevBuf Xs, Ks, KsT, Vc, mu, s2, post_part, split, gpart, dmu, ds2; // posteriors
     HostBuf hparams, hres, hinfo;
     int cap = 0;                                  // members the buffers hold
     int np = 0, ld = 0;
@@ -217,10 +199,12 @@ void gpx_groups_destroy(GpxGroups *g)
         DLOG("slot %d sync", si);
         if (s.stream) (void)hipStreamSynchronize(s.stream);
         DLOG("slot %d buffers", si);
-        Buf *bufs[] = {&s.A, &s.W, &s.Kinv, &s.r, &s.a, &s.alpha, &s.scalars, &s.partial,
+        // (the destructors would free these with the state below; here they go while the
+        // slot's stream still exists, as they always have)
+        DevBuf *bufs[] = {&s.A, &s.W, &s.Kinv, &s.r, &s.a, &s.alpha, &s.scalars, &s.partial,
                        &s.gv_part, &s.info, &s.pctl, &s.params, &s.Xs, &s.Ks, &s.KsT, &s.Vc, &s.mu,
                        &s.s2, &s.post_part, &s.split, &s.gpart, &s.dmu, &s.ds2};
-        for (Buf *b : bufs) b->release();
+        for (DevBuf *b : bufs) b->release();
         DLOG("slot %d events", si);
         for (hipEvent_t e : s.ev)
             if (e) (void)hipEventDestroy(e);
@@ -591,12 +575,10 @@ static int group_tri_product(Slot &s, const DenseWs &w, int count, int ta, const
     g.A = w.W; g.B = B; g.C = C;
     g.lda = w.ld; g.ldb = mcp; g.ldc = mcp;
     g.M = np; g.N = mcp; g.K = np;
-    g.alpha = 1.0; g.beta = 0.0;
     g.strideA = w.mstride; g.strideB = pstride; g.strideC = pstride;
     g.batch = count;
     g.flags = ta ? GEMM_KHI_M : GEMM_KLO_M;
-    g.tile = 0; g.order = ta ? 1 : 0; g.swizzle = 0; g.waves = 0; g.use_lists = 1;
-    g.tiles = nullptr;
+    g.order = ta ? 1 : 0;
     const long long tiles64 = (long long)(np / 64) * (mcp / 64);
     if (tiles64 > 1024 || np < 2048) return gpx_gemm(s.stream, ta, 0, g);
     const int kc = np >= 8192 ? 2048 : 1024;
@@ -649,7 +631,7 @@ static int group_posterior(Slot &s, const double *X, const double *y, int n, int
     const int CH = posterior_chunk(np);
     for (int64_t c0 = 0; c0 < m; c0 += CH) {
         const int mc = (int)std::min<int64_t>(CH, m - c0);
-        const int mcp = (mc + GPX_TILE - 1) / GPX_TILE * GPX_TILE;
+        const int mcp = round_up(mc, GPX_TILE);
         const long long pstride = (long long)np * mcp;
         GPX_TRY(s.Xs.reserve((size_t)mc * d * 8));
         GPX_TRY(s.Ks.reserve((size_t)count * pstride * 8));

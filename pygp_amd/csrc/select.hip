@@ -23,38 +23,15 @@
 
 namespace {
 
-struct SelBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    int reserve(size_t need)
-    {
-        if (need <= bytes) return 0;
-        if (p) GPX_HIP(hipFree(p));
-        p = nullptr;
-        bytes = 0;
-        GPX_HIP(hipMalloc(&p, need));
-        bytes = need;
-        return 0;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-    double *d() const { return static_cast<double *>(p); }
-    int *as_int() const { return static_cast<int *>(p); }
-};
-
 // words of the control block at the head of the result buffer
 enum { C_STOP = 0, C_COUNT, C_PIVOT, C_WORDS = 4 };
 
 }  // namespace
 
 struct GpxSelect {
-    SelBuf X;                       // the call's own copy of a host X
-    SelBuf L, dres, psum, pmax, pidx, coef, xs;
-    SelBuf res;                     // control block | piv[p] | trace[p] | idx[p] (int)
+    DevBuf X;                       // the call's own copy of a host X
+    DevBuf L, dres, psum, pmax, pidx, coef, xs;
+    DevBuf res;                     // control block | piv[p] | trace[p] | idx[p] (int)
     void *host = nullptr;           // pinned image of res
     size_t host_bytes = 0;
     hipEvent_t ev[2] = {};
@@ -220,9 +197,6 @@ __global__ __launch_bounds__(SEL_PT) void sel_pivot_kernel(
 void gpx_select_destroy(GpxSelect *st)
 {
     if (!st) return;
-    SelBuf *bufs[] = {&st->X, &st->L, &st->dres, &st->psum, &st->pmax, &st->pidx, &st->coef,
-                      &st->xs, &st->res};
-    for (SelBuf *b : bufs) b->release();
     if (st->host) (void)hipHostFree(st->host);
     for (hipEvent_t e : st->ev)
         if (e) (void)hipEventDestroy(e);
@@ -238,8 +212,7 @@ int gpx_select_run(GpxSelect **state, hipStream_t s, const KParams &kp, const do
 {
     if (!*state) *state = new GpxSelect();
     GpxSelect *st = *state;
-    const int pp = (int)(((int64_t)p + GPX_TILE - 1) / GPX_TILE * GPX_TILE);
-    const int np = (int)(((int64_t)n + GPX_TILE - 1) / GPX_TILE * GPX_TILE);
+    const int pp = round_up(p, GPX_TILE), np = round_up(n, GPX_TILE);
     const long long ld = np;
     const int nb = (np + SEL_T - 1) / SEL_T;
     const size_t off_piv = C_WORDS * sizeof(int), off_trace = off_piv + (size_t)p * 8,
@@ -277,11 +250,11 @@ int gpx_select_run(GpxSelect **state, hipStream_t s, const KParams &kp, const do
     GPX_HIP(hipMemsetAsync(st->res.p, 0, res_bytes, s));
     GPX_HIP(hipEventRecord(st->ev[0], s));
     hipLaunchKernelGGL(sel_init_kernel, dim3(nb), dim3(SEL_T), 0, s, st->dres.d(), n, np, prior,
-                       st->psum.d(), st->pmax.d(), st->pidx.as_int());
+                       st->psum.d(), st->pmax.d(), st->pidx.as<int>());
     GPX_HIP(hipGetLastError());
     for (int j = 0; j <= p; ++j) {
         hipLaunchKernelGGL(sel_pivot_kernel, dim3(1), dim3(SEL_PT), 0, s, j, p, nb, st->psum.d(),
-                           st->pmax.d(), st->pidx.as_int(), thresh, st->L.d(), ld, X, d,
+                           st->pmax.d(), st->pidx.as<int>(), thresh, st->L.d(), ld, X, d,
                            st->coef.d(), st->xs.d(), ctl, dpiv, dtrace, didx);
         GPX_HIP(hipGetLastError());
         if (j == p) break;
@@ -289,7 +262,7 @@ int gpx_select_run(GpxSelect **state, hipStream_t s, const KParams &kp, const do
                             st->L.d() + (size_t)j * ld));
         hipLaunchKernelGGL(sel_column_kernel, dim3(nb), dim3(SEL_T), 0, s, st->L.d(), ld, j, n,
                            np, st->coef.d(), st->dres.d(), ctl, dpiv, st->psum.d(),
-                           st->pmax.d(), st->pidx.as_int());
+                           st->pmax.d(), st->pidx.as<int>());
         GPX_HIP(hipGetLastError());
     }
     GPX_HIP(hipEventRecord(st->ev[1], s));

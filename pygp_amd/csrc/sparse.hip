@@ -17,7 +17,9 @@
 // the data and everything else is a sum over columns, so the update keeps I + V V^T (before
 // its factorisation) and V rt on the device, and m new observations cost the strip of their
 // columns plus the p x p re-factorisation. The panels have a leading dimension of their own
-// (ldn, the handle's data capacity) so that the columns have somewhere to go.
+// (ldn, the handle's data capacity) so that the columns have somewhere to go. The update and
+// the append run one column stage, sp_refined_v0 and sp_column_kernel, on the panel and on the
+// strip: what holds the append to the one-shot model is that there is one copy of it.
 #include "gpx_internal.h"
 #include <algorithm>
 #include <cmath>
@@ -26,29 +28,6 @@
 #define SP_T 256   // threads of the column and vector kernels
 
 namespace {
-
-struct SpBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    int reserve(size_t need)
-    {
-        if (need <= bytes) return 0;
-        if (p) GPX_HIP(hipFree(p));
-        p = nullptr;
-        bytes = 0;
-        GPX_HIP(hipMalloc(&p, need));
-        bytes = need;
-        return 0;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-    double *d() const { return static_cast<double *>(p); }
-    int *as_int() const { return static_cast<int *>(p); }
-};
 
 // slots of the device scalar array
 enum {
@@ -83,22 +62,22 @@ struct GpxSparse {
     double sn2 = 0, su2 = 0, mean = 0, prior = 0;
     bool ready = false;
     int gates_l[2] = {0, 0}, gates_a[2] = {0, 0};
-    SpBuf U, L, Lw, Lk, A, Aw, Ak, info, pctl;
+    DevBuf U, L, Lw, Lk, A, Aw, Ak, info, pctl;
     // p x N panels (ld ldn). P2 holds V from the update to the next update: the gradient
     // stage reads it and writes only P1 (B), P3 (W, then FITC's B diag(e)) and P4 (C W, then
     // G_ux), so a second gradient call on the same state sees the same V
-    SpBuf P1, P2, P3, P4;
-    SpBuf ell, rt, beta, gam, u, alpha, wv, vv, bq, sq, e;
-    SpBuf part, scal, acc_uu, acc_ux, pg_part, split, Cm, CC, BEB, Guu, R2;
-    SpBuf Xs, Ks, Q1, Q2, dKc, dK, dQ1, dQ2, mu, s2, dmu, ds2, Sig;
+    DevBuf P1, P2, P3, P4;
+    DevBuf ell, rt, beta, gam, u, alpha, wv, vv, bq, sq, e;
+    DevBuf part, scal, acc_uu, acc_ux, pg_part, split, Cm, CC, BEB, Guu, R2;
+    DevBuf Xs, Ks, Q1, Q2, dKc, dK, dQ1, dQ2, mu, s2, dmu, ds2, Sig;
     // the pseudo-input gradient (gpx_sparse_run_loglik_pseudo only): chunk partials, dU
-    SpBuf px_part, dU;
+    DevBuf px_part, dU;
     // kept from one update or append to the next: I + V V^T before its factorisation (pp x pp,
     // ld ldp, as A receives it) and V rt (pp)
-    SpBuf VV, vrt;
+    DevBuf VV, vrt;
     // gpx_sparse_run_append: three pp x round_up(m, 128) strips, the strip's share of V rt,
     // block partials and sums of its column kernel
-    SpBuf S1, S2, S3, svrt, spart, sscal;
+    DevBuf S1, S2, S3, svrt, spart, sscal;
     double hsc[S_COUNT];
     // HIP events around the last update, gradient stage and contraction pass, then the dU
     // pass (ms)
@@ -121,8 +100,6 @@ static double sp_elapsed(GpxSparse *st, int a, int b)
     return t;
 }
 
-static inline int sp_round(int64_t x, int m) { return (int)((x + m - 1) / m * m); }
-
 // ---- reductions --------------------------------------------------------------------
 // fixed-order tree over the 256 threads of a block; the sum lands in thread 0
 __device__ __forceinline__ double sp_block_sum(double v, double *red)
@@ -138,14 +115,14 @@ __device__ __forceinline__ double sp_block_sum(double v, double *red)
     return red[0];
 }
 
-// out[q] = sum_b part[b * nq + q], b < nb, in a fixed order
+// out[q] = sum_b part[b * stride + q], b < nb, in a fixed order; one block per q
 __global__ __launch_bounds__(SP_T) void sp_reduce_kernel(const double *__restrict__ part, int nb,
-                                                        int nq, double *__restrict__ out)
+                                                        int stride, double *__restrict__ out)
 {
     __shared__ double red[SP_T];
     const int q = blockIdx.x;
     double s = 0.0;
-    for (int b = threadIdx.x; b < nb; b += SP_T) s += part[(size_t)b * nq + q];
+    for (int b = threadIdx.x; b < nb; b += SP_T) s += part[(size_t)b * stride + q];
     s = sp_block_sum(s, red);
     if (threadIdx.x == 0) out[q] = s;
 }
@@ -169,101 +146,26 @@ __global__ __launch_bounds__(1024) void sp_dot_kernel(const double *__restrict__
 }
 
 // ---- column kernels ----------------------------------------------------------------
-// One thread per column j of the p x N panel V0 (ld ld, pp rows): ell_j, rt_j and the
-// column scaled to V = V0 / ell in place. Columns j >= n (padding) are zero, keep
-// ell = 1, rt = 0 and add nothing to the sums. part[block][4]: sum log ell, sum rt^2,
-// sum V^2, sum 1 / ell^2.
-__global__ __launch_bounds__(SP_T) void sp_colprep_kernel(
-    double *__restrict__ V, long long ld, int pp, int n, int np, const double *__restrict__ y,
-    double mean, double kxx, double sn2, int fitc, double *__restrict__ ell,
-    double *__restrict__ rt, double *__restrict__ part)
-{
-    __shared__ double red[SP_T];
-    const int j = blockIdx.x * SP_T + threadIdx.x;
-    double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
-    if (j < n) {
-        double sq = 0.0;
-        for (int i = 0; i < pp; ++i) {
-            const double v = V[(size_t)i * ld + j];
-            sq += v * v;
-        }
-        const double l = fitc ? sqrt(kxx + sn2 - sq) : sqrt(sn2);
-        double s2 = 0.0;
-        for (int i = 0; i < pp; ++i) {
-            const double v = V[(size_t)i * ld + j] / l;
-            V[(size_t)i * ld + j] = v;
-            s2 += v * v;
-        }
-        const double r = (y[j] - mean) / l;
-        ell[j] = l;
-        rt[j] = r;
-        q0 = log(l);
-        q1 = r * r;
-        q2 = s2;
-        q3 = 1.0 / (l * l);
-    } else if (j < np) {
-        ell[j] = 1.0;
-        rt[j] = 0.0;
-    }
-    double *po = part + (size_t)blockIdx.x * 4;
-    double s = sp_block_sum(q0, red);
-    if (threadIdx.x == 0) po[0] = s;
-    s = sp_block_sum(q1, red);
-    if (threadIdx.x == 0) po[1] = s;
-    s = sp_block_sum(q2, red);
-    if (threadIdx.x == 0) po[2] = s;
-    s = sp_block_sum(q3, red);
-    if (threadIdx.x == 0) po[3] = s;
-}
-
-// VFE: part[block] = sum over the block's columns j < n of kxx - sum_i V0_ij^2, from the
-// refined V0 before sp_colprep_kernel scales it. The difference cancels (it is FITC's ell^2
-// without sn2), so it is formed per column and the differences are summed.
-__global__ __launch_bounds__(SP_T) void sp_coltrace_kernel(const double *__restrict__ V0,
-                                                          long long ld, int pp, int n,
-                                                          double kxx, double *__restrict__ part)
-{
-    __shared__ double red[SP_T];
-    const int j = blockIdx.x * SP_T + threadIdx.x;
-    double q = 0.0;
-    if (j < n) {
-        double sq = 0.0;
-        for (int i = 0; i < pp; ++i) {
-            const double v = V0[(size_t)i * ld + j];
-            sq += v * v;
-        }
-        q = kxx - sq;
-    }
-    q = sp_block_sum(q, red);
-    if (threadIdx.x == 0) part[blockIdx.x] = q;
-}
-
-// x[i][j] += d[i][j] for i < rows, j < cols (both ld)
-__global__ __launch_bounds__(SP_T) void sp_add_panel_kernel(double *__restrict__ x,
-                                                           const double *__restrict__ d,
-                                                           long long ld, int cols)
-{
-    const int j = blockIdx.x * SP_T + threadIdx.x;
-    if (j >= cols) return;
-    const size_t o = (size_t)blockIdx.y * ld + j;
-    x[o] += d[o];
-}
-
-// The column kernel of an append, one thread per column c of [n_old, np_new): c < m is a new
-// observation whose refined V0 column sits in the strip S (pp rows, ld lds): ell, rt (and
-// VFE's kxx - |V0|^2 from the unscaled column), the column scaled to V in place in the strip
-// and copied to column n_old + c of the panel V (ld ld); the columns behind the new n up to
-// np_new are the padding of a block the append may have opened: zero, ell = 1, rt = 0.
-// part[block][5]: sum log ell, sum rt^2, sum V^2, sum 1 / ell^2, sum (kxx - |V0|^2).
-__global__ __launch_bounds__(SP_T) void sp_colappend_kernel(
-    double *__restrict__ S, long long lds, double *__restrict__ V, long long ld, int pp,
-    int n_old, int m, int np_new, const double *__restrict__ ynew, double mean, double kxx,
-    double sn2, int fitc, double *__restrict__ ell, double *__restrict__ rt,
+// The column stage of an update and of an append, one thread per column c of the launch;
+// c is global column j = j0 + c of the model. c < m: a live column whose refined V0 sits in
+// column c of S (pp rows, ld lds): ell_j, rt_j (y indexed by c), the column scaled to
+// V = V0 / ell in place and, with V2 (ld ld2), copied to column j there. j < jend behind them
+// is padding: ell = 1, rt = 0, a zero column of V2 (S is zero there already), nothing to the
+// sums. The update runs it over the whole panel in place (j0 = 0, no V2), the append over
+// its strip with the panel as V2 (j0 = n_old, jend the padded new n: the padding of a block
+// the append may have opened).
+// part[block][5]: sum log ell, sum rt^2, sum V^2, sum 1 / ell^2, sum (kxx - |V0|^2). The last
+// is VFE's t: it cancels (it is FITC's ell^2 without sn2), so it is formed per column, from
+// the unscaled column, and the differences are summed.
+__global__ __launch_bounds__(SP_T) void sp_column_kernel(
+    double *__restrict__ S, long long lds, int pp, int j0, int m, int jend,
+    double *__restrict__ V2, long long ld2, const double *__restrict__ y, double mean,
+    double kxx, double sn2, int fitc, double *__restrict__ ell, double *__restrict__ rt,
     double *__restrict__ part)
 {
     __shared__ double red[SP_T];
     const int c = blockIdx.x * SP_T + threadIdx.x;
-    const int j = n_old + c;
+    const int j = j0 + c;
     double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0, q4 = 0.0;
     if (c < m) {
         double sq = 0.0;
@@ -276,10 +178,10 @@ __global__ __launch_bounds__(SP_T) void sp_colappend_kernel(
         for (int i = 0; i < pp; ++i) {
             const double v = S[(size_t)i * lds + c] / l;
             S[(size_t)i * lds + c] = v;
-            V[(size_t)i * ld + j] = v;
+            if (V2) V2[(size_t)i * ld2 + j] = v;
             s2 += v * v;
         }
-        const double r = (ynew[c] - mean) / l;
+        const double r = (y[c] - mean) / l;
         ell[j] = l;
         rt[j] = r;
         q0 = log(l);
@@ -287,8 +189,9 @@ __global__ __launch_bounds__(SP_T) void sp_colappend_kernel(
         q2 = s2;
         q3 = 1.0 / (l * l);
         q4 = kxx - sq;
-    } else if (j < np_new) {
-        for (int i = 0; i < pp; ++i) V[(size_t)i * ld + j] = 0.0;
+    } else if (j < jend) {
+        if (V2)
+            for (int i = 0; i < pp; ++i) V2[(size_t)i * ld2 + j] = 0.0;
         ell[j] = 1.0;
         rt[j] = 0.0;
     }
@@ -303,6 +206,17 @@ __global__ __launch_bounds__(SP_T) void sp_colappend_kernel(
     if (threadIdx.x == 0) po[3] = s;
     s = sp_block_sum(q4, red);
     if (threadIdx.x == 0) po[4] = s;
+}
+
+// x[i][j] += d[i][j] for i < rows (blockIdx.y), j < cols (both ld)
+__global__ __launch_bounds__(SP_T) void sp_add_panel_kernel(double *__restrict__ x,
+                                                           const double *__restrict__ d,
+                                                           long long ld, int cols)
+{
+    const int j = blockIdx.x * SP_T + threadIdx.x;
+    if (j >= cols) return;
+    const size_t o = (size_t)blockIdx.y * ld + j;
+    x[o] += d[o];
 }
 
 // the kept sums take a strip's share, old + strip: scal[S_LOGELL .. S_IELL2] += sums[0 .. 3],
@@ -562,11 +476,6 @@ static int sp_gemm(hipStream_t s, int ta, int tb, const double *A, int lda, cons
     g.lda = lda; g.ldb = ldb; g.ldc = ldc;
     g.M = M; g.N = N; g.K = K;
     g.alpha = alpha; g.beta = beta;
-    g.strideA = g.strideB = g.strideC = 0;
-    g.batch = 1;
-    g.flags = 0;
-    g.tile = 0; g.order = 0; g.swizzle = 0; g.waves = 0; g.use_lists = 1;
-    g.tiles = nullptr;
     return gpx_gemm(s, ta, tb, g);
 }
 
@@ -580,7 +489,7 @@ static int sp_abt_split(GpxSparse *st, hipStream_t s, const double *A, const dou
     const long long tiles64 = (long long)(pp / 64) * (pp / 64);
     int nsplit = (int)std::max<long long>(1, (2048 + tiles64 - 1) / tiles64);
     nsplit = std::min(nsplit, std::max(1, K / 1024));
-    const int kc = sp_round((K + nsplit - 1) / nsplit, 128);
+    const int kc = round_up((K + nsplit - 1) / nsplit, 128);
     nsplit = (K + kc - 1) / kc;
     const long long stride = (long long)pp * pp;
     GPX_TRY(st->split.reserve((size_t)nsplit * stride * 8));
@@ -588,14 +497,10 @@ static int sp_abt_split(GpxSparse *st, hipStream_t s, const double *A, const dou
     g.A = A; g.B = B; g.C = st->split.d();
     g.lda = (int)ld; g.ldb = (int)ld; g.ldc = pp;
     g.M = pp; g.N = pp; g.K = K;
-    g.alpha = 1.0; g.beta = 0.0;
-    g.strideA = g.strideB = 0;
     g.strideC = stride;
     g.batch = nsplit;
     g.kchunk = kc;
-    g.flags = 0;
-    g.tile = 64; g.order = 0; g.swizzle = 0; g.waves = 0; g.use_lists = 1;
-    g.tiles = nullptr;
+    g.tile = 64;
     GPX_TRY(gpx_gemm(s, 0, 1, g));
     // a plain pp x pp result: the library's fixed-order sum; a factorisation's staging
     // matrix (ld ldp, + the identity) takes the kernel above, which writes it in one pass
@@ -606,9 +511,33 @@ static int sp_abt_split(GpxSparse *st, hipStream_t s, const double *A, const dou
     return 0;
 }
 
-static int sp_reduce(hipStream_t s, const double *part, int nb, int nq, double *out)
+// V (pp x mp, ld) = L^-T K(U, X) for the m rows X on the device, zero outside p x m, with one
+// step of refinement, V += L^-T (K - L^T V): the product with the explicit inverse alone has
+// the forward error of the inverse, and ell (FITC) takes kxx + sn2 - |V_j|^2, which cancels
+// (the exact path's posterior does the same, solve_rt_refined in gpx_api.hip). T1 and T2 are
+// scratch of V's shape. The update's panel, the append's strip and the posterior's test
+// columns all come through here.
+static int sp_refined_v0(GpxSparse *st, hipStream_t s, const double *X, int m, int mp, double *V,
+                         int ld, double *T1, double *T2)
 {
-    hipLaunchKernelGGL(sp_reduce_kernel, dim3(nq), dim3(SP_T), 0, s, part, nb, nq, out);
+    const int pp = st->pp, ldp = st->ldp;
+    GPX_TRY(gpx_kbuild<double>(s, st->kp, st->U.d(), st->p, pp, X, m, mp, st->d, T1, ld, false,
+                               false, 0.0));
+    GPX_TRY(sp_gemm(s, 1, 0, st->Lw.d(), ldp, T1, ld, V, ld, pp, mp, pp, 1.0, 0.0));
+    GPX_TRY(sp_gemm(s, 1, 0, st->L.d(), ldp, V, ld, T1, ld, pp, mp, pp, -1.0, 1.0));
+    GPX_TRY(sp_gemm(s, 1, 0, st->Lw.d(), ldp, T1, ld, T2, ld, pp, mp, pp, 1.0, 0.0));
+    hipLaunchKernelGGL(sp_add_panel_kernel, dim3((mp + SP_T - 1) / SP_T, pp), dim3(SP_T), 0, s,
+                       V, T2, (long long)ld, mp);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// (stride: doubles between the blocks' partials; 0: nq)
+static int sp_reduce(hipStream_t s, const double *part, int nb, int nq, double *out,
+                     int stride = 0)
+{
+    hipLaunchKernelGGL(sp_reduce_kernel, dim3(nq), dim3(SP_T), 0, s, part, nb,
+                       stride ? stride : nq, out);
     GPX_HIP(hipGetLastError());
     return 0;
 }
@@ -631,8 +560,8 @@ static int sp_factor(GpxSparse *st, hipStream_t s, double *F, double *Fw, double
     w.Kinv = Fk;
     w.np = st->pp;
     w.ld = st->ldp;
-    w.info = st->info.as_int();
-    w.pctl = static_cast<int *>(st->pctl.p);
+    w.info = st->info.as<int>();
+    w.pctl = st->pctl.as<int>();
     w.gate_total = gates;
     GPX_HIP(hipMemsetAsync(w.info, 0, sizeof(int), s));
     w.whole = gpx_potrf_whole(w, GPX_POTRF_W);
@@ -657,15 +586,6 @@ int gpx_sparse_nhyper(const GpxSparse *st) { return st ? st->kp.nhyper : -1; }
 void gpx_sparse_destroy(GpxSparse *st)
 {
     if (!st) return;
-    SpBuf *bufs[] = {&st->U, &st->L, &st->Lw, &st->Lk, &st->A, &st->Aw, &st->Ak, &st->info,
-                     &st->pctl, &st->P1, &st->P2, &st->P3, &st->P4, &st->ell, &st->rt, &st->beta,
-                     &st->gam, &st->u, &st->alpha, &st->wv, &st->vv, &st->bq, &st->sq, &st->e,
-                     &st->part, &st->scal, &st->acc_uu, &st->acc_ux, &st->pg_part, &st->split,
-                     &st->Cm, &st->CC, &st->BEB, &st->Guu, &st->R2, &st->Xs, &st->Ks, &st->Q1,
-                     &st->Q2, &st->dKc, &st->dK, &st->dQ1, &st->dQ2, &st->mu, &st->s2,
-                     &st->dmu, &st->ds2, &st->Sig, &st->px_part, &st->dU, &st->VV, &st->vrt,
-                     &st->S1, &st->S2, &st->S3, &st->svrt, &st->spart, &st->sscal};
-    for (SpBuf *b : bufs) b->release();
     for (hipEvent_t e : st->ev)
         if (e) (void)hipEventDestroy(e);
     delete st;
@@ -710,10 +630,10 @@ int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, i
     st->ready = false;
     st->method = method;
     st->p = p;
-    st->pp = sp_round(p, GPX_TILE);
+    st->pp = round_up(p, GPX_TILE);
     st->ldp = st->pp + 32;                 // rows off one HBM channel, as ld_for does
     st->n = n;
-    st->np = sp_round(n, GPX_TILE);
+    st->np = round_up(n, GPX_TILE);
     st->ldn = cap > st->np && cap % 2 == 0 && (long long)st->pp * cap < (1LL << 31) ? cap
                                                                                       : st->np;
     st->d = d;
@@ -740,6 +660,7 @@ int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, i
     }
     GPX_TRY(st->P1.reserve(panel));
     GPX_TRY(st->P2.reserve(panel));
+    GPX_TRY(st->P3.reserve(panel));
     GPX_TRY(st->ell.reserve(vec));
     GPX_TRY(st->rt.reserve(vec));
     GPX_TRY(st->beta.reserve((size_t)pp * 8));
@@ -747,7 +668,7 @@ int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, i
     GPX_TRY(st->vrt.reserve((size_t)pp * 8));
     const int nbc = (np + SP_T - 1) / SP_T;
     // (the block partials of the column kernels: for every n an append can reach)
-    GPX_TRY(st->part.reserve((size_t)std::max((ldn + SP_T - 1) / SP_T * 4, pp * 2) * 8));
+    GPX_TRY(st->part.reserve((size_t)std::max((ldn + SP_T - 1) / SP_T * 5, pp * 2) * 8));
     GPX_TRY(st->scal.reserve(S_COUNT * 8));
     GPX_HIP(hipMemsetAsync(st->scal.p, 0, S_COUNT * 8, s));
     GPX_HIP(hipMemcpyAsync(st->U.p, U, (size_t)p * d * 8, hipMemcpyHostToDevice, s));
@@ -762,35 +683,15 @@ int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, i
         if (r > 0 && info) *info = r;
         return r;
     }
-    // Kux (zero outside p x n), V0 = L^-T Kux, then ell, rt and V = V0 / ell in place
-    GPX_TRY(gpx_kbuild<double>(s, kp, st->U.d(), p, pp, X, n, np, d, st->P1.d(), ldn, false,
-                               false, 0.0));
-    GPX_TRY(sp_gemm(s, 1, 0, st->Lw.d(), ldp, st->P1.d(), ldn, st->P2.d(), ldn, pp, np, pp, 1.0,
-                    0.0));
-    // one step of refinement, V0 += L^-T (Kux - L^T V0): the product with the explicit
-    // inverse alone has the forward error of the inverse, and ell (FITC) takes
-    // kxx + sn2 - |V0_j|^2, which cancels (the exact path's posterior does the same,
-    // solve_rt_refined in gpx_api.hip)
-    GPX_TRY(st->P3.reserve(panel));
-    GPX_TRY(sp_gemm(s, 1, 0, st->L.d(), ldp, st->P2.d(), ldn, st->P1.d(), ldn, pp, np, pp, -1.0,
-                    1.0));
-    GPX_TRY(sp_gemm(s, 1, 0, st->Lw.d(), ldp, st->P1.d(), ldn, st->P3.d(), ldn, pp, np, pp, 1.0,
-                    0.0));
-    hipLaunchKernelGGL(sp_add_panel_kernel, dim3((np + SP_T - 1) / SP_T, pp), dim3(SP_T), 0, s,
-                       st->P2.d(), st->P3.d(), (long long)ldn, np);
-    GPX_HIP(hipGetLastError());
-    if (method == GPX_VFE) {
-        // t from the refined V0, one more read of the panel before it is scaled
-        hipLaunchKernelGGL(sp_coltrace_kernel, dim3(nbc), dim3(SP_T), 0, s, st->P2.d(),
-                           (long long)ldn, pp, n, st->prior, st->part.d());
-        GPX_HIP(hipGetLastError());
-        GPX_TRY(sp_reduce(s, st->part.d(), nbc, 1, st->scal.d() + S_T));
-    }
-    hipLaunchKernelGGL(sp_colprep_kernel, dim3(nbc), dim3(SP_T), 0, s, st->P2.d(),
-                       (long long)ldn, pp, n, np, y, mean, st->prior, st->sn2,
+    // V0 = L^-T Kux (zero outside p x n), then ell, rt, V = V0 / ell in place and the sums
+    GPX_TRY(sp_refined_v0(st, s, X, n, np, st->P2.d(), ldn, st->P1.d(), st->P3.d()));
+    hipLaunchKernelGGL(sp_column_kernel, dim3(nbc), dim3(SP_T), 0, s, st->P2.d(), (long long)ldn,
+                       pp, 0, n, np, (double *)nullptr, 0LL, y, mean, st->prior, st->sn2,
                        method == GPX_FITC ? 1 : 0, st->ell.d(), st->rt.d(), st->part.d());
     GPX_HIP(hipGetLastError());
-    GPX_TRY(sp_reduce(s, st->part.d(), nbc, 4, st->scal.d() + S_LOGELL));
+    GPX_TRY(sp_reduce(s, st->part.d(), nbc, 4, st->scal.d() + S_LOGELL, 5));
+    // (t stays 0 for FITC and DTC)
+    if (method == GPX_VFE) GPX_TRY(sp_reduce(s, st->part.d() + 4, nbc, 1, st->scal.d() + S_T, 5));
     // the kept sums I + V V^T and V rt, then A = chol(I + V V^T) and beta = A^-T (V rt)
     GPX_TRY(sp_abt_split(st, s, st->P2.d(), st->P2.d(), ldn, np, st->VV.d(), ldp, 1.0));
     hipLaunchKernelGGL(sp_gemv_rows_kernel, dim3(pp), dim3(SP_T), 0, s, st->P2.d(),
@@ -803,7 +704,7 @@ int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, i
 bool gpx_sparse_can_append(const GpxSparse *st, int n_old, int m)
 {
     return st && st->ready && st->n == n_old && m >= 1 &&
-           sp_round((int64_t)n_old + m, GPX_TILE) <= st->ldn;
+           round_up((int64_t)n_old + m, GPX_TILE) <= st->ldn;
 }
 
 // m new observations (rows Xnew, ynew on the device) behind the n_old the model holds: the
@@ -814,10 +715,10 @@ int gpx_sparse_run_append(GpxSparse *st, hipStream_t s, const double *Xnew, cons
                           int n_old, int m, int *info)
 {
     if (!gpx_sparse_can_append(st, n_old, m)) return -3;
-    const int n_new = n_old + m, np_new = sp_round(n_new, GPX_TILE);
+    const int n_new = n_old + m, np_new = round_up(n_new, GPX_TILE);
     st->ready = false;
-    const int p = st->p, pp = st->pp, ldp = st->ldp, ldn = st->ldn, d = st->d;
-    const int mp = sp_round(m, GPX_TILE);
+    const int pp = st->pp, ldp = st->ldp, ldn = st->ldn;
+    const int mp = round_up(m, GPX_TILE);
     const bool fitc = st->method == GPX_FITC, vfe = st->method == GPX_VFE;
     const size_t strip = (size_t)pp * mp * 8;
     const int width = np_new - n_old, nbs = (width + SP_T - 1) / SP_T;
@@ -830,18 +731,12 @@ int gpx_sparse_run_append(GpxSparse *st, hipStream_t s, const double *Xnew, cons
     double *S1 = st->S1.d(), *S2 = st->S2.d(), *S3 = st->S3.d();
     if (info) *info = 0;
     GPX_TRY(sp_event(st, s, 0));
-    // Kux on the strip (zero outside p x m), V0 = L^-T Kux and its refinement as the update's
-    GPX_TRY(gpx_kbuild<double>(s, st->kp, st->U.d(), p, pp, Xnew, m, mp, d, S1, mp, false, false,
-                               0.0));
-    GPX_TRY(sp_gemm(s, 1, 0, st->Lw.d(), ldp, S1, mp, S2, mp, pp, mp, pp, 1.0, 0.0));
-    GPX_TRY(sp_gemm(s, 1, 0, st->L.d(), ldp, S2, mp, S1, mp, pp, mp, pp, -1.0, 1.0));
-    GPX_TRY(sp_gemm(s, 1, 0, st->Lw.d(), ldp, S1, mp, S3, mp, pp, mp, pp, 1.0, 0.0));
-    GPX_TRY(gpx_add_inplace(s, S2, S3, (size_t)pp * mp));
-    // ell, rt, V on the strip and into the panel behind column n_old; the strip's sums
-    hipLaunchKernelGGL(sp_colappend_kernel, dim3(nbs), dim3(SP_T), 0, s, S2, (long long)mp,
-                       st->P2.d(), (long long)ldn, pp, n_old, m, np_new, ynew, st->mean,
-                       st->prior, st->sn2, fitc ? 1 : 0, st->ell.d(), st->rt.d(),
-                       st->spart.d());
+    // V0 on the strip, then ell, rt, V on the strip and into the panel behind column n_old;
+    // the strip's sums
+    GPX_TRY(sp_refined_v0(st, s, Xnew, m, mp, S2, mp, S1, S3));
+    hipLaunchKernelGGL(sp_column_kernel, dim3(nbs), dim3(SP_T), 0, s, S2, (long long)mp, pp,
+                       n_old, m, np_new, st->P2.d(), (long long)ldn, ynew, st->mean, st->prior,
+                       st->sn2, fitc ? 1 : 0, st->ell.d(), st->rt.d(), st->spart.d());
     GPX_HIP(hipGetLastError());
     GPX_TRY(sp_reduce(s, st->spart.d(), nbs, 5, st->sscal.d()));
     // kept sums: old + strip
@@ -1072,7 +967,7 @@ int gpx_sparse_run_posterior(GpxSparse *st, hipStream_t s, const double *Xs, int
     const int CH = Sigma ? 8192 : 4096;
     for (int64_t c0 = 0; c0 < m; c0 += CH) {
         const int mc = (int)std::min<int64_t>(CH, m - c0);
-        const int mcp = sp_round(mc, GPX_TILE);
+        const int mcp = round_up(mc, GPX_TILE);
         GPX_TRY(st->Xs.reserve((size_t)mc * d * 8));
         GPX_TRY(st->Ks.reserve((size_t)pp * mcp * 8));
         GPX_TRY(st->Q1.reserve((size_t)pp * mcp * 8));
@@ -1081,17 +976,9 @@ int gpx_sparse_run_posterior(GpxSparse *st, hipStream_t s, const double *Xs, int
         GPX_TRY(st->s2.reserve((size_t)mcp * 8));
         GPX_HIP(hipMemcpyAsync(st->Xs.p, Xs + c0 * d, (size_t)mc * d * 8, hipMemcpyHostToDevice,
                                s));
-        // K(U, X*), Q1 = L^-T K, Q2 = A^-T Q1 = (A L)^-T K
-        GPX_TRY(gpx_kbuild<double>(s, st->kp, st->U.d(), p, pp, st->Xs.d(), mc, mcp, d,
-                                   st->Ks.d(), mcp, false, false, 0.0));
-        GPX_TRY(sp_gemm(s, 1, 0, st->Lw.d(), ldp, st->Ks.d(), mcp, st->Q1.d(), mcp, pp, mcp, pp,
-                        1.0, 0.0));
-        GPX_TRY(st->Q2.reserve((size_t)pp * mcp * 8));
-        GPX_TRY(sp_gemm(s, 1, 0, st->L.d(), ldp, st->Q1.d(), mcp, st->Ks.d(), mcp, pp, mcp, pp,
-                        -1.0, 1.0));                       // (refined as V0 above)
-        GPX_TRY(sp_gemm(s, 1, 0, st->Lw.d(), ldp, st->Ks.d(), mcp, st->Q2.d(), mcp, pp, mcp, pp,
-                        1.0, 0.0));
-        GPX_TRY(gpx_add_inplace(s, st->Q1.d(), st->Q2.d(), (size_t)pp * mcp));
+        // Q1 = L^-T K(U, X*) (refined as V0 above), Q2 = A^-T Q1 = (A L)^-T K
+        GPX_TRY(sp_refined_v0(st, s, st->Xs.d(), mc, mcp, st->Q1.d(), mcp, st->Ks.d(),
+                              st->Q2.d()));
         GPX_TRY(sp_gemm(s, 1, 0, st->Aw.d(), ldp, st->Q1.d(), mcp, st->Q2.d(), mcp, pp, mcp, pp,
                         1.0, 0.0));
         hipLaunchKernelGGL(sp_post_kernel, dim3((mc + SP_T - 1) / SP_T), dim3(SP_T), 0, s,
@@ -1115,7 +1002,7 @@ int gpx_sparse_run_posterior(GpxSparse *st, hipStream_t s, const double *Xs, int
         }
         if (grads) {
             // dK = grady(U, X*): p x (m d), padded to pp x ldd; dQ1 = L^-T dK, dQ2 = A^-T dQ1
-            const int md = mc * d, ldd = sp_round(md, GPX_TILE);
+            const int md = mc * d, ldd = round_up(md, GPX_TILE);
             GPX_TRY(st->dKc.reserve((size_t)p * md * 8));
             GPX_TRY(st->dK.reserve((size_t)pp * ldd * 8));
             GPX_TRY(st->dQ1.reserve((size_t)pp * ldd * 8));

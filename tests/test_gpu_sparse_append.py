@@ -276,3 +276,40 @@ def test_sparse_append_makes_the_exact_factor_stale():
     want = other.exact_loglik(gp._kernel.nhyper)
     # the same factorisation of the same rows; a row that had not landed would move lZ by O(1)
     assert e1 != e0 and abs(e1 - want) <= 1e-10 * abs(want)
+
+
+# The column stage with p = 5 (pp = 128: 123 padding rows) and a strip of more than one block of
+# its kernel: the append of m = 300 behind N = 300 launches 256-column blocks from column 300
+# over the 340 columns up to the padded new n (640), so the live columns start in the first
+# block and end in the second (column 600), and 40 padding columns are left behind the new n.
+P5, M5 = 5, 300
+
+
+@pytest.mark.parametrize('method', METHODS, ids=IDS)
+def test_column_stage_strip_over_two_blocks(method):
+    """lZ, dlZ and the posterior with its input gradients against the host references, after
+    add_data and after the append, at the tolerances of the tests above."""
+    X, y, U, Xs = data(N0 + M5, D, P5, seed=29)
+    spec = helpers.oracle_spec(DESC)
+    gp = model(method, DESC, U)
+    theta = gp.get_hyper()
+    for k, n in enumerate((N0, N0 + M5)):
+        if k == 0:
+            gp.add_data(X[:N0], y[:N0])
+        else:
+            gp.append_data(X[N0:], y[N0:])
+        assert gp.ndata == n and gp._appends_in_place == k
+        if method == VFE:
+            want_lZ, want_dlZ = svr.vfe_eval(spec, theta, U, X[:n], y[:n])
+        else:
+            want_lZ, want_dlZ = sr.sparse_eval(spec, method, theta, U, X[:n], y[:n])
+        want = sr.sparse_posterior(spec, sr.DTC if method == VFE else method, theta, U, X[:n],
+                                   y[:n], Xs)
+        lZ, dlZ = gp.loglikelihood(True)
+        figures = [('lZ', abs(lZ - want_lZ) / abs(want_lZ), LZ_TOL),
+                   ('dlZ', relmax(dlZ, want_dlZ), DLZ_TOL)]
+        for got, key in zip(gp.posterior(Xs, grad=True), ('mu', 's2', 'dmu', 'ds2')):
+            figures.append((key, np.max(np.abs(got - want[key])), POST_TOL))
+        print('n=%d %s' % (n, ' '.join('%s=%.2e' % f[:2] for f in figures)))
+        for name, err, tol in figures:
+            assert err <= tol, (n, name, err, tol)
