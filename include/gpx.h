@@ -113,6 +113,12 @@ int gpx_kernel_grad(gpx_t *h, const gpx_kspec *k, const double *X1, int64_t n1,
  * wrt = 1 -> d k / d x1, wrt = 2 -> d k / d x2. */
 int gpx_kernel_gradx(gpx_t *h, const gpx_kspec *k, const double *X1, int64_t n1,
                      const double *X2, int64_t n2, int64_t d, int wrt, double *out);
+/* mixed second derivatives of the kernel (RealKernel.gradxy, _real.py:58-64):
+ * out[n1][n2][d][d], out[a][b][i][j] = d2 k(X1[a], X2[b]) / d X1[a][i] d X2[b][j]; X2 == NULL
+ * means X2 = X1. SE (se.py:88-99), Matern-3/2 and 5/2, RQ, Periodic (d = 1), sums and products;
+ * coincident points give the limit. A Matern-1/2 part has no derivative at r = 0: < 0. */
+int gpx_kernel_gradxy(gpx_t *h, const gpx_kspec *k, const double *X1, int64_t n1,
+                      const double *X2, int64_t n2, int64_t d, double *out);
 /* device-resident variant of gpx_kernel_get for benchmarking the build alone:
  * X1 is taken from the handle's resident data (gpx_set_data), the result stays
  * in HBM; returns the kernel time in ms through *ms. */
@@ -164,6 +170,14 @@ int gpx_exact_posterior_grad(gpx_t *h, const double *Xs, int64_t m, double *mu,
  * Sigma[m][m] = K(Xs, Xs) - V^T V, V = R^-T K(X, Xs); 1 <= m <= 8192. GP.sample
  * (_base.py:143-178) draws from it. */
 int gpx_exact_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma);
+/* The posterior of the gradient of f at m >= 1 test points, for the last update (own design;
+ * the reference has none): dmu[m][d] = E[grad f(x_m)] (the dmu of gpx_exact_posterior_grad)
+ * and S[m][d][d] = Cov[grad f(x_m)] = gradxy(x_m, x_m) - B^T B, B = R^-T d k(X, x_m) / d x_m,
+ * every block exactly symmetric. Either output may be NULL. Test points go through the device
+ * in passes of m_c d <= 8192 columns. Completes R^-1 as gpx_exact_posterior does and only
+ * reads the factorisation: later calls on the handle return the bits they return without
+ * this one. Kernels as gpx_kernel_gradxy. */
+int gpx_exact_posterior_gradient(gpx_t *h, const double *Xs, int64_t m, double *dmu, double *S);
 /* host copies of gp._R (n*n row-major upper, zero below the diagonal) and gp._a;
  * either may be NULL. n: the point count the caller sized R and a for; the call
  * fails when it is not the factor's. */

@@ -78,6 +78,8 @@ SIGNATURES = {
     'gpx_exact_posterior_full': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     'gpx_kernel_gradx': (C.c_int, [_vp, C.POINTER(_KSpec), _vp, _i64, _vp, _i64, _i64,
                                    C.c_int, _vp]),
+    'gpx_kernel_gradxy': (C.c_int, [_vp, C.POINTER(_KSpec), _vp, _i64, _vp, _i64, _i64, _vp]),
+    'gpx_exact_posterior_gradient': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     'gpx_exact_get_factor': (C.c_int, [_vp, _i64, _vp, _vp]),
     'gpx_sparse_update': (C.c_int, [_vp, C.POINTER(_KSpec), C.c_int, _vp, _i64, C.c_double,
                                     C.c_double, _ip]),
@@ -515,6 +517,29 @@ class Handle(object):
             check(self._L.gpx_kernel_gradx(self._h, spec.ref(), _ptr(X1), n1, _ptr(X2),
                                            n2, d, wrt, _ptr(out)))
         return out
+
+    def kernel_gradxy(self, spec, X1, X2=None):
+        X1 = _f64(X1, 2)
+        n1, d = X1.shape
+        if X2 is not None:
+            X2 = _f64(X2, 2)
+            n2 = X2.shape[0]
+        else:
+            n2 = n1
+        out = np.empty((n1, n2, d, d))
+        if out.size:
+            check(self._L.gpx_kernel_gradxy(self._h, spec.ref(), _ptr(X1), n1, _ptr(X2), n2, d,
+                                            _ptr(out)))
+        return out
+
+    def exact_posterior_gradient(self, Xs):
+        """mu (m, d) and S (m, d, d): mean and covariance of grad f at the rows of Xs."""
+        Xs = _f64(Xs, 2)
+        m, d = Xs.shape
+        mu, S = np.empty((m, d)), np.empty((m, d, d))
+        if m:
+            check(self._L.gpx_exact_posterior_gradient(self._h, _ptr(Xs), m, _ptr(mu), _ptr(S)))
+        return mu, S
 
     def exact_get_factor(self, n, want_R=True):
         R = np.empty((n, n)) if want_R else None

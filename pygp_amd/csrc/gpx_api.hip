@@ -1712,6 +1712,110 @@ int gpx_kernel_gradx(gpx_t *h, const gpx_kspec *k, const double *X1, int64_t n1,
     return 0;
 }
 
+int gpx_kernel_gradxy(gpx_t *h, const gpx_kspec *k, const double *X1, int64_t n1,
+                      const double *X2, int64_t n2, int64_t d, double *out)
+{
+    CHECK_H(h);
+    if (!X1 || !out || n1 < 0 || (X2 && n2 < 0)) {
+        gpx_set_error("gpx_kernel_gradxy: bad arguments");
+        return -1;
+    }
+    if (!X2) n2 = n1;
+    if (n1 == 0 || n2 == 0) return 0;
+    KParams kp;
+    GPX_TRY(gpx_flatten_kspec(k, d, &kp));
+    GPX_TRY(gpx_gradxy_check(kp, (int)d));
+    const size_t xb1 = (size_t)n1 * d * 8, xb2 = (size_t)n2 * d * 8;
+    const size_t ob = (size_t)n1 * n2 * d * d * 8;
+    GPX_TRY(h->t0.reserve(xb1));
+    GPX_TRY(h->t2.reserve(ob));
+    GPX_HIP(hipMemcpyAsync(h->t0.p, X1, xb1, hipMemcpyHostToDevice, h->stream));
+    const double *dX2 = h->t0.as<double>();
+    if (X2) {
+        GPX_TRY(h->t1.reserve(xb2));
+        GPX_HIP(hipMemcpyAsync(h->t1.p, X2, xb2, hipMemcpyHostToDevice, h->stream));
+        dX2 = h->t1.as<double>();
+    }
+    GPX_TRY(gpx_kgradxy(h->stream, kp, h->t0.as<double>(), (int)n1, dX2, (int)n2, (int)d,
+                        h->t2.as<double>()));
+    GPX_HIP(hipMemcpyAsync(out, h->t2.p, ob, hipMemcpyDeviceToHost, h->stream));
+    GPX_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// The posterior of grad f at m test points: dmu[m][d] = G_m^T alpha, S[m][d][d] =
+// gradxy(x_m, x_m) - B_m^T B_m, B_m = R^-T G_m, G_m = d k(X, x_m) / d x_m (N x d). A pass
+// takes the test points whose m_c d columns fit the bound of the full posterior (8192): the
+// build of all G_m as one right-hand side, the solve of gpx_exact_posterior_full, the
+// contraction of the diagonal blocks; one host synchronisation per pass. Like
+// gpx_exact_posterior it completes R^-1 and otherwise only reads the factorisation.
+int gpx_exact_posterior_gradient(gpx_t *h, const double *Xs, int64_t m, double *dmu, double *S)
+{
+    CHECK_H(h);
+    if (!h->have_factor) {
+        gpx_set_error("gpx_exact_posterior_gradient: no factorisation (call gpx_exact_update)");
+        return -1;
+    }
+    if (!Xs || m < 1) {
+        gpx_set_error("gpx_exact_posterior_gradient: bad arguments (m >= 1)");
+        return -1;
+    }
+    GPX_TRY(gpx_gradxy_check(h->kp, h->d));
+    if (!dmu && !S) return 0;
+    const DenseWs w = h->ws();
+    const int d = h->d;
+    if (!h->w_complete) {
+        GPX_TRY(gpx_trtri(h->stream, w));
+        h->w_complete = true;
+    }
+    if (dmu) {                                          // alpha = R^-1 a, as posterior_impl
+        GPX_TRY(h->alpha.reserve((size_t)h->np * 8));
+        GPX_TRY(gpx_trmv_upper(h->stream, w.W, h->ld, h->np, h->a.as<double>(),
+                               h->alpha.as<double>()));
+    }
+    const int CH = 8192 / d;                            // test points of a pass
+    StageClock clk(h);
+    for (int64_t c0 = 0; c0 < m; c0 += CH) {
+        const int mc = (int)std::min<int64_t>(CH, m - c0);
+        const int cols = mc * d, mcp = round_up(cols, GPX_TILE);
+        GPX_TRY(h->Xs.reserve((size_t)mc * d * 8));
+        GPX_TRY(h->Ks.reserve((size_t)h->np * mcp * 8));
+        GPX_HIP(hipMemcpyAsync(h->Xs.p, Xs + c0 * d, (size_t)mc * d * 8, hipMemcpyHostToDevice,
+                               h->stream));
+        double *G = h->Ks.as<double>();
+        GPX_TRY(gpx_gradpost_build(h->stream, h->kp, h->X.as<double>(), h->n, h->np,
+                                   h->Xs.as<double>(), mc, d, G, mcp));
+        if (dmu) {
+            // the column sums G^T alpha (the s2 output of the reduction is not used)
+            GPX_TRY(h->mu.reserve((size_t)mcp * 8));
+            GPX_TRY(h->s2.reserve((size_t)mcp * 8));
+            GPX_TRY(h->post_part.reserve(gpx_posterior_scratch(mcp) * 8));
+            GPX_TRY(gpx_posterior_reduce(h->stream, G, mcp, h->np, mcp, h->alpha.as<double>(),
+                                         0.0, 0.0, h->post_part.as<double>(),
+                                         h->mu.as<double>(), h->s2.as<double>()));
+            GPX_HIP(hipMemcpyAsync(dmu + c0 * d, h->mu.p, (size_t)cols * 8,
+                                   hipMemcpyDeviceToHost, h->stream));
+        }
+        clk.tick(T_POST_BUILD);                         // build and G^T alpha
+        if (S) {
+            GPX_TRY(h->KsT.reserve((size_t)h->np * mcp * 8));
+            GPX_TRY(h->gpart.reserve(gpx_gradpost_scratch(h->np, mc, d) * 8));
+            GPX_TRY(h->t2.reserve((size_t)cols * d * 8));
+            double *V = h->KsT.as<double>();
+            GPX_TRY(solve_rt_refined(h, G, V, mcp));
+            GPX_TRY(gpx_gradpost_contract(h->stream, h->kp, V, mcp, h->n, h->np,
+                                          h->Xs.as<double>(), mc, d, h->gpart.as<double>(),
+                                          h->t2.as<double>()));
+            GPX_HIP(hipMemcpyAsync(S + c0 * d * d, h->t2.p, (size_t)cols * d * 8,
+                                   hipMemcpyDeviceToHost, h->stream));
+            clk.tick(T_POST_SOLVE);                     // solve and contraction
+        }
+        GPX_HIP(hipStreamSynchronize(h->stream));
+        if (c0 == 0) clk.collect();
+    }
+    return 0;
+}
+
 // ---- FITC / DTC (pygp/inference/fitc.py, dtc.py) and VFE -----------------------------
 static int sparse_ready(gpx_ctx *h, const char *what)
 {

@@ -581,6 +581,21 @@ int gpx_posterior_grad(hipStream_t s, const KParams &kp, const double *X, int n,
                        const double *beta, int ldb, double *part, double *dmu, double *ds2,
                        const MemberBatch *mb = nullptr, long long bstride = 0);
 
+// d2 k / d x1_i d x2_j: out[n1][n2][d][d]. gpx_gradxy_check: < 0 (with a message) for a kernel
+// without one (a Matern-1/2 part; a periodic part on d != 1)
+int gpx_gradxy_check(const KParams &kp, int d);
+int gpx_kgradxy(hipStream_t s, const KParams &kp, const double *X1, int n1, const double *X2,
+                int n2, int d, double *out);
+// the posterior of the gradient at mc test points (gpx_exact_posterior_gradient):
+// build: G[i][m d + c] = d k(x_i, xs_m) / d xs_mc, np x ldg, zero for rows >= n and columns
+// >= mc d; contract: S[m] = gradxy(xs_m, xs_m) - B_m^T B_m for the d columns B_m of B (np x
+// ldb, rows >= n zero), exactly symmetric. part: scratch of gpx_gradpost_scratch doubles
+size_t gpx_gradpost_scratch(int np, int mc, int d);
+int gpx_gradpost_build(hipStream_t s, const KParams &kp, const double *X, int n, int np,
+                       const double *Xs, int mc, int d, double *G, int ldg);
+int gpx_gradpost_contract(hipStream_t s, const KParams &kp, const double *B, int ldb, int n,
+                          int np, const double *Xs, int mc, int d, double *part, double *S);
+
 // column strip [j0, j0+npc) of K + diag_add I for an appended block of observations
 // (j0 a multiple of 128); out_offdiag: the off-diagonal 128-tiles go there instead
 int gpx_kbuild_strip(hipStream_t s, const KParams &kp, const double *X, int n, int np,

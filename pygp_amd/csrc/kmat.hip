@@ -1996,3 +1996,345 @@ int gpx_posterior_grad(hipStream_t s, const KParams &kp, const double *X, int n,
     GPX_HIP(hipGetLastError());
     return 0;
 }
+
+// ---- mixed second derivatives ("gradxy") -----------------------------------------
+// d2 k(x1, x2) / d x1_i d x2_j. For a radial part k = g(s), s = sum_c u_c^2, u = (x1 - x2) /
+// scale, and w_c = u_c / scale_c. The difference is taken BEFORE the division (`get` and
+// part_grady divide first, as the reference does): w enters squared and over scale^2, and with
+// a short lengthscale x1 / scale - x2 / scale loses |x| / |x1 - x2| ulps to cancellation
+// (2e-14 of a block at ell = 1e-3, points 1e-4 apart) where x1 - x2 is exact.
+//   d k / d x2_j          = cf w_j                              cf = -2 g'   (part_grady)
+//   d2 k / d x1_i d x2_j  = h2 w_i w_j + h1 delta_ij / scale_i^2,   h1 = -2 g', h2 = -4 g''
+//   SE       g = sf^2 e^(-s/2):          h1 = K, h2 = -K                   (se.py:88-99)
+//   Matern   g = S f(r), S = sf^2 e^-r, r = sqrt(s), on the scaled distance of `get`:
+//            3/2: h1 = S, h2 = -S / r;   5/2: h1 = S (1 + r) / 3, h2 = -S / 3.
+//            h1 is finite at r = 0 as it stands; h2 w_i w_j -> 0 there (|w_i w_j| <= r^2 /
+//            (scale_i scale_j)), so h2 = 0 below r = 1e-12, the guard of part_grady.
+//            1/2 has no derivative at r = 0: refused on the host (gpx_gradxy_check).
+//   RQ       g = sf^2 E^-a, E = 1 + s / 2a: h1 = K / E, h2 = -(a + 1) / a K / E^2
+//   Periodic (one input dimension, from the gradx of periodic.py:84-97), D = (x1 - x2) pi / p,
+//            c = 2 pi / (ell^2 p): d k / d x2 = c K sin 2D,
+//            d2 k / d x1 d x2 = c K (2 pi / p cos 2D - c sin^2 2D); carried as cf and h1 with
+//            w = 1 and h2 = 0 (its scale is 1).
+struct MixedCoef { double K, cf, h1, h2; };
+__device__ __forceinline__ MixedCoef mixed_coef(const KPart &part, const double *__restrict__ x1,
+                                                const double *__restrict__ x2, int d, int i,
+                                                double *wi)
+{
+    MixedCoef c;
+    if (part.kind == GPX_PERIODIC) {
+        const double D = (x1[0] - x2[0]) * M_PI / part.period;
+        const double sn = sin(D) / part.ell;
+        const double cc = 2 * M_PI / (part.ell * part.ell) / part.period;
+        const double s2 = sin(2 * D);
+        c.K = part.sf2 * exp(-2 * (sn * sn));
+        c.cf = cc * c.K * s2;
+        c.h1 = cc * c.K * (2 * M_PI / part.period * cos(2 * D) - cc * (s2 * s2));
+        c.h2 = 0.0;
+        *wi = 1.0;
+        return c;
+    }
+    double D2 = 0.0;
+    for (int k = 0; k < d; ++k) {
+        const double u = (x1[k] - x2[k]) / part.scale[k];
+        D2 += u * u;
+    }
+    *wi = (x1[i] - x2[i]) / part.scale[i] / part.scale[i];
+    if (part.kind == GPX_RQ) {
+        const double E = 1 + 0.5 * D2 / part.alpha;
+        c.K = part.sf2 * pow(E, -part.alpha);
+        c.cf = c.K / E;
+        c.h1 = c.cf;
+        c.h2 = -((part.alpha + 1) / part.alpha) * (c.cf / E);
+    } else if (part.kind == GPX_SE) {
+        c.K = exp(part.two_logsf - D2 / 2);
+        c.cf = c.K;
+        c.h1 = c.K;
+        c.h2 = -c.K;
+    } else {                                           // Matern-3/2, 5/2
+        const double r = sqrt(D2);
+        const double S = exp(part.two_logsf - r);
+        if (part.kind == GPX_MATERN3) {
+            c.K = S * (1 + r);
+            c.cf = S;
+            c.h2 = r < 1e-12 ? 0.0 : -S / r;
+        } else {
+            c.K = S * (1 + r * (1 + r / 3.));
+            c.cf = S * (1 + r) / 3.;
+            c.h2 = -S / 3.;
+        }
+        c.h1 = c.cf;
+    }
+    return c;
+}
+
+// row[j] += A d2 k_q / d x1_i d x2_j + C d k_q / d x2_j, j < d, for the part q: row i of the
+// d x d block of one pair. The thread keeps the row in registers (compile-time indices only)
+// and reads x1_i, x2_i and scale_i, whose index is the thread's own, from memory.
+template <int DMAX>
+__device__ __forceinline__ void part_gradxy(const KPart &part, const double *__restrict__ x1,
+                                            const double *__restrict__ x2, int d, int i,
+                                            double A, double C, double (&row)[DMAX])
+{
+    double wi;
+    const MixedCoef c = mixed_coef(part, x1, x2, d, i, &wi);
+    const double ca = A * c.h2 * wi + C * c.cf;
+    const double cd = A * c.h1;
+    const bool periodic = part.kind == GPX_PERIODIC;
+#pragma unroll
+    for (int j = 0; j < DMAX; ++j)
+        if (j < d) {
+            const double sj = part.scale[j];
+            const double wj = periodic ? 1.0 : (x1[j] - x2[j]) / sj / sj;
+            row[j] += ca * wj;
+            if (j == i) row[j] += cd / (sj * sj);
+        }
+}
+
+// Row i of the block of the whole kernel. A group of factors k = prod_p k_p has
+//   k_xy = sum_p F_p (k_p)_xy + sum_{p != q} F_pq (k_p)_x (k_q)_y,
+// F_p, F_pq the products of the other factors' VALUES: nothing is divided by a factor
+// (_real.py:146-154 divides by K_i), so the block is defined where a factor is 0. The values
+// and x-derivatives of the parts go through the thread's column of sK, sG (LDS, stride ss).
+template <int DMAX>
+__device__ __forceinline__ void gradxy_row(const KParams &kp, const double *__restrict__ x1,
+                                           const double *__restrict__ x2, int d, int i,
+                                           double *sK, double *sG, int ss, double (&row)[DMAX])
+{
+#pragma unroll
+    for (int j = 0; j < DMAX; ++j) row[j] = 0.0;
+    const bool products = kp.nprod != 0;
+    if (products)
+        for (int p = 0; p < kp.nparts; ++p) {
+            double wi;
+            const MixedCoef c = mixed_coef(kp.part[p], x1, x2, d, i, &wi);
+            sK[p * ss] = c.K;
+            sG[p * ss] = -(c.cf * wi);                 // d k_p / d x1_i
+        }
+    for (int q = 0; q < kp.nparts; ++q) {
+        double A = 1.0, C = 0.0;
+        if (products) {
+            const int grp = kp.part[q].group;
+            for (int p = 0; p < kp.nparts; ++p) {
+                if (p == q || kp.part[p].group != grp) continue;
+                A *= sK[p * ss];
+                double F = sG[p * ss];
+                for (int r = 0; r < kp.nparts; ++r)
+                    if (r != p && r != q && kp.part[r].group == grp) F *= sK[r * ss];
+                C += F;
+            }
+        }
+        part_gradxy<DMAX>(kp.part[q], x1, x2, d, i, A, C, row);
+    }
+}
+
+// one thread per (pair, row i): out[a][b][i][0 .. d)
+template <int DMAX>
+__global__ __launch_bounds__(256) void kgradxy_kernel(KParams kp, const double *__restrict__ X1,
+                                                      int n1, const double *__restrict__ X2,
+                                                      int n2, int d, double *__restrict__ out)
+{
+    __shared__ double sK[GPX_MAX_PARTS][256], sG[GPX_MAX_PARTS][256];
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long long)n1 * n2 * d) return;
+    const int i = (int)(t % d);
+    const long long pair = t / d;
+    const int b = (int)(pair % n2), a = (int)(pair / n2);
+    double row[DMAX];
+    gradxy_row<DMAX>(kp, X1 + (size_t)a * d, X2 + (size_t)b * d, d, i, &sK[0][threadIdx.x],
+                     &sG[0][threadIdx.x], 256, row);
+    double *o = out + (size_t)t * d;
+#pragma unroll
+    for (int j = 0; j < DMAX; ++j)
+        if (j < d) o[j] = row[j];
+}
+
+int gpx_gradxy_check(const KParams &kp, int d)
+{
+    for (int p = 0; p < kp.nparts; ++p) {
+        if (kp.part[p].kind == GPX_MATERN1) {
+            gpx_set_error("gradxy: the Matern-1/2 kernel has no derivative at r = 0");
+            return -1;
+        }
+        if (kp.part[p].kind == GPX_PERIODIC && d != 1) {
+            gpx_set_error("input gradients of the periodic kernel need ndim == 1");
+            return -1;
+        }
+    }
+    return 0;
+}
+
+int gpx_kgradxy(hipStream_t s, const KParams &kp, const double *X1, int n1, const double *X2,
+                int n2, int d, double *out)
+{
+    GPX_TRY(gpx_gradxy_check(kp, d));
+    const long long blocks = ((long long)n1 * n2 * d + 255) / 256;
+    if (blocks > 0x7fffffffLL) {
+        gpx_set_error("gradxy: n1 * n2 * d = %lld is too large for one launch",
+                      (long long)n1 * n2 * d);
+        return -1;
+    }
+    const dim3 grid((unsigned)blocks);
+    if (d <= 8)
+        hipLaunchKernelGGL(kgradxy_kernel<8>, grid, dim3(256), 0, s, kp, X1, n1, X2, n2, d, out);
+    else if (d <= 16)
+        hipLaunchKernelGGL(kgradxy_kernel<16>, grid, dim3(256), 0, s, kp, X1, n1, X2, n2, d, out);
+    else
+        hipLaunchKernelGGL(kgradxy_kernel<32>, grid, dim3(256), 0, s, kp, X1, n1, X2, n2, d, out);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- the posterior of the gradient (gpx_exact_posterior_gradient) ------------------
+// G[i][m d + c] = d k(x_i, xs_m) / d xs_mc for the mc test points of a pass: the np x ldg
+// right-hand side of the solve against R, in the tile engine's padded layout (rows >= n and
+// columns >= mc d zero). One thread per (row, test point), d contiguous doubles each.
+template <int DMAX>
+__global__ __launch_bounds__(256) void gradpost_build_kernel(
+    KParams kp, const double *__restrict__ X, int n, const double *__restrict__ Xs, int mc, int d,
+    double *__restrict__ G, int ldg)
+{
+    const int i = blockIdx.x;                              // < np
+    const int mj = blockIdx.y * 256 + threadIdx.x;
+    double *row = G + (size_t)i * ldg;
+    if (blockIdx.y == 0)
+        for (int c = mc * d + threadIdx.x; c < ldg; c += 256) row[c] = 0.0;
+    if (mj >= mc) return;
+    double g[DMAX];
+#pragma unroll
+    for (int c = 0; c < DMAX; ++c) g[c] = 0.0;
+    if (i < n) {
+        const double *xi = X + (size_t)i * d, *xs = Xs + (size_t)mj * d;
+        for (int p = 0; p < kp.nparts; ++p)
+            part_grady<DMAX>(kp.part[p], xi, xs, d, group_factor(kp, p, xi, xs, d), g);
+    }
+    double *o = row + (size_t)mj * d;
+#pragma unroll
+    for (int c = 0; c < DMAX; ++c)
+        if (c < d) o[c] = g[c];
+}
+
+// part[chunk][m][i][j] = sum over the chunk's rows k of B[k][m d + i] B[k][m d + j]: only the
+// mc diagonal d x d blocks of B^T B (the full product would do mc times the work), B read
+// once. Block = one test point x one row chunk; thread = (row lane, i), its row of the block
+// in registers; b_i comes from memory (the index is the thread's own). Reduced over the lanes
+// in a fixed order: shuffles inside a wave, the four waves through LDS.
+template <int DMAX>
+__global__ __launch_bounds__(256) void gradpost_contract_kernel(
+    const double *__restrict__ B, int ldb, int n, int mc, int d, double *__restrict__ part)
+{
+    constexpr int RL = 256 / DMAX;                         // row lanes of the block
+    __shared__ double red[4][DMAX][DMAX + 1];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i = tid % DMAX, rl = tid / DMAX;
+    const int m = blockIdx.x;
+    const int rows = (n + (int)gridDim.y - 1) / (int)gridDim.y;
+    const int kbeg = (int)blockIdx.y * rows, kend = min(n, kbeg + rows);
+    const double *col = B + (size_t)m * d;
+    const int ic = min(i, d - 1);
+    double acc[DMAX];
+#pragma unroll
+    for (int j = 0; j < DMAX; ++j) acc[j] = 0.0;
+    for (int k = kbeg + rl; k < kend; k += RL) {
+        const double *b = col + (size_t)k * ldb;
+        const double bi = b[ic];
+#pragma unroll
+        for (int j = 0; j < DMAX; ++j) acc[j] = fma(bi, j < d ? b[j] : 0.0, acc[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < DMAX; ++j) {
+        double v = acc[j];
+#pragma unroll
+        for (int off = 32; off >= DMAX; off >>= 1) v += __shfl_down(v, off, 64);
+        if (lane < DMAX) red[wave][i][j] = v;
+    }
+    __syncthreads();
+    double *po = part + ((size_t)blockIdx.y * mc + m) * d * d;
+    for (int e = tid; e < d * d; e += 256) {
+        const int ii = e / d, jj = e - ii * d;
+        if (jj >= ii)
+            po[e] = ((red[0][ii][jj] + red[1][ii][jj]) + red[2][ii][jj]) + red[3][ii][jj];
+    }
+}
+
+// S[m][i][j] = S[m][j][i] = gradxy(xs_m, xs_m)[i][j] - sum over the chunks of part, for
+// i <= j: one value, stored in both places. Thread = (test point, row i); the prior row comes
+// from gradxy_row.
+template <int DMAX>
+__global__ __launch_bounds__(256) void gradpost_final_kernel(
+    KParams kp, const double *__restrict__ Xs, int mc, int d, const double *__restrict__ part,
+    int chunks, double *__restrict__ S)
+{
+    __shared__ double sK[GPX_MAX_PARTS][256], sG[GPX_MAX_PARTS][256];
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= mc * d) return;
+    const int m = t / d, i = t - m * d;
+    const double *x = Xs + (size_t)m * d;
+    double row[DMAX];
+    gradxy_row<DMAX>(kp, x, x, d, i, &sK[0][threadIdx.x], &sG[0][threadIdx.x], 256, row);
+    double *Sm = S + (size_t)m * d * d;
+    const size_t cstride = (size_t)mc * d * d;
+    const double *pm = part + ((size_t)m * d + i) * d;
+#pragma unroll
+    for (int j = 0; j < DMAX; ++j)
+        if (j < d && j >= i) {
+            double w = 0.0;
+            for (int c = 0; c < chunks; ++c) w += pm[(size_t)c * cstride + j];
+            const double v = row[j] - w;
+            Sm[(size_t)i * d + j] = v;
+            Sm[(size_t)j * d + i] = v;
+        }
+}
+
+// row chunks of the contraction: a function of the padded order alone, so that a test
+// point's sums do not depend on how many points share its pass
+static int gradpost_chunks(int np) { return std::max(1, std::min(64, np / 256)); }
+
+size_t gpx_gradpost_scratch(int np, int mc, int d)
+{
+    return (size_t)gradpost_chunks(np) * mc * d * d;
+}
+
+int gpx_gradpost_build(hipStream_t s, const KParams &kp, const double *X, int n, int np,
+                       const double *Xs, int mc, int d, double *G, int ldg)
+{
+    GPX_TRY(gpx_gradxy_check(kp, d));
+    if (n < 1 || mc < 1 || np < n || ldg < mc * d) {
+        gpx_set_error("gradpost_build: bad shape n=%d np=%d mc=%d d=%d ldg=%d", n, np, mc, d, ldg);
+        return -1;
+    }
+    GPX_TRY(gpx_test_jitter(s));
+    const dim3 grid(np, (mc + 255) / 256);
+    if (d <= 8)
+        hipLaunchKernelGGL(gradpost_build_kernel<8>, grid, dim3(256), 0, s, kp, X, n, Xs, mc, d,
+                           G, ldg);
+    else if (d <= 16)
+        hipLaunchKernelGGL(gradpost_build_kernel<16>, grid, dim3(256), 0, s, kp, X, n, Xs, mc, d,
+                           G, ldg);
+    else
+        hipLaunchKernelGGL(gradpost_build_kernel<32>, grid, dim3(256), 0, s, kp, X, n, Xs, mc, d,
+                           G, ldg);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+int gpx_gradpost_contract(hipStream_t s, const KParams &kp, const double *B, int ldb, int n,
+                          int np, const double *Xs, int mc, int d, double *part, double *S)
+{
+    GPX_TRY(gpx_gradxy_check(kp, d));
+    const int chunks = gradpost_chunks(np);
+    const dim3 grid(mc, chunks), fgrid((mc * d + 255) / 256);
+#define GPX_GP(DM)                                                                           \
+    do {                                                                                     \
+        hipLaunchKernelGGL(gradpost_contract_kernel<DM>, grid, dim3(256), 0, s, B, ldb, n, mc, \
+                           d, part);                                                         \
+        hipLaunchKernelGGL(gradpost_final_kernel<DM>, fgrid, dim3(256), 0, s, kp, Xs, mc, d, \
+                           part, chunks, S);                                                 \
+    } while (0)
+    if (d <= 8) GPX_GP(8);
+    else if (d <= 16) GPX_GP(16);
+    else GPX_GP(32);
+#undef GPX_GP
+    GPX_HIP(hipGetLastError());
+    return 0;
+}

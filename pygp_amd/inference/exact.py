@@ -124,6 +124,11 @@ class GP(Parameterized):
     def _full_posterior(self, X):
         raise NotImplementedError
 
+    def gradient_posterior(self, X):
+        """(mu, S): mean (m, d) and covariance (m, d, d) of grad f at the rows of X."""
+        raise NotImplementedError(
+            'the posterior of the gradient is provided by exact inference only')
+
 
 class ExactGP(GP):
     """Exact inference; the likelihood must be Gaussian (exact.py:28-35)."""
@@ -269,6 +274,27 @@ class ExactGP(GP):
         if X.shape[1] != self._X.shape[1]:
             raise ValueError('test inputs have the wrong dimension')
         return self._dev().exact_posterior_full(X)
+
+    def gradient_posterior(self, X):
+        """The distribution of grad f at the rows of X: mu (m, d) = E[grad f(x_m)], the dmu
+        of posterior(X, grad=True), and S (m, d, d) = Cov[grad f(x_m)] = gradxy(x_m, x_m) -
+        B^T B with B = R^-T d k(X_data, x_m) / d x_m. Without data: the prior, zeros (the
+        mean is constant) and gradxy(x_m, x_m). No counterpart in the reference."""
+        X = self._kernel.transform(X)
+        self._kernel._check_gradxy()
+        if self._X is None:
+            # every kernel here is stationary: one block, the same at every x
+            m, d = X.shape
+            if X.shape[1] != self._kernel.ndim:
+                raise ValueError('test inputs have the wrong dimension')
+            S = np.empty((m, d, d))
+            if m:
+                S[:] = self._kernel.gradxy(X[:1])[0, 0]
+            return np.zeros_like(X), S
+        self._ensure()
+        if X.shape[1] != self._X.shape[1]:
+            raise ValueError('test inputs have the wrong dimension')
+        return self._dev().exact_posterior_gradient(X)
 
     # gp._R / gp._a as the reference exposes them (upper factor, R^-T (y-m))
     @property

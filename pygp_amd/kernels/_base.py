@@ -93,8 +93,17 @@ class RealKernel(Kernel):
         return self._dev().kernel_gradx(self._kspec(), X1, X2, wrt)
 
     def gradxy(self, X1, X2=None):
-        # mixed second derivatives are not on the accelerated path
-        raise NotImplementedError
+        """d2 k(x1, x2) / d x1 d x2, an (n1, n2, d, d) array whose element (a, b, i, j) is
+        the derivative with respect to X1[a, i] and X2[b, j] (_real.py:58-64)."""
+        self._check_gradxy()
+        X1 = self.transform(X1)
+        X2 = None if X2 is None else self.transform(X2)
+        self._check_dim(X1, X2)
+        return self._dev().kernel_gradxy(self._kspec(), X1, X2)
+
+    def _check_gradxy(self):
+        """Raise NotImplementedError, before any device call, where the kernel has no mixed
+        second derivative."""
 
     def sample_spectrum(self, N, rng=None):
         raise NotImplementedError

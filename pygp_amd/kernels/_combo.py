@@ -87,6 +87,10 @@ class ComboKernel(RealKernel):
         return _lib.KSpecHolder(self._kind, False, self.ndim,
                                 parts=[p._kspec() for p in self._parts])
 
+    def _check_gradxy(self):
+        for p in self._parts:
+            p._check_gradxy()
+
 
 class SumKernel(ComboKernel):
     _verb = 'add'

@@ -80,6 +80,11 @@ class Matern(_ARDKernel):
         return _lib.KSpecHolder(_lib.KIND_MATERN[self._d], self._iso, self.ndim,
                                 self.get_hyper())
 
+    def _check_gradxy(self):
+        if self._d == 1:
+            raise NotImplementedError(
+                'the Matern-1/2 kernel is not differentiable at r = 0: no gradxy')
+
 
 @printable
 class RQ(_ARDKernel):
