@@ -178,6 +178,37 @@ int gpx_exact_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, 
  * reads the factorisation: later calls on the handle return the bits they return without
  * this one. Kernels as gpx_kernel_gradxy. */
 int gpx_exact_posterior_gradient(gpx_t *h, const double *Xs, int64_t m, double *dmu, double *S);
+/* ---- exact inference with gradient observations (own design; GPML section 9.4) ----
+ * n >= 0 function values y at X (n x d) and ng >= 1 gradients G (ng x d, G[a][i] = d f / d x_i
+ * at Xg[a]) are one Gaussian observation vector r = [y - mean ; vec(G)] of order M = n + ng d,
+ * gradient rows point-major (row n + a d + i, the order of gpx_kernel_gradxy's output), with
+ * covariance K_aug: k(X, X) + sn^2 I, d k(X_a, Xg_b) / d x'_j (gpx_kernel_gradx, wrt = 2) and
+ * d2 k(Xg_a, Xg_b) / d x_i d x'_j + grad_noise^2 I (gpx_kernel_gradxy). K_aug is built on the
+ * device into the workspace of the exact path and factorised, solved and reduced by the code of
+ * gpx_exact_update / gpx_exact_posterior; kernels as gpx_kernel_gradxy (a Matern-1/2 part: < 0).
+ * Upload: replaces whatever data the handle held. d <= GPX_MAX_DIM, M <= 2^20; X and y may be
+ * NULL when n == 0. While a handle holds gradient observations every gpx_exact_*,
+ * gpx_loglik_batch, gpx_posterior_batch, gpx_batch_plan, gpx_sparse_update / _append,
+ * gpx_select_pivots (X == NULL) and gpx_kernel_build_resident call on it returns < 0 with an
+ * error text: they would read K_aug's factor as that of plain data. gpx_set_data returns the
+ * handle to them. */
+int gpx_gradobs_set_data(gpx_t *h, const double *X, int64_t n, const double *y,
+                         const double *Xg, int64_t ng, const double *G, int64_t d);
+/* K_aug, R = chol(K_aug), a = R^-T r for the uploaded observations. grad_noise >= 0 is the
+ * standard deviation of the gradient observations' noise (not a hyperparameter). *info as
+ * gpx_exact_update: > 0 is the pivot at which K_aug is not positive definite. */
+int gpx_gradobs_update(gpx_t *h, const gpx_kspec *k, double log_sn, double grad_noise,
+                       double mean, int *info);
+/* log N(r; 0, K_aug) = -a.a / 2 - sum log R_ii - M / 2 log 2 pi of the last update. There is
+ * no gradient with respect to the hyperparameters. */
+int gpx_gradobs_loglik(gpx_t *h, double *lZ);
+/* predictive mean and variance of f at m test points: the cross-covariance of x* to the
+ * observations is [k(X, x*) ; d k(Xg_b, x*) / d x_j] (derivative in the first argument). Passes
+ * of test points as gpx_exact_posterior. */
+int gpx_gradobs_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2);
+/* mu[m] and the full covariance Sigma[m][m] of f at the test points; 1 <= m <= 8192, as
+ * gpx_exact_posterior_full. */
+int gpx_gradobs_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma);
 /* host copies of gp._R (n*n row-major upper, zero below the diagonal) and gp._a;
  * either may be NULL. n: the point count the caller sized R and a for; the call
  * fails when it is not the factor's. */

@@ -80,6 +80,12 @@ SIGNATURES = {
                                    C.c_int, _vp]),
     'gpx_kernel_gradxy': (C.c_int, [_vp, C.POINTER(_KSpec), _vp, _i64, _vp, _i64, _i64, _vp]),
     'gpx_exact_posterior_gradient': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    'gpx_gradobs_set_data': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64]),
+    'gpx_gradobs_update': (C.c_int, [_vp, C.POINTER(_KSpec), C.c_double, C.c_double,
+                                     C.c_double, _ip]),
+    'gpx_gradobs_loglik': (C.c_int, [_vp, _dp]),
+    'gpx_gradobs_posterior': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    'gpx_gradobs_posterior_full': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     'gpx_exact_get_factor': (C.c_int, [_vp, _i64, _vp, _vp]),
     'gpx_sparse_update': (C.c_int, [_vp, C.POINTER(_KSpec), C.c_int, _vp, _i64, C.c_double,
                                     C.c_double, _ip]),
@@ -399,6 +405,46 @@ class Handle(object):
         m = Xs.shape[0]
         mu, Sigma = np.empty(m), np.empty((m, m))
         check(self._L.gpx_exact_posterior_full(self._h, _ptr(Xs), m, _ptr(mu), _ptr(Sigma)))
+        return mu, Sigma
+
+    # -- exact GP with gradient observations --
+    def gradobs_set_data(self, X, y, Xg, G):
+        """n >= 0 function values y at X and ng >= 1 gradients G (ng, d) at Xg."""
+        Xg, G = _f64(Xg, 2), _f64(G, 2)
+        if G.shape != Xg.shape:
+            raise ValueError('Xg and G disagree')
+        n = 0 if X is None else len(X)
+        if n:
+            X, y = _f64(X, 2), _f64(y, 1)
+            if X.shape[0] != y.shape[0] or X.shape[1] != Xg.shape[1]:
+                raise ValueError('X, y and Xg disagree')
+        else:
+            X = y = None
+        check(self._L.gpx_gradobs_set_data(self._h, _ptr(X), n, _ptr(y), _ptr(Xg), Xg.shape[0],
+                                           _ptr(G), Xg.shape[1]))
+
+    def gradobs_update(self, spec, log_sn, grad_noise, mean):
+        info = C.c_int(0)
+        check(self._L.gpx_gradobs_update(self._h, spec.ref(), float(log_sn), float(grad_noise),
+                                         float(mean), C.byref(info)))
+
+    def gradobs_loglik(self):
+        lZ = C.c_double(0)
+        check(self._L.gpx_gradobs_loglik(self._h, C.byref(lZ)))
+        return lZ.value
+
+    def gradobs_posterior(self, Xs):
+        Xs = _f64(Xs, 2)
+        m = Xs.shape[0]
+        mu, s2 = np.empty(m), np.empty(m)
+        check(self._L.gpx_gradobs_posterior(self._h, _ptr(Xs), m, _ptr(mu), _ptr(s2)))
+        return mu, s2
+
+    def gradobs_posterior_full(self, Xs):
+        Xs = _f64(Xs, 2)
+        m = Xs.shape[0]
+        mu, Sigma = np.empty(m), np.empty((m, m))
+        check(self._L.gpx_gradobs_posterior_full(self._h, _ptr(Xs), m, _ptr(mu), _ptr(Sigma)))
         return mu, Sigma
 
     # -- sparse pseudo-input models (FITC / DTC / VFE) on the resident data --

@@ -42,6 +42,14 @@ struct gpx_ctx {
                                    // for gpx_exact_append to open new 128-blocks
     long data_version = 0;         // bumped by gpx_set_data (twin refresh)
     DevBuf X, y, Xf32;
+    // gradient observations (gpx_gradobs_set_data): n is then the order M = go_n + go_ng d of
+    // K_aug, y the stacked observations [y ; vec(G)], X the go_n data points, Xg the go_ng
+    // gradient locations, and the factorisation below is that of K_aug. Entries that read
+    // the handle as plain data refuse it (PLAIN_ONLY); gpx_set_data returns it to them.
+    bool gradobs = false;
+    int go_n = 0, go_ng = 0;
+    double grad_noise = 0;
+    DevBuf Xg;
     // factorisation state
     DevBuf A, W, Kinv, r, a, alpha, scalars, partial, info, gv_part, pctl;
     double *acc = nullptr;         // the trace accumulators: a view of scalars
@@ -142,6 +150,15 @@ static int ld_for(int np)
             return -1;                                                         \
         }                                                                      \
         GPX_HIP(hipSetDevice((h)->device));                                    \
+    } while (0)
+
+#define PLAIN_ONLY(h, what)                                                    \
+    do {                                                                       \
+        if ((h)->gradobs) {                                                    \
+            gpx_set_error(what ": the handle holds gradient observations "     \
+                               "(gpx_gradobs_*); gpx_set_data returns it to plain data"); \
+            return -1;                                                         \
+        }                                                                      \
     } while (0)
 
 // stage timer: measures from the previous tick to this one
@@ -689,6 +706,7 @@ int gpx_kernel_build_resident(gpx_t *h, const gpx_kspec *k, int dtype, int reps,
                               double *ms)
 {
     CHECK_H(h);
+    PLAIN_ONLY(h, "gpx_kernel_build_resident");
     if (h->n <= 0) {
         gpx_set_error("gpx_kernel_build_resident: no data (gpx_set_data first)");
         return -1;
@@ -752,6 +770,8 @@ int gpx_set_data(gpx_t *h, const double *X, int64_t n, int64_t d, const double *
     h->ld = ld_for(h->cap);
     h->data_version++;
     h->have_factor = h->have_inverse = false;
+    h->gradobs = false;
+    h->go_n = h->go_ng = 0;
     return 0;
 }
 
@@ -797,7 +817,7 @@ static int enqueue_update(gpx_ctx *h, StageClock &clk, int mode, bool grad_follo
     const GpxBlocks lb(h->np, mode == GPX_POTRF_KINV);
     const int lead_rows = lb.count >= 2 && lb.len(1) <= GPX_PANEL_MAX ? lb.off(2) : lb.len(0);
     hipEvent_t lead_ev = gpx_potrf_lead_event(w);
-    const bool lead = lead_on && lead_ev && w.crit && lead_rows < h->np;
+    const bool lead = !h->gradobs && lead_on && lead_ev && w.crit && lead_rows < h->np;
     if (lead) {
         GPX_TRY(gpx_kbuild<double>(h->stream, h->kp, h->X.as<double>(), h->n, h->np,
                                    h->X.as<double>(), h->n, h->np, h->d, w.A, h->ld, true,
@@ -815,6 +835,11 @@ static int enqueue_update(gpx_ctx *h, StageClock &clk, int mode, bool grad_follo
                                    true, sn2, w.Kinv, lead_rows, h->np - lead_rows));
         w.lead = lead_ev;
         w.lead_rows = lead_rows;
+    } else if (h->gradobs) {
+        // K_aug in the same places (kmat.hip); the whole matrix before the factorisation starts
+        GPX_TRY(gpx_kaug_build(h->stream, h->kp, h->X.as<double>(), h->go_n, h->Xg.as<double>(),
+                               h->go_ng, h->d, sn2, h->grad_noise * h->grad_noise, w.A, w.Kinv,
+                               h->ld, h->np));
     } else {
         GPX_TRY(gpx_kbuild<double>(h->stream, h->kp, h->X.as<double>(), h->n, h->np,
                                    h->X.as<double>(), h->n, h->np, h->d, w.A, h->ld, true,
@@ -838,8 +863,12 @@ static int enqueue_update(gpx_ctx *h, StageClock &clk, int mode, bool grad_follo
     const bool aug = gpx_potrf_rhs_ok(w, mode);
     if (aug) {
         // (one kernel: the residual into column np of the staging matrix, zeros right of it)
-        GPX_TRY(gpx_residual_rhs(h->stream, h->y.as<double>(), h->mean, h->n, h->np, nullptr,
-                                 w.Kinv, h->ld));
+        if (h->gradobs)
+            GPX_TRY(gpx_gradobs_residual(h->stream, h->y.as<double>(), h->go_n, h->n, h->np,
+                                         h->mean, nullptr, w.Kinv, h->ld));
+        else
+            GPX_TRY(gpx_residual_rhs(h->stream, h->y.as<double>(), h->mean, h->n, h->np, nullptr,
+                                     w.Kinv, h->ld));
         w.aug_rhs = true;
     }
     GPX_TRY(gpx_potrf(h->stream, w, mode, true));
@@ -853,8 +882,12 @@ static int enqueue_update(gpx_ctx *h, StageClock &clk, int mode, bool grad_follo
         GPX_TRY(gpx_column_out(h->stream, w.A, h->ld, h->np, h->np, h->a.as<double>(),
                                MemberBatch()));
     } else {
-        GPX_TRY(gpx_residual(h->stream, h->y.as<double>(), h->mean, h->n, h->np,
-                             h->r.as<double>()));
+        if (h->gradobs)
+            GPX_TRY(gpx_gradobs_residual(h->stream, h->y.as<double>(), h->go_n, h->n, h->np,
+                                         h->mean, h->r.as<double>(), nullptr, h->ld));
+        else
+            GPX_TRY(gpx_residual(h->stream, h->y.as<double>(), h->mean, h->n, h->np,
+                                 h->r.as<double>()));
         GPX_TRY(gpx_trsv_rt(h->stream, w, full_inverse, h->r.as<double>(), h->a.as<double>(),
                             h->gv_part.as<double>()));
     }
@@ -980,6 +1013,7 @@ static int check_ready(gpx_ctx *h, const gpx_kspec *k, double log_sn, double mea
 int gpx_exact_update(gpx_t *h, const gpx_kspec *k, double log_sn, double mean, int *info)
 {
     CHECK_H(h);
+    PLAIN_ONLY(h, "gpx_exact_update");
     GPX_TRY(check_ready(h, k, log_sn, mean));
     GPX_TRY(reserve_factor(h, false));
     h->have_factor = h->have_inverse = false;
@@ -993,6 +1027,7 @@ int gpx_exact_update(gpx_t *h, const gpx_kspec *k, double log_sn, double mean, i
 int gpx_exact_loglik(gpx_t *h, double *lZ, double *dlZ)
 {
     CHECK_H(h);
+    PLAIN_ONLY(h, "gpx_exact_loglik");
     if (!h->have_factor) {
         gpx_set_error("gpx_exact_loglik: no factorisation (call gpx_exact_update)");
         return -1;
@@ -1026,6 +1061,7 @@ static int reserve_loo(gpx_ctx *h, bool grad)
 int gpx_exact_loo(gpx_t *h, double *L, double *dL, double *mu, double *s2)
 {
     CHECK_H(h);
+    PLAIN_ONLY(h, "gpx_exact_loo");
     if (!h->have_factor) {
         gpx_set_error("gpx_exact_loo: no factorisation (call gpx_exact_update)");
         return -1;
@@ -1067,6 +1103,7 @@ int gpx_exact_eval(gpx_t *h, const gpx_kspec *k, double log_sn, double mean,
                    int want_grad, double *lZ, double *dlZ, int *info)
 {
     CHECK_H(h);
+    PLAIN_ONLY(h, "gpx_exact_eval");
     GPX_TRY(check_ready(h, k, log_sn, mean));
     const bool grad = want_grad && dlZ;
     GPX_TRY(reserve_factor(h, grad));
@@ -1200,6 +1237,7 @@ static int append_block(gpx_ctx *h, int j0)
 int gpx_exact_append(gpx_t *h, const double *Xnew, const double *ynew, int64_t m, int *info)
 {
     CHECK_H(h);
+    PLAIN_ONLY(h, "gpx_exact_append");
     if (!Xnew || !ynew || m < 1) {
         gpx_set_error("gpx_exact_append: bad arguments");
         return -1;
@@ -1262,6 +1300,7 @@ static bool batch_in_groups(const gpx_ctx *h, int64_t B)
 int gpx_batch_plan(gpx_t *h, int64_t B, int want_grad, int *plan)
 {
     CHECK_H(h);
+    PLAIN_ONLY(h, "gpx_batch_plan");
     if (!plan || B < 0) {
         gpx_set_error("gpx_batch_plan: bad arguments");
         return -1;
@@ -1291,6 +1330,7 @@ int gpx_loglik_batch(gpx_t *h, const gpx_kspec *k, const double *thetas, int64_t
                      int want_grad, double *lZ, double *dlZ, int *info)
 {
     CHECK_H(h);
+    PLAIN_ONLY(h, "gpx_loglik_batch");
     if (!k || !thetas || !lZ || B < 0) {
         gpx_set_error("gpx_loglik_batch: bad arguments");
         return -1;
@@ -1435,10 +1475,31 @@ static int solve_rt_refined(gpx_ctx *h, double *K, double *V, int mcp)
     return gpx_add_inplace(h->stream, V, h->Vc.as<double>(), (size_t)h->np * mcp);
 }
 
+// the right-hand side of the posterior solve for the mc test points in h->Xs: K(X, Xs), or with
+// gradient observations the cross matrix of K_aug; np x mcp, zero outside the live part
+static int build_cross(gpx_ctx *h, int mc, int mcp)
+{
+    if (h->gradobs)
+        return gpx_kaug_cross(h->stream, h->kp, h->X.as<double>(), h->go_n, h->Xg.as<double>(),
+                              h->go_ng, h->d, h->np, h->Xs.as<double>(), mc, h->Ks.as<double>(),
+                              mcp);
+    return gpx_kbuild<double>(h->stream, h->kp, h->X.as<double>(), h->n, h->np,
+                              h->Xs.as<double>(), mc, mcp, h->d, h->Ks.as<double>(), mcp, false,
+                              false, 0.0);
+}
+
+// gradobs: the caller is a gpx_gradobs_* entry; the handle must be in the same state
 static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2,
-                          double *dmu, double *ds2)
+                          double *dmu, double *ds2, bool gradobs = false)
 {
     CHECK_H(h);
+    if (h->gradobs != gradobs) {
+        gpx_set_error(gradobs ? "gpx_gradobs_posterior: the handle holds no gradient observations "
+                                "(gpx_gradobs_set_data)"
+                              : "gpx_exact_posterior: the handle holds gradient observations "
+                                "(gpx_gradobs_*); gpx_set_data returns it to plain data");
+        return -1;
+    }
     if (!h->have_factor) {
         gpx_set_error("gpx_exact_posterior: no factorisation (call gpx_exact_update)");
         return -1;
@@ -1479,9 +1540,7 @@ static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, dou
         GPX_HIP(hipMemcpyAsync(h->Xs.p, Xs + c0 * h->d, (size_t)mc * h->d * 8,
                                hipMemcpyHostToDevice, h->stream));
         // K(X, Xs): np x mcp, zero outside n x mc (exact.py:87)
-        GPX_TRY(gpx_kbuild<double>(h->stream, h->kp, h->X.as<double>(), h->n, h->np,
-                                   h->Xs.as<double>(), mc, mcp, h->d, h->Ks.as<double>(),
-                                   mcp, false, false, 0.0));
+        GPX_TRY(build_cross(h, mc, mcp));
         clk.tick(T_POST_BUILD);
         // RK = R^-T K (exact.py:88)
         double *V = h->KsT.as<double>();
@@ -1520,9 +1579,17 @@ static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, dou
 // ExactGP._full_posterior (exact.py:64-79): mean vector and FULL covariance
 // Sigma = K(Xs, Xs) - V^T V, V = R^-T K(X, Xs); GP.sample draws from it
 // (_base.py:143-178). One pass, m <= 8192.
-int gpx_exact_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma)
+static int posterior_full_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma,
+                               bool gradobs)
 {
     CHECK_H(h);
+    if (h->gradobs != gradobs) {
+        gpx_set_error(gradobs ? "gpx_gradobs_posterior_full: the handle holds no gradient "
+                                "observations (gpx_gradobs_set_data)"
+                              : "gpx_exact_posterior_full: the handle holds gradient observations "
+                                "(gpx_gradobs_*); gpx_set_data returns it to plain data");
+        return -1;
+    }
     if (!h->have_factor) {
         gpx_set_error("gpx_exact_posterior_full: no factorisation (call gpx_exact_update)");
         return -1;
@@ -1546,9 +1613,7 @@ int gpx_exact_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, 
     GPX_TRY(h->t2.reserve((size_t)mcp * mcp * 8));
     GPX_HIP(hipMemcpyAsync(h->Xs.p, Xs, (size_t)mc * h->d * 8, hipMemcpyHostToDevice,
                            h->stream));
-    GPX_TRY(gpx_kbuild<double>(h->stream, h->kp, h->X.as<double>(), h->n, h->np,
-                               h->Xs.as<double>(), mc, mcp, h->d, h->Ks.as<double>(), mcp,
-                               false, false, 0.0));
+    GPX_TRY(build_cross(h, mc, mcp));
     double *V = h->KsT.as<double>();
     GPX_TRY(solve_rt_refined(h, h->Ks.as<double>(), V, mcp));
     GPX_TRY(gpx_posterior_reduce(h->stream, V, mcp, h->np, mcp, h->a.as<double>(), h->mean,
@@ -1569,6 +1634,11 @@ int gpx_exact_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, 
                              hipMemcpyDeviceToHost, h->stream));
     GPX_HIP(hipStreamSynchronize(h->stream));
     return 0;
+}
+
+int gpx_exact_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma)
+{
+    return posterior_full_impl(h, Xs, m, mu, Sigma, false);
 }
 
 int gpx_exact_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2)
@@ -1595,6 +1665,7 @@ int gpx_posterior_batch(gpx_t *h, const gpx_kspec *k, const double *thetas, int6
                         double *ds2, int *info)
 {
     CHECK_H(h);
+    PLAIN_ONLY(h, "gpx_posterior_batch");
     if (!k || !thetas || !Xs || !mu || !s2 || B < 0 || m < 0 || (!dmu) != (!ds2)) {
         gpx_set_error("gpx_posterior_batch: bad arguments");
         return -1;
@@ -1752,6 +1823,7 @@ int gpx_kernel_gradxy(gpx_t *h, const gpx_kspec *k, const double *X1, int64_t n1
 int gpx_exact_posterior_gradient(gpx_t *h, const double *Xs, int64_t m, double *dmu, double *S)
 {
     CHECK_H(h);
+    PLAIN_ONLY(h, "gpx_exact_posterior_gradient");
     if (!h->have_factor) {
         gpx_set_error("gpx_exact_posterior_gradient: no factorisation (call gpx_exact_update)");
         return -1;
@@ -1817,6 +1889,95 @@ int gpx_exact_posterior_gradient(gpx_t *h, const double *Xs, int64_t m, double *
 }
 
 // ---- FITC / DTC (pygp/inference/fitc.py, dtc.py) and VFE -----------------------------
+// ---- gradient observations: exact inference on [y ; vec(G)] (GPML section 9.4) -----------
+int gpx_gradobs_set_data(gpx_t *h, const double *X, int64_t n, const double *y,
+                         const double *Xg, int64_t ng, const double *G, int64_t d)
+{
+    CHECK_H(h);
+    if (!Xg || !G || ng < 1 || d < 1 || d > GPX_MAX_DIM || n < 0 || (n > 0 && (!X || !y)) ||
+        n > (1 << 20) || ng > (1 << 20) || n + ng * d > (1 << 20)) {
+        gpx_set_error("gpx_gradobs_set_data: bad shape n=%lld ng=%lld d=%lld (ng >= 1, d <= %d, "
+                      "n + ng d <= %d)", (long long)n, (long long)ng, (long long)d, GPX_MAX_DIM,
+                      1 << 20);
+        return -1;
+    }
+    const int64_t M = n + ng * d;
+    const size_t cap = (size_t)round_up(M + 256, 1024);      // as gpx_set_data
+    GPX_TRY(h->X.reserve(cap * d * 8));
+    GPX_TRY(h->y.reserve(cap * 8));
+    GPX_TRY(h->Xg.reserve((size_t)ng * d * 8));
+    // a failure from here on leaves the buffers half written: no data of either kind
+    h->n = 0;
+    h->have_factor = h->have_inverse = false;
+    h->gradobs = false;
+    h->data_version++;
+    if (n > 0) {
+        GPX_HIP(hipMemcpyAsync(h->X.p, X, (size_t)n * d * 8, hipMemcpyHostToDevice, h->stream));
+        GPX_HIP(hipMemcpyAsync(h->y.p, y, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+    }
+    GPX_HIP(hipMemcpyAsync(h->Xg.p, Xg, (size_t)ng * d * 8, hipMemcpyHostToDevice, h->stream));
+    GPX_HIP(hipMemcpyAsync(h->y.as<double>() + n, G, (size_t)ng * d * 8, hipMemcpyHostToDevice,
+                           h->stream));
+    GPX_HIP(hipStreamSynchronize(h->stream));
+    h->n = (int)M;
+    h->d = (int)d;
+    h->np = round_up(M, GPX_TILE);
+    h->cap = (int)cap;
+    h->ld = ld_for(h->cap);
+    h->gradobs = true;
+    h->go_n = (int)n;
+    h->go_ng = (int)ng;
+    return 0;
+}
+
+int gpx_gradobs_update(gpx_t *h, const gpx_kspec *k, double log_sn, double grad_noise,
+                       double mean, int *info)
+{
+    CHECK_H(h);
+    if (!h->gradobs) {
+        gpx_set_error("gpx_gradobs_update: no gradient observations (gpx_gradobs_set_data)");
+        return -1;
+    }
+    if (!std::isfinite(log_sn) || !std::isfinite(mean) || !std::isfinite(grad_noise) ||
+        grad_noise < 0) {
+        gpx_set_error("gpx_gradobs_update: non-finite hyperparameters or grad_noise < 0");
+        return -1;
+    }
+    h->have_factor = h->have_inverse = false;
+    GPX_TRY(gpx_flatten_kspec(k, h->d, &h->kp));
+    GPX_TRY(gpx_gradxy_check(h->kp, h->d));
+    h->log_sn = log_sn;
+    h->mean = mean;
+    h->grad_noise = grad_noise;
+    GPX_TRY(reserve_factor(h, false));
+    StageClock clk(h);
+    GPX_TRY(enqueue_update(h, clk, GPX_POTRF_R));
+    int r = finish(h, clk, false, nullptr, nullptr, info);
+    if (r == 0) h->have_factor = true;
+    return r;
+}
+
+int gpx_gradobs_loglik(gpx_t *h, double *lZ)
+{
+    CHECK_H(h);
+    if (!h->gradobs || !h->have_factor) {
+        gpx_set_error("gpx_gradobs_loglik: no factorisation (call gpx_gradobs_update)");
+        return -1;
+    }
+    if (lZ) *lZ = h->lZ;
+    return 0;
+}
+
+int gpx_gradobs_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2)
+{
+    return posterior_impl(h, Xs, m, mu, s2, nullptr, nullptr, true);
+}
+
+int gpx_gradobs_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma)
+{
+    return posterior_full_impl(h, Xs, m, mu, Sigma, true);
+}
+
 static int sparse_ready(gpx_ctx *h, const char *what)
 {
     if (!h->sparse || h->sparse_version < 0) {
@@ -1834,6 +1995,7 @@ int gpx_sparse_update(gpx_t *h, const gpx_kspec *k, int method, const double *U,
                       double log_sn, double mean, int *info)
 {
     CHECK_H(h);
+    PLAIN_ONLY(h, "gpx_sparse_update");
     if (info) *info = 0;
     h->sparse_version = -1;
     if (h->n <= 0) {
@@ -1880,6 +2042,7 @@ int gpx_sparse_update(gpx_t *h, const gpx_kspec *k, int method, const double *U,
 int gpx_sparse_append(gpx_t *h, const double *Xnew, const double *ynew, int64_t m, int *info)
 {
     CHECK_H(h);
+    PLAIN_ONLY(h, "gpx_sparse_append");
     if (info) *info = 0;
     if (!Xnew || !ynew || m < 1) {
         gpx_set_error("gpx_sparse_append: bad arguments");
@@ -1995,6 +2158,7 @@ int gpx_select_pivots(gpx_t *h, const gpx_kspec *k, const double *X, int64_t n, 
                       int64_t *count)
 {
     CHECK_H(h);
+    PLAIN_ONLY(h, "gpx_select_pivots");
     if (!k || !idx || !count) {
         gpx_set_error("gpx_select_pivots: k, idx and count must not be null");
         return -1;
@@ -2054,6 +2218,7 @@ int gpx_select_timing(gpx_t *h, double *ms)
 int gpx_exact_get_factor(gpx_t *h, int64_t n, double *R, double *a)
 {
     CHECK_H(h);
+    PLAIN_ONLY(h, "gpx_exact_get_factor");
     if (!h->have_factor) {
         gpx_set_error("gpx_exact_get_factor: no factorisation");
         return -1;

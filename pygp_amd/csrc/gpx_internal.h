@@ -596,6 +596,21 @@ int gpx_gradpost_build(hipStream_t s, const KParams &kp, const double *X, int n,
 int gpx_gradpost_contract(hipStream_t s, const KParams &kp, const double *B, int ldb, int n,
                           int np, const double *Xs, int mc, int d, double *part, double *S);
 
+// gradient observations (gpx_gradobs_*): K_aug of n function values at X and ng gradients at
+// Xg (order M = n + ng d <= np, rows n + b d + j), f-f + sn2 I, f-g = grady, g-g = gradxy +
+// gn2 I, in the layout gpx_kbuild(sym, upper_only, out_offdiag = S) leaves for gpx_potrf
+// (identity in the padding); n = 0: gradients only, X is not read
+int gpx_kaug_build(hipStream_t s, const KParams &kp, const double *X, int n, const double *Xg,
+                   int ng, int d, double sn2, double gn2, double *A, double *S, int ld, int np);
+// its cross matrix to mc test points, np x ldk: k(X_a, xs_m) and d k(Xg_b, xs_m) / d x_j (first
+// argument), zero for rows >= M and columns >= mc
+int gpx_kaug_cross(hipStream_t s, const KParams &kp, const double *X, int n, const double *Xg,
+                   int ng, int d, int np, const double *Xs, int mc, double *Ks, int ldk);
+// r = [obs[0 .. n) - mean ; obs[n .. M)], zero up to np: into r (may be null) and, with aug, into
+// column np of the staging matrix as gpx_residual_rhs does
+int gpx_gradobs_residual(hipStream_t s, const double *obs, int n, int M, int np, double mean,
+                         double *r, double *aug, int ld);
+
 // column strip [j0, j0+npc) of K + diag_add I for an appended block of observations
 // (j0 a multiple of 128); out_offdiag: the off-diagonal 128-tiles go there instead
 int gpx_kbuild_strip(hipStream_t s, const KParams &kp, const double *X, int n, int np,

@@ -2338,3 +2338,214 @@ int gpx_gradpost_contract(hipStream_t s, const KParams &kp, const double *B, int
     GPX_HIP(hipGetLastError());
     return 0;
 }
+
+// ---- gradient observations (gpx_gradobs_*) --------------------------------------------
+// K_aug of n function values at X and ng gradients at Xg, order M = n + ng d, gradient rows
+// point-major ([n + b d + j], the order of gradxy's output):
+//   f-f  k(X_a, X_b) + sn2 delta_ab
+//   f-g  d k(X_a, Xg_b) / d x'_j                                   (part_grady)
+//   g-g  d2 k(Xg_a, Xg_b) / d x_i d x'_j + gn2 delta_ab delta_ij   (gradxy_row)
+// written where kbuild_kernel (sym, upper_only, out_offdiag) leaves K + sn2 I for gpx_potrf:
+// only the 128-tiles with column tile >= row tile, diagonal tiles (both triangles) in A, the
+// others in the staging matrix S, identity in the padding M .. np. Every entry is computed
+// once, for row entity <= column entity, and offered to both places (kaug_put2): the two
+// triangles of a diagonal tile hold the same bits.
+__device__ __forceinline__ void kaug_put(double *__restrict__ A, double *__restrict__ S, int ld,
+                                         int gi, int gj, double v)
+{
+    const int ti = gi / GPX_TILE, tj = gj / GPX_TILE;
+    if (tj < ti) return;
+    (ti == tj ? A : S)[(size_t)gi * ld + gj] = v;
+}
+__device__ __forceinline__ void kaug_put2(double *__restrict__ A, double *__restrict__ S, int ld,
+                                          int gi, int gj, double v)
+{
+    kaug_put(A, S, ld, gi, gj, v);
+    if (gi != gj) kaug_put(A, S, ld, gj, gi, v);
+}
+
+// Three launches, one per kind of block, so that the f-f and f-g threads do not carry the
+// registers and LDS of the g-g rows:
+//   KAUG_FF  blockIdx.x = row a < n, threads over b >= a: one value per pair (the per-pair code
+//            of kcolumn_kernel; n^2 / 2 of the M^2 / 2 entries); behind them one block row per
+//            padding column q in [M, np), threads over the rows gi <= q
+//   KAUG_FG  blockIdx.x = a < n, threads over b < ng: the strip of d contiguous doubles
+//   KAUG_GG  blockIdx.x = a < ng, threads over (b >= a, row i): row i of the d x d block in DMAX
+//            registers indexed at compile time, as kgradxy_kernel; the block a == b from its
+//            entries j >= i
+enum { KAUG_FF = 0, KAUG_FG = 1, KAUG_GG = 2 };
+template <int DMAX, int REGION>
+__global__ __launch_bounds__(256) void kaug_build_kernel(
+    KParams kp, const double *__restrict__ X, int n, const double *__restrict__ Xg, int ng, int d,
+    double sn2, double gn2, double *__restrict__ A, double *__restrict__ S, int ld, int np)
+{
+    const int t = blockIdx.y * 256 + threadIdx.x;
+    if constexpr (REGION == KAUG_FF) {
+        const int a = blockIdx.x;
+        if (a >= n) {                                      // the padding: identity
+            const int q = n + ng * d + (a - n);
+            if (q < np && t <= q) kaug_put2(A, S, ld, t, q, t == q ? 1.0 : 0.0);
+            return;
+        }
+        if (t < a || t >= n) return;
+        const double *xa = X + (size_t)a * d, *xb = X + (size_t)t * d;
+        double v = 0.0;
+        for (int p = 0; p < kp.nparts; ++p) {
+            if (p > 0 && kp.part[p].group == kp.part[p - 1].group) continue;
+            v += part_value_pair(kp.part[p], xa, xb, d) * group_factor(kp, p, xa, xb, d);
+        }
+        kaug_put2(A, S, ld, a, t, t == a ? v + sn2 : v);
+    } else if constexpr (REGION == KAUG_FG) {
+        const int a = blockIdx.x;
+        if (t >= ng) return;
+        const double *xa = X + (size_t)a * d, *xb = Xg + (size_t)t * d;
+        double g[DMAX];
+#pragma unroll
+        for (int c = 0; c < DMAX; ++c) g[c] = 0.0;
+        for (int p = 0; p < kp.nparts; ++p)
+            part_grady<DMAX>(kp.part[p], xa, xb, d, group_factor(kp, p, xa, xb, d), g);
+        const int col = n + t * d;
+#pragma unroll
+        for (int c = 0; c < DMAX; ++c)
+            if (c < d) kaug_put2(A, S, ld, a, col + c, g[c]);
+    } else {
+        __shared__ double sK[GPX_MAX_PARTS][256], sG[GPX_MAX_PARTS][256];
+        const int a = blockIdx.x;
+        const int b = t / d, i = t - b * d;
+        if (b < a || b >= ng) return;
+        double row[DMAX];
+        gradxy_row<DMAX>(kp, Xg + (size_t)a * d, Xg + (size_t)b * d, d, i, &sK[0][threadIdx.x],
+                         &sG[0][threadIdx.x], 256, row);
+        const int gi = n + a * d + i, col = n + b * d;
+#pragma unroll
+        for (int j = 0; j < DMAX; ++j)
+            if (j < d && (a != b || j >= i))
+                kaug_put2(A, S, ld, gi, col + j, (a == b && j == i) ? row[j] + gn2 : row[j]);
+    }
+}
+
+int gpx_kaug_build(hipStream_t s, const KParams &kp, const double *X, int n, const double *Xg,
+                   int ng, int d, double sn2, double gn2, double *A, double *S, int ld, int np)
+{
+    GPX_TRY(gpx_gradxy_check(kp, d));
+    const long long M = (long long)n + (long long)ng * d;
+    if (n < 0 || ng < 1 || d < 1 || d > GPX_MAX_DIM || M > np || np % GPX_TILE || ld < np ||
+        np - M >= GPX_TILE || !A || !S) {
+        gpx_set_error("kaug_build: bad shape n=%d ng=%d d=%d np=%d ld=%d", n, ng, d, np, ld);
+        return -1;
+    }
+    GPX_TRY(gpx_test_jitter(s));
+    const int pad = np - (int)M;
+    if (n + pad > 0)
+        hipLaunchKernelGGL((kaug_build_kernel<8, KAUG_FF>), dim3(n + pad, (np + 255) / 256),
+                           dim3(256), 0, s, kp, X, n, Xg, ng, d, sn2, gn2, A, S, ld, np);
+    const dim3 fg(n, (ng + 255) / 256), gg(ng, (ng * d + 255) / 256);
+#define GPX_KA(DM)                                                                           \
+    do {                                                                                     \
+        if (n > 0)                                                                           \
+            hipLaunchKernelGGL((kaug_build_kernel<DM, KAUG_FG>), fg, dim3(256), 0, s, kp, X, n, \
+                               Xg, ng, d, sn2, gn2, A, S, ld, np);                           \
+        hipLaunchKernelGGL((kaug_build_kernel<DM, KAUG_GG>), gg, dim3(256), 0, s, kp, X, n, Xg, \
+                           ng, d, sn2, gn2, A, S, ld, np);                                   \
+    } while (0)
+    if (d <= 8) GPX_KA(8);
+    else if (d <= 16) GPX_KA(16);
+    else GPX_KA(32);
+#undef GPX_KA
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// The cross matrix of a pass of mc test points, np x ldk (ldk = mc rounded up to the tile),
+// straight into the right-hand side of the solve against R: row a < n holds k(X_a, xs_m), row
+// n + b d + j holds d k(Xg_b, xs_m) / d x_j, the derivative in the FIRST argument (minus
+// part_grady); rows >= M and columns >= mc are zero. blockIdx.x = a data point, a gradient
+// point (its d rows) or a padding row; threads over the columns.
+template <int DMAX>
+__global__ __launch_bounds__(256) void kaug_cross_kernel(
+    KParams kp, const double *__restrict__ X, int n, const double *__restrict__ Xg, int ng, int d,
+    const double *__restrict__ Xs, int mc, double *__restrict__ Ks, int ldk)
+{
+    const int e = blockIdx.x;
+    const int mj = blockIdx.y * 256 + threadIdx.x;
+    if (mj >= ldk) return;
+    const bool live = mj < mc;
+    const double *xs = Xs + (size_t)(live ? mj : 0) * d;
+    if (e < n) {
+        const double *xa = X + (size_t)e * d;
+        double v = 0.0;
+        if (live)
+            for (int p = 0; p < kp.nparts; ++p) {
+                if (p > 0 && kp.part[p].group == kp.part[p - 1].group) continue;
+                v += part_value_pair(kp.part[p], xa, xs, d) * group_factor(kp, p, xa, xs, d);
+            }
+        Ks[(size_t)e * ldk + mj] = v;
+    } else if (e < n + ng) {
+        const int b = e - n;
+        const double *xb = Xg + (size_t)b * d;
+        double g[DMAX];
+#pragma unroll
+        for (int c = 0; c < DMAX; ++c) g[c] = 0.0;
+        if (live)
+            for (int p = 0; p < kp.nparts; ++p)
+                part_grady<DMAX>(kp.part[p], xb, xs, d, group_factor(kp, p, xb, xs, d), g);
+        double *o = Ks + (size_t)(n + b * d) * ldk + mj;
+#pragma unroll
+        for (int c = 0; c < DMAX; ++c)
+            if (c < d) o[(size_t)c * ldk] = live ? -g[c] : 0.0;
+    } else {
+        Ks[(size_t)(n + ng * d + (e - n - ng)) * ldk + mj] = 0.0;
+    }
+}
+
+int gpx_kaug_cross(hipStream_t s, const KParams &kp, const double *X, int n, const double *Xg,
+                   int ng, int d, int np, const double *Xs, int mc, double *Ks, int ldk)
+{
+    GPX_TRY(gpx_gradxy_check(kp, d));
+    const long long M = (long long)n + (long long)ng * d;
+    if (n < 0 || ng < 1 || d < 1 || d > GPX_MAX_DIM || M > np || mc < 1 || ldk < mc) {
+        gpx_set_error("kaug_cross: bad shape n=%d ng=%d d=%d np=%d mc=%d ldk=%d", n, ng, d, np,
+                      mc, ldk);
+        return -1;
+    }
+    GPX_TRY(gpx_test_jitter(s));
+    const dim3 grid(n + ng + (np - (int)M), (ldk + 255) / 256);
+    if (d <= 8)
+        hipLaunchKernelGGL(kaug_cross_kernel<8>, grid, dim3(256), 0, s, kp, X, n, Xg, ng, d, Xs,
+                           mc, Ks, ldk);
+    else if (d <= 16)
+        hipLaunchKernelGGL(kaug_cross_kernel<16>, grid, dim3(256), 0, s, kp, X, n, Xg, ng, d, Xs,
+                           mc, Ks, ldk);
+    else
+        hipLaunchKernelGGL(kaug_cross_kernel<32>, grid, dim3(256), 0, s, kp, X, n, Xg, ng, d, Xs,
+                           mc, Ks, ldk);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// r = [y - mean ; vec(G)] from the stacked observations obs (M of them, the first n function
+// values; the constant mean has no gradient), zero in the padding: into r (may be null) and,
+// with aug, into column np of the staging matrix with the 127 columns right of it zero, as
+// gpx_residual_rhs leaves it for a factorisation that takes the right-hand side along
+__global__ void gradobs_residual_kernel(const double *__restrict__ obs, int n, int M, int np,
+                                        double mean, double *__restrict__ r,
+                                        double *__restrict__ aug, int ld)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    const int i = e >> 6, c = e & 63;
+    if (i >= np) return;
+    const double v = i < n ? obs[i] - mean : (i < M ? obs[i] : 0.0);
+    if (r && c == 0) r[i] = v;
+    if (aug)
+        reinterpret_cast<double2 *>(aug + (size_t)i * ld + np)[c] =
+            make_double2(c == 0 ? v : 0.0, 0.0);
+}
+
+int gpx_gradobs_residual(hipStream_t s, const double *obs, int n, int M, int np, double mean,
+                         double *r, double *aug, int ld)
+{
+    hipLaunchKernelGGL(gradobs_residual_kernel, dim3((np * 64 + 255) / 256), dim3(256), 0, s, obs,
+                       n, M, np, mean, r, aug, ld);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}

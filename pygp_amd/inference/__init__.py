@@ -1,8 +1,9 @@
 from .exact import GP, ExactGP
 from .basic import BasicGP
+from .gradobs import GradientGP
 from .fitc import FITC
 from .dtc import DTC
 from .vfe import VFE
 from .select import select_pseudoinputs
 
-__all__ = ['GP', 'ExactGP', 'BasicGP', 'FITC', 'DTC', 'VFE', 'select_pseudoinputs']
+__all__ = ['GP', 'ExactGP', 'BasicGP', 'GradientGP', 'FITC', 'DTC', 'VFE', 'select_pseudoinputs']

@@ -44,6 +44,10 @@ class HyperEnsemble(object):
             # sparse model's
             raise TypeError('HyperEnsemble runs exact GPs only; %s is a sparse model'
                             % type(model).__name__)
+        if getattr(model, 'ngrad', 0) > 0:
+            # ... on (X, y) alone: the gradient observations would be left out
+            raise TypeError('HyperEnsemble runs GPs on function values only; this %s holds '
+                            'gradient observations' % type(model).__name__)
         self._model = model.copy()
         self._hypers = np.array(hypers, dtype=float, ndmin=2)
         if self._hypers.shape[1] != self._model.nhyper:
