@@ -209,6 +209,28 @@ int gpx_gradobs_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, dou
 /* mu[m] and the full covariance Sigma[m][m] of f at the test points; 1 <= m <= 8192, as
  * gpx_exact_posterior_full. */
 int gpx_gradobs_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma);
+/* ---- T outputs at the same inputs under one kernel (own design; GPML section 9.1, shared
+ * hyperparameters) ----
+ * Y holds 1 <= T <= 32 observation vectors at the n points of X, column t as n contiguous
+ * doubles at Y + t n. The outputs are independent GPs with the same kernel, noise and constant
+ * mean, so K + sn^2 I is built and factorised once and the T right-hand sides share R:
+ * lZ = sum_t lZ_t = -1/2 sum_t a_t.a_t - T sum log R_ii - n T / 2 log 2 pi, a_t = R^-T (y_t - mean).
+ * Upload: replaces whatever data the handle held. While a handle holds multi-output data every
+ * entry that gpx_gradobs_set_data's comment lists, and every gpx_gradobs_* entry but
+ * gpx_gradobs_set_data, returns < 0 with an error text; gpx_set_data and gpx_gradobs_set_data
+ * return it to those families. The gpx_mo_* entries below refuse a handle in another state. */
+int gpx_mo_set_data(gpx_t *h, const double *X, int64_t n, const double *Y, int64_t T, int64_t d);
+/* K + sn^2 I, R and the T vectors a_t for the uploaded data; *info as gpx_exact_update. */
+int gpx_mo_update(gpx_t *h, const gpx_kspec *k, double log_sn, double mean, int *info);
+/* lZ of the last update; dlZ (may be NULL) = sum_t dlZ_t in the layout of gpx_exact_loglik
+ * [log sn | kernel | mean]: one trace pass with the weight T K^-1 - A A^T, A = [alpha_1 .. alpha_T];
+ * completes R^-1 and K^-1 as gpx_exact_loglik does. */
+int gpx_mo_loglik(gpx_t *h, double *lZ, double *dlZ);
+/* predictive means mu[t m + j] (T rows of m doubles) and the variance s2[j] the outputs share, at
+ * m test points; passes of test points as gpx_exact_posterior. */
+int gpx_mo_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2);
+/* mu as above and the full covariance Sigma[m][m] the outputs share; 1 <= m <= 8192. */
+int gpx_mo_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma);
 /* host copies of gp._R (n*n row-major upper, zero below the diagonal) and gp._a;
  * either may be NULL. n: the point count the caller sized R and a for; the call
  * fails when it is not the factor's. */

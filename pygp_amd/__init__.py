@@ -14,8 +14,10 @@ from . import inference
 from . import learning
 from . import batch
 from . import meta
-from .inference import BasicGP, ExactGP, GradientGP, FITC, DTC, VFE, select_pseudoinputs
+from .inference import (BasicGP, ExactGP, GradientGP, MultiOutputGP, FITC, DTC, VFE,
+                        select_pseudoinputs)
 from .learning import optimize
 
-__all__ = ['BasicGP', 'ExactGP', 'GradientGP', 'FITC', 'DTC', 'VFE', 'select_pseudoinputs',
-           'optimize', 'kernels', 'likelihoods', 'inference', 'learning', 'batch', 'meta']
+__all__ = ['BasicGP', 'ExactGP', 'GradientGP', 'MultiOutputGP', 'FITC', 'DTC', 'VFE',
+           'select_pseudoinputs', 'optimize', 'kernels', 'likelihoods', 'inference', 'learning',
+           'batch', 'meta']

@@ -86,6 +86,11 @@ SIGNATURES = {
     'gpx_gradobs_loglik': (C.c_int, [_vp, _dp]),
     'gpx_gradobs_posterior': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     'gpx_gradobs_posterior_full': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    'gpx_mo_set_data': (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64]),
+    'gpx_mo_update': (C.c_int, [_vp, C.POINTER(_KSpec), C.c_double, C.c_double, _ip]),
+    'gpx_mo_loglik': (C.c_int, [_vp, _dp, _vp]),
+    'gpx_mo_posterior': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    'gpx_mo_posterior_full': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     'gpx_exact_get_factor': (C.c_int, [_vp, _i64, _vp, _vp]),
     'gpx_sparse_update': (C.c_int, [_vp, C.POINTER(_KSpec), C.c_int, _vp, _i64, C.c_double,
                                     C.c_double, _ip]),
@@ -446,6 +451,42 @@ class Handle(object):
         mu, Sigma = np.empty(m), np.empty((m, m))
         check(self._L.gpx_gradobs_posterior_full(self._h, _ptr(Xs), m, _ptr(mu), _ptr(Sigma)))
         return mu, Sigma
+
+    # -- T outputs at the same inputs (MultiOutputGP) --
+    def mo_set_data(self, X, Y):
+        """X (n, d) and Y (n, T), 1 <= T <= 32."""
+        X, Y = _f64(X, 2), _f64(Y, 2)
+        if X.shape[0] != Y.shape[0]:
+            raise ValueError('X and Y disagree')
+        Yt = np.ascontiguousarray(Y.T)              # the C entry takes column t contiguous
+        self._mo_T = Y.shape[1]
+        check(self._L.gpx_mo_set_data(self._h, _ptr(X), X.shape[0], _ptr(Yt), Y.shape[1],
+                                      X.shape[1]))
+
+    def mo_update(self, spec, log_sn, mean):
+        info = C.c_int(0)
+        check(self._L.gpx_mo_update(self._h, spec.ref(), float(log_sn), float(mean),
+                                    C.byref(info)))
+
+    def mo_loglik(self, nhyper_kernel, grad=False):
+        lZ = C.c_double(0)
+        dlZ = np.empty(nhyper_kernel + 2) if grad else None
+        check(self._L.gpx_mo_loglik(self._h, C.byref(lZ), _ptr(dlZ)))
+        return (lZ.value, dlZ) if grad else lZ.value
+
+    def mo_posterior(self, Xs):
+        Xs = _f64(Xs, 2)
+        m = Xs.shape[0]
+        mu, s2 = np.empty((self._mo_T, m)), np.empty(m)
+        check(self._L.gpx_mo_posterior(self._h, _ptr(Xs), m, _ptr(mu), _ptr(s2)))
+        return np.ascontiguousarray(mu.T), s2
+
+    def mo_posterior_full(self, Xs):
+        Xs = _f64(Xs, 2)
+        m = Xs.shape[0]
+        mu, Sigma = np.empty((self._mo_T, m)), np.empty((m, m))
+        check(self._L.gpx_mo_posterior_full(self._h, _ptr(Xs), m, _ptr(mu), _ptr(Sigma)))
+        return np.ascontiguousarray(mu.T), Sigma
 
     # -- sparse pseudo-input models (FITC / DTC / VFE) on the resident data --
     def sparse_update(self, spec, method, U, log_sn, mean):

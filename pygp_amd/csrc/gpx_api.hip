@@ -50,6 +50,11 @@ struct gpx_ctx {
     int go_n = 0, go_ng = 0;
     double grad_noise = 0;
     DevBuf Xg;
+    // multi-output data (gpx_mo_set_data): mo_T > 0 outputs observed at the n points of X. y, r,
+    // a and alpha then hold mo_T columns, column t at + t * cap; the factorisation is that of
+    // plain data on X. Handled like the state above: the plain and the gradobs entries refuse
+    // the handle, gpx_set_data / gpx_gradobs_set_data return it to them.
+    int mo_T = 0;
     // factorisation state
     DevBuf A, W, Kinv, r, a, alpha, scalars, partial, info, gv_part, pctl;
     double *acc = nullptr;         // the trace accumulators: a view of scalars
@@ -157,6 +162,11 @@ static int ld_for(int np)
         if ((h)->gradobs) {                                                    \
             gpx_set_error(what ": the handle holds gradient observations "     \
                                "(gpx_gradobs_*); gpx_set_data returns it to plain data"); \
+            return -1;                                                         \
+        }                                                                      \
+        if ((h)->mo_T) {                                                       \
+            gpx_set_error(what ": the handle holds multi-output data "         \
+                               "(gpx_mo_*); gpx_set_data returns it to plain data"); \
             return -1;                                                         \
         }                                                                      \
     } while (0)
@@ -772,6 +782,7 @@ int gpx_set_data(gpx_t *h, const double *X, int64_t n, int64_t d, const double *
     h->have_factor = h->have_inverse = false;
     h->gradobs = false;
     h->go_n = h->go_ng = 0;
+    h->mo_T = 0;
     return 0;
 }
 
@@ -860,7 +871,8 @@ static int enqueue_update(gpx_ctx *h, StageClock &clk, int mode, bool grad_follo
     // decided here, once: gpx_potrf takes the whole-matrix launch iff w.whole says so
     w.whole = gpx_potrf_whole(w, mode);
     w.full_w = grad_follows && gpx_grad_full_w(w, mode);
-    const bool aug = gpx_potrf_rhs_ok(w, mode);
+    // (multi-output data: the T right-hand sides are solved behind the factorisation)
+    const bool aug = !h->mo_T && gpx_potrf_rhs_ok(w, mode);
     if (aug) {
         // (one kernel: the residual into column np of the staging matrix, zeros right of it)
         if (h->gradobs)
@@ -881,6 +893,9 @@ static int enqueue_update(gpx_ctx *h, StageClock &clk, int mode, bool grad_follo
     if (aug) {
         GPX_TRY(gpx_column_out(h->stream, w.A, h->ld, h->np, h->np, h->a.as<double>(),
                                MemberBatch()));
+    } else if (h->mo_T) {
+        GPX_TRY(gpx_mo_trsv_rt(h->stream, w, h->y.as<double>(), h->mo_T, h->mean, h->n, h->cap,
+                               h->r.as<double>(), h->a.as<double>(), h->gv_part.as<double>()));
     } else {
         if (h->gradobs)
             GPX_TRY(gpx_gradobs_residual(h->stream, h->y.as<double>(), h->go_n, h->n, h->np,
@@ -905,9 +920,13 @@ static int enqueue_inverse(gpx_ctx *h, StageClock &clk)
         h->w_complete = true;
         clk.tick(T_TRTRI);
     }
-    GPX_TRY(gpx_trmv_upper(h->stream, w.W, h->ld, h->np, h->a.as<double>(),
-                           h->alpha.as<double>()));
-    if (h->kinv_pending) {
+    if (h->mo_T)
+        GPX_TRY(gpx_mo_trmv_upper(h->stream, w.W, h->ld, h->np, h->a.as<double>(), h->mo_T, h->cap,
+                                  h->alpha.as<double>()));
+    else
+        GPX_TRY(gpx_trmv_upper(h->stream, w.W, h->ld, h->np, h->a.as<double>(),
+                               h->alpha.as<double>()));
+    if (h->kinv_pending && !h->mo_T) {
         // a = R^-T r and alpha = R^-1 a ran beside the last K^-1 update of the sweep, and so
         // do the scalar terms (one workgroup, 44 us): wait for the update here; the potrf
         // stage (factor + inverse) ends with it
@@ -935,9 +954,14 @@ static int enqueue_grad(gpx_ctx *h, StageClock &clk)
 {
     GPX_TRY(enqueue_inverse(h, clk));
     const DenseWs w = h->ws();
-    GPX_TRY(gpx_trace_grad(h->stream, h->kp, h->X.as<double>(), h->n, h->np, h->d, w.Kinv,
-                           h->ld, h->alpha.as<double>(), h->partial.as<double>(),
-                           h->acc));
+    if (h->mo_T)
+        GPX_TRY(gpx_mo_trace_grad(h->stream, h->kp, h->X.as<double>(), h->n, h->np, h->d, w.Kinv,
+                                  h->ld, h->alpha.as<double>(), h->mo_T, h->cap,
+                                  h->partial.as<double>(), h->acc));
+    else
+        GPX_TRY(gpx_trace_grad(h->stream, h->kp, h->X.as<double>(), h->n, h->np, h->d, w.Kinv,
+                               h->ld, h->alpha.as<double>(), h->partial.as<double>(),
+                               h->acc));
     clk.tick(T_TRACE);
     return 0;
 }
@@ -945,7 +969,11 @@ static int enqueue_grad(gpx_ctx *h, StageClock &clk)
 // scalars + asynchronous copy of the few result doubles to pinned host memory
 static int enqueue_finish(gpx_ctx *h, StageClock &clk, bool grad)
 {
-    if (!(grad && h->lz_enqueued))
+    if (h->mo_T)
+        GPX_TRY(gpx_mo_lz_terms(h->stream, h->A.as<double>(), h->ld, h->n, h->a.as<double>(),
+                                grad ? h->alpha.as<double>() : nullptr, h->mo_T, h->cap,
+                                h->scalars.as<double>(), h->info.as<int>()));
+    else if (!(grad && h->lz_enqueued))
         GPX_TRY(gpx_lz_terms(h->stream, h->A.as<double>(), h->ld, h->n, h->a.as<double>(),
                              grad ? h->alpha.as<double>() : nullptr, h->scalars.as<double>(), 1,
                              0, 0, 0, h->info.as<int>()));
@@ -981,7 +1009,7 @@ static int collect(gpx_ctx *h, StageClock &clk, double *lZ, double *dlZ, int *in
         return inf;
     }
     // exact.py:119-121
-    h->lZ = gpx_assemble_lz(sc, h->n);
+    h->lZ = h->mo_T ? gpx_mo_assemble_lz(sc, h->n, h->mo_T) : gpx_assemble_lz(sc, h->n);
     if (lZ) *lZ = h->lZ;
     if (grad && dlZ) gpx_assemble_dlz(sc, acc, exp(h->log_sn * 2), h->kp.nhyper, dlZ);
     return 0;
@@ -1488,18 +1516,30 @@ static int build_cross(gpx_ctx *h, int mc, int mcp)
                               false, 0.0);
 }
 
-// gradobs: the caller is a gpx_gradobs_* entry; the handle must be in the same state
+// the state a handle is in, and the check that an entry of one family finds its own
+enum { ST_PLAIN = 0, ST_GRADOBS = 1, ST_MO = 2 };
+static int state_of(const gpx_ctx *h) { return h->mo_T ? ST_MO : (h->gradobs ? ST_GRADOBS : ST_PLAIN); }
+static int check_state(const gpx_ctx *h, int want, const char *what)
+{
+    static const char *holds[3] = {"plain data (gpx_set_data)",
+                                   "gradient observations (gpx_gradobs_*)",
+                                   "multi-output data (gpx_mo_*)"};
+    const int st = state_of(h);
+    if (st == want) return 0;
+    gpx_set_error("%s: the handle holds %s%s", what, holds[st],
+                  want == ST_PLAIN ? "; gpx_set_data returns it to plain data" : "");
+    return -1;
+}
+
+// state: the family of the calling entry; the handle must be in the same state. ST_MO: mu is
+// mo_T rows of m doubles.
 static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2,
-                          double *dmu, double *ds2, bool gradobs = false)
+                          double *dmu, double *ds2, int state = ST_PLAIN)
 {
     CHECK_H(h);
-    if (h->gradobs != gradobs) {
-        gpx_set_error(gradobs ? "gpx_gradobs_posterior: the handle holds no gradient observations "
-                                "(gpx_gradobs_set_data)"
-                              : "gpx_exact_posterior: the handle holds gradient observations "
-                                "(gpx_gradobs_*); gpx_set_data returns it to plain data");
-        return -1;
-    }
+    GPX_TRY(check_state(h, state, state == ST_MO ? "gpx_mo_posterior"
+                                  : state == ST_GRADOBS ? "gpx_gradobs_posterior"
+                                                        : "gpx_exact_posterior"));
     if (!h->have_factor) {
         gpx_set_error("gpx_exact_posterior: no factorisation (call gpx_exact_update)");
         return -1;
@@ -1534,9 +1574,10 @@ static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, dou
         GPX_TRY(h->Xs.reserve((size_t)mc * h->d * 8));
         GPX_TRY(h->Ks.reserve((size_t)h->np * mcp * 8));
         GPX_TRY(h->KsT.reserve((size_t)h->np * mcp * 8));
-        GPX_TRY(h->mu.reserve((size_t)mcp * 8));
+        GPX_TRY(h->mu.reserve((size_t)mcp * 8 * (h->mo_T ? h->mo_T : 1)));
         GPX_TRY(h->s2.reserve((size_t)mcp * 8));
-        GPX_TRY(h->post_part.reserve(gpx_posterior_scratch(mcp) * 8));
+        GPX_TRY(h->post_part.reserve((h->mo_T ? gpx_mo_posterior_scratch(mcp)
+                                              : gpx_posterior_scratch(mcp)) * 8));
         GPX_HIP(hipMemcpyAsync(h->Xs.p, Xs + c0 * h->d, (size_t)mc * h->d * 8,
                                hipMemcpyHostToDevice, h->stream));
         // K(X, Xs): np x mcp, zero outside n x mc (exact.py:87)
@@ -1545,10 +1586,16 @@ static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, dou
         // RK = R^-T K (exact.py:88)
         double *V = h->KsT.as<double>();
         GPX_TRY(solve_rt_refined(h, h->Ks.as<double>(), V, mcp));
-        GPX_TRY(gpx_posterior_reduce(h->stream, V, mcp, h->np, mcp,
-                                     h->a.as<double>(), h->mean, prior,
-                                     h->post_part.as<double>(), h->mu.as<double>(),
-                                     h->s2.as<double>()));
+        if (h->mo_T)
+            GPX_TRY(gpx_mo_posterior_reduce(h->stream, V, mcp, h->np, mcp, h->a.as<double>(),
+                                            h->mo_T, h->cap, h->mean, prior,
+                                            h->post_part.as<double>(), h->mu.as<double>(),
+                                            h->s2.as<double>()));
+        else
+            GPX_TRY(gpx_posterior_reduce(h->stream, V, mcp, h->np, mcp,
+                                         h->a.as<double>(), h->mean, prior,
+                                         h->post_part.as<double>(), h->mu.as<double>(),
+                                         h->s2.as<double>()));
         clk.tick(T_POST_SOLVE);
         if (grads) {
             // beta = W V (V = R^-T K*): W upper -> k >= row tile
@@ -1566,8 +1613,12 @@ static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, dou
             GPX_HIP(hipMemcpyAsync(ds2 + c0 * h->d, h->t1.p, (size_t)mc * h->d * 8,
                                    hipMemcpyDeviceToHost, h->stream));
         }
-        GPX_HIP(hipMemcpyAsync(mu + c0, h->mu.p, (size_t)mc * 8, hipMemcpyDeviceToHost,
-                               h->stream));
+        if (h->mo_T)         // row t of the device's mo_T x mcp block -> mu[t][c0 ..)
+            GPX_HIP(hipMemcpy2DAsync(mu + c0, (size_t)m * 8, h->mu.p, (size_t)mcp * 8,
+                                     (size_t)mc * 8, h->mo_T, hipMemcpyDeviceToHost, h->stream));
+        else
+            GPX_HIP(hipMemcpyAsync(mu + c0, h->mu.p, (size_t)mc * 8, hipMemcpyDeviceToHost,
+                                   h->stream));
         GPX_HIP(hipMemcpyAsync(s2 + c0, h->s2.p, (size_t)mc * 8, hipMemcpyDeviceToHost,
                                h->stream));
         GPX_HIP(hipStreamSynchronize(h->stream));
@@ -1580,16 +1631,12 @@ static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, dou
 // Sigma = K(Xs, Xs) - V^T V, V = R^-T K(X, Xs); GP.sample draws from it
 // (_base.py:143-178). One pass, m <= 8192.
 static int posterior_full_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma,
-                               bool gradobs)
+                               int state)
 {
     CHECK_H(h);
-    if (h->gradobs != gradobs) {
-        gpx_set_error(gradobs ? "gpx_gradobs_posterior_full: the handle holds no gradient "
-                                "observations (gpx_gradobs_set_data)"
-                              : "gpx_exact_posterior_full: the handle holds gradient observations "
-                                "(gpx_gradobs_*); gpx_set_data returns it to plain data");
-        return -1;
-    }
+    GPX_TRY(check_state(h, state, state == ST_MO ? "gpx_mo_posterior_full"
+                                  : state == ST_GRADOBS ? "gpx_gradobs_posterior_full"
+                                                        : "gpx_exact_posterior_full"));
     if (!h->have_factor) {
         gpx_set_error("gpx_exact_posterior_full: no factorisation (call gpx_exact_update)");
         return -1;
@@ -1607,18 +1654,24 @@ static int posterior_full_impl(gpx_t *h, const double *Xs, int64_t m, double *mu
     GPX_TRY(h->Xs.reserve((size_t)mc * h->d * 8));
     GPX_TRY(h->Ks.reserve((size_t)h->np * mcp * 8));
     GPX_TRY(h->KsT.reserve((size_t)h->np * mcp * 8));
-    GPX_TRY(h->mu.reserve((size_t)mcp * 8));
+    GPX_TRY(h->mu.reserve((size_t)mcp * 8 * (h->mo_T ? h->mo_T : 1)));
     GPX_TRY(h->s2.reserve((size_t)mcp * 8));
-    GPX_TRY(h->post_part.reserve(gpx_posterior_scratch(mcp) * 8));
+    GPX_TRY(h->post_part.reserve((h->mo_T ? gpx_mo_posterior_scratch(mcp)
+                                          : gpx_posterior_scratch(mcp)) * 8));
     GPX_TRY(h->t2.reserve((size_t)mcp * mcp * 8));
     GPX_HIP(hipMemcpyAsync(h->Xs.p, Xs, (size_t)mc * h->d * 8, hipMemcpyHostToDevice,
                            h->stream));
     GPX_TRY(build_cross(h, mc, mcp));
     double *V = h->KsT.as<double>();
     GPX_TRY(solve_rt_refined(h, h->Ks.as<double>(), V, mcp));
-    GPX_TRY(gpx_posterior_reduce(h->stream, V, mcp, h->np, mcp, h->a.as<double>(), h->mean,
-                                 0.0, h->post_part.as<double>(), h->mu.as<double>(),
-                                 h->s2.as<double>()));
+    if (h->mo_T)
+        GPX_TRY(gpx_mo_posterior_reduce(h->stream, V, mcp, h->np, mcp, h->a.as<double>(), h->mo_T,
+                                        h->cap, h->mean, 0.0, h->post_part.as<double>(),
+                                        h->mu.as<double>(), h->s2.as<double>()));
+    else
+        GPX_TRY(gpx_posterior_reduce(h->stream, V, mcp, h->np, mcp, h->a.as<double>(), h->mean,
+                                     0.0, h->post_part.as<double>(), h->mu.as<double>(),
+                                     h->s2.as<double>()));
     // Sigma = K(Xs, Xs) - V^T V on the padded mcp x mcp block
     GPX_TRY(gpx_kbuild<double>(h->stream, h->kp, h->Xs.as<double>(), mc, mcp,
                                h->Xs.as<double>(), mc, mcp, h->d, h->t2.as<double>(), mcp,
@@ -1629,7 +1682,11 @@ static int posterior_full_impl(gpx_t *h, const double *Xs, int64_t m, double *mu
     g.M = mcp; g.N = mcp; g.K = h->np;
     g.alpha = -1.0; g.beta = 1.0;
     GPX_TRY(gpx_gemm(h->stream, 1, 0, g));
-    GPX_HIP(hipMemcpyAsync(mu, h->mu.p, (size_t)mc * 8, hipMemcpyDeviceToHost, h->stream));
+    if (h->mo_T)
+        GPX_HIP(hipMemcpy2DAsync(mu, (size_t)mc * 8, h->mu.p, (size_t)mcp * 8, (size_t)mc * 8,
+                                 h->mo_T, hipMemcpyDeviceToHost, h->stream));
+    else
+        GPX_HIP(hipMemcpyAsync(mu, h->mu.p, (size_t)mc * 8, hipMemcpyDeviceToHost, h->stream));
     GPX_HIP(hipMemcpy2DAsync(Sigma, (size_t)mc * 8, h->t2.p, (size_t)mcp * 8, (size_t)mc * 8, mc,
                              hipMemcpyDeviceToHost, h->stream));
     GPX_HIP(hipStreamSynchronize(h->stream));
@@ -1638,7 +1695,7 @@ static int posterior_full_impl(gpx_t *h, const double *Xs, int64_t m, double *mu
 
 int gpx_exact_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma)
 {
-    return posterior_full_impl(h, Xs, m, mu, Sigma, false);
+    return posterior_full_impl(h, Xs, m, mu, Sigma, ST_PLAIN);
 }
 
 int gpx_exact_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2)
@@ -1910,6 +1967,7 @@ int gpx_gradobs_set_data(gpx_t *h, const double *X, int64_t n, const double *y,
     h->n = 0;
     h->have_factor = h->have_inverse = false;
     h->gradobs = false;
+    h->mo_T = 0;
     h->data_version++;
     if (n > 0) {
         GPX_HIP(hipMemcpyAsync(h->X.p, X, (size_t)n * d * 8, hipMemcpyHostToDevice, h->stream));
@@ -1970,12 +2028,103 @@ int gpx_gradobs_loglik(gpx_t *h, double *lZ)
 
 int gpx_gradobs_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2)
 {
-    return posterior_impl(h, Xs, m, mu, s2, nullptr, nullptr, true);
+    return posterior_impl(h, Xs, m, mu, s2, nullptr, nullptr, ST_GRADOBS);
 }
 
 int gpx_gradobs_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma)
 {
-    return posterior_full_impl(h, Xs, m, mu, Sigma, true);
+    return posterior_full_impl(h, Xs, m, mu, Sigma, ST_GRADOBS);
+}
+
+// ---- multi-output data: T outputs at the same inputs, one kernel, one factorisation --------
+int gpx_mo_set_data(gpx_t *h, const double *X, int64_t n, const double *Y, int64_t T, int64_t d)
+{
+    CHECK_H(h);
+    if (!X || !Y || n < 1 || d < 1 || d > GPX_MAX_DIM || n > (1 << 20) || T < 1 ||
+        T > GPX_MO_TMAX) {
+        gpx_set_error("gpx_mo_set_data: bad shape n=%lld T=%lld d=%lld (1 <= T <= %d, d <= %d)",
+                      (long long)n, (long long)T, (long long)d, GPX_MO_TMAX, GPX_MAX_DIM);
+        return -1;
+    }
+    const size_t cap = (size_t)round_up(n + 256, 1024);      // as gpx_set_data
+    GPX_TRY(h->X.reserve(cap * d * 8));
+    GPX_TRY(h->y.reserve(cap * T * 8));
+    // a failure from here on leaves the buffers half written: no data of any kind
+    h->n = 0;
+    h->have_factor = h->have_inverse = false;
+    h->gradobs = false;
+    h->go_n = h->go_ng = 0;
+    h->mo_T = 0;
+    h->data_version++;
+    GPX_HIP(hipMemcpyAsync(h->X.p, X, (size_t)n * d * 8, hipMemcpyHostToDevice, h->stream));
+    // column t of Y (n contiguous doubles) -> y + t cap
+    GPX_HIP(hipMemcpy2DAsync(h->y.p, cap * 8, Y, (size_t)n * 8, (size_t)n * 8, (size_t)T,
+                             hipMemcpyHostToDevice, h->stream));
+    GPX_HIP(hipStreamSynchronize(h->stream));
+    h->n = (int)n;
+    h->d = (int)d;
+    h->np = round_up(n, GPX_TILE);
+    h->cap = (int)cap;
+    h->ld = ld_for(h->cap);
+    h->mo_T = (int)T;
+    return 0;
+}
+
+// the T-column vectors behind reserve_factor's (which sizes them for one column)
+static int reserve_mo(gpx_ctx *h, bool inverse)
+{
+    GPX_TRY(reserve_factor(h, inverse));
+    const size_t vecs = (size_t)h->cap * h->mo_T * 8;
+    GPX_TRY(h->r.reserve(vecs));
+    GPX_TRY(h->a.reserve(vecs));
+    GPX_TRY(h->gv_part.reserve(gpx_mo_trsv_scratch(h->np, h->mo_T) * 8));
+    if (inverse) GPX_TRY(h->alpha.reserve(vecs));
+    return 0;
+}
+
+int gpx_mo_update(gpx_t *h, const gpx_kspec *k, double log_sn, double mean, int *info)
+{
+    CHECK_H(h);
+    GPX_TRY(check_state(h, ST_MO, "gpx_mo_update"));
+    GPX_TRY(check_ready(h, k, log_sn, mean));
+    h->have_factor = h->have_inverse = false;
+    GPX_TRY(reserve_mo(h, false));
+    StageClock clk(h);
+    GPX_TRY(enqueue_update(h, clk, GPX_POTRF_R));
+    int r = finish(h, clk, false, nullptr, nullptr, info);
+    if (r == 0) h->have_factor = true;
+    return r;
+}
+
+int gpx_mo_loglik(gpx_t *h, double *lZ, double *dlZ)
+{
+    CHECK_H(h);
+    GPX_TRY(check_state(h, ST_MO, "gpx_mo_loglik"));
+    if (!h->have_factor) {
+        gpx_set_error("gpx_mo_loglik: no factorisation (call gpx_mo_update)");
+        return -1;
+    }
+    if (!dlZ) {
+        if (lZ) *lZ = h->lZ;
+        return 0;
+    }
+    // (a, written by the update, is as large as reserve_mo asks: nothing is reallocated)
+    GPX_TRY(reserve_mo(h, true));
+    StageClock clk(h);
+    GPX_TRY(enqueue_grad(h, clk));
+    int r = finish(h, clk, true, lZ, dlZ, nullptr);
+    if (r == 0) h->have_inverse = true;
+    return r;
+}
+
+int gpx_mo_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2)
+{
+    return posterior_impl(h, Xs, m, mu, s2, nullptr, nullptr, ST_MO);
+}
+
+int gpx_mo_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma)
+{
+    return posterior_full_impl(h, Xs, m, mu, Sigma, ST_MO);
 }
 
 static int sparse_ready(gpx_ctx *h, const char *what)

@@ -497,6 +497,38 @@ int gpx_trace_grad(hipStream_t s, const KParams &kp, const double *X, int n,
                    double *partial, double *acc, const MemberBatch *mb = nullptr,
                    int astride = 0);
 
+// ---- multi-output (gpx_mo_*; vec.hip, kmat.hip) ------------------------------------------
+// T <= GPX_MO_TMAX outputs share X, the kernel and the factorisation. Column t of Y, r, a and
+// A = [alpha_1 .. alpha_T] lies t * vs doubles behind column 0 (vs: the handle's capacity).
+#define GPX_MO_TMAX 32
+// a_t = R^-T (y_t - mean) for every t: the block substitution of gpx_trsv_rt with every tile of
+// W and R read once for the T columns; the mean is subtracted while Y is loaded. r: T columns
+// of scratch; partial: gpx_mo_trsv_scratch(np, T) doubles.
+size_t gpx_mo_trsv_scratch(int np, int T);
+int gpx_mo_trsv_rt(hipStream_t s, const DenseWs &w, const double *Y, int T, double mean, int n,
+                   long long vs, double *r, double *a, double *partial);
+// A = W a for the T columns (W = R^-1 complete)
+int gpx_mo_trmv_upper(hipStream_t s, const double *W, int ld, int np, const double *v, int T,
+                      long long vs, double *out);
+// scalars[0..3] = sum_t a_t.a_t, sum log R_ii, sum_t sum_i alpha_it (alpha may be null), status
+int gpx_mo_lz_terms(hipStream_t s, const double *R, int ld, int n, const double *a,
+                    const double *alpha, int T, long long vs, double *scalars, const int *info);
+static inline double gpx_mo_assemble_lz(const double *sc, int n, int T)
+{
+    return -0.5 * sc[0] - T * sc[1] - 0.5 * log(2 * M_PI) * n * T;
+}
+// mu[t][j] = mean + V[:, j].a_t (t < T, rows of m doubles), s2[j] = prior - |V[:, j]|^2, V read
+// once; part: gpx_mo_posterior_scratch(m) doubles
+size_t gpx_mo_posterior_scratch(int m);
+int gpx_mo_posterior_reduce(hipStream_t s, const double *V, int ldv, int np, int m,
+                            const double *a, int T, long long vs, double mean, double prior,
+                            double *part, double *mu, double *s2);
+// gpx_trace_grad with the pair weight q_ij = T Kinv_ij - sum_t alpha_it alpha_jt: the same
+// accumulators (acc[0] = tr(Q)), scratch and second stage
+int gpx_mo_trace_grad(hipStream_t s, const KParams &kp, const double *X, int n, int np, int d,
+                      const double *Kinv, int ld, const double *A, int T, long long vs,
+                      double *partial, double *acc);
+
 // ---- leave-one-out cross-validation (loo.hip) ----------------------------------------
 // From w.Kinv (upper) and alpha = K^-1 (y - m): out[0] = sum_i [1/2 log q_i - 1/2 alpha_i^2 /
 // q_i], q = diag K^-1; the LOO means and variances into vec[0 .. np) and vec[np .. 2 np).

@@ -1437,6 +1437,340 @@ int gpx_trace_grad(hipStream_t s, const KParams &kp, const double *X, int n, int
     return 0;
 }
 
+// ---- trace_grad for T outputs over one factorisation (gpx_mo_*) ----------------------
+// dlZ = sum_t dlZ_t needs sum_ij q_ij dK_ij with the pair weight q_ij = T Kinv_ij - sum_t
+// alpha_it alpha_jt: the two kernels above with that weight and nothing else changed. A = [alpha_1
+// .. alpha_T], column t at A + t vs. The 64 x T block of the row side is staged in LDS once per
+// workgroup (ai_s[t][r]: a wave reads one address, a broadcast); the column side is one load per
+// lane and t, held in a register for the sixteen rows it meets. sum_t runs t = 0 .. T-1 in one
+// FMA chain per pair, so nothing N x N is formed for A A^T and the bits do not depend on the
+// launch. Accumulators, dup handling, partial layout and second stage are gpx_trace_grad's.
+template <int DMAX, int KIND>
+__global__ __launch_bounds__(256, (DMAX == 16 ? 2 : 1)) void mo_trace_grad_rows_kernel(
+    KParams kp, const double *__restrict__ Xs, int n, const double *__restrict__ Kinv, int ld,
+    const double *__restrict__ A, int T, long long vs, double *__restrict__ partial, int nacc,
+    int do_trq)
+{
+    const int TT = gridDim.y, C = gridDim.x;
+    const int bi = blockIdx.y, c0 = blockIdx.x;
+    double *pout = partial + ((size_t)bi * C + c0) * nacc;
+    const int tid = threadIdx.x;
+    if (bi + c0 >= TT) {                         // no tile of this row for this chunk
+        if (tid == 0 && do_trq) pout[0] = 0.0;
+        for (int p = 0; p < kp.nparts; ++p)
+            if (kp.part[p].kind == KIND && tid < kp.part[p].nhyper)
+                pout[1 + kp.part[p].hoff + tid] = 0.0;
+        return;
+    }
+    __shared__ double xi_s[KT][DMAX + 1];
+    __shared__ __attribute__((aligned(16))) double ai_s[GPX_MO_TMAX][KT];
+    __shared__ double red[4][DMAX + 3];
+    const int lane = tid & 63, ig = tid >> 6;
+    const int i0 = bi * KT;
+    for (int e = tid; e < T * KT; e += 256) {
+        const int t = e / KT, r = e - t * KT;
+        ai_s[t][r] = A[t * vs + min(i0 + r, n - 1)];
+    }
+    const double Tf = (double)T;
+    double trq = 0.0;
+    // rows i0 .. i0 + 63 of K^-1 (byte offsets inside: < 64 ld 8 + 8 np, far below 2 GB)
+    const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<double *>(Kinv + (size_t)i0 * ld), 0, 0x7fffffff, 0x00020000);
+    const int rowoff = __builtin_amdgcn_readfirstlane(ig * 16 * ld * 8);
+
+    bool first = true;
+    for (int p = 0; p < kp.nparts; ++p) {
+        const KPart &part = kp.part[p];
+        if (part.kind != KIND) continue;
+        const double *__restrict__ xs = Xs + (size_t)p * gridDim.y * KT * DMAX;
+        __syncthreads();
+        for (int e = tid; e < KT * DMAX; e += 256) {
+            const int r = e / DMAX, c = e - r * DMAX;
+            xi_s[r][c] = xs[(size_t)(i0 + r) * DMAX + c];
+        }
+        __syncthreads();
+        double a_sf = 0.0, a_e[DMAX];
+#pragma unroll
+        for (int c = 0; c < DMAX; ++c) a_e[c] = 0.0;
+
+        for (int bj = bi + c0; bj < TT; bj += C) {
+            const int j0 = bj * KT;
+            const int gj = j0 + lane;
+            const int cj = min(gj, n - 1);
+            double q[16], xj[DMAX];
+#pragma unroll
+            for (int ii = 0; ii < 16; ++ii)
+                q[ii] = __builtin_bit_cast(
+                    double, __builtin_amdgcn_raw_buffer_load_b64(rK, gj * 8, rowoff + ii * ld * 8, 0));
+            const double2 *__restrict__ xp =
+                reinterpret_cast<const double2 *>(xs + (size_t)gj * DMAX);
+#pragma unroll
+            for (int c = 0; c < DMAX; c += 2) {
+                const double2 v = xp[c / 2];
+                xj[c] = v.x;
+                xj[c + 1] = v.y;
+            }
+            // sum_t alpha_it alpha_jt for this thread's sixteen pairs
+            double aa[16];
+#pragma unroll
+            for (int ii = 0; ii < 16; ++ii) aa[ii] = 0.0;
+            for (int t = 0; t < T; ++t) {
+                const double aj = A[t * vs + cj];
+#pragma unroll
+                for (int ii = 0; ii < 16; ++ii) aa[ii] = fma(ai_s[t][ig * 16 + ii], aj, aa[ii]);
+            }
+            // weights: the full symmetric sum from the upper triangle
+            double wq[16];
+            if (bj > bi && i0 + KT <= n && j0 + KT <= n) {
+#pragma unroll
+                for (int ii = 0; ii < 16; ++ii) wq[ii] = 2.0 * (Tf * q[ii] - aa[ii]);
+            } else {
+#pragma unroll
+                for (int ii = 0; ii < 16; ++ii) {
+                    const int gi = i0 + ig * 16 + ii;
+                    double w = 0.0;
+                    if (gi < n && gj < n) w = gi < gj ? 2.0 : (gi == gj ? 1.0 : 0.0);
+                    const double qq = w != 0.0 ? Tf * q[ii] - aa[ii] : 0.0;
+                    if (first && gi == gj && w != 0.0) trq += qq;
+                    wq[ii] = w * qq;
+                }
+            }
+            trace_pairs<DMAX, KIND>(part, &xi_s[ig * 16], xj, wq, a_sf, a_e);
+        }
+        first = false;
+        const int nh = part.nhyper;
+        double v = wave_sum(2.0 * a_sf);
+        if (lane == 0) red[ig][0] = v;
+#pragma unroll
+        for (int c = 0; c < DMAX; ++c)
+            if (c < nh - 1) {
+                v = wave_sum(a_e[c]);
+                if (lane == 0) red[ig][1 + c] = v;
+            }
+        __syncthreads();
+        if (tid < nh)
+            pout[1 + part.hoff + tid] =
+                red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+    }
+    __syncthreads();
+    if (do_trq) {
+        double v = wave_sum(trq);
+        if (lane == 0) red[ig][0] = v;
+        __syncthreads();
+        if (tid == 0) pout[0] = red[0][0] + red[1][0] + red[2][0] + red[3][0];
+    }
+}
+
+// the generic form (RQ, periodic, products; MODE as trace_grad_kernel)
+template <int DMAX, int MODE>
+__global__ __launch_bounds__(256) void mo_trace_grad_kernel(
+    KParams kp, const double *__restrict__ X, int n, int d, const double *__restrict__ Kinv,
+    int ld, const double *__restrict__ A, int T, long long vs, double *__restrict__ partial,
+    int nacc)
+{
+    const int TT = gridDim.y;                   // tiles per side
+    const int bi = blockIdx.y, bj = blockIdx.x;
+    const int blin = bi * TT + bj;
+    double *pout = partial + (size_t)blin * nacc;
+    const int tid = threadIdx.x;
+    if (bj < bi) {
+        for (int h = tid; h < nacc; h += 256) pout[h] = 0.0;
+        return;
+    }
+    __shared__ double xi_s[KT][DMAX + 1];
+    __shared__ __attribute__((aligned(16))) double ai_s[GPX_MO_TMAX][KT];
+    __shared__ double red[4][DMAX + 3];
+
+    const int lane = tid & 63, ig = tid >> 6;
+    const int i0 = bi * KT, j0 = bj * KT;
+    const int gj = j0 + lane;
+    const int cj = min(gj, n - 1);
+    for (int e = tid; e < T * KT; e += 256) {
+        const int t = e / KT, r = e - t * KT;
+        ai_s[t][r] = A[t * vs + min(i0 + r, n - 1)];
+    }
+    __syncthreads();
+    double aa[16];
+#pragma unroll
+    for (int ii = 0; ii < 16; ++ii) aa[ii] = 0.0;
+    for (int t = 0; t < T; ++t) {
+        const double aj = A[t * vs + cj];
+#pragma unroll
+        for (int ii = 0; ii < 16; ++ii) aa[ii] = fma(ai_s[t][ig * 16 + ii], aj, aa[ii]);
+    }
+    const double Tf = (double)T;
+
+    // q weights for this thread's 16 pairs (shared by all parts)
+    double wq[16];
+    double trq = 0.0;
+#pragma unroll
+    for (int ii = 0; ii < 16; ++ii) {
+        const int gi = i0 + ig * 16 + ii;
+        double w = 0.0;
+        if (gi < n && gj < n) w = gi < gj ? 2.0 : (gi == gj ? 1.0 : 0.0);
+        double q = 0.0;
+        if (w != 0.0) {
+            q = Tf * Kinv[(size_t)gi * ld + gj] - aa[ii];
+            if (gi == gj) trq += q;
+        }
+        wq[ii] = w * q;
+    }
+
+    for (int p = 0; p < kp.nparts; ++p) {
+        const KPart &part = kp.part[p];
+        __syncthreads();
+        for (int e = tid; e < KT * DMAX; e += 256) {
+            const int r = e / DMAX, c = e - r * DMAX;
+            const int gi = min(i0 + r, n - 1);
+            xi_s[r][c] = c < d ? X[(size_t)gi * d + c] / part.scale[c] : 0.0;
+        }
+        double xj[DMAX];
+#pragma unroll
+        for (int c = 0; c < DMAX; ++c)
+            xj[c] = c < d ? X[(size_t)cj * d + c] / part.scale[c] : 0.0;
+        __syncthreads();
+
+        double a_sf = 0.0, a_x = 0.0, a_e[DMAX];
+#pragma unroll
+        for (int c = 0; c < DMAX; ++c) a_e[c] = 0.0;
+
+        for (int ii = 0; ii < 16; ++ii) {
+            double t = wq[ii];
+            if (MODE == 0 && kp.nprod != 0 && t != 0.0)
+                t *= group_factor(kp, p, X + (size_t)min(i0 + ig * 16 + ii, n - 1) * d,
+                                  X + (size_t)cj * d, d);
+            const double *xi = xi_s[ig * 16 + ii];
+            double dd[DMAX], D2 = 0.0;
+#pragma unroll
+            for (int c = 0; c < DMAX; ++c) {
+                const double df = xi[c] - xj[c];
+                dd[c] = df * df;
+                D2 += dd[c];
+            }
+            if (MODE == 0 && part.kind == GPX_PERIODIC) {
+                const PeriodicGrad g =
+                    periodic_grad(part.sf2, part.ell, part.period, D2);
+                a_sf += t * g.g0;
+                if (DMAX >= 2) {
+                    a_e[0] += t * g.g1;
+                    a_e[DMAX >= 2 ? 1 : 0] += t * g.g2;
+                }
+                continue;
+            }
+            const RadialGrad g = radial_grad_t<MODE == 0>(part.kind, part.two_logsf, part.sf2,
+                                                          part.alpha, D2);
+            a_sf += t * (2 * g.K);
+            if (MODE == 0) a_x += t * g.xval;
+            if (part.iso) {
+                a_e[0] += t * g.isoval;
+            } else {
+                const double cf = g.zero ? 0.0 : t * (g.Mv / g.rdiv);
+#pragma unroll
+                for (int c = 0; c < DMAX; ++c) a_e[c] += cf * dd[c];
+            }
+        }
+        const int nh = part.nhyper;
+        const int ne = part.kind == GPX_RQ ? nh - 2 : nh - 1;
+        double v = wave_sum(a_sf);
+        if (lane == 0) red[ig][0] = v;
+#pragma unroll
+        for (int c = 0; c < DMAX; ++c)
+            if (c < ne) {
+                v = wave_sum(a_e[c]);
+                if (lane == 0) red[ig][1 + c] = v;
+            }
+        if (part.kind == GPX_RQ) {
+            v = wave_sum(a_x);
+            if (lane == 0) red[ig][nh - 1] = v;
+        }
+        __syncthreads();
+        if (tid < nh) {
+            const double v4 = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+            pout[1 + part.hoff + tid] = part.dup ? pout[1 + part.hoff + tid] + v4 : v4;
+        }
+    }
+    __syncthreads();
+    {
+        double v = wave_sum(trq);
+        if (lane == 0) red[ig][0] = v;
+        __syncthreads();
+        if (tid == 0) pout[0] = red[0][0] + red[1][0] + red[2][0] + red[3][0];
+    }
+}
+
+int gpx_mo_trace_grad(hipStream_t s, const KParams &kp, const double *X, int n, int np, int d,
+                      const double *Kinv, int ld, const double *A, int T, long long vs,
+                      double *partial, double *acc)
+{
+    if (T < 1 || T > GPX_MO_TMAX) {
+        gpx_set_error("gpx_mo_trace_grad: bad arguments (T = %d)", T);
+        return -1;
+    }
+    const int TT = np / KT;
+    const int nacc = 1 + kp.nhyper;
+    bool simple = kp.nprod == 0;
+    for (int p = 0; p < kp.nparts; ++p)
+        simple = simple && (kp.part[p].kind == GPX_SE || kp.part[p].kind == GPX_MATERN1 ||
+                            kp.part[p].kind == GPX_MATERN3 || kp.part[p].kind == GPX_MATERN5);
+    const int rows_env = gpx_env().trace_rows;
+    if (simple && rows_env > 0) {
+        const int C = std::min(TT, rows_env);
+        const dim3 rgrid(C, TT);
+        const int dmax = d <= 8 ? 8 : (d <= 16 ? 16 : 32);
+        double *Xs = partial + (size_t)TT * TT * TG_MAXACC;
+        const dim3 xgrid((np * dmax + 255) / 256, kp.nparts);
+        hipLaunchKernelGGL(xscale_kernel<false>, xgrid, dim3(256), 0, s, kp, X, n, d, np, dmax, Xs,
+                           (const MemberParams *)nullptr, 0LL);
+        GPX_HIP(hipGetLastError());
+        bool trq_done = false;
+        const int kinds[4] = {GPX_SE, GPX_MATERN1, GPX_MATERN3, GPX_MATERN5};
+        for (int kind : kinds) {
+            bool present = false;
+            for (int p = 0; p < kp.nparts; ++p) present = present || kp.part[p].kind == kind;
+            if (!present) continue;
+            const int do_trq = trq_done ? 0 : 1;
+            trq_done = true;
+#define GPX_MTR(DM, KD)                                                                      \
+    hipLaunchKernelGGL((mo_trace_grad_rows_kernel<DM, KD>), rgrid, dim3(256), 0, s, kp, Xs, n, \
+                       Kinv, ld, A, T, vs, partial, nacc, do_trq)
+#define GPX_MTRD(KD)                                                                         \
+    do {                                                                                     \
+        if (d <= 8) GPX_MTR(8, KD);                                                          \
+        else if (d <= 16) GPX_MTR(16, KD);                                                   \
+        else GPX_MTR(32, KD);                                                                \
+    } while (0)
+            if (kind == GPX_SE) GPX_MTRD(GPX_SE);
+            else if (kind == GPX_MATERN1) GPX_MTRD(GPX_MATERN1);
+            else if (kind == GPX_MATERN3) GPX_MTRD(GPX_MATERN3);
+            else GPX_MTRD(GPX_MATERN5);
+#undef GPX_MTRD
+#undef GPX_MTR
+            GPX_HIP(hipGetLastError());
+        }
+        hipLaunchKernelGGL(trace_reduce_kernel, dim3(nacc), dim3(256), 0, s, partial, TT * C, nacc,
+                           acc, 0LL, 0);
+        GPX_HIP(hipGetLastError());
+        return 0;
+    }
+    const dim3 grid(TT, TT);
+#define GPX_MTG(DM, MODE)                                                                    \
+    hipLaunchKernelGGL((mo_trace_grad_kernel<DM, MODE>), grid, dim3(256), 0, s, kp, X, n, d, Kinv, \
+                       ld, A, T, vs, partial, nacc)
+    if (d <= 8) {
+        if (simple) GPX_MTG(8, 1); else GPX_MTG(8, 0);
+    } else if (d <= 16) {
+        if (simple) GPX_MTG(16, 1); else GPX_MTG(16, 0);
+    } else {
+        if (simple) GPX_MTG(32, 1); else GPX_MTG(32, 0);
+    }
+#undef GPX_MTG
+    GPX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(trace_reduce_kernel, dim3(nacc), dim3(256), 0, s, partial, TT * TT, nacc,
+                       acc, 0LL, 0);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
 // ---- weighted gradient over a rectangular pair set (sparse models, sparse.hip) -------
 // acc[1 + h] = sum_{i < n1, j < n2} G[i][j] dK_h(x1_i, x2_j). One workgroup owns a 64-row
 // block of X1 and walks the 64-column tiles bj = c0, c0 + C, ... of X2 (row-persistent, like

@@ -5,6 +5,7 @@
 //   trmv      alpha = R^-1 a as W a (W = R^-1)       exact.py:128
 //   lz_terms  sum a^2, sum log R_ii, sum alpha       exact.py:119-121,141
 //   posterior mu = m + V^T a, s2 = k** - colsum(V^2) exact.py:93-94
+//   mo_*      the same for T right-hand sides over one factorisation (gpx_mo_*)
 //
 // (paths relative to /root/reference/pygp/inference/)
 
@@ -504,6 +505,328 @@ int gpx_symmetrize(hipStream_t s, const double *A, int np, int n, double *out)
 {
     hipLaunchKernelGGL(symmetrize_kernel, dim3((n + 255) / 256, n), dim3(256), 0, s, A, np,
                        n, out);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- multi-output (gpx_mo_*): T <= GPX_MO_TMAX right-hand sides over one factorisation ----
+// Column t of Y, r, a and A = [alpha_1 .. alpha_T] lies t * vs doubles behind column 0 (vs
+// the handle's capacity, even). TB is the register block of the T columns (8 or 32); columns
+// t >= T are zeros in LDS and are never loaded or stored.
+#define MO_GC 64              // columns of M per workgroup (one per lane)
+#define MO_GR 128             // rows staged per step: one diagonal tile
+
+// out[j][t] = sum_{i0 <= i < i1} M[i][j] x[i][t]            (sub == 0)
+// out[j][t] = src[j][t] - that sum                          (sub != 0; src may be out)
+// for ncols columns j from jbase on and every t < T, in two deterministic stages as gemvt above.
+// Stage one: workgroup (column chunk, row chunk) reads its MO_GR x MO_GC tile of M once
+// (coalesced along j, wave w takes rows w, w + 4, ...: its 32 loads are in flight before the
+// staging of x waits) and applies it to the T columns of x staged in LDS; the four waves' sums
+// are added in a fixed order into partial[row chunk][t][column]. Stage two adds the row chunks
+// in order. tri: M is upper triangular with the origin of rows and columns at (0, 0) and nothing
+// below the 128-block of column j was ever written (such tiles give zeros). x_raw / src_raw:
+// that operand is Y itself, read as y - mean (0 from row n on): no residual pass of its own.
+template <int TB>
+__global__ __launch_bounds__(256) void mo_gemvt_partial_kernel(
+    const double *__restrict__ M, int ld, int i0, int i1, int jbase, int tri,
+    const double *__restrict__ x, int x_raw, double mean, int n, int T, long long vs,
+    double *__restrict__ partial, int ncols)
+{
+    __shared__ __attribute__((aligned(16))) double xs[MO_GR][TB + 2];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int j0 = jbase + blockIdx.x * MO_GC, j = j0 + lane;
+    const int ib = i0 + blockIdx.y * MO_GR;
+    const int iend = tri ? min(i1, (j0 / LB + 1) * LB) : i1;
+    const int rows = min(MO_GR, iend - ib);            // (one value per workgroup; <= 0: no tile)
+    double acc[TB];
+#pragma unroll
+    for (int t = 0; t < TB; ++t) acc[t] = 0.0;
+    if (rows > 0) {
+        double m[MO_GR / 4];
+        const double *Mp = M + (size_t)ib * ld + j;
+#pragma unroll
+        for (int q = 0; q < MO_GR / 4; ++q) {
+            const int r = wv + 4 * q;
+            m[q] = r < rows ? Mp[(size_t)r * ld] : 0.0;
+        }
+#pragma unroll
+        for (int it = 0; it < MO_GR * TB / 256; ++it) {
+            const int e = tid + it * 256;
+            const int t = e / MO_GR, r = e - t * MO_GR, gi = ib + r;
+            const bool live = t < T && r < rows && (!x_raw || gi < n);
+            double v = live ? x[t * vs + gi] : 0.0;
+            if (x_raw && live) v -= mean;
+            xs[r][t] = v;
+        }
+        __syncthreads();
+        // (fully unrolled: m[] is indexed at compile time and stays in registers)
+#pragma unroll
+        for (int q = 0; q < MO_GR / 4; ++q) {
+            const int r = wv + 4 * q;
+#pragma unroll
+            for (int t = 0; t < TB; ++t) acc[t] = fma(m[q], xs[r][t], acc[t]);
+        }
+    }
+    // waves 1 .. 3 hand their sums to wave 0 through the staging buffer, half of TB at a time
+    // (3 x TB/2 x 64 doubles fit into it)
+    double *red = &xs[0][0];
+    constexpr int HB = TB / 2;
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+        __syncthreads();
+        if (wv > 0) {
+#pragma unroll
+            for (int t = 0; t < HB; ++t) red[((wv - 1) * HB + t) * 64 + lane] = acc[hh * HB + t];
+        }
+        __syncthreads();
+        if (wv == 0) {
+#pragma unroll
+            for (int t = 0; t < HB; ++t)
+                acc[hh * HB + t] = ((acc[hh * HB + t] + red[t * 64 + lane]) +
+                                    red[(HB + t) * 64 + lane]) + red[(2 * HB + t) * 64 + lane];
+        }
+    }
+    if (wv != 0) return;
+    double *p = partial + (size_t)blockIdx.y * T * ncols + (j - jbase);
+#pragma unroll
+    for (int t = 0; t < TB; ++t)
+        if (t < T) p[(size_t)t * ncols] = acc[t];
+}
+
+// blockIdx.y = t: the row chunks of column j in order, then src - sum or the sum
+__global__ __launch_bounds__(256) void mo_gemvt_finish_kernel(
+    const double *__restrict__ partial, int nchunk, int ncols, int jbase, int T, const double *src,
+    int src_raw, int sub, double mean, int n, long long vs, double *out)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x, t = blockIdx.y;
+    if (e >= ncols) return;
+    const int j = jbase + e;
+    double v = 0.0;
+    for (int c = 0; c < nchunk; ++c) v += partial[((size_t)c * T + t) * ncols + e];
+    if (sub) {
+        double s0;
+        if (!src_raw) s0 = src[t * vs + j];
+        else s0 = j < n ? src[t * vs + j] - mean : 0.0;
+        v = s0 - v;
+    }
+    out[t * vs + j] = v;
+}
+
+static int mo_gemvt(hipStream_t s, int T, const double *M, int ld, int i0, int i1, int jbase,
+                    int ncols, bool tri, const double *x, bool x_raw, const double *src,
+                    bool src_raw, bool sub, double mean, int n, long long vs, double *out,
+                    double *partial)
+{
+    if (ncols <= 0 || i1 <= i0) return 0;
+    const int nchunk = (i1 - i0) / MO_GR;
+    const dim3 grid(ncols / MO_GC, nchunk);
+    if (T <= 8)
+        hipLaunchKernelGGL(mo_gemvt_partial_kernel<8>, grid, dim3(256), 0, s, M, ld, i0, i1, jbase,
+                           tri ? 1 : 0, x, x_raw ? 1 : 0, mean, n, T, vs, partial, ncols);
+    else
+        hipLaunchKernelGGL(mo_gemvt_partial_kernel<32>, grid, dim3(256), 0, s, M, ld, i0, i1,
+                           jbase, tri ? 1 : 0, x, x_raw ? 1 : 0, mean, n, T, vs, partial, ncols);
+    hipLaunchKernelGGL(mo_gemvt_finish_kernel, dim3((ncols + 255) / 256, T), dim3(256), 0, s,
+                       partial, nchunk, ncols, jbase, T, src, src_raw ? 1 : 0, sub ? 1 : 0, mean, n,
+                       vs, out);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// doubles of `partial`: [row chunks of the longest diagonal block][T][np]
+size_t gpx_mo_trsv_scratch(int np, int T)
+{
+    const GpxBlocks bl(np);
+    int longest = 0;
+    for (int k = 0; k < bl.count; ++k) longest = std::max(longest, bl.len(k));
+    return (size_t)(longest / MO_GR) * T * np;
+}
+
+// a_t = R^-T (y_t - mean) for all T columns: block forward substitution over the diagonal
+// blocks of the factorisation with the inverses every gpx_potrf leaves in W, as gpx_trsv_rt,
+// every tile of W and R read once for the T columns. r: T columns of scratch (untouched when
+// there is one block); partial: gpx_mo_trsv_scratch(np, T) doubles.
+int gpx_mo_trsv_rt(hipStream_t s, const DenseWs &w, const double *Y, int T, double mean, int n,
+                   long long vs, double *r, double *a, double *partial)
+{
+    if (T < 1 || T > GPX_MO_TMAX || w.np % LB || (vs & 1)) {
+        gpx_set_error("gpx_mo_trsv_rt: bad arguments (T = %d)", T);
+        return -1;
+    }
+    const int np = w.np, ld = w.ld;
+    const GpxBlocks bl(np);
+    for (int k = 0; k < bl.count; ++k) {
+        const int ok = bl.off(k), o1 = bl.off(k + 1);
+        // a_k = W_kk^T r_k (rows and columns of block k; the first block reads Y itself)
+        GPX_TRY(mo_gemvt(s, T, w.W, ld, ok, o1, ok, o1 - ok, true, k == 0 ? Y : r, k == 0, nullptr,
+                         false, false, mean, n, vs, a, partial));
+        // r[o1:] -= R[k, o1:]^T a_k (the first block starts the columns of r from Y - mean)
+        GPX_TRY(mo_gemvt(s, T, w.A, ld, ok, o1, o1, np - o1, false, a, false, k == 0 ? Y : r,
+                         k == 0, true, mean, n, vs, r, partial));
+    }
+    return 0;
+}
+
+// A = W a for the T columns, W upper triangular: one wave per row, as trmv_upper_kernel; the
+// row of W is read once for all columns
+template <int TB>
+__global__ __launch_bounds__(256) void mo_trmv_upper_kernel(const double *__restrict__ W, int ld,
+                                                            int np, const double *__restrict__ v,
+                                                            int T, long long vs,
+                                                            double *__restrict__ out)
+{
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= np) return;
+    const double *Wr = W + (size_t)row * ld;
+    const int j0 = (row / LB) * LB;
+    double acc[TB];
+#pragma unroll
+    for (int t = 0; t < TB; ++t) acc[t] = 0.0;
+    for (int j = j0 + 2 * lane; j < np; j += 128) {
+        const double2 wv = *reinterpret_cast<const double2 *>(Wr + j);
+#pragma unroll
+        for (int t = 0; t < TB; ++t)
+            if (t < T) {
+                const double2 vv = *reinterpret_cast<const double2 *>(v + t * vs + j);
+                acc[t] += wv.x * vv.x + wv.y * vv.y;
+            }
+    }
+#pragma unroll
+    for (int t = 0; t < TB; ++t)
+        if (t < T) {
+            const double r = wave_sum64(acc[t]);
+            if (lane == 0) out[t * vs + row] = r;
+        }
+}
+
+int gpx_mo_trmv_upper(hipStream_t s, const double *W, int ld, int np, const double *v, int T,
+                      long long vs, double *out)
+{
+    if (T < 1 || T > GPX_MO_TMAX || (vs & 1)) {
+        gpx_set_error("gpx_mo_trmv_upper: bad arguments (T = %d)", T);
+        return -1;
+    }
+    if (T <= 8)
+        hipLaunchKernelGGL(mo_trmv_upper_kernel<8>, dim3((np + 3) / 4), dim3(256), 0, s, W, ld, np,
+                           v, T, vs, out);
+    else
+        hipLaunchKernelGGL(mo_trmv_upper_kernel<32>, dim3((np + 3) / 4), dim3(256), 0, s, W, ld,
+                           np, v, T, vs, out);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// scalars of lZ = sum_t lZ_t: [sum_t a_t.a_t | sum log R_ii (once) | sum_t sum_i alpha_it |
+// status word]; the sums over t run inside the sum over i, in the order t = 0 .. T-1
+__global__ __launch_bounds__(1024) void mo_lz_terms_kernel(const double *__restrict__ R, int ld,
+                                                           int n, const double *__restrict__ a,
+                                                           const double *__restrict__ alpha, int T,
+                                                           long long vs,
+                                                           double *__restrict__ scalars,
+                                                           const int *__restrict__ info)
+{
+    __shared__ double red[3][16];
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int i = threadIdx.x; i < n; i += 1024) {
+        for (int t = 0; t < T; ++t) {
+            const double ai = a[t * vs + i];
+            s0 += ai * ai;
+            if (alpha) s2 += alpha[t * vs + i];
+        }
+        s1 += log(R[(size_t)i * ld + i]);
+    }
+    s0 = wave_sum64(s0);
+    s1 = wave_sum64(s1);
+    s2 = wave_sum64(s2);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) {
+        red[0][wave] = s0;
+        red[1][wave] = s1;
+        red[2][wave] = s2;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        double t = 0.0;
+        for (int wv = 0; wv < 16; ++wv) t += red[threadIdx.x][wv];
+        scalars[threadIdx.x] = t;
+    }
+    if (threadIdx.x == 3 && info) scalars[3] = (double)info[0];
+}
+
+int gpx_mo_lz_terms(hipStream_t s, const double *R, int ld, int n, const double *a,
+                    const double *alpha, int T, long long vs, double *scalars, const int *info)
+{
+    hipLaunchKernelGGL(mo_lz_terms_kernel, dim3(1), dim3(1024), 0, s, R, ld, n, a, alpha, T, vs,
+                       scalars, info);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// posterior reductions for T outputs: V (np x m, the solve of the shared cross-covariance) is
+// read once; part[chunk][k][j], k < T: sum_i V[i][j] a_t[i], k == T: sum_i V[i][j]^2
+template <int TB>
+__global__ __launch_bounds__(256) void mo_posterior_partial_kernel(
+    const double *__restrict__ V, int ldv, int np, int m, const double *__restrict__ a, int T,
+    long long vs, double *__restrict__ part)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    const int chunk = blockIdx.y;
+    const int rows = (np + (int)gridDim.y - 1) / (int)gridDim.y;
+    const int i0 = chunk * rows, i1 = min(np, i0 + rows);
+    if (j >= m) return;
+    double smu[TB], ssq = 0.0;
+#pragma unroll
+    for (int t = 0; t < TB; ++t) smu[t] = 0.0;
+    for (int i = i0; i < i1; ++i) {
+        const double v = V[(size_t)i * ldv + j];
+#pragma unroll
+        for (int t = 0; t < TB; ++t)
+            if (t < T) smu[t] = fma(v, a[t * vs + i], smu[t]);
+        ssq += v * v;
+    }
+    double *p = part + (size_t)chunk * (T + 1) * m + j;
+#pragma unroll
+    for (int t = 0; t < TB; ++t)
+        if (t < T) p[(size_t)t * m] = smu[t];
+    p[(size_t)T * m] = ssq;
+}
+
+// blockIdx.y = k: mu[k][j] = mean + sum of the chunks (k < T), s2[j] = prior - ... (k == T)
+__global__ __launch_bounds__(256) void mo_posterior_final_kernel(const double *__restrict__ part,
+                                                                 int m, int chunks, int T,
+                                                                 double mean, double prior,
+                                                                 double *__restrict__ mu,
+                                                                 double *__restrict__ s2)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
+    if (j >= m) return;
+    double acc = 0.0;
+    for (int c = 0; c < chunks; ++c) acc += part[((size_t)c * (T + 1) + k) * m + j];
+    if (k < T) mu[(size_t)k * m + j] = mean + acc;
+    else s2[j] = prior - acc;
+}
+
+size_t gpx_mo_posterior_scratch(int m) { return (size_t)(GPX_MO_TMAX + 1) * PR_CHUNKS * m; }
+
+int gpx_mo_posterior_reduce(hipStream_t s, const double *V, int ldv, int np, int m,
+                            const double *a, int T, long long vs, double mean, double prior,
+                            double *part, double *mu, double *s2)
+{
+    if (T < 1 || T > GPX_MO_TMAX) {
+        gpx_set_error("gpx_mo_posterior_reduce: bad arguments (T = %d)", T);
+        return -1;
+    }
+    const int chunks = std::min(PR_CHUNKS, std::max(16, np / 64));
+    const dim3 grid((m + 255) / 256, chunks);
+    if (T <= 8)
+        hipLaunchKernelGGL(mo_posterior_partial_kernel<8>, grid, dim3(256), 0, s, V, ldv, np, m, a,
+                           T, vs, part);
+    else
+        hipLaunchKernelGGL(mo_posterior_partial_kernel<32>, grid, dim3(256), 0, s, V, ldv, np, m,
+                           a, T, vs, part);
+    hipLaunchKernelGGL(mo_posterior_final_kernel, dim3((m + 255) / 256, T + 1), dim3(256), 0, s,
+                       part, m, chunks, T, mean, prior, mu, s2);
     GPX_HIP(hipGetLastError());
     return 0;
 }

@@ -48,6 +48,10 @@ class HyperEnsemble(object):
             # ... on (X, y) alone: the gradient observations would be left out
             raise TypeError('HyperEnsemble runs GPs on function values only; this %s holds '
                             'gradient observations' % type(model).__name__)
+        if getattr(model, 'nout', 0) > 0:
+            # ... with one observation vector: the batch entries know nothing of Y's columns
+            raise TypeError('HyperEnsemble runs GPs with one output only; this %s holds %d'
+                            % (type(model).__name__, model.nout))
         self._model = model.copy()
         self._hypers = np.array(hypers, dtype=float, ndmin=2)
         if self._hypers.shape[1] != self._model.nhyper:
