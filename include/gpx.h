@@ -389,10 +389,30 @@ const char *gpx_timing_name(int i);
 
 /* ---- dense building blocks (exposed for tests and micro-benchmarks) ------ */
 /* C = alpha * op(A) * op(B) + beta * C on host row-major matrices; M, N, K are
- * padded internally. ta/tb: 0 = as stored, 1 = transposed. */
+ * padded internally. ta/tb: 0 = as stored, 1 = transposed. alpha == 0 with
+ * beta != 0 is refused (the engine applies beta as beta / alpha). */
 int gpx_la_gemm(gpx_t *h, int ta, int tb, int64_t M, int64_t N, int64_t K,
                 double alpha, const double *A, int64_t lda, const double *B,
                 int64_t ldb, double beta, double *C, int64_t ldc);
+/* One call of the tile engine with every field of its argument block given by the
+ * caller (tests of the engine's structured and batched modes). No padding and no
+ * layout work: the host buffers A, B, C and C2 (nA, nB, nC, nC2 doubles; C2 may be
+ * NULL with nC2 = 0) are uploaded verbatim, the operands start off* elements into
+ * them, and C and C2 come back whole. Every address the launch can read or write
+ * is checked against the buffers on the host first; the GP state of the handle is
+ * cleared. Fields as in GemmArgs (pygp_amd/csrc/gpx_internal.h). */
+typedef struct gpx_gemm_ex_args {
+    int64_t ta, tb, M, N, K, lda, ldb, ldc;
+    double alpha, beta;
+    int64_t flags, tile, waves, order, swizzle, use_lists, kshift, beta0_from;
+    int64_t batch, strideA, strideB, strideC, strideC2;
+    int64_t kchunk, nsplit, mstrideA, mstrideB, mstrideC;
+    int64_t offA, offB, offC, offC2;
+    int64_t b_is_c;     /* 1: op(B) is read from the C buffer at offB (B, nB unused) */
+} gpx_gemm_ex_args;
+int gpx_la_gemm_ex(gpx_t *h, const gpx_gemm_ex_args *a, const double *A, int64_t nA,
+                   const double *B, int64_t nB, double *C, int64_t nC, double *C2,
+                   int64_t nC2);
 /* in: symmetric A (n*n, upper triangle used); out: R (upper, R^T R = A),
  * optionally Rinv (upper) and Ainv (symmetric, full) -- any may be NULL. */
 int gpx_la_potrf(gpx_t *h, const double *A, int64_t n, double *R, double *Rinv,

@@ -52,6 +52,18 @@ _i64 = C.c_int64
 GPX_FITC, GPX_DTC, GPX_VFE = 1, 2, 3          # enum gpx_sparse_method
 GPX_SPARSE_MAX_P = 4096
 
+
+class _GemmExArgs(C.Structure):
+    """gpx_gemm_ex_args of include/gpx.h."""
+    _INTS1 = ('ta', 'tb', 'M', 'N', 'K', 'lda', 'ldb', 'ldc')
+    _INTS2 = ('flags', 'tile', 'waves', 'order', 'swizzle', 'use_lists', 'kshift', 'beta0_from',
+              'batch', 'strideA', 'strideB', 'strideC', 'strideC2',
+              'kchunk', 'nsplit', 'mstrideA', 'mstrideB', 'mstrideC',
+              'offA', 'offB', 'offC', 'offC2', 'b_is_c')
+    _fields_ = ([(n, _i64) for n in _INTS1] + [('alpha', C.c_double), ('beta', C.c_double)] +
+                [(n, _i64) for n in _INTS2])
+
+
 SIGNATURES = {
     'gpx_version': (C.c_int, []),
     'gpx_last_error': (C.c_char_p, []),
@@ -133,6 +145,7 @@ SIGNATURES = {
     'gpx_multi_enable_timing': (C.c_int, [C.c_int, C.c_int]),
     'gpx_multi_batch_info': (C.c_int, [C.c_int, _i64, C.c_int, _dp, C.POINTER(_i64), _ip]),
     'gpx_panel_grid_check': (C.c_int, [C.c_int, C.c_int, _ip, _ip]),
+    'gpx_la_gemm_ex': (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]),
     'gpx_la_potrf': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _ip]),
     'gpx_la_gemm_bench': (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, _dp]),
     'gpx_la_gemm_bench_ex': (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, C.c_int,
@@ -706,6 +719,26 @@ class Handle(object):
                                   _ptr(A), A.shape[1], _ptr(B), B.shape[1], beta,
                                   _ptr(out), N))
         return out
+
+    def la_gemm_ex(self, A, B, Cin, C2=None, **args):
+        """One call of the tile engine with every GemmArgs field given (gpx_la_gemm_ex): the
+        flat float64 buffers A, B, Cin and C2 go to the device verbatim, `args` are the fields
+        of gpx_gemm_ex_args (unnamed ones: use_lists = 1, beta0_from = -1, batch = 1, alpha =
+        1, the rest 0). B is None with b_is_c = 1. Returns the whole C and C2 buffers."""
+        a = _GemmExArgs(use_lists=1, beta0_from=-1, batch=1, alpha=1.0)
+        names = {n for n, _ in _GemmExArgs._fields_}
+        for k, v in args.items():
+            if k not in names:
+                raise TypeError('la_gemm_ex: unknown field %r' % k)
+            setattr(a, k, float(v) if k in ('alpha', 'beta') else int(v))
+        A = _f64(A, 1)
+        B = None if B is None else _f64(B, 1)
+        out = _f64(Cin, 1).copy()
+        out2 = None if C2 is None else _f64(C2, 1).copy()
+        check(self._L.gpx_la_gemm_ex(self._h, C.byref(a), _ptr(A), A.size,
+                                     _ptr(B), 0 if B is None else B.size, _ptr(out), out.size,
+                                     _ptr(out2), 0 if out2 is None else out2.size))
+        return out, out2
 
     def la_potrf(self, A, inverse=False):
         A = _f64(A, 2)

@@ -538,12 +538,26 @@ int gpx_test_jitter(hipStream_t s)
 int gpx_gemm(hipStream_t s, int ta, int tb, const GemmArgs &g)
 {
     if (g.M <= 0 || g.N <= 0) return 0;
-    GPX_TRY(gpx_test_jitter(s));
     if (g.M % GPX_TILE || g.N % GPX_TILE || g.K % (2 * BK) || g.lda % 2 || g.ldb % 2) {
         gpx_set_error("gpx_gemm: unpadded operands M=%d N=%d K=%d lda=%d ldb=%d", g.M,
                       g.N, g.K, g.lda, g.ldb);
         return -1;
     }
+    // beta enters as beta / alpha on the initial accumulator (see the kernel)
+    if (g.alpha == 0.0 && g.beta != 0.0) {
+        gpx_set_error("gpx_gemm: alpha == 0 with beta = %g is not supported", g.beta);
+        return -1;
+    }
+    // every k-range must be a whole number of slice PAIRS: the kernels with two slices in
+    // flight have no tail and would add the last slice of an odd range twice (measured:
+    // kshift = 16 and kchunk = 48 return the product plus that slice)
+    if (((g.flags & (GEMM_KLO_M | GEMM_KLO_N)) && g.kshift % (2 * BK)) ||
+        (g.kchunk > 0 && g.kchunk % (2 * BK))) {
+        gpx_set_error("gpx_gemm: kshift=%d / kchunk=%d must be multiples of %d", g.kshift,
+                      g.kchunk, 2 * BK);
+        return -1;
+    }
+    GPX_TRY(gpx_test_jitter(s));
     LaunchCtx lc;
     GPX_HIP(hipGetDevice(&lc.device));
     lc.xcd_order = tile_order(lc.device);

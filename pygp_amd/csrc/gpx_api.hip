@@ -2431,6 +2431,113 @@ int gpx_la_gemm(gpx_t *h, int ta, int tb, int64_t M, int64_t N, int64_t K, doubl
     return 0;
 }
 
+// [lo, hi] element range one operand of a gpx_la_gemm_ex launch spans inside its buffer:
+// rows x cols at leading dimension ld from `off`, moved by zb * stride + zm * mstride for
+// every batch index the kernel forms (gemm_f64_kernel: z = member * nsplit + chunk)
+static bool gemm_ex_fits(const char *what, int64_t count, int64_t off, int64_t rows,
+                         int64_t cols, int64_t ld, const gpx_gemm_ex_args &a, int64_t stride,
+                         int64_t mstride)
+{
+    const int64_t span = (rows - 1) * ld + cols;
+    const int64_t nz = a.batch > 0 ? a.batch : 1;
+    const bool members = a.kchunk > 0 && a.nsplit > 0;
+    bool ok = off >= 0 && ld >= cols && stride >= 0 && mstride >= 0;
+    for (int64_t z = 0; ok && z < nz; ++z) {
+        const int64_t zm = members ? z / a.nsplit : 0, zb = z - zm * (members ? a.nsplit : 0);
+        const int64_t first = off + zb * stride + zm * mstride;
+        ok = first + span <= count;
+    }
+    if (!ok)
+        gpx_set_error("gpx_la_gemm_ex: %s (%lld x %lld, ld %lld, offset %lld, strides %lld / "
+                      "%lld, batch %lld) does not fit its buffer of %lld doubles", what,
+                      (long long)rows, (long long)cols, (long long)ld, (long long)off,
+                      (long long)stride, (long long)mstride, (long long)nz, (long long)count);
+    return ok;
+}
+
+int gpx_la_gemm_ex(gpx_t *h, const gpx_gemm_ex_args *a, const double *A, int64_t nA,
+                   const double *B, int64_t nB, double *C, int64_t nC, double *C2, int64_t nC2)
+{
+    CHECK_H(h);
+    const int64_t lim = (int64_t)1 << 28;           // doubles per buffer, and every count below
+    if (!a || !A || !C || nA < 1 || nC < 1 || nA > lim || nC > lim ||
+        (a->b_is_c ? 0 : (!B || nB < 1 || nB > lim)) || (C2 ? (nC2 < 1 || nC2 > lim) : nC2 != 0)) {
+        gpx_set_error("gpx_la_gemm_ex: bad buffers");
+        return -1;
+    }
+    const int64_t small[] = {a->M, a->N, a->K, a->lda, a->ldb, a->ldc, a->strideA, a->strideB,
+                             a->strideC, a->strideC2, a->mstrideA, a->mstrideB, a->mstrideC,
+                             a->offA, a->offB, a->offC, a->offC2};
+    bool ok = a->M >= 1 && a->N >= 1 && a->K >= 1 && a->lda >= 1 && a->ldb >= 1 && a->ldc >= 1 &&
+              a->batch >= 1 && a->batch <= 1024 && a->nsplit >= 0 && a->nsplit <= 1024 &&
+              a->kchunk >= 0 && a->kchunk <= lim && a->kshift >= -lim && a->kshift <= lim &&
+              a->beta0_from >= -1 && a->beta0_from <= lim &&
+              (a->tile == 0 || a->tile == 64 || a->tile == 128) &&
+              (a->waves == 0 || a->waves == 4 || a->waves == 8) && a->order >= 0 && a->order <= 3 &&
+              (a->swizzle == 0 || a->swizzle == 1) && (a->use_lists == 0 || a->use_lists == 1) &&
+              (a->ta == 0 || a->ta == 1) && (a->tb == 0 || a->tb == 1) && a->flags >= 0 &&
+              a->flags < 64;
+    for (int64_t v : small) ok = ok && v >= 0 && v <= lim;
+    if (!ok) {
+        gpx_set_error("gpx_la_gemm_ex: bad arguments");
+        return -1;
+    }
+    // the slice loaders read 16 bytes at a time
+    if ((a->offA | a->offB | a->strideA | a->strideB | a->mstrideA | a->mstrideB) & 1) {
+        gpx_set_error("gpx_la_gemm_ex: odd offset or stride of A or B");
+        return -1;
+    }
+    // stored shapes: A is (ta ? K x M : M x K), B is (tb ? N x K : K x N); the engine may
+    // read any of it and write any of C (the structure flags only take away)
+    if (!gemm_ex_fits("A", nA, a->offA, a->ta ? a->K : a->M, a->ta ? a->M : a->K, a->lda, *a,
+                      a->strideA, a->mstrideA) ||
+        !gemm_ex_fits("B", a->b_is_c ? nC : nB, a->offB, a->tb ? a->N : a->K,
+                      a->tb ? a->K : a->N, a->ldb, *a, a->strideB, a->mstrideB) ||
+        !gemm_ex_fits("C", nC, a->offC, a->M, a->N, a->ldc, *a, a->strideC, a->mstrideC) ||
+        (C2 && !gemm_ex_fits("C2", nC2, a->offC2, a->M, a->N, a->ldc, *a, a->strideC2, 0)))
+        return -1;
+    h->have_factor = h->have_inverse = false;
+    h->n = 0;                                   // the GP state is gone
+    h->bench_n = 0;
+    GPX_TRY(h->t0.reserve((size_t)nA * 8));
+    if (!a->b_is_c) GPX_TRY(h->t1.reserve((size_t)nB * 8));
+    GPX_TRY(h->t2.reserve((size_t)nC * 8));
+    if (C2) GPX_TRY(h->split.reserve((size_t)nC2 * 8));
+    GPX_HIP(hipMemcpyAsync(h->t0.p, A, (size_t)nA * 8, hipMemcpyHostToDevice, h->stream));
+    if (!a->b_is_c)
+        GPX_HIP(hipMemcpyAsync(h->t1.p, B, (size_t)nB * 8, hipMemcpyHostToDevice, h->stream));
+    GPX_HIP(hipMemcpyAsync(h->t2.p, C, (size_t)nC * 8, hipMemcpyHostToDevice, h->stream));
+    if (C2)
+        GPX_HIP(hipMemcpyAsync(h->split.p, C2, (size_t)nC2 * 8, hipMemcpyHostToDevice, h->stream));
+    GemmArgs g;
+    g.A = h->t0.d() + a->offA;
+    g.B = (a->b_is_c ? h->t2.d() : h->t1.d()) + a->offB;
+    g.C = h->t2.d() + a->offC;
+    g.C2 = C2 ? h->split.d() + a->offC2 : nullptr;
+    g.lda = (int)a->lda; g.ldb = (int)a->ldb; g.ldc = (int)a->ldc;
+    g.M = (int)a->M; g.N = (int)a->N; g.K = (int)a->K;
+    g.alpha = a->alpha; g.beta = a->beta;
+    g.strideA = a->strideA; g.strideB = a->strideB; g.strideC = a->strideC;
+    g.strideC2 = a->strideC2;
+    g.batch = (int)a->batch;
+    g.flags = (int)a->flags;
+    g.tile = (int)a->tile; g.order = (int)a->order; g.swizzle = (int)a->swizzle;
+    g.waves = (int)a->waves; g.use_lists = (int)a->use_lists;
+    g.kshift = (int)a->kshift; g.beta0_from = (int)a->beta0_from;
+    g.kchunk = (int)a->kchunk; g.nsplit = (int)a->nsplit;
+    g.mstrideA = a->mstrideA; g.mstrideB = a->mstrideB; g.mstrideC = a->mstrideC;
+    const int rc = gpx_gemm(h->stream, (int)a->ta, (int)a->tb, g);
+    if (rc < 0) {                               // refused: the uploads still read the host buffers
+        (void)hipStreamSynchronize(h->stream);
+        return rc;
+    }
+    GPX_HIP(hipMemcpyAsync(C, h->t2.p, (size_t)nC * 8, hipMemcpyDeviceToHost, h->stream));
+    if (C2)
+        GPX_HIP(hipMemcpyAsync(C2, h->split.p, (size_t)nC2 * 8, hipMemcpyDeviceToHost, h->stream));
+    GPX_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
 __global__ void pad_identity_kernel(double *__restrict__ A, int ld, int np, int n)
 {
     const int j = blockIdx.x * 256 + threadIdx.x;

@@ -137,7 +137,7 @@ struct GemmArgs {
     double *C = nullptr;
     int lda = 0, ldb = 0, ldc = 0;
     int M = 0, N = 0, K = 0;   // multiples of GPX_TILE (K: multiple of GPX_BK)
-    double alpha = 1.0, beta = 0.0;
+    double alpha = 1.0, beta = 0.0;   // alpha == 0 with beta != 0 is refused (beta / alpha)
     long long strideA = 0, strideB = 0, strideC = 0;   // batch strides (elements)
     int batch = 1;
     int flags = 0;
@@ -154,7 +154,8 @@ struct GemmArgs {
                            // are read and written at C2 (same ldc) instead of C
     int kshift = 0;        // GEMM_KLO_*: the zero structure starts kshift columns in,
                            // op(A)[m][k] == 0 for k < m0 - kshift (a block column of a
-                           // triangular matrix whose diagonal block sits kshift rows down)
+                           // triangular matrix whose diagonal block sits kshift rows down);
+                           // a multiple of 32, as kchunk: k-ranges are whole slice pairs
     int beta0_from = -1;   // >= 0: tiles with n0 >= beta0_from take beta = 0 (a new block
                            // column of an accumulated matrix)
     int overlap = 0;       // 1: launches of other streams run beside this one (look-ahead):

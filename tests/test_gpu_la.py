@@ -20,7 +20,8 @@ def dev():
 @pytest.mark.parametrize('ta', [False, True])
 @pytest.mark.parametrize('tb', [False, True])
 @pytest.mark.parametrize('shape', [(16, 16, 4), (200, 150, 70), (256, 384, 128),
-                                   (129, 257, 513)])
+                                   (129, 257, 513),
+                                   (2560, 2560, 40)])     # 400 tiles of 128: the 128-tile kernel
 def test_gemm(dev, ta, tb, shape):
     M, N, K = shape
     rng = np.random.RandomState(M + 3 * N + 7 * K)
