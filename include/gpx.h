@@ -119,6 +119,11 @@ int gpx_kernel_gradx(gpx_t *h, const gpx_kspec *k, const double *X1, int64_t n1,
  * coincident points give the limit. A Matern-1/2 part has no derivative at r = 0: < 0. */
 int gpx_kernel_gradxy(gpx_t *h, const gpx_kspec *k, const double *X1, int64_t n1,
                       const double *X2, int64_t n2, int64_t d, double *out);
+/* out[n][nv] = K(X, X) V for V[n][nv], 1 <= nv <= 4 columns, without storing K (own design):
+ * N^2 kernel values against N nv doubles of traffic, sums in a fixed order. d <= GPX_MAX_DIM,
+ * n <= 2^20. Does not touch the data or a factorisation of the handle. */
+int gpx_kernel_matvec(gpx_t *h, const gpx_kspec *k, const double *X, int64_t n, int64_t d,
+                      const double *V, int64_t nv, double *out);
 /* device-resident variant of gpx_kernel_get for benchmarking the build alone:
  * X1 is taken from the handle's resident data (gpx_set_data), the result stays
  * in HBM; returns the kernel time in ms through *ms. */
@@ -231,6 +236,44 @@ int gpx_mo_loglik(gpx_t *h, double *lZ, double *dlZ);
 int gpx_mo_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2);
 /* mu as above and the full covariance Sigma[m][m] the outputs share; 1 <= m <= 8192. */
 int gpx_mo_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma);
+/* ---- binary classification by Laplace's approximation (own design; GPML algorithms 3.1, 3.2,
+ * 5.1 with a constant mean) ----
+ * Labels y in {-1, +1} at X under a Logistic or Probit likelihood; the latent is f = mean + K a.
+ * gpx_laplace_update finds the mode by Newton's method: every step builds B = I + sW K sW^T
+ * (sW = sqrt W, W = -d2 log p / d f2) in the workspace of the exact path, factorises it with the
+ * code of gpx_exact_update and multiplies by K without storing it (the product of
+ * gpx_kernel_matvec). A step that lowers Psi(a) = -a.(f - mean) / 2 + sum log p(y | f) by more
+ * than 1e-10 (1 + |Psi|), the rounding of the sums, is halved, at most 10 times; the iteration stops when max |f_new - f_old| <= tol (1 + max |f_new|) and
+ * fails (< 0) after max_iter steps. At the mode the terms are recomputed and B factorised once
+ * more: lZ = Psi - sum log R_ii.
+ * Upload: replaces whatever data the handle held; labels other than -1 / +1 are refused,
+ * d <= GPX_MAX_DIM, n <= 65536. While a handle holds labels every entry that
+ * gpx_gradobs_set_data's comment lists and every gpx_gradobs_* / gpx_mo_* entry but their
+ * set_data returns < 0 with an error text and touches nothing; gpx_set_data (and those two)
+ * return it to the other families. The gpx_laplace_* entries refuse a handle in another state. */
+enum gpx_likelihood { GPX_LIK_LOGISTIC = 1, GPX_LIK_PROBIT = 2 };
+int gpx_laplace_set_data(gpx_t *h, const double *X, int64_t n, int64_t d, const double *y);
+/* warm != 0: start from the mode the handle holds for the same data (a result that depends on
+ * the calls before it, to rounding), else from f = mean: the same call gives the same bits.
+ * *iters: Newton steps taken; *info as gpx_exact_update (B is never singular in exact
+ * arithmetic). After a failure the handle has no mode: its other calls fail until the next
+ * successful update. */
+int gpx_laplace_update(gpx_t *h, const gpx_kspec *k, int lik, double mean, double tol,
+                       int max_iter, int warm, int *iters, int *info);
+/* lZ of the last update; dlZ (may be NULL) [nhyper_kernel + 1] in order [kernel..., mean]:
+ * completes R^-1 and B^-1 as gpx_exact_loglik does, turns B^-1 into the pair weight of the
+ * implicit and explicit terms and runs the exact path's trace pass over it. */
+int gpx_laplace_loglik(gpx_t *h, double *lZ, double *dlZ);
+/* latent predictive mean mu[m] = mean + k*^T g and variance s2[m] = k** - |R^-T (sW o k*)|^2 */
+int gpx_laplace_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2);
+/* mu[m] and the full latent covariance Sigma[m][m]; 1 <= m <= 8192 */
+int gpx_laplace_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma);
+/* the mode f[n] and g[n] = d log p / d f there (f - mean = K g); either may be NULL */
+int gpx_laplace_get_mode(gpx_t *h, int64_t n, double *f, double *g);
+/* HIP-event ms of the last gpx_laplace_update: ms[0] the whole update, ms[1..4] of its FIRST
+ * Newton step the build + scaling, the factorisation (with the rest of R^-1), the two products
+ * with K, and the solves and vector work between them (needs gpx_enable_timing) */
+int gpx_laplace_timings(gpx_t *h, double *ms);
 /* host copies of gp._R (n*n row-major upper, zero below the diagonal) and gp._a;
  * either may be NULL. n: the point count the caller sized R and a for; the call
  * fails when it is not the factor's. */

@@ -98,6 +98,15 @@ SIGNATURES = {
     'gpx_gradobs_loglik': (C.c_int, [_vp, _dp]),
     'gpx_gradobs_posterior': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     'gpx_gradobs_posterior_full': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    'gpx_kernel_matvec': (C.c_int, [_vp, C.POINTER(_KSpec), _vp, _i64, _i64, _vp, _i64, _vp]),
+    'gpx_laplace_set_data': (C.c_int, [_vp, _vp, _i64, _i64, _vp]),
+    'gpx_laplace_update': (C.c_int, [_vp, C.POINTER(_KSpec), C.c_int, C.c_double, C.c_double,
+                                     C.c_int, C.c_int, _ip, _ip]),
+    'gpx_laplace_loglik': (C.c_int, [_vp, _dp, _vp]),
+    'gpx_laplace_posterior': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    'gpx_laplace_posterior_full': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    'gpx_laplace_get_mode': (C.c_int, [_vp, _i64, _vp, _vp]),
+    'gpx_laplace_timings': (C.c_int, [_vp, _vp]),
     'gpx_mo_set_data': (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64]),
     'gpx_mo_update': (C.c_int, [_vp, C.POINTER(_KSpec), C.c_double, C.c_double, _ip]),
     'gpx_mo_loglik': (C.c_int, [_vp, _dp, _vp]),
@@ -352,6 +361,19 @@ class Handle(object):
                                       n2, d, _ptr(out)))
         return out
 
+    def kernel_matvec(self, spec, X, V):
+        """K(X, X) V for V (n,) or (n, nv <= 4), without storing K."""
+        X, V = _f64(X, 2), _f64(V)
+        flat = V.ndim == 1
+        V2 = np.ascontiguousarray(V.reshape(len(V), -1))
+        if V2.ndim != 2 or V2.shape[0] != X.shape[0] or not 1 <= V2.shape[1] <= 4:
+            raise ValueError('V must have a row per point and one to four columns')
+        out = np.empty_like(V2)
+        if out.size:
+            check(self._L.gpx_kernel_matvec(self._h, spec.ref(), _ptr(X), X.shape[0], X.shape[1],
+                                            _ptr(V2), V2.shape[1], _ptr(out)))
+        return out[:, 0] if flat else out
+
     def kernel_build_resident(self, spec, dtype=np.float64, reps=5):
         ms = C.c_double(0)
         dt = F32 if np.dtype(dtype) == np.float32 else F64
@@ -464,6 +486,56 @@ class Handle(object):
         mu, Sigma = np.empty(m), np.empty((m, m))
         check(self._L.gpx_gradobs_posterior_full(self._h, _ptr(Xs), m, _ptr(mu), _ptr(Sigma)))
         return mu, Sigma
+
+    # -- binary classification by Laplace's approximation (LaplaceGP) --
+    def laplace_set_data(self, X, y):
+        """Labels y in {-1, +1} at X."""
+        X, y = _f64(X, 2), _f64(y, 1)
+        if X.shape[0] != y.shape[0]:
+            raise ValueError('X and y disagree')
+        check(self._L.gpx_laplace_set_data(self._h, _ptr(X), X.shape[0], X.shape[1], _ptr(y)))
+
+    def laplace_update(self, spec, lik, mean, tol=1e-8, max_iter=50, warm=False):
+        """Newton's method to the mode; returns the number of steps."""
+        iters, info = C.c_int(0), C.c_int(0)
+        check(self._L.gpx_laplace_update(self._h, spec.ref(), int(lik), float(mean), float(tol),
+                                         int(max_iter), int(bool(warm)), C.byref(iters),
+                                         C.byref(info)))
+        return iters.value
+
+    def laplace_loglik(self, nhyper_kernel, grad=False):
+        lZ = C.c_double(0)
+        dlZ = np.empty(nhyper_kernel + 1) if grad else None
+        check(self._L.gpx_laplace_loglik(self._h, C.byref(lZ), _ptr(dlZ)))
+        return (lZ.value, dlZ) if grad else lZ.value
+
+    def laplace_posterior(self, Xs):
+        Xs = _f64(Xs, 2)
+        m = Xs.shape[0]
+        mu, s2 = np.empty(m), np.empty(m)
+        check(self._L.gpx_laplace_posterior(self._h, _ptr(Xs), m, _ptr(mu), _ptr(s2)))
+        return mu, s2
+
+    def laplace_posterior_full(self, Xs):
+        Xs = _f64(Xs, 2)
+        m = Xs.shape[0]
+        mu, Sigma = np.empty(m), np.empty((m, m))
+        check(self._L.gpx_laplace_posterior_full(self._h, _ptr(Xs), m, _ptr(mu), _ptr(Sigma)))
+        return mu, Sigma
+
+    def laplace_get_mode(self, n):
+        """(f, g): the mode and the gradient of log p(y | f) there."""
+        f, g = np.empty(n), np.empty(n)
+        check(self._L.gpx_laplace_get_mode(self._h, n, _ptr(f), _ptr(g)))
+        return f, g
+
+    def laplace_timings(self):
+        """HIP-event ms of the last laplace_update (enable_timing): the whole update, then of
+        its first Newton step the build + scaling, the factorisation, the two products with K
+        and the solves."""
+        ms = np.zeros(5)
+        check(self._L.gpx_laplace_timings(self._h, _ptr(ms)))
+        return dict(zip(('update', 'build_scale', 'factor', 'matvec', 'solve'), ms))
 
     # -- T outputs at the same inputs (MultiOutputGP) --
     def mo_set_data(self, X, Y):

@@ -55,6 +55,19 @@ struct gpx_ctx {
     // plain data on X. Handled like the state above: the plain and the gradobs entries refuse
     // the handle, gpx_set_data / gpx_gradobs_set_data return it to them.
     int mo_T = 0;
+    // binary labels under a Logistic / Probit likelihood (gpx_laplace_set_data): y holds the n
+    // labels, the factorisation below is that of B = I + sW K sW^T at the mode, lp_vec the vectors
+    // of the Newton iteration (LV_* in the Laplace section, cap doubles each). Handled like the two
+    // states above: the plain, gradobs and multi-output entries refuse the handle, their set_data
+    // calls return it to them.
+    bool laplace = false;
+    int lp_lik = 0;
+    bool lp_mode = false;          // lp_vec holds a converged mode for the resident data
+    int lp_iters = 0;
+    DevBuf lp_vec, lp_kmv, lp_sc, lp_mu;
+    std::vector<double> lp_dlz;    // the gradient of the last update, once computed
+    hipEvent_t lp_ev[8] = {};
+    double lp_ms[5] = {};
     // factorisation state
     DevBuf A, W, Kinv, r, a, alpha, scalars, partial, info, gv_part, pctl;
     double *acc = nullptr;         // the trace accumulators: a view of scalars
@@ -167,6 +180,11 @@ static int ld_for(int np)
         if ((h)->mo_T) {                                                       \
             gpx_set_error(what ": the handle holds multi-output data "         \
                                "(gpx_mo_*); gpx_set_data returns it to plain data"); \
+            return -1;                                                         \
+        }                                                                      \
+        if ((h)->laplace) {                                                    \
+            gpx_set_error(what ": the handle holds classification labels "     \
+                               "(gpx_laplace_*); gpx_set_data returns it to plain data"); \
             return -1;                                                         \
         }                                                                      \
     } while (0)
@@ -522,11 +540,14 @@ int gpx_destroy(gpx_t *h)
     DevBuf *bufs[] = {&h->X, &h->y, &h->Xf32, &h->A, &h->W, &h->Kinv, &h->r, &h->a,
                       &h->alpha, &h->scalars, &h->partial, &h->info, &h->gv_part, &h->pctl, &h->Ks, &h->KsT, &h->Vc,
                       &h->Xs, &h->mu, &h->s2, &h->post_part, &h->t0, &h->t1, &h->t2, &h->split, &h->gpart,
-                      &h->loo_S, &h->loo_M, &h->loo_vec, &h->loo_out};
+                      &h->loo_S, &h->loo_M, &h->loo_vec, &h->loo_out, &h->lp_vec, &h->lp_kmv,
+                      &h->lp_sc, &h->lp_mu};
     for (DevBuf *b : bufs) b->release();
     DLOG("events");
     for (int i = 0; i <= GPX_NTIMERS; ++i)
         if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
+    for (hipEvent_t e : h->lp_ev)
+        if (e) (void)hipEventDestroy(e);
     DLOG("host buffers");
     if (h->hres) (void)hipHostFree(h->hres);
     if (h->hinfo) (void)hipHostFree(h->hinfo);
@@ -712,6 +733,39 @@ __global__ void f64_to_f32_kernel(const double *__restrict__ in, float *__restri
     if (i < n) out[i] = (float)in[i];
 }
 
+int gpx_kernel_matvec(gpx_t *h, const gpx_kspec *k, const double *X, int64_t n, int64_t d,
+                      const double *V, int64_t nv, double *out)
+{
+    CHECK_H(h);
+    if (!X || !V || !out || n < 1 || n > (1 << 20) || d < 1 || d > GPX_MAX_DIM || nv < 1 ||
+        nv > 4) {
+        gpx_set_error("gpx_kernel_matvec: bad arguments n=%lld d=%lld nv=%lld (d <= %d, 1 <= nv "
+                      "<= 4)", (long long)n, (long long)d, (long long)nv, GPX_MAX_DIM);
+        return -1;
+    }
+    KParams kp;
+    GPX_TRY(gpx_flatten_kspec(k, d, &kp));
+    // buffers of the call's own (the posterior's scratch): X, the columns of V, the columns of out
+    GPX_TRY(h->t0.reserve((size_t)n * d * 8));
+    GPX_TRY(h->t1.reserve((size_t)n * nv * 8));
+    GPX_TRY(h->t2.reserve((size_t)n * nv * 8));
+    GPX_TRY(h->lp_kmv.reserve(gpx_kmatvec_scratch((int)n) * 8));
+    std::vector<double> cols((size_t)n * nv);
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t c = 0; c < nv; ++c) cols[(size_t)c * n + i] = V[i * nv + c];
+    GPX_HIP(hipMemcpyAsync(h->t0.p, X, (size_t)n * d * 8, hipMemcpyHostToDevice, h->stream));
+    GPX_HIP(hipMemcpyAsync(h->t1.p, cols.data(), (size_t)n * nv * 8, hipMemcpyHostToDevice,
+                           h->stream));
+    GPX_TRY(gpx_kmatvec(h->stream, kp, h->t0.as<double>(), (int)n, (int)d, h->t1.as<double>(), n,
+                        (int)nv, 0.0, h->lp_kmv.as<double>(), h->t2.as<double>(), n));
+    GPX_HIP(hipMemcpyAsync(cols.data(), h->t2.p, (size_t)n * nv * 8, hipMemcpyDeviceToHost,
+                           h->stream));
+    GPX_HIP(hipStreamSynchronize(h->stream));
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t c = 0; c < nv; ++c) out[i * nv + c] = cols[(size_t)c * n + i];
+    return 0;
+}
+
 int gpx_kernel_build_resident(gpx_t *h, const gpx_kspec *k, int dtype, int reps,
                               double *ms)
 {
@@ -783,6 +837,7 @@ int gpx_set_data(gpx_t *h, const double *X, int64_t n, int64_t d, const double *
     h->gradobs = false;
     h->go_n = h->go_ng = 0;
     h->mo_T = 0;
+    h->laplace = h->lp_mode = false;
     return 0;
 }
 
@@ -1516,14 +1571,32 @@ static int build_cross(gpx_ctx *h, int mc, int mcp)
                               false, 0.0);
 }
 
+// the vectors of the Laplace state: cap doubles each in lp_vec
+enum { LV_A = 0, LV_F, LV_G, LV_W, LV_SW, LV_D3, LV_B, LV_T, LV_C, LV_X, LV_AN, LV_FN, LV_S2, LV_U,
+       LV_COUNT };
+static double *lpv(const gpx_ctx *h, int k) { return h->lp_vec.d() + (size_t)k * h->cap; }
+
+// a Laplace handle's posterior: the mean from the unscaled cross-covariance in h->Ks (np x mcp)
+// into lp_mu, then its rows times sW: the solve with the factor of B follows
+static int laplace_cross(gpx_ctx *h, int mcp)
+{
+    GPX_TRY(h->lp_mu.reserve((size_t)mcp * 8));
+    return gpx_laplace_cross(h->stream, h->Ks.as<double>(), mcp, h->n, mcp, lpv(h, LV_G),
+                             lpv(h, LV_SW), h->mean, h->lp_mu.as<double>());
+}
+
 // the state a handle is in, and the check that an entry of one family finds its own
-enum { ST_PLAIN = 0, ST_GRADOBS = 1, ST_MO = 2 };
-static int state_of(const gpx_ctx *h) { return h->mo_T ? ST_MO : (h->gradobs ? ST_GRADOBS : ST_PLAIN); }
+enum { ST_PLAIN = 0, ST_GRADOBS = 1, ST_MO = 2, ST_LAPLACE = 3 };
+static int state_of(const gpx_ctx *h)
+{
+    return h->laplace ? ST_LAPLACE : (h->mo_T ? ST_MO : (h->gradobs ? ST_GRADOBS : ST_PLAIN));
+}
 static int check_state(const gpx_ctx *h, int want, const char *what)
 {
-    static const char *holds[3] = {"plain data (gpx_set_data)",
+    static const char *holds[4] = {"plain data (gpx_set_data)",
                                    "gradient observations (gpx_gradobs_*)",
-                                   "multi-output data (gpx_mo_*)"};
+                                   "multi-output data (gpx_mo_*)",
+                                   "classification labels (gpx_laplace_*)"};
     const int st = state_of(h);
     if (st == want) return 0;
     gpx_set_error("%s: the handle holds %s%s", what, holds[st],
@@ -1539,6 +1612,7 @@ static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, dou
     CHECK_H(h);
     GPX_TRY(check_state(h, state, state == ST_MO ? "gpx_mo_posterior"
                                   : state == ST_GRADOBS ? "gpx_gradobs_posterior"
+                                  : state == ST_LAPLACE ? "gpx_laplace_posterior"
                                                         : "gpx_exact_posterior"));
     if (!h->have_factor) {
         gpx_set_error("gpx_exact_posterior: no factorisation (call gpx_exact_update)");
@@ -1582,6 +1656,7 @@ static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, dou
                                hipMemcpyHostToDevice, h->stream));
         // K(X, Xs): np x mcp, zero outside n x mc (exact.py:87)
         GPX_TRY(build_cross(h, mc, mcp));
+        if (h->laplace) GPX_TRY(laplace_cross(h, mcp));
         clk.tick(T_POST_BUILD);
         // RK = R^-T K (exact.py:88)
         double *V = h->KsT.as<double>();
@@ -1617,8 +1692,8 @@ static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, dou
             GPX_HIP(hipMemcpy2DAsync(mu + c0, (size_t)m * 8, h->mu.p, (size_t)mcp * 8,
                                      (size_t)mc * 8, h->mo_T, hipMemcpyDeviceToHost, h->stream));
         else
-            GPX_HIP(hipMemcpyAsync(mu + c0, h->mu.p, (size_t)mc * 8, hipMemcpyDeviceToHost,
-                                   h->stream));
+            GPX_HIP(hipMemcpyAsync(mu + c0, h->laplace ? h->lp_mu.p : h->mu.p, (size_t)mc * 8,
+                                   hipMemcpyDeviceToHost, h->stream));
         GPX_HIP(hipMemcpyAsync(s2 + c0, h->s2.p, (size_t)mc * 8, hipMemcpyDeviceToHost,
                                h->stream));
         GPX_HIP(hipStreamSynchronize(h->stream));
@@ -1636,6 +1711,7 @@ static int posterior_full_impl(gpx_t *h, const double *Xs, int64_t m, double *mu
     CHECK_H(h);
     GPX_TRY(check_state(h, state, state == ST_MO ? "gpx_mo_posterior_full"
                                   : state == ST_GRADOBS ? "gpx_gradobs_posterior_full"
+                                  : state == ST_LAPLACE ? "gpx_laplace_posterior_full"
                                                         : "gpx_exact_posterior_full"));
     if (!h->have_factor) {
         gpx_set_error("gpx_exact_posterior_full: no factorisation (call gpx_exact_update)");
@@ -1662,6 +1738,7 @@ static int posterior_full_impl(gpx_t *h, const double *Xs, int64_t m, double *mu
     GPX_HIP(hipMemcpyAsync(h->Xs.p, Xs, (size_t)mc * h->d * 8, hipMemcpyHostToDevice,
                            h->stream));
     GPX_TRY(build_cross(h, mc, mcp));
+    if (h->laplace) GPX_TRY(laplace_cross(h, mcp));
     double *V = h->KsT.as<double>();
     GPX_TRY(solve_rt_refined(h, h->Ks.as<double>(), V, mcp));
     if (h->mo_T)
@@ -1686,7 +1763,8 @@ static int posterior_full_impl(gpx_t *h, const double *Xs, int64_t m, double *mu
         GPX_HIP(hipMemcpy2DAsync(mu, (size_t)mc * 8, h->mu.p, (size_t)mcp * 8, (size_t)mc * 8,
                                  h->mo_T, hipMemcpyDeviceToHost, h->stream));
     else
-        GPX_HIP(hipMemcpyAsync(mu, h->mu.p, (size_t)mc * 8, hipMemcpyDeviceToHost, h->stream));
+        GPX_HIP(hipMemcpyAsync(mu, h->laplace ? h->lp_mu.p : h->mu.p, (size_t)mc * 8,
+                               hipMemcpyDeviceToHost, h->stream));
     GPX_HIP(hipMemcpy2DAsync(Sigma, (size_t)mc * 8, h->t2.p, (size_t)mcp * 8, (size_t)mc * 8, mc,
                              hipMemcpyDeviceToHost, h->stream));
     GPX_HIP(hipStreamSynchronize(h->stream));
@@ -1968,6 +2046,7 @@ int gpx_gradobs_set_data(gpx_t *h, const double *X, int64_t n, const double *y,
     h->have_factor = h->have_inverse = false;
     h->gradobs = false;
     h->mo_T = 0;
+    h->laplace = h->lp_mode = false;
     h->data_version++;
     if (n > 0) {
         GPX_HIP(hipMemcpyAsync(h->X.p, X, (size_t)n * d * 8, hipMemcpyHostToDevice, h->stream));
@@ -1993,7 +2072,10 @@ int gpx_gradobs_update(gpx_t *h, const gpx_kspec *k, double log_sn, double grad_
 {
     CHECK_H(h);
     if (!h->gradobs) {
-        gpx_set_error("gpx_gradobs_update: no gradient observations (gpx_gradobs_set_data)");
+        gpx_set_error(h->laplace ? "gpx_gradobs_update: the handle holds classification labels "
+                                   "(gpx_laplace_*)"
+                                 : "gpx_gradobs_update: no gradient observations "
+                                   "(gpx_gradobs_set_data)");
         return -1;
     }
     if (!std::isfinite(log_sn) || !std::isfinite(mean) || !std::isfinite(grad_noise) ||
@@ -2036,6 +2118,321 @@ int gpx_gradobs_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu
     return posterior_full_impl(h, Xs, m, mu, Sigma, ST_GRADOBS);
 }
 
+// ---- binary classification: Laplace's approximation (GPML algorithms 3.1, 3.2, 5.1) ------------
+int gpx_laplace_set_data(gpx_t *h, const double *X, int64_t n, int64_t d, const double *y)
+{
+    CHECK_H(h);
+    if (!X || !y || n < 1 || d < 1 || d > GPX_MAX_DIM || n > 65536) {
+        gpx_set_error("gpx_laplace_set_data: bad shape n=%lld d=%lld (d <= %d, n <= 65536)",
+                      (long long)n, (long long)d, GPX_MAX_DIM);
+        return -1;
+    }
+    for (int64_t i = 0; i < n; ++i)
+        if (!(y[i] == 1.0 || y[i] == -1.0)) {
+            gpx_set_error("gpx_laplace_set_data: label %lld is %g, not -1 or +1", (long long)i,
+                          y[i]);
+            return -1;
+        }
+    GPX_TRY(gpx_set_data(h, X, n, d, y));
+    h->laplace = true;
+    h->lp_mode = false;
+    return 0;
+}
+
+static int laplace_reserve(gpx_ctx *h)
+{
+    GPX_TRY(reserve_factor(h, true));
+    GPX_TRY(h->lp_vec.reserve((size_t)LV_COUNT * h->cap * 8));
+    GPX_TRY(h->lp_kmv.reserve(gpx_kmatvec_scratch(h->n) * 8));
+    GPX_TRY(h->lp_sc.reserve(16 * 8));
+    return 0;
+}
+
+// out = bias + K v on the resident X
+static int laplace_kv(gpx_ctx *h, const double *v, double bias, double *out)
+{
+    return gpx_kmatvec(h->stream, h->kp, h->X.as<double>(), h->n, h->d, v, 0, 1, bias,
+                       h->lp_kmv.as<double>(), out, 0);
+}
+
+// K -> B = I + sW K sW^T -> R (value-only factorisation, GPX_POTRF_R); complete: also the rest of
+// R^-1, which the solves of a Newton step multiply by; built: recorded behind the build
+static int laplace_factor(gpx_ctx *h, bool complete, hipEvent_t built = nullptr)
+{
+    DenseWs w = h->ws();
+    if (h->kinv_pending) {            // (as enqueue_update: a deferred update nobody joined)
+        DenseWs wj = w;
+        wj.defer_kinv = true;
+        GPX_TRY(gpx_potrf_join(h->stream, wj));
+        h->kinv_pending = false;
+    }
+    GPX_HIP(hipMemsetAsync(h->info.p, 0, sizeof(int), h->stream));
+    GPX_TRY(gpx_kbuild<double>(h->stream, h->kp, h->X.as<double>(), h->n, h->np,
+                               h->X.as<double>(), h->n, h->np, h->d, w.A, h->ld, true, true, 0.0,
+                               w.Kinv));
+    GPX_TRY(gpx_laplace_scale(h->stream, w.A, w.Kinv, h->ld, h->n, lpv(h, LV_SW)));
+    if (built) GPX_HIP(hipEventRecord(built, h->stream));
+    w.whole = gpx_potrf_whole(w, GPX_POTRF_R);
+    GPX_TRY(gpx_potrf(h->stream, w, GPX_POTRF_R, true));
+    h->w_complete = GpxBlocks(h->np).count == 1;
+    h->kinv_ready = false;
+    h->lz_enqueued = false;
+    h->posterior_calls = 0;
+    if (complete && !h->w_complete) {
+        GPX_TRY(gpx_trtri(h->stream, w));
+        h->w_complete = true;
+    }
+    return 0;
+}
+
+// x = B^-1 t = R^-1 R^-T t; t is destroyed
+static int laplace_solve(gpx_ctx *h, double *t, double *x)
+{
+    const DenseWs w = h->ws();
+    GPX_TRY(gpx_trsv_rt(h->stream, w, true, t, lpv(h, LV_C), h->gv_part.as<double>()));
+    return gpx_trmv_upper(h->stream, w.W, h->ld, h->np, lpv(h, LV_C), x);
+}
+
+// the three doubles of gpx_laplace_psi and the factorisation's status word; one host sync
+static int laplace_read(gpx_ctx *h, const double *a, const double *f, const double *f_old,
+                        bool with_info)
+{
+    GPX_TRY(gpx_laplace_psi(h->stream, h->lp_lik, h->y.as<double>(), a, f, f_old, h->mean, h->n,
+                            h->lp_sc.as<double>()));
+    GPX_HIP(hipMemcpyAsync(h->hres, h->lp_sc.p, 3 * sizeof(double), hipMemcpyDeviceToHost,
+                           h->stream));
+    if (with_info)
+        GPX_HIP(hipMemcpyAsync(h->hinfo, h->info.p, sizeof(int), hipMemcpyDeviceToHost,
+                               h->stream));
+    GPX_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+static int laplace_status(gpx_ctx *h, int inf, int *info)
+{
+    if (info) *info = inf;
+    if (inf < 0) {
+        gpx_set_error("internal: the panel kernel timed out waiting for a dependency");
+        return -1;
+    }
+    if (inf > 0 && inf <= h->n) {
+        gpx_set_error("matrix is not positive definite: pivot %d", inf);
+        return inf;
+    }
+    if (info) *info = 0;
+    return 0;
+}
+
+int gpx_laplace_update(gpx_t *h, const gpx_kspec *k, int lik, double mean, double tol,
+                       int max_iter, int warm, int *iters, int *info)
+{
+    CHECK_H(h);
+    GPX_TRY(check_state(h, ST_LAPLACE, "gpx_laplace_update"));
+    if ((lik != GPX_LIK_LOGISTIC && lik != GPX_LIK_PROBIT) || !std::isfinite(mean) ||
+        !(tol > 0) || !std::isfinite(tol) || max_iter < 1) {
+        gpx_set_error("gpx_laplace_update: bad arguments (a likelihood of gpx_likelihood, a finite "
+                      "mean, tol > 0, max_iter >= 1)");
+        return -1;
+    }
+    if (iters) *iters = 0;
+    if (info) *info = 0;
+    GPX_TRY(gpx_flatten_kspec(k, h->d, &h->kp));
+    const bool use_warm = warm && h->lp_mode;
+    h->have_factor = h->have_inverse = false;
+    h->lp_mode = false;
+    h->lp_dlz.clear();
+    h->mean = mean;
+    h->lp_lik = lik;
+    GPX_TRY(laplace_reserve(h));
+    hipStream_t s = h->stream;
+    const int n = h->n, np = h->np;
+    const double *y = h->y.as<double>();
+    double *a = lpv(h, LV_A), *f = lpv(h, LV_F), *an = lpv(h, LV_AN), *fn = lpv(h, LV_FN);
+    double *t = lpv(h, LV_T), *c = lpv(h, LV_C), *x = lpv(h, LV_X);
+    double *g = lpv(h, LV_G), *W = lpv(h, LV_W), *sW = lpv(h, LV_SW), *d3 = lpv(h, LV_D3);
+    double *b = lpv(h, LV_B);
+    if (h->timing) {
+        for (hipEvent_t &e : h->lp_ev)
+            if (!e) GPX_HIP(hipEventCreate(&e));
+        for (double &m : h->lp_ms) m = 0.0;
+        GPX_HIP(hipEventRecord(h->lp_ev[0], s));
+    }
+    if (use_warm) {
+        GPX_TRY(laplace_kv(h, a, mean, f));
+    } else {
+        GPX_TRY(gpx_laplace_fill(s, 0.0, n, np, a));
+        GPX_TRY(gpx_laplace_fill(s, mean, n, np, f));
+    }
+    GPX_TRY(laplace_read(h, a, f, f, false));
+    double psi_old = h->hres[0];
+    bool converged = false;
+    int it = 0;
+    while (it < max_iter && !converged) {
+        ++it;
+        const bool timed = h->timing && it == 1;
+        GPX_TRY(gpx_lik_terms(s, lik, y, f, mean, n, np, g, W, sW, d3, b, h->lp_sc.as<double>() + 4));
+        if (timed) GPX_HIP(hipEventRecord(h->lp_ev[1], s));
+        GPX_TRY(laplace_factor(h, true, timed ? h->lp_ev[2] : nullptr));
+        if (timed) GPX_HIP(hipEventRecord(h->lp_ev[3], s));
+        // a_new = b - sW o B^-1 (sW o K b), f_new = mean + K a_new
+        GPX_TRY(laplace_kv(h, b, 0.0, x));
+        if (timed) GPX_HIP(hipEventRecord(h->lp_ev[4], s));
+        GPX_TRY(gpx_laplace_mul(s, sW, x, n, np, t));
+        GPX_TRY(laplace_solve(h, t, x));
+        GPX_TRY(gpx_laplace_nmulsub(s, b, sW, x, n, np, an));
+        if (timed) GPX_HIP(hipEventRecord(h->lp_ev[5], s));
+        GPX_TRY(laplace_kv(h, an, mean, fn));
+        if (timed) GPX_HIP(hipEventRecord(h->lp_ev[6], s));
+        GPX_TRY(laplace_read(h, an, fn, f, true));
+        const int st = laplace_status(h, *h->hinfo, info);
+        if (st != 0) return st;
+        double psi_new = h->hres[0];
+        const double *acc_a = an, *acc_f = fn;
+        // a step that lowers Psi (or leaves the numbers) is halved: a_old + s (a_new - a_old).
+        // A decrease below 1e-10 (1 + |Psi|) is the rounding of the two sums: halving a
+        // converging step for it would stop the iteration an error of the step's size short.
+        double step = 1.0;
+        const double floor_psi = psi_old - 1e-10 * (1.0 + fabs(psi_old));
+        for (int halvings = 0; !(psi_new >= floor_psi) && halvings < 10; ++halvings) {
+            step *= 0.5;
+            GPX_TRY(gpx_laplace_lerp(s, a, an, step, n, np, t));
+            GPX_TRY(laplace_kv(h, t, mean, c));
+            GPX_TRY(laplace_read(h, t, c, f, false));
+            psi_new = h->hres[0];
+            acc_a = t;
+            acc_f = c;
+        }
+        if (!std::isfinite(psi_new)) {
+            gpx_set_error("gpx_laplace_update: the Newton iteration left the numbers at step %d",
+                          it);
+            return -1;
+        }
+        const double df = h->hres[1], fmax = h->hres[2];
+        GPX_HIP(hipMemcpyAsync(a, acc_a, (size_t)np * 8, hipMemcpyDeviceToDevice, s));
+        GPX_HIP(hipMemcpyAsync(f, acc_f, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
+        psi_old = psi_new;
+        converged = df <= tol * (1.0 + fmax);
+    }
+    if (iters) *iters = it;
+    h->lp_iters = it;
+    if (!converged) {
+        gpx_set_error("gpx_laplace_update: no convergence in %d Newton steps (max_iter)", it);
+        return -1;
+    }
+    // at the mode: the terms and the factor of B once more, lZ = Psi - sum log R_ii
+    GPX_TRY(gpx_lik_terms(s, lik, y, f, mean, n, np, g, W, sW, d3, b, h->lp_sc.as<double>() + 4));
+    GPX_TRY(laplace_factor(h, false));
+    GPX_TRY(gpx_lz_terms(s, h->A.as<double>(), h->ld, n, a, nullptr, h->scalars.as<double>(), 1, 0,
+                         0, 0, h->info.as<int>()));
+    GPX_TRY(gpx_laplace_psi(s, lik, y, a, f, f, mean, n, h->lp_sc.as<double>()));
+    GPX_HIP(hipMemcpyAsync(h->hres, h->scalars.p, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipMemcpyAsync(h->hres + 4, h->lp_sc.p, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (h->timing) GPX_HIP(hipEventRecord(h->lp_ev[7], s));
+    GPX_HIP(hipStreamSynchronize(s));
+    const int st = laplace_status(h, (int)h->hres[3], info);
+    if (st != 0) return st;
+    h->lZ = h->hres[4] - h->hres[1];
+    if (h->timing) {
+        auto span = [&](int e0, int e1) {
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, h->lp_ev[e0], h->lp_ev[e1]);
+            return (double)ms;
+        };
+        h->lp_ms[0] = span(0, 7);
+        h->lp_ms[1] = span(1, 2);
+        h->lp_ms[2] = span(2, 3);
+        h->lp_ms[3] = span(3, 4) + span(5, 6);
+        h->lp_ms[4] = span(4, 5);
+    }
+    h->have_factor = true;
+    h->lp_mode = true;
+    return 0;
+}
+
+int gpx_laplace_loglik(gpx_t *h, double *lZ, double *dlZ)
+{
+    CHECK_H(h);
+    GPX_TRY(check_state(h, ST_LAPLACE, "gpx_laplace_loglik"));
+    if (!h->have_factor) {
+        gpx_set_error("gpx_laplace_loglik: no mode (call gpx_laplace_update)");
+        return -1;
+    }
+    if (lZ) *lZ = h->lZ;
+    if (!dlZ) return 0;
+    const int nh = h->kp.nhyper;
+    if (h->lp_dlz.empty()) {
+        // (B^-1's buffer becomes the pair weight below: the gradient is computed once per update)
+        hipStream_t s = h->stream;
+        const DenseWs w = h->ws();
+        const int n = h->n, np = h->np;
+        double *g = lpv(h, LV_G), *sW = lpv(h, LV_SW), *s2 = lpv(h, LV_S2), *u = lpv(h, LV_U);
+        double *t = lpv(h, LV_T), *c = lpv(h, LV_C), *x = lpv(h, LV_X);
+        if (!h->w_complete) {
+            GPX_TRY(gpx_trtri(s, w));
+            h->w_complete = true;
+        }
+        GPX_TRY(gpx_lauum(s, w));                                   // B^-1 (upper)
+        GPX_TRY(gpx_laplace_sigma(s, w.Kinv, h->ld, lpv(h, LV_W), lpv(h, LV_D3), n, np, s2));
+        // u = s2 - Rt (K s2), Rt = sW sW^T o B^-1, before B^-1 is overwritten
+        GPX_TRY(laplace_kv(h, s2, 0.0, x));
+        GPX_TRY(gpx_laplace_mul(s, sW, x, n, np, t));
+        GPX_TRY(gpx_laplace_symv(s, w.Kinv, h->ld, n, t, c));
+        GPX_TRY(gpx_laplace_nmulsub(s, s2, sW, c, n, np, u));
+        GPX_TRY(gpx_laplace_sums(s, g, u, n, h->lp_sc.as<double>() + 8));
+        GPX_TRY(gpx_laplace_weight(s, w.Kinv, h->ld, n, sW, g, u));
+        GPX_TRY(gpx_trace_grad(s, h->kp, h->X.as<double>(), n, np, h->d, w.Kinv, h->ld, g,
+                               h->partial.as<double>(), h->acc));
+        GPX_HIP(hipMemcpyAsync(h->hres, h->acc, (1 + nh) * sizeof(double), hipMemcpyDeviceToHost,
+                               s));
+        GPX_HIP(hipMemcpyAsync(h->hres + 1 + nh, h->lp_sc.as<double>() + 8, 2 * sizeof(double),
+                               hipMemcpyDeviceToHost, s));
+        GPX_HIP(hipStreamSynchronize(s));
+        // d lZ / d theta = 1/2 sum_ij (g_i g_j - Wt_ij) dK_ij; d lZ / d mean = sum g + sum u
+        h->lp_dlz.resize(nh + 1);
+        for (int i = 0; i < nh; ++i) h->lp_dlz[i] = -0.5 * h->hres[1 + i];
+        h->lp_dlz[nh] = h->hres[1 + nh] + h->hres[2 + nh];
+        h->have_inverse = true;
+    }
+    for (int i = 0; i <= nh; ++i) dlZ[i] = h->lp_dlz[i];
+    return 0;
+}
+
+int gpx_laplace_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2)
+{
+    return posterior_impl(h, Xs, m, mu, s2, nullptr, nullptr, ST_LAPLACE);
+}
+
+int gpx_laplace_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma)
+{
+    return posterior_full_impl(h, Xs, m, mu, Sigma, ST_LAPLACE);
+}
+
+int gpx_laplace_get_mode(gpx_t *h, int64_t n, double *f, double *g)
+{
+    CHECK_H(h);
+    GPX_TRY(check_state(h, ST_LAPLACE, "gpx_laplace_get_mode"));
+    if (!h->have_factor || n != h->n) {
+        gpx_set_error("gpx_laplace_get_mode: no mode for %lld points (call gpx_laplace_update)",
+                      (long long)n);
+        return -1;
+    }
+    if (f) GPX_HIP(hipMemcpyAsync(f, lpv(h, LV_F), (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+    if (g) GPX_HIP(hipMemcpyAsync(g, lpv(h, LV_G), (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+    GPX_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int gpx_laplace_timings(gpx_t *h, double *ms)
+{
+    CHECK_H(h);
+    if (!ms) {
+        gpx_set_error("gpx_laplace_timings: null output");
+        return -1;
+    }
+    for (int i = 0; i < 5; ++i) ms[i] = h->lp_ms[i];
+    return 0;
+}
+
 // ---- multi-output data: T outputs at the same inputs, one kernel, one factorisation --------
 int gpx_mo_set_data(gpx_t *h, const double *X, int64_t n, const double *Y, int64_t T, int64_t d)
 {
@@ -2055,6 +2452,7 @@ int gpx_mo_set_data(gpx_t *h, const double *X, int64_t n, const double *Y, int64
     h->gradobs = false;
     h->go_n = h->go_ng = 0;
     h->mo_T = 0;
+    h->laplace = h->lp_mode = false;
     h->data_version++;
     GPX_HIP(hipMemcpyAsync(h->X.p, X, (size_t)n * d * 8, hipMemcpyHostToDevice, h->stream));
     // column t of Y (n contiguous doubles) -> y + t cap

@@ -649,3 +649,39 @@ int gpx_gradobs_residual(hipStream_t s, const double *obs, int n, int M, int np,
 int gpx_kbuild_strip(hipStream_t s, const KParams &kp, const double *X, int n, int np,
                      int j0, int npc, int d, double *out, long long ldo, double diag_add,
                      double *out_offdiag = nullptr);
+
+// ---- K v without K (kmat.hip) --------------------------------------------------------------
+// out[c * os + j] = bias + sum_i k(x_j, x_i) V[c * vs + i] for j < n and the nv <= 4 columns c;
+// scratch: gpx_kmatvec_scratch(n) doubles. Fixed-order sums: the same call gives the same bits.
+size_t gpx_kmatvec_scratch(int n);
+int gpx_kmatvec(hipStream_t s, const KParams &kp, const double *X, int n, int d, const double *V,
+                long long vs, int nv, double bias, double *scratch, double *out, long long os);
+
+// ---- Laplace's approximation for classification (laplace.hip; driver in gpx_api.hip) ----------
+// g, W, sW, d3, b = W (f - mean) + g at f (zero in the padding), sums[0] = sum log p(y | f)
+int gpx_lik_terms(hipStream_t s, int lik, const double *y, const double *f, double mean, int n,
+                  int np, double *g, double *W, double *sW, double *d3, double *b, double *sums);
+// out[0] = Psi(a, f), out[1] = max |f - f_old|, out[2] = max |f|
+int gpx_laplace_psi(hipStream_t s, int lik, const double *y, const double *a, const double *f,
+                    const double *f_old, double mean, int n, double *out);
+// vectors of np doubles, zero beyond n: out = p q; out = r - p q; out = p + t (q - p); out = v
+int gpx_laplace_mul(hipStream_t s, const double *p, const double *q, int n, int np, double *out);
+int gpx_laplace_nmulsub(hipStream_t s, const double *r, const double *p, const double *q, int n,
+                        int np, double *out);
+int gpx_laplace_lerp(hipStream_t s, const double *p, const double *q, double t, int n, int np,
+                     double *out);
+int gpx_laplace_fill(hipStream_t s, double v, int n, int np, double *out);
+// K (as gpx_kbuild with out_offdiag = S left it) -> B = I + sW K sW^T, i, j < n
+int gpx_laplace_scale(hipStream_t s, double *A, double *S, int ld, int n, const double *sW);
+// s2 = 1/2 diag(Sigma) d3 from diag B^-1; out = M v for a symmetric M stored by its upper
+// triangle; the upper triangle of B^-1 -> sW_i sW_j (B^-1)_ij - u_i g_j - g_i u_j;
+// sc[0] = sum g, sc[1] = sum u
+int gpx_laplace_sigma(hipStream_t s, const double *Binv, int ld, const double *W, const double *d3,
+                      int n, int np, double *s2);
+int gpx_laplace_symv(hipStream_t s, const double *M, int ld, int n, const double *v, double *out);
+int gpx_laplace_weight(hipStream_t s, double *Binv, int ld, int n, const double *sW,
+                       const double *g, const double *u);
+int gpx_laplace_sums(hipStream_t s, const double *g, const double *u, int n, double *sc);
+// mu[j] = mean + Ks[:, j].g (j < mcp) from the unscaled Ks (np x ldk), then row i of Ks times sW_i
+int gpx_laplace_cross(hipStream_t s, double *Ks, int ldk, int n, int mcp, const double *g,
+                      const double *sW, double mean, double *mu);

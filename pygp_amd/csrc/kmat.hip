@@ -2883,3 +2883,157 @@ int gpx_gradobs_residual(hipStream_t s, const double *obs, int n, int M, int np,
     GPX_HIP(hipGetLastError());
     return 0;
 }
+
+// ---- K(X, X) V without K (gpx_kernel_matvec, the Newton steps of gpx_laplace_update) ----------
+// out[j][c] = bias + sum_i k(x_j, x_i) V[i][c] for nv <= 4 columns: N^2 kernel values (one exp,
+// pow or sin per part and pair) against N nv 8 bytes of traffic. The layout of
+// trace_grad_rows_kernel turned by the symmetry of K: a lane owns the OUTPUT row j, keeps its
+// scaled x_j and its nv sums in registers and meets the x_i and V_i of a 64-row tile as LDS
+// broadcasts, so no sum crosses lanes. The four waves of a workgroup take 16 rows of the tile
+// each; workgroup (bj, c0) takes the tiles c0, c0 + C, .. and leaves its sums in a slab that
+// kmv_reduce_kernel adds over c0 in a fixed order: the same call gives the same bits.
+// Values are those of part_value on the scaled squared distance, parts of one group multiplied
+// and groups added (group_factor's rule); inputs are divided by the part's scale once per call.
+#define KMV_NV 4
+__global__ __launch_bounds__(256) void kmv_xscale_kernel(KParams kp, const double *__restrict__ X,
+                                                         int n, int d, int np, int dmax,
+                                                         double *__restrict__ Xs)
+{
+    // xscale_kernel for every family: Xs[p][r][c], rows >= n repeat row n - 1, columns >= d zero
+    const int p = blockIdx.y;
+    const KPart &part = kp.part[p];
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= np * dmax) return;
+    const int r = e / dmax, c = e - r * dmax;
+    const int gi = min(r, n - 1);
+    Xs[(size_t)p * np * dmax + e] = c < d ? X[(size_t)gi * d + c] / part.scale[c] : 0.0;
+}
+
+template <int DMAX>
+__global__ __launch_bounds__(256) void kmatvec_kernel(KParams kp, const double *__restrict__ Xs,
+                                                      int n, int np,
+                                                      const double *__restrict__ V, long long vs,
+                                                      int nv, double *__restrict__ slab)
+{
+    const int T = np / KT, C = gridDim.y;
+    const int bj = blockIdx.x, c0 = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, ig = tid >> 6;
+    const int j = bj * KT + lane;
+    __shared__ double xi_s[KT][DMAX + 1];
+    __shared__ double vi_s[KT][KMV_NV];
+    __shared__ double red[4][KT][KMV_NV];
+    double acc[KMV_NV];
+#pragma unroll
+    for (int c = 0; c < KMV_NV; ++c) acc[c] = 0.0;
+    double xj[DMAX];
+    auto load_xj = [&](int p) {
+        const double2 *__restrict__ xp =
+            reinterpret_cast<const double2 *>(Xs + ((size_t)p * np + j) * DMAX);
+#pragma unroll
+        for (int c = 0; c < DMAX; c += 2) {
+            const double2 v = xp[c / 2];
+            xj[c] = v.x;
+            xj[c + 1] = v.y;
+        }
+    };
+    for (int p0 = 0; p0 < kp.nparts;) {
+        int p1 = p0 + 1;
+        while (p1 < kp.nparts && kp.part[p1].group == kp.part[p0].group) ++p1;
+        const bool single = p1 - p0 == 1;
+        if (single) load_xj(p0);
+        for (int bi = c0; bi < T; bi += C) {
+            const int i0 = bi * KT;
+            double prod[16];
+#pragma unroll
+            for (int ii = 0; ii < 16; ++ii) prod[ii] = 1.0;
+            for (int p = p0; p < p1; ++p) {
+                const KPart &part = kp.part[p];
+                const double *__restrict__ xs = Xs + ((size_t)p * np + i0) * DMAX;
+                __syncthreads();
+                for (int e = tid; e < KT * DMAX; e += 256) {
+                    const int r = e / DMAX, c = e - r * DMAX;
+                    xi_s[r][c] = xs[e];
+                }
+                if (p == p0) {
+                    const int r = tid >> 2, c = tid & 3;
+                    vi_s[r][c] = (i0 + r < n && c < nv) ? V[(size_t)c * vs + i0 + r] : 0.0;
+                }
+                __syncthreads();
+                if (!single) load_xj(p);
+#pragma unroll
+                for (int ii = 0; ii < 16; ++ii) {
+                    double D2 = 0.0;
+#pragma unroll
+                    for (int c = 0; c < DMAX; ++c) {
+                        const double df = xi_s[ig * 16 + ii][c] - xj[c];
+                        D2 += df * df;
+                    }
+                    prod[ii] *= part_value<double>(part.kind, part.two_logsf, part.sf2, part.ell,
+                                                   part.period, part.alpha, D2);
+                }
+            }
+#pragma unroll
+            for (int ii = 0; ii < 16; ++ii)
+#pragma unroll
+                for (int c = 0; c < KMV_NV; ++c) acc[c] += prod[ii] * vi_s[ig * 16 + ii][c];
+        }
+        p0 = p1;
+    }
+#pragma unroll
+    for (int c = 0; c < KMV_NV; ++c) red[ig][lane][c] = acc[c];
+    __syncthreads();
+    if (ig == 0) {
+        double *o = slab + ((size_t)c0 * np + j) * KMV_NV;
+#pragma unroll
+        for (int c = 0; c < KMV_NV; ++c)
+            o[c] = red[0][lane][c] + red[1][lane][c] + red[2][lane][c] + red[3][lane][c];
+    }
+}
+
+__global__ __launch_bounds__(256) void kmv_reduce_kernel(const double *__restrict__ slab, int C,
+                                                         int np, int n, int nv, double bias,
+                                                         double *__restrict__ out, long long os)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    const int j = e >> 2, c = e & 3;
+    if (j >= n || c >= nv) return;
+    double s = 0.0;
+    for (int c0 = 0; c0 < C; ++c0) s += slab[((size_t)c0 * np + j) * KMV_NV + c];
+    out[(size_t)c * os + j] = bias + s;
+}
+
+static int kmv_chunks(int T) { return std::min(T, std::max(1, 2048 / T)); }
+
+size_t gpx_kmatvec_scratch(int n)
+{
+    const size_t np = (size_t)round_up(n, KT);
+    return (size_t)GPX_MAX_PARTS * np * GPX_MAX_DIM + (size_t)kmv_chunks((int)(np / KT)) * np * KMV_NV;
+}
+
+int gpx_kmatvec(hipStream_t s, const KParams &kp, const double *X, int n, int d, const double *V,
+                long long vs, int nv, double bias, double *scratch, double *out, long long os)
+{
+    if (nv < 1 || nv > KMV_NV) {
+        gpx_set_error("gpx_kmatvec: 1 <= nv <= %d columns", KMV_NV);
+        return -1;
+    }
+    const int np = round_up(n, KT), T = np / KT, C = kmv_chunks(T);
+    const int dmax = d <= 8 ? 8 : (d <= 16 ? 16 : 32);
+    double *Xs = scratch;
+    double *slab = scratch + (size_t)GPX_MAX_PARTS * np * GPX_MAX_DIM;
+    hipLaunchKernelGGL(kmv_xscale_kernel, dim3((np * dmax + 255) / 256, kp.nparts), dim3(256), 0, s,
+                       kp, X, n, d, np, dmax, Xs);
+    GPX_HIP(hipGetLastError());
+    const dim3 grid(T, C);
+    if (dmax == 8)
+        hipLaunchKernelGGL(kmatvec_kernel<8>, grid, dim3(256), 0, s, kp, Xs, n, np, V, vs, nv, slab);
+    else if (dmax == 16)
+        hipLaunchKernelGGL(kmatvec_kernel<16>, grid, dim3(256), 0, s, kp, Xs, n, np, V, vs, nv, slab);
+    else
+        hipLaunchKernelGGL(kmatvec_kernel<32>, grid, dim3(256), 0, s, kp, Xs, n, np, V, vs, nv, slab);
+    GPX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(kmv_reduce_kernel, dim3((n * KMV_NV + 255) / 256), dim3(256), 0, s, slab, C,
+                       np, n, nv, bias, out, os);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}

@@ -2,10 +2,11 @@ from .exact import GP, ExactGP
 from .basic import BasicGP
 from .gradobs import GradientGP
 from .multiout import MultiOutputGP
+from .laplace import LaplaceGP
 from .fitc import FITC
 from .dtc import DTC
 from .vfe import VFE
 from .select import select_pseudoinputs
 
-__all__ = ['GP', 'ExactGP', 'BasicGP', 'GradientGP', 'MultiOutputGP', 'FITC', 'DTC', 'VFE',
+__all__ = ['GP', 'ExactGP', 'BasicGP', 'GradientGP', 'MultiOutputGP', 'LaplaceGP', 'FITC', 'DTC', 'VFE',
            'select_pseudoinputs']

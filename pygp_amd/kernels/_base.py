@@ -57,6 +57,13 @@ class Kernel(Parameterized):
         G = self._dev().kernel_grad(self._kspec(), X1, X2)
         return iter(G)
 
+    def matvec(self, X, V):
+        """K(X, X) V for V (n,) or (n, nv <= 4) without storing K: N^2 kernel values on the
+        device against N nv doubles of traffic."""
+        X = self.transform(X)
+        self._check_dim(X, None)
+        return self._dev().kernel_matvec(self._kspec(), X, V)
+
     def _check_dim(self, X1, X2):
         for X in (X1, X2):
             if X is not None and X.shape[1] != self.ndim:

@@ -44,6 +44,11 @@ class HyperEnsemble(object):
             # sparse model's
             raise TypeError('HyperEnsemble runs exact GPs only; %s is a sparse model'
                             % type(model).__name__)
+        from .inference.laplace import LaplaceGP
+        if isinstance(model, LaplaceGP):
+            # ... with Gaussian noise: a classifier's hypers have no noise slot
+            raise TypeError('HyperEnsemble runs exact GPs only; %s is a classifier'
+                            % type(model).__name__)
         if getattr(model, 'ngrad', 0) > 0:
             # ... on (X, y) alone: the gradient observations would be left out
             raise TypeError('HyperEnsemble runs GPs on function values only; this %s holds '
