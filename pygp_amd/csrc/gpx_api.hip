@@ -33,34 +33,35 @@ static const char *kTimerNames[GPX_NTIMERS] = {
     "kernel_build", "potrf", "trsv", "trtri", "trmv", "lauum", "trace_grad",
     "scalars", "posterior_build", "posterior_solve"};
 
+// What the resident data of a handle is: set by the family's set_data (commit_data), asked for
+// by every entry that reads the data (require_state).
+enum { ST_PLAIN = 0, ST_GRADOBS, ST_MO, ST_LAPLACE };
+
 struct gpx_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     // resident data (GP.add_data)
+    int state = ST_PLAIN;
     int n = 0, d = 0, np = 0, ld = 0;
     int cap = 0;                   // rows the matrices are allocated for (>= np): room
                                    // for gpx_exact_append to open new 128-blocks
     long data_version = 0;         // bumped by gpx_set_data (twin refresh)
     DevBuf X, y, Xf32;
-    // gradient observations (gpx_gradobs_set_data): n is then the order M = go_n + go_ng d of
-    // K_aug, y the stacked observations [y ; vec(G)], X the go_n data points, Xg the go_ng
-    // gradient locations, and the factorisation below is that of K_aug. Entries that read
-    // the handle as plain data refuse it (PLAIN_ONLY); gpx_set_data returns it to them.
-    bool gradobs = false;
+    // ST_GRADOBS, gradient observations (gpx_gradobs_set_data): n is then the order
+    // M = go_n + go_ng d of K_aug, y the stacked observations [y ; vec(G)], X the go_n data
+    // points, Xg the go_ng gradient locations, and the factorisation below is that of K_aug.
     int go_n = 0, go_ng = 0;
     double grad_noise = 0;
     DevBuf Xg;
-    // multi-output data (gpx_mo_set_data): mo_T > 0 outputs observed at the n points of X. y, r,
-    // a and alpha then hold mo_T columns, column t at + t * cap; the factorisation is that of
-    // plain data on X. Handled like the state above: the plain and the gradobs entries refuse
-    // the handle, gpx_set_data / gpx_gradobs_set_data return it to them.
+    // ST_MO, multi-output data (gpx_mo_set_data): mo_T outputs observed at the n points of X
+    // (0 in every other state). y, r, a and alpha then hold mo_T columns, column t at + t * cap;
+    // the factorisation is that of plain data on X.
     int mo_T = 0;
-    // binary labels under a Logistic / Probit likelihood (gpx_laplace_set_data): y holds the n
-    // labels, the factorisation below is that of B = I + sW K sW^T at the mode, lp_vec the vectors
-    // of the Newton iteration (LV_* in the Laplace section, cap doubles each). Handled like the two
-    // states above: the plain, gradobs and multi-output entries refuse the handle, their set_data
-    // calls return it to them.
-    bool laplace = false;
+    // ST_LAPLACE, binary labels under a Logistic / Probit likelihood (gpx_laplace_set_data): y
+    // holds the n labels, the factorisation below is that of B = I + sW K sW^T at the mode, lp_vec
+    // the vectors of the Newton iteration (LV_* in the Laplace section, cap doubles each).
+    // In each of the three states the entries of the other families refuse the handle; any
+    // set_data moves it to its own state.
     int lp_lik = 0;
     bool lp_mode = false;          // lp_vec holds a converged mode for the resident data
     int lp_iters = 0;
@@ -170,24 +171,42 @@ static int ld_for(int np)
         GPX_HIP(hipSetDevice((h)->device));                                    \
     } while (0)
 
-#define PLAIN_ONLY(h, what)                                                    \
-    do {                                                                       \
-        if ((h)->gradobs) {                                                    \
-            gpx_set_error(what ": the handle holds gradient observations "     \
-                               "(gpx_gradobs_*); gpx_set_data returns it to plain data"); \
-            return -1;                                                         \
-        }                                                                      \
-        if ((h)->mo_T) {                                                       \
-            gpx_set_error(what ": the handle holds multi-output data "         \
-                               "(gpx_mo_*); gpx_set_data returns it to plain data"); \
-            return -1;                                                         \
-        }                                                                      \
-        if ((h)->laplace) {                                                    \
-            gpx_set_error(what ": the handle holds classification labels "     \
-                               "(gpx_laplace_*); gpx_set_data returns it to plain data"); \
-            return -1;                                                         \
-        }                                                                      \
-    } while (0)
+// the one refusal of a handle in another state than the calling entry's family (`what`) needs
+static int require_state(const gpx_ctx *h, int want, const char *what)
+{
+    static const char *holds[4] = {"plain data (gpx_set_data)",
+                                   "gradient observations (gpx_gradobs_*)",
+                                   "multi-output data (gpx_mo_*)",
+                                   "classification labels (gpx_laplace_*)"};
+    if (h->state == want) return 0;
+    gpx_set_error("%s: the handle holds %s%s", what, holds[h->state],
+                  want == ST_PLAIN ? "; gpx_set_data returns it to plain data" : "");
+    return -1;
+}
+
+// The two halves of every set_data. drop_data, once the buffers are reserved and before the
+// first copy into them: a failure from there on leaves them half written, so the handle holds no
+// data of any kind. commit_data, once the copies have arrived.
+static void drop_data(gpx_ctx *h)
+{
+    h->n = 0;
+    h->have_factor = h->have_inverse = false;
+    h->state = ST_PLAIN;
+    h->go_n = h->go_ng = 0;
+    h->mo_T = 0;
+    h->lp_mode = false;
+    h->data_version++;
+}
+
+static void commit_data(gpx_ctx *h, int state, int64_t n, int64_t d, size_t cap)
+{
+    h->n = (int)n;
+    h->d = (int)d;
+    h->np = round_up(n, GPX_TILE);
+    h->cap = (int)cap;
+    h->ld = ld_for(h->cap);
+    h->state = state;
+}
 
 // stage timer: measures from the previous tick to this one
 struct StageClock {
@@ -770,7 +789,7 @@ int gpx_kernel_build_resident(gpx_t *h, const gpx_kspec *k, int dtype, int reps,
                               double *ms)
 {
     CHECK_H(h);
-    PLAIN_ONLY(h, "gpx_kernel_build_resident");
+    GPX_TRY(require_state(h, ST_PLAIN, "gpx_kernel_build_resident"));
     if (h->n <= 0) {
         gpx_set_error("gpx_kernel_build_resident: no data (gpx_set_data first)");
         return -1;
@@ -824,20 +843,11 @@ int gpx_set_data(gpx_t *h, const double *X, int64_t n, int64_t d, const double *
     const size_t cap = (size_t)round_up(n + 256, 1024);
     GPX_TRY(h->X.reserve(cap * d * 8));
     GPX_TRY(h->y.reserve(cap * 8));
+    drop_data(h);
     GPX_HIP(hipMemcpyAsync(h->X.p, X, (size_t)n * d * 8, hipMemcpyHostToDevice, h->stream));
     GPX_HIP(hipMemcpyAsync(h->y.p, y, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
     GPX_HIP(hipStreamSynchronize(h->stream));
-    h->n = (int)n;
-    h->d = (int)d;
-    h->np = round_up(n, GPX_TILE);
-    h->cap = (int)cap;
-    h->ld = ld_for(h->cap);
-    h->data_version++;
-    h->have_factor = h->have_inverse = false;
-    h->gradobs = false;
-    h->go_n = h->go_ng = 0;
-    h->mo_T = 0;
-    h->laplace = h->lp_mode = false;
+    commit_data(h, ST_PLAIN, n, d, cap);
     return 0;
 }
 
@@ -883,7 +893,7 @@ static int enqueue_update(gpx_ctx *h, StageClock &clk, int mode, bool grad_follo
     const GpxBlocks lb(h->np, mode == GPX_POTRF_KINV);
     const int lead_rows = lb.count >= 2 && lb.len(1) <= GPX_PANEL_MAX ? lb.off(2) : lb.len(0);
     hipEvent_t lead_ev = gpx_potrf_lead_event(w);
-    const bool lead = !h->gradobs && lead_on && lead_ev && w.crit && lead_rows < h->np;
+    const bool lead = h->state != ST_GRADOBS && lead_on && lead_ev && w.crit && lead_rows < h->np;
     if (lead) {
         GPX_TRY(gpx_kbuild<double>(h->stream, h->kp, h->X.as<double>(), h->n, h->np,
                                    h->X.as<double>(), h->n, h->np, h->d, w.A, h->ld, true,
@@ -901,7 +911,7 @@ static int enqueue_update(gpx_ctx *h, StageClock &clk, int mode, bool grad_follo
                                    true, sn2, w.Kinv, lead_rows, h->np - lead_rows));
         w.lead = lead_ev;
         w.lead_rows = lead_rows;
-    } else if (h->gradobs) {
+    } else if (h->state == ST_GRADOBS) {
         // K_aug in the same places (kmat.hip); the whole matrix before the factorisation starts
         GPX_TRY(gpx_kaug_build(h->stream, h->kp, h->X.as<double>(), h->go_n, h->Xg.as<double>(),
                                h->go_ng, h->d, sn2, h->grad_noise * h->grad_noise, w.A, w.Kinv,
@@ -927,10 +937,10 @@ static int enqueue_update(gpx_ctx *h, StageClock &clk, int mode, bool grad_follo
     w.whole = gpx_potrf_whole(w, mode);
     w.full_w = grad_follows && gpx_grad_full_w(w, mode);
     // (multi-output data: the T right-hand sides are solved behind the factorisation)
-    const bool aug = !h->mo_T && gpx_potrf_rhs_ok(w, mode);
+    const bool aug = h->state != ST_MO && gpx_potrf_rhs_ok(w, mode);
     if (aug) {
         // (one kernel: the residual into column np of the staging matrix, zeros right of it)
-        if (h->gradobs)
+        if (h->state == ST_GRADOBS)
             GPX_TRY(gpx_gradobs_residual(h->stream, h->y.as<double>(), h->go_n, h->n, h->np,
                                          h->mean, nullptr, w.Kinv, h->ld));
         else
@@ -948,11 +958,11 @@ static int enqueue_update(gpx_ctx *h, StageClock &clk, int mode, bool grad_follo
     if (aug) {
         GPX_TRY(gpx_column_out(h->stream, w.A, h->ld, h->np, h->np, h->a.as<double>(),
                                MemberBatch()));
-    } else if (h->mo_T) {
+    } else if (h->state == ST_MO) {
         GPX_TRY(gpx_mo_trsv_rt(h->stream, w, h->y.as<double>(), h->mo_T, h->mean, h->n, h->cap,
                                h->r.as<double>(), h->a.as<double>(), h->gv_part.as<double>()));
     } else {
-        if (h->gradobs)
+        if (h->state == ST_GRADOBS)
             GPX_TRY(gpx_gradobs_residual(h->stream, h->y.as<double>(), h->go_n, h->n, h->np,
                                          h->mean, h->r.as<double>(), nullptr, h->ld));
         else
@@ -975,13 +985,13 @@ static int enqueue_inverse(gpx_ctx *h, StageClock &clk)
         h->w_complete = true;
         clk.tick(T_TRTRI);
     }
-    if (h->mo_T)
+    if (h->state == ST_MO)
         GPX_TRY(gpx_mo_trmv_upper(h->stream, w.W, h->ld, h->np, h->a.as<double>(), h->mo_T, h->cap,
                                   h->alpha.as<double>()));
     else
         GPX_TRY(gpx_trmv_upper(h->stream, w.W, h->ld, h->np, h->a.as<double>(),
                                h->alpha.as<double>()));
-    if (h->kinv_pending && !h->mo_T) {
+    if (h->kinv_pending && h->state != ST_MO) {
         // a = R^-T r and alpha = R^-1 a ran beside the last K^-1 update of the sweep, and so
         // do the scalar terms (one workgroup, 44 us): wait for the update here; the potrf
         // stage (factor + inverse) ends with it
@@ -1009,7 +1019,7 @@ static int enqueue_grad(gpx_ctx *h, StageClock &clk)
 {
     GPX_TRY(enqueue_inverse(h, clk));
     const DenseWs w = h->ws();
-    if (h->mo_T)
+    if (h->state == ST_MO)
         GPX_TRY(gpx_mo_trace_grad(h->stream, h->kp, h->X.as<double>(), h->n, h->np, h->d, w.Kinv,
                                   h->ld, h->alpha.as<double>(), h->mo_T, h->cap,
                                   h->partial.as<double>(), h->acc));
@@ -1024,7 +1034,7 @@ static int enqueue_grad(gpx_ctx *h, StageClock &clk)
 // scalars + asynchronous copy of the few result doubles to pinned host memory
 static int enqueue_finish(gpx_ctx *h, StageClock &clk, bool grad)
 {
-    if (h->mo_T)
+    if (h->state == ST_MO)
         GPX_TRY(gpx_mo_lz_terms(h->stream, h->A.as<double>(), h->ld, h->n, h->a.as<double>(),
                                 grad ? h->alpha.as<double>() : nullptr, h->mo_T, h->cap,
                                 h->scalars.as<double>(), h->info.as<int>()));
@@ -1064,7 +1074,7 @@ static int collect(gpx_ctx *h, StageClock &clk, double *lZ, double *dlZ, int *in
         return inf;
     }
     // exact.py:119-121
-    h->lZ = h->mo_T ? gpx_mo_assemble_lz(sc, h->n, h->mo_T) : gpx_assemble_lz(sc, h->n);
+    h->lZ = h->state == ST_MO ? gpx_mo_assemble_lz(sc, h->n, h->mo_T) : gpx_assemble_lz(sc, h->n);
     if (lZ) *lZ = h->lZ;
     if (grad && dlZ) gpx_assemble_dlz(sc, acc, exp(h->log_sn * 2), h->kp.nhyper, dlZ);
     return 0;
@@ -1096,7 +1106,7 @@ static int check_ready(gpx_ctx *h, const gpx_kspec *k, double log_sn, double mea
 int gpx_exact_update(gpx_t *h, const gpx_kspec *k, double log_sn, double mean, int *info)
 {
     CHECK_H(h);
-    PLAIN_ONLY(h, "gpx_exact_update");
+    GPX_TRY(require_state(h, ST_PLAIN, "gpx_exact_update"));
     GPX_TRY(check_ready(h, k, log_sn, mean));
     GPX_TRY(reserve_factor(h, false));
     h->have_factor = h->have_inverse = false;
@@ -1110,7 +1120,7 @@ int gpx_exact_update(gpx_t *h, const gpx_kspec *k, double log_sn, double mean, i
 int gpx_exact_loglik(gpx_t *h, double *lZ, double *dlZ)
 {
     CHECK_H(h);
-    PLAIN_ONLY(h, "gpx_exact_loglik");
+    GPX_TRY(require_state(h, ST_PLAIN, "gpx_exact_loglik"));
     if (!h->have_factor) {
         gpx_set_error("gpx_exact_loglik: no factorisation (call gpx_exact_update)");
         return -1;
@@ -1144,7 +1154,7 @@ static int reserve_loo(gpx_ctx *h, bool grad)
 int gpx_exact_loo(gpx_t *h, double *L, double *dL, double *mu, double *s2)
 {
     CHECK_H(h);
-    PLAIN_ONLY(h, "gpx_exact_loo");
+    GPX_TRY(require_state(h, ST_PLAIN, "gpx_exact_loo"));
     if (!h->have_factor) {
         gpx_set_error("gpx_exact_loo: no factorisation (call gpx_exact_update)");
         return -1;
@@ -1186,7 +1196,7 @@ int gpx_exact_eval(gpx_t *h, const gpx_kspec *k, double log_sn, double mean,
                    int want_grad, double *lZ, double *dlZ, int *info)
 {
     CHECK_H(h);
-    PLAIN_ONLY(h, "gpx_exact_eval");
+    GPX_TRY(require_state(h, ST_PLAIN, "gpx_exact_eval"));
     GPX_TRY(check_ready(h, k, log_sn, mean));
     const bool grad = want_grad && dlZ;
     GPX_TRY(reserve_factor(h, grad));
@@ -1320,7 +1330,7 @@ static int append_block(gpx_ctx *h, int j0)
 int gpx_exact_append(gpx_t *h, const double *Xnew, const double *ynew, int64_t m, int *info)
 {
     CHECK_H(h);
-    PLAIN_ONLY(h, "gpx_exact_append");
+    GPX_TRY(require_state(h, ST_PLAIN, "gpx_exact_append"));
     if (!Xnew || !ynew || m < 1) {
         gpx_set_error("gpx_exact_append: bad arguments");
         return -1;
@@ -1383,7 +1393,7 @@ static bool batch_in_groups(const gpx_ctx *h, int64_t B)
 int gpx_batch_plan(gpx_t *h, int64_t B, int want_grad, int *plan)
 {
     CHECK_H(h);
-    PLAIN_ONLY(h, "gpx_batch_plan");
+    GPX_TRY(require_state(h, ST_PLAIN, "gpx_batch_plan"));
     if (!plan || B < 0) {
         gpx_set_error("gpx_batch_plan: bad arguments");
         return -1;
@@ -1413,7 +1423,7 @@ int gpx_loglik_batch(gpx_t *h, const gpx_kspec *k, const double *thetas, int64_t
                      int want_grad, double *lZ, double *dlZ, int *info)
 {
     CHECK_H(h);
-    PLAIN_ONLY(h, "gpx_loglik_batch");
+    GPX_TRY(require_state(h, ST_PLAIN, "gpx_loglik_batch"));
     if (!k || !thetas || !lZ || B < 0) {
         gpx_set_error("gpx_loglik_batch: bad arguments");
         return -1;
@@ -1562,7 +1572,7 @@ static int solve_rt_refined(gpx_ctx *h, double *K, double *V, int mcp)
 // gradient observations the cross matrix of K_aug; np x mcp, zero outside the live part
 static int build_cross(gpx_ctx *h, int mc, int mcp)
 {
-    if (h->gradobs)
+    if (h->state == ST_GRADOBS)
         return gpx_kaug_cross(h->stream, h->kp, h->X.as<double>(), h->go_n, h->Xg.as<double>(),
                               h->go_ng, h->d, h->np, h->Xs.as<double>(), mc, h->Ks.as<double>(),
                               mcp);
@@ -1585,92 +1595,110 @@ static int laplace_cross(gpx_ctx *h, int mcp)
                              lpv(h, LV_SW), h->mean, h->lp_mu.as<double>());
 }
 
-// the state a handle is in, and the check that an entry of one family finds its own
-enum { ST_PLAIN = 0, ST_GRADOBS = 1, ST_MO = 2, ST_LAPLACE = 3 };
-static int state_of(const gpx_ctx *h)
+// what every posterior entry (`what`, of the family `state`) asks of the handle first
+static int posterior_ready(const gpx_ctx *h, int state, const char *what)
 {
-    return h->laplace ? ST_LAPLACE : (h->mo_T ? ST_MO : (h->gradobs ? ST_GRADOBS : ST_PLAIN));
-}
-static int check_state(const gpx_ctx *h, int want, const char *what)
-{
-    static const char *holds[4] = {"plain data (gpx_set_data)",
-                                   "gradient observations (gpx_gradobs_*)",
-                                   "multi-output data (gpx_mo_*)",
-                                   "classification labels (gpx_laplace_*)"};
-    const int st = state_of(h);
-    if (st == want) return 0;
-    gpx_set_error("%s: the handle holds %s%s", what, holds[st],
-                  want == ST_PLAIN ? "; gpx_set_data returns it to plain data" : "");
-    return -1;
-}
-
-// state: the family of the calling entry; the handle must be in the same state. ST_MO: mu is
-// mo_T rows of m doubles.
-static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2,
-                          double *dmu, double *ds2, int state = ST_PLAIN)
-{
-    CHECK_H(h);
-    GPX_TRY(check_state(h, state, state == ST_MO ? "gpx_mo_posterior"
-                                  : state == ST_GRADOBS ? "gpx_gradobs_posterior"
-                                  : state == ST_LAPLACE ? "gpx_laplace_posterior"
-                                                        : "gpx_exact_posterior"));
+    static const char *update[4] = {"gpx_exact_update", "gpx_gradobs_update", "gpx_mo_update",
+                                    "gpx_laplace_update"};
+    GPX_TRY(require_state(h, state, what));
     if (!h->have_factor) {
-        gpx_set_error("gpx_exact_posterior: no factorisation (call gpx_exact_update)");
+        gpx_set_error("%s: no factorisation (call %s)", what, update[state]);
         return -1;
     }
+    return 0;
+}
+
+// W = R^-1 in full: V = R^-T K* is a triangle-aware product with W^T and one step of refinement
+// (solve_rt_refined), so the rest of W is completed first if the factorisation left only the
+// inverses of its diagonal blocks (a fraction of the factorisation's cost)
+static int complete_w(gpx_ctx *h)
+{
+    if (h->w_complete) return 0;
+    GPX_TRY(gpx_trtri(h->stream, h->ws()));
+    h->w_complete = true;
+    return 0;
+}
+
+// alpha = R^-1 a (one column; W complete)
+static int solve_alpha(gpx_ctx *h)
+{
+    GPX_TRY(h->alpha.reserve((size_t)h->np * 8));
+    return gpx_trmv_upper(h->stream, h->W.as<double>(), h->ld, h->np, h->a.as<double>(),
+                          h->alpha.as<double>());
+}
+
+// One pass of the posterior over the mc test points at Xs (host memory; mcp: mc rounded up to
+// the tile): the cross matrix of the handle's state, V = R^-T K* (np x mcp, returned in *V) and
+// the state's reduction: the mean(s) into h->mu (a Laplace handle: h->lp_mu), prior - |V_j|^2
+// into h->s2. The clock, if one is given, is ticked between the build and the solve.
+static int posterior_pass(gpx_ctx *h, const double *Xs, int mc, int mcp, double prior, double **V,
+                          StageClock *clk = nullptr)
+{
+    const bool mo = h->state == ST_MO;
+    GPX_TRY(h->Xs.reserve((size_t)mc * h->d * 8));
+    GPX_TRY(h->Ks.reserve((size_t)h->np * mcp * 8));
+    GPX_TRY(h->KsT.reserve((size_t)h->np * mcp * 8));
+    GPX_TRY(h->mu.reserve((size_t)mcp * 8 * (mo ? h->mo_T : 1)));
+    GPX_TRY(h->s2.reserve((size_t)mcp * 8));
+    GPX_TRY(h->post_part.reserve((mo ? gpx_mo_posterior_scratch(mcp)
+                                     : gpx_posterior_scratch(mcp)) * 8));
+    GPX_HIP(hipMemcpyAsync(h->Xs.p, Xs, (size_t)mc * h->d * 8, hipMemcpyHostToDevice,
+                           h->stream));
+    // K(X, Xs): np x mcp, zero outside n x mc (exact.py:87)
+    GPX_TRY(build_cross(h, mc, mcp));
+    if (h->state == ST_LAPLACE) GPX_TRY(laplace_cross(h, mcp));
+    if (clk) clk->tick(T_POST_BUILD);
+    // RK = R^-T K (exact.py:88)
+    *V = h->KsT.as<double>();
+    GPX_TRY(solve_rt_refined(h, h->Ks.as<double>(), *V, mcp));
+    if (mo)
+        return gpx_mo_posterior_reduce(h->stream, *V, mcp, h->np, mcp, h->a.as<double>(),
+                                       h->mo_T, h->cap, h->mean, prior,
+                                       h->post_part.as<double>(), h->mu.as<double>(),
+                                       h->s2.as<double>());
+    return gpx_posterior_reduce(h->stream, *V, mcp, h->np, mcp, h->a.as<double>(), h->mean, prior,
+                                h->post_part.as<double>(), h->mu.as<double>(),
+                                h->s2.as<double>());
+}
+
+// the mean of the mc test points of a pass to the host: mc doubles, from a multi-output handle
+// mo_T rows of mc, `stride` doubles apart at mu
+static int copy_mean(gpx_ctx *h, double *mu, size_t stride, int mc, int mcp)
+{
+    if (h->state == ST_MO)       // row t of the device's mo_T x mcp block -> mu[t][0 .. mc)
+        GPX_HIP(hipMemcpy2DAsync(mu, stride * 8, h->mu.p, (size_t)mcp * 8, (size_t)mc * 8,
+                                 h->mo_T, hipMemcpyDeviceToHost, h->stream));
+    else
+        GPX_HIP(hipMemcpyAsync(mu, h->state == ST_LAPLACE ? h->lp_mu.p : h->mu.p, (size_t)mc * 8,
+                               hipMemcpyDeviceToHost, h->stream));
+    return 0;
+}
+
+// what: the calling entry, of the family `state`; the handle must be in that state. ST_MO: mu is
+// mo_T rows of m doubles.
+static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2,
+                          double *dmu, double *ds2, int state, const char *what)
+{
+    CHECK_H(h);
+    GPX_TRY(posterior_ready(h, state, what));
     if (!Xs || !mu || !s2 || m < 0) {
-        gpx_set_error("gpx_exact_posterior: bad arguments");
+        gpx_set_error("%s: bad arguments", what);
         return -1;
     }
     // test points per pass: as many as keep the two np x CH panels within ~2 GB
     // (one pass = one host synchronisation)
     const int CH = h->np <= 8192 ? 8192 : (h->np <= 16384 ? 4096 : 2048);
-    const DenseWs w = h->ws();
     const bool grads = dmu && ds2;
-    // V = R^-T K* is a triangle-aware product with W^T and one step of refinement
-    // (solve_rt_refined), so W = R^-1 is completed first if the factorisation left only
-    // the inverses of its diagonal blocks (a fraction of the factorisation's cost)
     ++h->posterior_calls;
-    if (!h->w_complete) {
-        GPX_TRY(gpx_trtri(h->stream, w));
-        h->w_complete = true;
-    }
-    if (grads) {
-        GPX_TRY(h->alpha.reserve((size_t)h->np * 8));
-        GPX_TRY(gpx_trmv_upper(h->stream, w.W, h->ld, h->np, h->a.as<double>(),
-                               h->alpha.as<double>()));
-    }
+    GPX_TRY(complete_w(h));
+    if (grads) GPX_TRY(solve_alpha(h));
     const double prior = gpx_kernel_prior(h->kp);
     StageClock clk(h);
     for (int64_t c0 = 0; c0 < m; c0 += CH) {
         const int mc = (int)std::min<int64_t>(CH, m - c0);
         const int mcp = round_up(mc, GPX_TILE);
-        GPX_TRY(h->Xs.reserve((size_t)mc * h->d * 8));
-        GPX_TRY(h->Ks.reserve((size_t)h->np * mcp * 8));
-        GPX_TRY(h->KsT.reserve((size_t)h->np * mcp * 8));
-        GPX_TRY(h->mu.reserve((size_t)mcp * 8 * (h->mo_T ? h->mo_T : 1)));
-        GPX_TRY(h->s2.reserve((size_t)mcp * 8));
-        GPX_TRY(h->post_part.reserve((h->mo_T ? gpx_mo_posterior_scratch(mcp)
-                                              : gpx_posterior_scratch(mcp)) * 8));
-        GPX_HIP(hipMemcpyAsync(h->Xs.p, Xs + c0 * h->d, (size_t)mc * h->d * 8,
-                               hipMemcpyHostToDevice, h->stream));
-        // K(X, Xs): np x mcp, zero outside n x mc (exact.py:87)
-        GPX_TRY(build_cross(h, mc, mcp));
-        if (h->laplace) GPX_TRY(laplace_cross(h, mcp));
-        clk.tick(T_POST_BUILD);
-        // RK = R^-T K (exact.py:88)
-        double *V = h->KsT.as<double>();
-        GPX_TRY(solve_rt_refined(h, h->Ks.as<double>(), V, mcp));
-        if (h->mo_T)
-            GPX_TRY(gpx_mo_posterior_reduce(h->stream, V, mcp, h->np, mcp, h->a.as<double>(),
-                                            h->mo_T, h->cap, h->mean, prior,
-                                            h->post_part.as<double>(), h->mu.as<double>(),
-                                            h->s2.as<double>()));
-        else
-            GPX_TRY(gpx_posterior_reduce(h->stream, V, mcp, h->np, mcp,
-                                         h->a.as<double>(), h->mean, prior,
-                                         h->post_part.as<double>(), h->mu.as<double>(),
-                                         h->s2.as<double>()));
+        double *V;
+        GPX_TRY(posterior_pass(h, Xs + c0 * h->d, mc, mcp, prior, &V, &clk));
         clk.tick(T_POST_SOLVE);
         if (grads) {
             // beta = W V (V = R^-T K*): W upper -> k >= row tile
@@ -1688,12 +1716,7 @@ static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, dou
             GPX_HIP(hipMemcpyAsync(ds2 + c0 * h->d, h->t1.p, (size_t)mc * h->d * 8,
                                    hipMemcpyDeviceToHost, h->stream));
         }
-        if (h->mo_T)         // row t of the device's mo_T x mcp block -> mu[t][c0 ..)
-            GPX_HIP(hipMemcpy2DAsync(mu + c0, (size_t)m * 8, h->mu.p, (size_t)mcp * 8,
-                                     (size_t)mc * 8, h->mo_T, hipMemcpyDeviceToHost, h->stream));
-        else
-            GPX_HIP(hipMemcpyAsync(mu + c0, h->laplace ? h->lp_mu.p : h->mu.p, (size_t)mc * 8,
-                                   hipMemcpyDeviceToHost, h->stream));
+        GPX_TRY(copy_mean(h, mu + c0, (size_t)m, mc, mcp));
         GPX_HIP(hipMemcpyAsync(s2 + c0, h->s2.p, (size_t)mc * 8, hipMemcpyDeviceToHost,
                                h->stream));
         GPX_HIP(hipStreamSynchronize(h->stream));
@@ -1706,49 +1729,19 @@ static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, dou
 // Sigma = K(Xs, Xs) - V^T V, V = R^-T K(X, Xs); GP.sample draws from it
 // (_base.py:143-178). One pass, m <= 8192.
 static int posterior_full_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma,
-                               int state)
+                               int state, const char *what)
 {
     CHECK_H(h);
-    GPX_TRY(check_state(h, state, state == ST_MO ? "gpx_mo_posterior_full"
-                                  : state == ST_GRADOBS ? "gpx_gradobs_posterior_full"
-                                  : state == ST_LAPLACE ? "gpx_laplace_posterior_full"
-                                                        : "gpx_exact_posterior_full"));
-    if (!h->have_factor) {
-        gpx_set_error("gpx_exact_posterior_full: no factorisation (call gpx_exact_update)");
-        return -1;
-    }
+    GPX_TRY(posterior_ready(h, state, what));
     if (!Xs || !mu || !Sigma || m < 1 || m > 8192) {
-        gpx_set_error("gpx_exact_posterior_full: bad arguments (1 <= m <= 8192)");
+        gpx_set_error("%s: bad arguments (1 <= m <= 8192)", what);
         return -1;
     }
-    const DenseWs w = h->ws();
-    if (!h->w_complete) {
-        GPX_TRY(gpx_trtri(h->stream, w));
-        h->w_complete = true;
-    }
+    GPX_TRY(complete_w(h));
     const int mc = (int)m, mcp = round_up(mc, GPX_TILE);
-    GPX_TRY(h->Xs.reserve((size_t)mc * h->d * 8));
-    GPX_TRY(h->Ks.reserve((size_t)h->np * mcp * 8));
-    GPX_TRY(h->KsT.reserve((size_t)h->np * mcp * 8));
-    GPX_TRY(h->mu.reserve((size_t)mcp * 8 * (h->mo_T ? h->mo_T : 1)));
-    GPX_TRY(h->s2.reserve((size_t)mcp * 8));
-    GPX_TRY(h->post_part.reserve((h->mo_T ? gpx_mo_posterior_scratch(mcp)
-                                          : gpx_posterior_scratch(mcp)) * 8));
     GPX_TRY(h->t2.reserve((size_t)mcp * mcp * 8));
-    GPX_HIP(hipMemcpyAsync(h->Xs.p, Xs, (size_t)mc * h->d * 8, hipMemcpyHostToDevice,
-                           h->stream));
-    GPX_TRY(build_cross(h, mc, mcp));
-    if (h->laplace) GPX_TRY(laplace_cross(h, mcp));
-    double *V = h->KsT.as<double>();
-    GPX_TRY(solve_rt_refined(h, h->Ks.as<double>(), V, mcp));
-    if (h->mo_T)
-        GPX_TRY(gpx_mo_posterior_reduce(h->stream, V, mcp, h->np, mcp, h->a.as<double>(), h->mo_T,
-                                        h->cap, h->mean, 0.0, h->post_part.as<double>(),
-                                        h->mu.as<double>(), h->s2.as<double>()));
-    else
-        GPX_TRY(gpx_posterior_reduce(h->stream, V, mcp, h->np, mcp, h->a.as<double>(), h->mean,
-                                     0.0, h->post_part.as<double>(), h->mu.as<double>(),
-                                     h->s2.as<double>()));
+    double *V;
+    GPX_TRY(posterior_pass(h, Xs, mc, mcp, 0.0, &V));
     // Sigma = K(Xs, Xs) - V^T V on the padded mcp x mcp block
     GPX_TRY(gpx_kbuild<double>(h->stream, h->kp, h->Xs.as<double>(), mc, mcp,
                                h->Xs.as<double>(), mc, mcp, h->d, h->t2.as<double>(), mcp,
@@ -1759,12 +1752,7 @@ static int posterior_full_impl(gpx_t *h, const double *Xs, int64_t m, double *mu
     g.M = mcp; g.N = mcp; g.K = h->np;
     g.alpha = -1.0; g.beta = 1.0;
     GPX_TRY(gpx_gemm(h->stream, 1, 0, g));
-    if (h->mo_T)
-        GPX_HIP(hipMemcpy2DAsync(mu, (size_t)mc * 8, h->mu.p, (size_t)mcp * 8, (size_t)mc * 8,
-                                 h->mo_T, hipMemcpyDeviceToHost, h->stream));
-    else
-        GPX_HIP(hipMemcpyAsync(mu, h->laplace ? h->lp_mu.p : h->mu.p, (size_t)mc * 8,
-                               hipMemcpyDeviceToHost, h->stream));
+    GPX_TRY(copy_mean(h, mu, (size_t)mc, mc, mcp));
     GPX_HIP(hipMemcpy2DAsync(Sigma, (size_t)mc * 8, h->t2.p, (size_t)mcp * 8, (size_t)mc * 8, mc,
                              hipMemcpyDeviceToHost, h->stream));
     GPX_HIP(hipStreamSynchronize(h->stream));
@@ -1773,12 +1761,12 @@ static int posterior_full_impl(gpx_t *h, const double *Xs, int64_t m, double *mu
 
 int gpx_exact_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma)
 {
-    return posterior_full_impl(h, Xs, m, mu, Sigma, ST_PLAIN);
+    return posterior_full_impl(h, Xs, m, mu, Sigma, ST_PLAIN, "gpx_exact_posterior_full");
 }
 
 int gpx_exact_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2)
 {
-    return posterior_impl(h, Xs, m, mu, s2, nullptr, nullptr);
+    return posterior_impl(h, Xs, m, mu, s2, nullptr, nullptr, ST_PLAIN, "gpx_exact_posterior");
 }
 
 int gpx_exact_posterior_grad(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2,
@@ -1788,7 +1776,7 @@ int gpx_exact_posterior_grad(gpx_t *h, const double *Xs, int64_t m, double *mu, 
         gpx_set_error("gpx_exact_posterior_grad: null gradient outputs");
         return -1;
     }
-    return posterior_impl(h, Xs, m, mu, s2, dmu, ds2);
+    return posterior_impl(h, Xs, m, mu, s2, dmu, ds2, ST_PLAIN, "gpx_exact_posterior_grad");
 }
 
 // [m.posterior(X, grad) for m in samples] of the reference's meta-models
@@ -1800,7 +1788,7 @@ int gpx_posterior_batch(gpx_t *h, const gpx_kspec *k, const double *thetas, int6
                         double *ds2, int *info)
 {
     CHECK_H(h);
-    PLAIN_ONLY(h, "gpx_posterior_batch");
+    GPX_TRY(require_state(h, ST_PLAIN, "gpx_posterior_batch"));
     if (!k || !thetas || !Xs || !mu || !s2 || B < 0 || m < 0 || (!dmu) != (!ds2)) {
         gpx_set_error("gpx_posterior_batch: bad arguments");
         return -1;
@@ -1857,7 +1845,8 @@ int gpx_posterior_batch(gpx_t *h, const gpx_kspec *k, const double *thetas, int6
         double *dmub = grads ? dmu + b * m * c->d : nullptr;
         double *ds2b = grads ? ds2 + b * m * c->d : nullptr;
         int r = 0;
-        if (m > 0) r = posterior_impl(c, Xs, m, mub, s2b, dmub, ds2b);
+        if (m > 0)
+            r = posterior_impl(c, Xs, m, mub, s2b, dmub, ds2b, ST_PLAIN, "gpx_posterior_batch");
         else GPX_HIP(hipStreamSynchronize(c->stream));
         if (r < 0) return r;
         const int inf = *c->hinfo;
@@ -1958,28 +1947,16 @@ int gpx_kernel_gradxy(gpx_t *h, const gpx_kspec *k, const double *X1, int64_t n1
 int gpx_exact_posterior_gradient(gpx_t *h, const double *Xs, int64_t m, double *dmu, double *S)
 {
     CHECK_H(h);
-    PLAIN_ONLY(h, "gpx_exact_posterior_gradient");
-    if (!h->have_factor) {
-        gpx_set_error("gpx_exact_posterior_gradient: no factorisation (call gpx_exact_update)");
-        return -1;
-    }
+    GPX_TRY(posterior_ready(h, ST_PLAIN, "gpx_exact_posterior_gradient"));
     if (!Xs || m < 1) {
         gpx_set_error("gpx_exact_posterior_gradient: bad arguments (m >= 1)");
         return -1;
     }
     GPX_TRY(gpx_gradxy_check(h->kp, h->d));
     if (!dmu && !S) return 0;
-    const DenseWs w = h->ws();
     const int d = h->d;
-    if (!h->w_complete) {
-        GPX_TRY(gpx_trtri(h->stream, w));
-        h->w_complete = true;
-    }
-    if (dmu) {                                          // alpha = R^-1 a, as posterior_impl
-        GPX_TRY(h->alpha.reserve((size_t)h->np * 8));
-        GPX_TRY(gpx_trmv_upper(h->stream, w.W, h->ld, h->np, h->a.as<double>(),
-                               h->alpha.as<double>()));
-    }
+    GPX_TRY(complete_w(h));
+    if (dmu) GPX_TRY(solve_alpha(h));
     const int CH = 8192 / d;                            // test points of a pass
     StageClock clk(h);
     for (int64_t c0 = 0; c0 < m; c0 += CH) {
@@ -2041,13 +2018,7 @@ int gpx_gradobs_set_data(gpx_t *h, const double *X, int64_t n, const double *y,
     GPX_TRY(h->X.reserve(cap * d * 8));
     GPX_TRY(h->y.reserve(cap * 8));
     GPX_TRY(h->Xg.reserve((size_t)ng * d * 8));
-    // a failure from here on leaves the buffers half written: no data of either kind
-    h->n = 0;
-    h->have_factor = h->have_inverse = false;
-    h->gradobs = false;
-    h->mo_T = 0;
-    h->laplace = h->lp_mode = false;
-    h->data_version++;
+    drop_data(h);
     if (n > 0) {
         GPX_HIP(hipMemcpyAsync(h->X.p, X, (size_t)n * d * 8, hipMemcpyHostToDevice, h->stream));
         GPX_HIP(hipMemcpyAsync(h->y.p, y, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
@@ -2056,12 +2027,7 @@ int gpx_gradobs_set_data(gpx_t *h, const double *X, int64_t n, const double *y,
     GPX_HIP(hipMemcpyAsync(h->y.as<double>() + n, G, (size_t)ng * d * 8, hipMemcpyHostToDevice,
                            h->stream));
     GPX_HIP(hipStreamSynchronize(h->stream));
-    h->n = (int)M;
-    h->d = (int)d;
-    h->np = round_up(M, GPX_TILE);
-    h->cap = (int)cap;
-    h->ld = ld_for(h->cap);
-    h->gradobs = true;
+    commit_data(h, ST_GRADOBS, M, d, cap);
     h->go_n = (int)n;
     h->go_ng = (int)ng;
     return 0;
@@ -2071,13 +2037,7 @@ int gpx_gradobs_update(gpx_t *h, const gpx_kspec *k, double log_sn, double grad_
                        double mean, int *info)
 {
     CHECK_H(h);
-    if (!h->gradobs) {
-        gpx_set_error(h->laplace ? "gpx_gradobs_update: the handle holds classification labels "
-                                   "(gpx_laplace_*)"
-                                 : "gpx_gradobs_update: no gradient observations "
-                                   "(gpx_gradobs_set_data)");
-        return -1;
-    }
+    GPX_TRY(require_state(h, ST_GRADOBS, "gpx_gradobs_update"));
     if (!std::isfinite(log_sn) || !std::isfinite(mean) || !std::isfinite(grad_noise) ||
         grad_noise < 0) {
         gpx_set_error("gpx_gradobs_update: non-finite hyperparameters or grad_noise < 0");
@@ -2100,7 +2060,8 @@ int gpx_gradobs_update(gpx_t *h, const gpx_kspec *k, double log_sn, double grad_
 int gpx_gradobs_loglik(gpx_t *h, double *lZ)
 {
     CHECK_H(h);
-    if (!h->gradobs || !h->have_factor) {
+    GPX_TRY(require_state(h, ST_GRADOBS, "gpx_gradobs_loglik"));
+    if (!h->have_factor) {
         gpx_set_error("gpx_gradobs_loglik: no factorisation (call gpx_gradobs_update)");
         return -1;
     }
@@ -2110,12 +2071,13 @@ int gpx_gradobs_loglik(gpx_t *h, double *lZ)
 
 int gpx_gradobs_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2)
 {
-    return posterior_impl(h, Xs, m, mu, s2, nullptr, nullptr, ST_GRADOBS);
+    return posterior_impl(h, Xs, m, mu, s2, nullptr, nullptr, ST_GRADOBS,
+                          "gpx_gradobs_posterior");
 }
 
 int gpx_gradobs_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma)
 {
-    return posterior_full_impl(h, Xs, m, mu, Sigma, ST_GRADOBS);
+    return posterior_full_impl(h, Xs, m, mu, Sigma, ST_GRADOBS, "gpx_gradobs_posterior_full");
 }
 
 // ---- binary classification: Laplace's approximation (GPML algorithms 3.1, 3.2, 5.1) ------------
@@ -2134,8 +2096,7 @@ int gpx_laplace_set_data(gpx_t *h, const double *X, int64_t n, int64_t d, const 
             return -1;
         }
     GPX_TRY(gpx_set_data(h, X, n, d, y));
-    h->laplace = true;
-    h->lp_mode = false;
+    h->state = ST_LAPLACE;
     return 0;
 }
 
@@ -2227,7 +2188,7 @@ int gpx_laplace_update(gpx_t *h, const gpx_kspec *k, int lik, double mean, doubl
                        int max_iter, int warm, int *iters, int *info)
 {
     CHECK_H(h);
-    GPX_TRY(check_state(h, ST_LAPLACE, "gpx_laplace_update"));
+    GPX_TRY(require_state(h, ST_LAPLACE, "gpx_laplace_update"));
     if ((lik != GPX_LIK_LOGISTIC && lik != GPX_LIK_PROBIT) || !std::isfinite(mean) ||
         !(tol > 0) || !std::isfinite(tol) || max_iter < 1) {
         gpx_set_error("gpx_laplace_update: bad arguments (a likelihood of gpx_likelihood, a finite "
@@ -2352,7 +2313,7 @@ int gpx_laplace_update(gpx_t *h, const gpx_kspec *k, int lik, double mean, doubl
 int gpx_laplace_loglik(gpx_t *h, double *lZ, double *dlZ)
 {
     CHECK_H(h);
-    GPX_TRY(check_state(h, ST_LAPLACE, "gpx_laplace_loglik"));
+    GPX_TRY(require_state(h, ST_LAPLACE, "gpx_laplace_loglik"));
     if (!h->have_factor) {
         gpx_set_error("gpx_laplace_loglik: no mode (call gpx_laplace_update)");
         return -1;
@@ -2399,18 +2360,19 @@ int gpx_laplace_loglik(gpx_t *h, double *lZ, double *dlZ)
 
 int gpx_laplace_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2)
 {
-    return posterior_impl(h, Xs, m, mu, s2, nullptr, nullptr, ST_LAPLACE);
+    return posterior_impl(h, Xs, m, mu, s2, nullptr, nullptr, ST_LAPLACE,
+                          "gpx_laplace_posterior");
 }
 
 int gpx_laplace_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma)
 {
-    return posterior_full_impl(h, Xs, m, mu, Sigma, ST_LAPLACE);
+    return posterior_full_impl(h, Xs, m, mu, Sigma, ST_LAPLACE, "gpx_laplace_posterior_full");
 }
 
 int gpx_laplace_get_mode(gpx_t *h, int64_t n, double *f, double *g)
 {
     CHECK_H(h);
-    GPX_TRY(check_state(h, ST_LAPLACE, "gpx_laplace_get_mode"));
+    GPX_TRY(require_state(h, ST_LAPLACE, "gpx_laplace_get_mode"));
     if (!h->have_factor || n != h->n) {
         gpx_set_error("gpx_laplace_get_mode: no mode for %lld points (call gpx_laplace_update)",
                       (long long)n);
@@ -2446,24 +2408,13 @@ int gpx_mo_set_data(gpx_t *h, const double *X, int64_t n, const double *Y, int64
     const size_t cap = (size_t)round_up(n + 256, 1024);      // as gpx_set_data
     GPX_TRY(h->X.reserve(cap * d * 8));
     GPX_TRY(h->y.reserve(cap * T * 8));
-    // a failure from here on leaves the buffers half written: no data of any kind
-    h->n = 0;
-    h->have_factor = h->have_inverse = false;
-    h->gradobs = false;
-    h->go_n = h->go_ng = 0;
-    h->mo_T = 0;
-    h->laplace = h->lp_mode = false;
-    h->data_version++;
+    drop_data(h);
     GPX_HIP(hipMemcpyAsync(h->X.p, X, (size_t)n * d * 8, hipMemcpyHostToDevice, h->stream));
     // column t of Y (n contiguous doubles) -> y + t cap
     GPX_HIP(hipMemcpy2DAsync(h->y.p, cap * 8, Y, (size_t)n * 8, (size_t)n * 8, (size_t)T,
                              hipMemcpyHostToDevice, h->stream));
     GPX_HIP(hipStreamSynchronize(h->stream));
-    h->n = (int)n;
-    h->d = (int)d;
-    h->np = round_up(n, GPX_TILE);
-    h->cap = (int)cap;
-    h->ld = ld_for(h->cap);
+    commit_data(h, ST_MO, n, d, cap);
     h->mo_T = (int)T;
     return 0;
 }
@@ -2483,7 +2434,7 @@ static int reserve_mo(gpx_ctx *h, bool inverse)
 int gpx_mo_update(gpx_t *h, const gpx_kspec *k, double log_sn, double mean, int *info)
 {
     CHECK_H(h);
-    GPX_TRY(check_state(h, ST_MO, "gpx_mo_update"));
+    GPX_TRY(require_state(h, ST_MO, "gpx_mo_update"));
     GPX_TRY(check_ready(h, k, log_sn, mean));
     h->have_factor = h->have_inverse = false;
     GPX_TRY(reserve_mo(h, false));
@@ -2497,7 +2448,7 @@ int gpx_mo_update(gpx_t *h, const gpx_kspec *k, double log_sn, double mean, int 
 int gpx_mo_loglik(gpx_t *h, double *lZ, double *dlZ)
 {
     CHECK_H(h);
-    GPX_TRY(check_state(h, ST_MO, "gpx_mo_loglik"));
+    GPX_TRY(require_state(h, ST_MO, "gpx_mo_loglik"));
     if (!h->have_factor) {
         gpx_set_error("gpx_mo_loglik: no factorisation (call gpx_mo_update)");
         return -1;
@@ -2517,12 +2468,13 @@ int gpx_mo_loglik(gpx_t *h, double *lZ, double *dlZ)
 
 int gpx_mo_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2)
 {
-    return posterior_impl(h, Xs, m, mu, s2, nullptr, nullptr, ST_MO);
+    return posterior_impl(h, Xs, m, mu, s2, nullptr, nullptr, ST_MO,
+                          "gpx_mo_posterior");
 }
 
 int gpx_mo_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma)
 {
-    return posterior_full_impl(h, Xs, m, mu, Sigma, ST_MO);
+    return posterior_full_impl(h, Xs, m, mu, Sigma, ST_MO, "gpx_mo_posterior_full");
 }
 
 static int sparse_ready(gpx_ctx *h, const char *what)
@@ -2542,7 +2494,7 @@ int gpx_sparse_update(gpx_t *h, const gpx_kspec *k, int method, const double *U,
                       double log_sn, double mean, int *info)
 {
     CHECK_H(h);
-    PLAIN_ONLY(h, "gpx_sparse_update");
+    GPX_TRY(require_state(h, ST_PLAIN, "gpx_sparse_update"));
     if (info) *info = 0;
     h->sparse_version = -1;
     if (h->n <= 0) {
@@ -2589,7 +2541,7 @@ int gpx_sparse_update(gpx_t *h, const gpx_kspec *k, int method, const double *U,
 int gpx_sparse_append(gpx_t *h, const double *Xnew, const double *ynew, int64_t m, int *info)
 {
     CHECK_H(h);
-    PLAIN_ONLY(h, "gpx_sparse_append");
+    GPX_TRY(require_state(h, ST_PLAIN, "gpx_sparse_append"));
     if (info) *info = 0;
     if (!Xnew || !ynew || m < 1) {
         gpx_set_error("gpx_sparse_append: bad arguments");
@@ -2705,7 +2657,7 @@ int gpx_select_pivots(gpx_t *h, const gpx_kspec *k, const double *X, int64_t n, 
                       int64_t *count)
 {
     CHECK_H(h);
-    PLAIN_ONLY(h, "gpx_select_pivots");
+    GPX_TRY(require_state(h, ST_PLAIN, "gpx_select_pivots"));
     if (!k || !idx || !count) {
         gpx_set_error("gpx_select_pivots: k, idx and count must not be null");
         return -1;
@@ -2765,7 +2717,7 @@ int gpx_select_timing(gpx_t *h, double *ms)
 int gpx_exact_get_factor(gpx_t *h, int64_t n, double *R, double *a)
 {
     CHECK_H(h);
-    PLAIN_ONLY(h, "gpx_exact_get_factor");
+    GPX_TRY(require_state(h, ST_PLAIN, "gpx_exact_get_factor"));
     if (!h->have_factor) {
         gpx_set_error("gpx_exact_get_factor: no factorisation");
         return -1;

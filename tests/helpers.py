@@ -52,3 +52,13 @@ def amd_kernel(desc):
 def relerr(a, b):
     a, b = np.asarray(a, float), np.asarray(b, float)
     return np.max(np.abs(a - b) / np.maximum(np.abs(b), 1e-300)) if a.size else 0.0
+
+
+def assert_refused(h, calls, families, holds):
+    """Every entry of these families of tests/handle_calls.py returns -1 on the handle h and
+    says what the handle holds."""
+    for name, call in sorted(sum((list(calls[f].items()) for f in families), [])):
+        code = call()
+        text = h._L.gpx_last_error().decode()
+        assert code == -1, (holds, name, code)
+        assert 'the handle holds ' + holds in text, (holds, name, text)

@@ -4,7 +4,6 @@ float64 NumPy / SciPy reference of tests/gradobs_ref.py, which tests/test_gradob
 to longdouble a hundred times tighter than the tolerances here."""
 
 import copy
-import ctypes as C
 import functools
 import pickle
 
@@ -14,7 +13,8 @@ import pytest
 
 import gradobs_ref as gor
 import gradxy_ref as gr
-from helpers import amd_kernel, oracle_spec
+from handle_calls import handle_calls
+from helpers import amd_kernel, assert_refused, oracle_spec
 from oracle import gp_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -193,50 +193,15 @@ def test_a_gradient_handle_refuses_the_plain_entries():
     desc = gr.family('se_ard', 3)
     spec = amd_kernel(desc)._kspec()
     h = _lib.Handle()
-    L, hp, ptr = h._L, h._h, _lib._ptr
     h.gradobs_set_data(X, y, Xg, G)
     h.gradobs_update(spec, np.log(SN), GN, MEAN)
     nt.assert_allclose(h.gradobs_loglik(),
                        gor.fit(oracle_spec(desc), np.log(SN), GN, MEAN, X, y, Xg, G)['lZ'],
                        rtol=RTOL_LZ)
-    M, nth = 20 + 5 * 3, spec.c.nhyper + 2
-    lZ, info, cnt = C.c_double(0), C.c_int(0), C.c_int64(0)
-    buf = [np.zeros(max(M * M, 64)) for _ in range(4)]
     theta = np.r_[np.log(SN), amd_kernel(desc).get_hyper(), MEAN]
-    calls = {
-        'gpx_exact_update': lambda: L.gpx_exact_update(hp, spec.ref(), np.log(SN), MEAN,
-                                                       C.byref(info)),
-        'gpx_exact_loglik': lambda: L.gpx_exact_loglik(hp, C.byref(lZ), None),
-        'gpx_exact_loglik dlZ': lambda: L.gpx_exact_loglik(hp, C.byref(lZ), ptr(buf[0])),
-        'gpx_exact_eval': lambda: L.gpx_exact_eval(hp, spec.ref(), np.log(SN), MEAN, 1,
-                                                   C.byref(lZ), ptr(buf[0]), C.byref(info)),
-        'gpx_exact_append': lambda: L.gpx_exact_append(hp, ptr(X[:2].copy()), ptr(y[:2].copy()),
-                                                       2, C.byref(info)),
-        'gpx_exact_loo': lambda: L.gpx_exact_loo(hp, C.byref(lZ), None, None, None),
-        'gpx_exact_posterior': lambda: L.gpx_exact_posterior(hp, ptr(Xs), 4, ptr(buf[0]),
-                                                             ptr(buf[1])),
-        'gpx_exact_posterior_grad': lambda: L.gpx_exact_posterior_grad(
-            hp, ptr(Xs), 4, ptr(buf[0]), ptr(buf[1]), ptr(buf[2]), ptr(buf[3])),
-        'gpx_exact_posterior_full': lambda: L.gpx_exact_posterior_full(hp, ptr(Xs), 4,
-                                                                       ptr(buf[0]), ptr(buf[1])),
-        'gpx_exact_posterior_gradient': lambda: L.gpx_exact_posterior_gradient(
-            hp, ptr(Xs), 4, ptr(buf[0]), ptr(buf[1])),
-        'gpx_exact_get_factor': lambda: L.gpx_exact_get_factor(hp, M, ptr(buf[0]), ptr(buf[1])),
-        'gpx_loglik_batch': lambda: L.gpx_loglik_batch(hp, spec.ref(), ptr(theta), 1, 0,
-                                                       ptr(buf[0]), None, None),
-        'gpx_posterior_batch': lambda: L.gpx_posterior_batch(
-            hp, spec.ref(), ptr(theta), 1, ptr(Xs), 4, ptr(buf[0]), ptr(buf[1]), None, None,
-            None),
-        'gpx_sparse_update': lambda: L.gpx_sparse_update(hp, spec.ref(), _lib.GPX_DTC,
-                                                         ptr(X[:4].copy()), 4, np.log(SN), MEAN,
-                                                         C.byref(info)),
-    }
-    assert len(theta) == nth
-    for name, call in sorted(calls.items()):
-        code = call()
-        text = L.gpx_last_error().decode()
-        assert code < 0 and code != -3, (name, code)
-        assert 'gradient observations' in text, (name, text)
+    assert len(theta) == spec.c.nhyper + 2
+    calls = handle_calls(h, spec, theta, X, y, Xs)
+    assert_refused(h, calls, set(calls) - {'gradobs'}, 'gradient observations')
     # the refusals left the factorisation alone ...
     mu, s2 = h.gradobs_posterior(Xs)
     ref = gor.fit(oracle_spec(desc), np.log(SN), GN, MEAN, X, y, Xg, G)
@@ -246,9 +211,7 @@ def test_a_gradient_handle_refuses_the_plain_entries():
     # ... and gpx_set_data returns the handle to the plain entries
     h.set_data(X, y)
     for name in ('gpx_gradobs_loglik', 'gpx_gradobs_posterior'):
-        code = (L.gpx_gradobs_loglik(hp, C.byref(lZ)) if name.endswith('loglik') else
-                L.gpx_gradobs_posterior(hp, ptr(Xs), 4, ptr(buf[0]), ptr(buf[1])))
-        assert code < 0, name
+        assert calls['gradobs'][name]() < 0, name
     h.exact_update(spec, np.log(SN), MEAN)
     R, a = orc.exact_update(oracle_spec(desc), np.log(SN), MEAN, X, y)
     nt.assert_allclose(h.exact_loglik(spec.c.nhyper),

@@ -4,7 +4,6 @@ the float64 NumPy / SciPy reference of tests/laplace_ref.py, which tests/test_la
 holds to longdouble a hundred times tighter than the tolerances here."""
 
 import copy
-import ctypes as C
 import functools
 import pickle
 
@@ -13,7 +12,8 @@ import numpy.testing as nt
 import pytest
 
 import laplace_ref as lr
-from helpers import amd_kernel, oracle_spec
+from handle_calls import handle_calls
+from helpers import amd_kernel, assert_refused, oracle_spec
 from oracle import gp_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -196,62 +196,13 @@ def test_a_laplace_handle_refuses_the_other_entries():
     spec = amd_kernel(desc)._kspec()
     ref = lr.fit(oracle_spec(desc), 'probit', MEAN, X, y)
     h = _lib.Handle()
-    L, hp, ptr = h._L, h._h, _lib._ptr
     h.laplace_set_data(X, y)
     h.laplace_update(spec, lr.CODE['probit'], MEAN)
     nt.assert_allclose(h.laplace_loglik(spec.c.nhyper), ref['lZ'], rtol=RTOL_LZ)
-    lZ, info, cnt = C.c_double(0), C.c_int(0), C.c_int64(0)
-    buf = [np.zeros(1024) for _ in range(4)]
-    idx = np.zeros(4, dtype=np.int64)
     sn = np.log(0.1)
     theta = np.r_[sn, amd_kernel(desc).get_hyper(), MEAN]
-    calls = {
-        'gpx_exact_update': lambda: L.gpx_exact_update(hp, spec.ref(), sn, MEAN, C.byref(info)),
-        'gpx_exact_loglik': lambda: L.gpx_exact_loglik(hp, C.byref(lZ), None),
-        'gpx_exact_loglik dlZ': lambda: L.gpx_exact_loglik(hp, C.byref(lZ), ptr(buf[0])),
-        'gpx_exact_eval': lambda: L.gpx_exact_eval(hp, spec.ref(), sn, MEAN, 1, C.byref(lZ),
-                                                   ptr(buf[0]), C.byref(info)),
-        'gpx_exact_append': lambda: L.gpx_exact_append(hp, ptr(X[:2].copy()), ptr(y[:2].copy()),
-                                                       2, C.byref(info)),
-        'gpx_exact_loo': lambda: L.gpx_exact_loo(hp, C.byref(lZ), None, None, None),
-        'gpx_exact_posterior': lambda: L.gpx_exact_posterior(hp, ptr(Xs), 4, ptr(buf[0]),
-                                                             ptr(buf[1])),
-        'gpx_exact_posterior_grad': lambda: L.gpx_exact_posterior_grad(
-            hp, ptr(Xs), 4, ptr(buf[0]), ptr(buf[1]), ptr(buf[2]), ptr(buf[3])),
-        'gpx_exact_posterior_full': lambda: L.gpx_exact_posterior_full(hp, ptr(Xs), 4,
-                                                                       ptr(buf[0]), ptr(buf[1])),
-        'gpx_exact_posterior_gradient': lambda: L.gpx_exact_posterior_gradient(
-            hp, ptr(Xs), 4, ptr(buf[0]), ptr(buf[1])),
-        'gpx_exact_get_factor': lambda: L.gpx_exact_get_factor(hp, 20, ptr(buf[0]), ptr(buf[1])),
-        'gpx_loglik_batch': lambda: L.gpx_loglik_batch(hp, spec.ref(), ptr(theta), 1, 0,
-                                                       ptr(buf[0]), None, None),
-        'gpx_posterior_batch': lambda: L.gpx_posterior_batch(
-            hp, spec.ref(), ptr(theta), 1, ptr(Xs), 4, ptr(buf[0]), ptr(buf[1]), None, None,
-            None),
-        'gpx_batch_plan': lambda: L.gpx_batch_plan(hp, 4, 0, C.cast(ptr(idx), _lib._ip)),
-        'gpx_sparse_update': lambda: L.gpx_sparse_update(hp, spec.ref(), _lib.GPX_DTC,
-                                                         ptr(X[:4].copy()), 4, sn, MEAN,
-                                                         C.byref(info)),
-        'gpx_select_pivots': lambda: L.gpx_select_pivots(hp, spec.ref(), None, 20, 3, 4, 0.0,
-                                                         ptr(idx), None, None, C.byref(cnt)),
-        'gpx_gradobs_update': lambda: L.gpx_gradobs_update(hp, spec.ref(), sn, 0.0, MEAN,
-                                                           C.byref(info)),
-        'gpx_gradobs_loglik': lambda: L.gpx_gradobs_loglik(hp, C.byref(lZ)),
-        'gpx_gradobs_posterior': lambda: L.gpx_gradobs_posterior(hp, ptr(Xs), 4, ptr(buf[0]),
-                                                                 ptr(buf[1])),
-        'gpx_gradobs_posterior_full': lambda: L.gpx_gradobs_posterior_full(
-            hp, ptr(Xs), 4, ptr(buf[0]), ptr(buf[1])),
-        'gpx_mo_update': lambda: L.gpx_mo_update(hp, spec.ref(), sn, MEAN, C.byref(info)),
-        'gpx_mo_loglik': lambda: L.gpx_mo_loglik(hp, C.byref(lZ), None),
-        'gpx_mo_posterior': lambda: L.gpx_mo_posterior(hp, ptr(Xs), 4, ptr(buf[0]), ptr(buf[1])),
-        'gpx_mo_posterior_full': lambda: L.gpx_mo_posterior_full(hp, ptr(Xs), 4, ptr(buf[0]),
-                                                                 ptr(buf[1])),
-    }
-    for name, call in sorted(calls.items()):
-        code = call()
-        text = L.gpx_last_error().decode()
-        assert code < 0 and code != -3, (name, code)
-        assert text, name
+    calls = handle_calls(h, spec, theta, X, y, Xs)
+    assert_refused(h, calls, set(calls) - {'laplace'}, 'classification labels')
     # the refusals left the mode and the factorisation alone ...
     mu, s2 = h.laplace_posterior(Xs)
     want = lr.posterior(ref, Xs)
@@ -261,10 +212,8 @@ def test_a_laplace_handle_refuses_the_other_entries():
     # ... gpx_set_data returns the handle to the plain entries, which the Laplace entries refuse
     yr = np.sin(X.sum(axis=1))
     h.set_data(X, yr)
-    assert L.gpx_laplace_loglik(hp, C.byref(lZ), None) < 0
-    assert L.gpx_laplace_posterior(hp, ptr(Xs), 4, ptr(buf[0]), ptr(buf[1])) < 0
-    assert L.gpx_laplace_update(hp, spec.ref(), 1, MEAN, 1e-8, 50, 0, C.byref(info),
-                                C.byref(info)) < 0
+    for name in ('gpx_laplace_loglik', 'gpx_laplace_posterior', 'gpx_laplace_update'):
+        assert calls['laplace'][name]() < 0, name
     h.exact_update(spec, sn, MEAN)
     ospec = oracle_spec(desc)
     R, a = orc.exact_update(ospec, sn, MEAN, X, yr)

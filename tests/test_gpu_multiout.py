@@ -6,7 +6,6 @@ tests/test_multiout_host.py holds to longdouble a hundred times tighter than the
 and against T runs of ExactGP on the columns."""
 
 import copy
-import ctypes as C
 import functools
 import pickle
 
@@ -18,7 +17,8 @@ import scipy.linalg as sla
 import gradobs_ref as gor
 import gradxy_ref as gr
 import multiout_ref as mor
-from helpers import amd_kernel, oracle_spec
+from handle_calls import handle_calls
+from helpers import amd_kernel, assert_refused, oracle_spec
 from oracle import gp_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -214,61 +214,15 @@ def test_a_multi_output_handle_refuses_the_other_entries():
     spec = amd_kernel(desc)._kspec()
     ref = mor.fit(oracle_spec(desc), np.log(SN), MEAN, X, Y)
     h = _lib.Handle()
-    L, hp, ptr = h._L, h._h, _lib._ptr
     h.mo_set_data(X, Y)
     h.mo_update(spec, np.log(SN), MEAN)
     nt.assert_allclose(h.mo_loglik(spec.c.nhyper), ref['lZ'], rtol=RTOL_LZ)
     before = h.mo_posterior(Xs)
-    nth = spec.c.nhyper + 2
-    lZ, info = C.c_double(0), C.c_int(0)
-    buf = [np.zeros(max(20 * 20, 64)) for _ in range(4)]
-    plan = (C.c_int * 64)()
     theta = np.r_[np.log(SN), amd_kernel(desc).get_hyper(), MEAN]
+    assert len(theta) == spec.c.nhyper + 2
     y0 = Y[:, 0].copy()
-    plain = {
-        'gpx_exact_update': lambda: L.gpx_exact_update(hp, spec.ref(), np.log(SN), MEAN,
-                                                       C.byref(info)),
-        'gpx_exact_loglik': lambda: L.gpx_exact_loglik(hp, C.byref(lZ), None),
-        'gpx_exact_loglik dlZ': lambda: L.gpx_exact_loglik(hp, C.byref(lZ), ptr(buf[0])),
-        'gpx_exact_eval': lambda: L.gpx_exact_eval(hp, spec.ref(), np.log(SN), MEAN, 1,
-                                                   C.byref(lZ), ptr(buf[0]), C.byref(info)),
-        'gpx_exact_append': lambda: L.gpx_exact_append(hp, ptr(X[:2].copy()), ptr(y0[:2].copy()),
-                                                       2, C.byref(info)),
-        'gpx_exact_loo': lambda: L.gpx_exact_loo(hp, C.byref(lZ), None, None, None),
-        'gpx_exact_posterior': lambda: L.gpx_exact_posterior(hp, ptr(Xs), 4, ptr(buf[0]),
-                                                             ptr(buf[1])),
-        'gpx_exact_posterior_grad': lambda: L.gpx_exact_posterior_grad(
-            hp, ptr(Xs), 4, ptr(buf[0]), ptr(buf[1]), ptr(buf[2]), ptr(buf[3])),
-        'gpx_exact_posterior_full': lambda: L.gpx_exact_posterior_full(hp, ptr(Xs), 4,
-                                                                       ptr(buf[0]), ptr(buf[1])),
-        'gpx_exact_posterior_gradient': lambda: L.gpx_exact_posterior_gradient(
-            hp, ptr(Xs), 4, ptr(buf[0]), ptr(buf[1])),
-        'gpx_exact_get_factor': lambda: L.gpx_exact_get_factor(hp, 20, ptr(buf[0]), ptr(buf[1])),
-        'gpx_batch_plan': lambda: L.gpx_batch_plan(hp, 4, 0, plan),
-        'gpx_loglik_batch': lambda: L.gpx_loglik_batch(hp, spec.ref(), ptr(theta), 1, 0,
-                                                       ptr(buf[0]), None, None),
-        'gpx_posterior_batch': lambda: L.gpx_posterior_batch(
-            hp, spec.ref(), ptr(theta), 1, ptr(Xs), 4, ptr(buf[0]), ptr(buf[1]), None, None,
-            None),
-        'gpx_sparse_update': lambda: L.gpx_sparse_update(hp, spec.ref(), _lib.GPX_DTC,
-                                                         ptr(X[:4].copy()), 4, np.log(SN), MEAN,
-                                                         C.byref(info)),
-    }
-    gradobs = {
-        'gpx_gradobs_update': lambda: L.gpx_gradobs_update(hp, spec.ref(), np.log(SN), 0.05, MEAN,
-                                                           C.byref(info)),
-        'gpx_gradobs_loglik': lambda: L.gpx_gradobs_loglik(hp, C.byref(lZ)),
-        'gpx_gradobs_posterior': lambda: L.gpx_gradobs_posterior(hp, ptr(Xs), 4, ptr(buf[0]),
-                                                                 ptr(buf[1])),
-        'gpx_gradobs_posterior_full': lambda: L.gpx_gradobs_posterior_full(
-            hp, ptr(Xs), 4, ptr(buf[0]), ptr(buf[1])),
-    }
-    assert len(theta) == nth
-    for name, call in sorted(plain.items()) + sorted(gradobs.items()):
-        code = call()
-        text = L.gpx_last_error().decode()
-        assert code == -1, (name, code)
-        assert text and ('multi-output' in text or name in gradobs), (name, text)
+    calls = handle_calls(h, spec, theta, X, y0, Xs)
+    assert_refused(h, calls, set(calls) - {'mo'}, 'multi-output')
     # the refusals left the factorisation alone ...
     for a, b in zip(h.mo_posterior(Xs), before):
         nt.assert_array_equal(a, b)
@@ -280,20 +234,8 @@ def test_a_multi_output_handle_refuses_the_other_entries():
 
     # ... gpx_set_data returns the handle to the plain entries, and the gpx_mo_* entries refuse
     # a plain handle and a gradient-observation handle
-    def mo_calls():
-        return {
-            'gpx_mo_update': L.gpx_mo_update(hp, spec.ref(), np.log(SN), MEAN, C.byref(info)),
-            'gpx_mo_loglik': L.gpx_mo_loglik(hp, C.byref(lZ), None),
-            'gpx_mo_loglik dlZ': L.gpx_mo_loglik(hp, C.byref(lZ), ptr(buf[0])),
-            'gpx_mo_posterior': L.gpx_mo_posterior(hp, ptr(Xs), 4, ptr(buf[0]), ptr(buf[1])),
-            'gpx_mo_posterior_full': L.gpx_mo_posterior_full(hp, ptr(Xs), 4, ptr(buf[0]),
-                                                             ptr(buf[1])),
-        }
-
     h.set_data(X, y0)
-    for name, code in sorted(mo_calls().items()):
-        assert code == -1, (name, code)
-        assert 'plain data' in L.gpx_last_error().decode(), name
+    assert_refused(h, calls, ['mo'], 'plain data')
     h.exact_update(spec, np.log(SN), MEAN)
     R, a = orc.exact_update(oracle_spec(desc), np.log(SN), MEAN, X, y0)
     nt.assert_allclose(h.exact_loglik(spec.c.nhyper),
@@ -303,16 +245,13 @@ def test_a_multi_output_handle_refuses_the_other_entries():
     nt.assert_allclose(mu, wmu, rtol=TOL_POST, atol=TOL_POST)
     nt.assert_allclose(s2, ws2, rtol=TOL_POST, atol=TOL_POST)
     after_plain = h.exact_posterior(Xs)
-    for name, code in sorted(mo_calls().items()):
-        assert code == -1, (name, code)
+    assert_refused(h, calls, ['mo'], 'plain data')
     for a_, b_ in zip(h.exact_posterior(Xs), after_plain):
         nt.assert_array_equal(a_, b_)
     gX, gy, Xg, G, _ = gor.problem(20, 5, 3, 4)
     h.gradobs_set_data(gX, gy, Xg, G)
     h.gradobs_update(amd_kernel(gr.family('se_ard', 3))._kspec(), np.log(SN), 0.05, MEAN)
-    for name, code in sorted(mo_calls().items()):
-        assert code == -1, (name, code)
-        assert 'gradient observations' in L.gpx_last_error().decode(), name
+    assert_refused(h, calls, ['mo'], 'gradient observations')
     # and back: gpx_mo_set_data enters the state from either of the others
     h.mo_set_data(X, Y)
     h.mo_update(spec, np.log(SN), MEAN)
