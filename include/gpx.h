@@ -274,6 +274,40 @@ int gpx_laplace_get_mode(gpx_t *h, int64_t n, double *f, double *g);
  * Newton step the build + scaling, the factorisation (with the rest of R^-1), the two products
  * with K, and the solves and vector work between them (needs gpx_enable_timing) */
 int gpx_laplace_timings(gpx_t *h, double *ms);
+/* ---- binary classification by expectation propagation (own design; GPML sections 3.6 and 5.5.2
+ * with a constant mean; Probit likelihood, whose moments are closed forms) ----
+ * The labels are those of gpx_laplace_set_data: EP is a second approximation on the same data,
+ * and the handle records which of the two filled it. After gpx_ep_update the result entries of
+ * gpx_laplace_* (loglik, posterior, posterior_full, get_mode) fail as before any update, after
+ * gpx_laplace_update the gpx_ep_* result entries do; every set_data clears both.
+ * Sites in natural parameters tau_i >= 0 and nu_i, sW = sqrt tau, B = I + sW K sW^T = R^T R.
+ * gpx_ep_update runs parallel EP: one sweep is one pass over all sites (cavity, moments, new
+ * site, damped by `damping` in (0, 1]), then B, its factorisation and all of R^-1 by the code of
+ * gpx_exact_update, b = nu' - sW o B^-1 (sW o K nu') (nu' = nu - tau mean), mu = mean + K b with
+ * the product of gpx_kernel_matvec, and Sigma_ii = (1 - sum_j (R^-1)_ij^2) / tau_i. It stops
+ * when max(max |tau_new - tau|, max |nu_new - nu|) <= tol (1 + max(max tau, max |nu|)), measured
+ * before the damped step, and fails (< 0) when max_iter sweeps did not get there. tau_i never
+ * falls below 1e-10 / K_ii (a site whose precision underflows keeps a divisor). One host
+ * synchronisation per sweep. *iters: sweeps taken; *info as gpx_exact_update. After a failure
+ * the handle has no fixed point: its other calls fail until the next successful update. The
+ * same call gives the same bits. */
+int gpx_ep_update(gpx_t *h, const gpx_kspec *k, double mean, double tol, int max_iter,
+                  double damping, int *iters, int *info);
+/* lZ of the last update; dlZ (may be NULL) [nhyper_kernel + 1] in order [kernel..., mean]:
+ * d lZ / d theta = 1/2 sum_ij (b_i b_j - sW_i sW_j (B^-1)_ij) dK_ij / d theta (lZ is stationary
+ * in the sites), one run of the exact path's trace pass; d lZ / d mean = sum b. */
+int gpx_ep_loglik(gpx_t *h, double *lZ, double *dlZ);
+/* latent predictive mean mu[m] = mean + k*^T b and variance s2[m] = k** - |R^-T (sW o k*)|^2 */
+int gpx_ep_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2);
+/* mu[m] and the full latent covariance Sigma[m][m]; 1 <= m <= 8192 */
+int gpx_ep_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma);
+/* the sites tau[n], nu[n] and the marginals mu[n], s2[n] = Sigma_ii they give; any may be NULL */
+int gpx_ep_get_sites(gpx_t *h, int64_t n, double *tau, double *nu, double *mu, double *s2);
+/* HIP-event ms of the last gpx_ep_update: ms[0] the whole update, ms[1..5] of its FIRST sweep
+ * the build + scaling, the factorisation with the rest of R^-1, the two products with K, the
+ * solve and vector work between them, and the row-norm and site passes (needs
+ * gpx_enable_timing) */
+int gpx_ep_timings(gpx_t *h, double *ms);
 /* host copies of gp._R (n*n row-major upper, zero below the diagonal) and gp._a;
  * either may be NULL. n: the point count the caller sized R and a for; the call
  * fails when it is not the factor's. */

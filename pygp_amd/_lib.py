@@ -107,6 +107,13 @@ SIGNATURES = {
     'gpx_laplace_posterior_full': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     'gpx_laplace_get_mode': (C.c_int, [_vp, _i64, _vp, _vp]),
     'gpx_laplace_timings': (C.c_int, [_vp, _vp]),
+    'gpx_ep_update': (C.c_int, [_vp, C.POINTER(_KSpec), C.c_double, C.c_double, C.c_int,
+                                C.c_double, _ip, _ip]),
+    'gpx_ep_loglik': (C.c_int, [_vp, _dp, _vp]),
+    'gpx_ep_posterior': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    'gpx_ep_posterior_full': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    'gpx_ep_get_sites': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    'gpx_ep_timings': (C.c_int, [_vp, _vp]),
     'gpx_mo_set_data': (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64]),
     'gpx_mo_update': (C.c_int, [_vp, C.POINTER(_KSpec), C.c_double, C.c_double, _ip]),
     'gpx_mo_loglik': (C.c_int, [_vp, _dp, _vp]),
@@ -536,6 +543,49 @@ class Handle(object):
         ms = np.zeros(5)
         check(self._L.gpx_laplace_timings(self._h, _ptr(ms)))
         return dict(zip(('update', 'build_scale', 'factor', 'matvec', 'solve'), ms))
+
+    # -- binary classification by expectation propagation (EPGP); the labels come in through
+    # laplace_set_data --
+    def ep_update(self, spec, mean, tol=1e-10, max_iter=200, damping=0.8):
+        """Damped parallel EP to a fixed point of the sites; returns the number of sweeps."""
+        iters, info = C.c_int(0), C.c_int(0)
+        check(self._L.gpx_ep_update(self._h, spec.ref(), float(mean), float(tol), int(max_iter),
+                                    float(damping), C.byref(iters), C.byref(info)))
+        return iters.value
+
+    def ep_loglik(self, nhyper_kernel, grad=False):
+        lZ = C.c_double(0)
+        dlZ = np.empty(nhyper_kernel + 1) if grad else None
+        check(self._L.gpx_ep_loglik(self._h, C.byref(lZ), _ptr(dlZ)))
+        return (lZ.value, dlZ) if grad else lZ.value
+
+    def ep_posterior(self, Xs):
+        Xs = _f64(Xs, 2)
+        m = Xs.shape[0]
+        mu, s2 = np.empty(m), np.empty(m)
+        check(self._L.gpx_ep_posterior(self._h, _ptr(Xs), m, _ptr(mu), _ptr(s2)))
+        return mu, s2
+
+    def ep_posterior_full(self, Xs):
+        Xs = _f64(Xs, 2)
+        m = Xs.shape[0]
+        mu, Sigma = np.empty(m), np.empty((m, m))
+        check(self._L.gpx_ep_posterior_full(self._h, _ptr(Xs), m, _ptr(mu), _ptr(Sigma)))
+        return mu, Sigma
+
+    def ep_get_sites(self, n):
+        """(tau, nu, mu, s2): the sites and the marginals of the latent at the data."""
+        out = [np.empty(n) for _ in range(4)]
+        check(self._L.gpx_ep_get_sites(self._h, n, *[_ptr(a) for a in out]))
+        return tuple(out)
+
+    def ep_timings(self):
+        """HIP-event ms of the last ep_update (enable_timing): the whole update, then of its
+        first sweep the build + scaling, the factorisation, the two products with K, the solve
+        and the row-norm and site passes."""
+        ms = np.zeros(6)
+        check(self._L.gpx_ep_timings(self._h, _ptr(ms)))
+        return dict(zip(('update', 'build_scale', 'factor', 'matvec', 'solve', 'sites'), ms))
 
     # -- T outputs at the same inputs (MultiOutputGP) --
     def mo_set_data(self, X, Y):

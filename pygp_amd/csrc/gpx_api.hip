@@ -36,6 +36,8 @@ static const char *kTimerNames[GPX_NTIMERS] = {
 // What the resident data of a handle is: set by the family's set_data (commit_data), asked for
 // by every entry that reads the data (require_state).
 enum { ST_PLAIN = 0, ST_GRADOBS, ST_MO, ST_LAPLACE };
+// ... and which approximation filled a handle that holds labels
+enum { LP_NONE = 0, LP_LAPLACE, LP_EP };
 
 struct gpx_ctx {
     int device = 0;
@@ -62,6 +64,10 @@ struct gpx_ctx {
     // the vectors of the Newton iteration (LV_* in the Laplace section, cap doubles each).
     // In each of the three states the entries of the other families refuse the handle; any
     // set_data moves it to its own state.
+    // Labels are also what expectation propagation reads (gpx_ep_update): lp_approx says which of
+    // the two approximations the factorisation and lp_vec belong to, and the result entries of
+    // the other one find no update.
+    int lp_approx = LP_NONE;
     int lp_lik = 0;
     bool lp_mode = false;          // lp_vec holds a converged mode for the resident data
     int lp_iters = 0;
@@ -69,6 +75,8 @@ struct gpx_ctx {
     std::vector<double> lp_dlz;    // the gradient of the last update, once computed
     hipEvent_t lp_ev[8] = {};
     double lp_ms[5] = {};
+    hipEvent_t ep_ev[9] = {};
+    double ep_ms[6] = {};
     // factorisation state
     DevBuf A, W, Kinv, r, a, alpha, scalars, partial, info, gv_part, pctl;
     double *acc = nullptr;         // the trace accumulators: a view of scalars
@@ -195,6 +203,7 @@ static void drop_data(gpx_ctx *h)
     h->go_n = h->go_ng = 0;
     h->mo_T = 0;
     h->lp_mode = false;
+    h->lp_approx = LP_NONE;
     h->data_version++;
 }
 
@@ -566,6 +575,8 @@ int gpx_destroy(gpx_t *h)
     for (int i = 0; i <= GPX_NTIMERS; ++i)
         if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     for (hipEvent_t e : h->lp_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : h->ep_ev)
         if (e) (void)hipEventDestroy(e);
     DLOG("host buffers");
     if (h->hres) (void)hipHostFree(h->hres);
@@ -1595,14 +1606,16 @@ static int laplace_cross(gpx_ctx *h, int mcp)
                              lpv(h, LV_SW), h->mean, h->lp_mu.as<double>());
 }
 
-// what every posterior entry (`what`, of the family `state`) asks of the handle first
-static int posterior_ready(const gpx_ctx *h, int state, const char *what)
+// what every posterior entry (`what`, of the family `state`; on labels: of the approximation
+// `approx`) asks of the handle first
+static int posterior_ready(const gpx_ctx *h, int state, int approx, const char *what)
 {
-    static const char *update[4] = {"gpx_exact_update", "gpx_gradobs_update", "gpx_mo_update",
-                                    "gpx_laplace_update"};
+    static const char *update[5] = {"gpx_exact_update", "gpx_gradobs_update", "gpx_mo_update",
+                                    "gpx_laplace_update", "gpx_ep_update"};
     GPX_TRY(require_state(h, state, what));
-    if (!h->have_factor) {
-        gpx_set_error("%s: no factorisation (call %s)", what, update[state]);
+    if (!h->have_factor || h->lp_approx != approx) {
+        gpx_set_error("%s: no factorisation (call %s)", what,
+                      update[approx == LP_EP ? 4 : state]);
         return -1;
     }
     return 0;
@@ -1677,10 +1690,11 @@ static int copy_mean(gpx_ctx *h, double *mu, size_t stride, int mc, int mcp)
 // what: the calling entry, of the family `state`; the handle must be in that state. ST_MO: mu is
 // mo_T rows of m doubles.
 static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2,
-                          double *dmu, double *ds2, int state, const char *what)
+                          double *dmu, double *ds2, int state, const char *what,
+                          int approx = LP_NONE)
 {
     CHECK_H(h);
-    GPX_TRY(posterior_ready(h, state, what));
+    GPX_TRY(posterior_ready(h, state, approx, what));
     if (!Xs || !mu || !s2 || m < 0) {
         gpx_set_error("%s: bad arguments", what);
         return -1;
@@ -1729,10 +1743,10 @@ static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, dou
 // Sigma = K(Xs, Xs) - V^T V, V = R^-T K(X, Xs); GP.sample draws from it
 // (_base.py:143-178). One pass, m <= 8192.
 static int posterior_full_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma,
-                               int state, const char *what)
+                               int state, const char *what, int approx = LP_NONE)
 {
     CHECK_H(h);
-    GPX_TRY(posterior_ready(h, state, what));
+    GPX_TRY(posterior_ready(h, state, approx, what));
     if (!Xs || !mu || !Sigma || m < 1 || m > 8192) {
         gpx_set_error("%s: bad arguments (1 <= m <= 8192)", what);
         return -1;
@@ -1947,7 +1961,7 @@ int gpx_kernel_gradxy(gpx_t *h, const gpx_kspec *k, const double *X1, int64_t n1
 int gpx_exact_posterior_gradient(gpx_t *h, const double *Xs, int64_t m, double *dmu, double *S)
 {
     CHECK_H(h);
-    GPX_TRY(posterior_ready(h, ST_PLAIN, "gpx_exact_posterior_gradient"));
+    GPX_TRY(posterior_ready(h, ST_PLAIN, LP_NONE, "gpx_exact_posterior_gradient"));
     if (!Xs || m < 1) {
         gpx_set_error("gpx_exact_posterior_gradient: bad arguments (m >= 1)");
         return -1;
@@ -2201,6 +2215,7 @@ int gpx_laplace_update(gpx_t *h, const gpx_kspec *k, int lik, double mean, doubl
     const bool use_warm = warm && h->lp_mode;
     h->have_factor = h->have_inverse = false;
     h->lp_mode = false;
+    h->lp_approx = LP_NONE;
     h->lp_dlz.clear();
     h->mean = mean;
     h->lp_lik = lik;
@@ -2307,6 +2322,7 @@ int gpx_laplace_update(gpx_t *h, const gpx_kspec *k, int lik, double mean, doubl
     }
     h->have_factor = true;
     h->lp_mode = true;
+    h->lp_approx = LP_LAPLACE;
     return 0;
 }
 
@@ -2314,7 +2330,7 @@ int gpx_laplace_loglik(gpx_t *h, double *lZ, double *dlZ)
 {
     CHECK_H(h);
     GPX_TRY(require_state(h, ST_LAPLACE, "gpx_laplace_loglik"));
-    if (!h->have_factor) {
+    if (!h->have_factor || h->lp_approx != LP_LAPLACE) {
         gpx_set_error("gpx_laplace_loglik: no mode (call gpx_laplace_update)");
         return -1;
     }
@@ -2361,19 +2377,20 @@ int gpx_laplace_loglik(gpx_t *h, double *lZ, double *dlZ)
 int gpx_laplace_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2)
 {
     return posterior_impl(h, Xs, m, mu, s2, nullptr, nullptr, ST_LAPLACE,
-                          "gpx_laplace_posterior");
+                          "gpx_laplace_posterior", LP_LAPLACE);
 }
 
 int gpx_laplace_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma)
 {
-    return posterior_full_impl(h, Xs, m, mu, Sigma, ST_LAPLACE, "gpx_laplace_posterior_full");
+    return posterior_full_impl(h, Xs, m, mu, Sigma, ST_LAPLACE, "gpx_laplace_posterior_full",
+                               LP_LAPLACE);
 }
 
 int gpx_laplace_get_mode(gpx_t *h, int64_t n, double *f, double *g)
 {
     CHECK_H(h);
     GPX_TRY(require_state(h, ST_LAPLACE, "gpx_laplace_get_mode"));
-    if (!h->have_factor || n != h->n) {
+    if (!h->have_factor || h->lp_approx != LP_LAPLACE || n != h->n) {
         gpx_set_error("gpx_laplace_get_mode: no mode for %lld points (call gpx_laplace_update)",
                       (long long)n);
         return -1;
@@ -2392,6 +2409,208 @@ int gpx_laplace_timings(gpx_t *h, double *ms)
         return -1;
     }
     for (int i = 0; i < 5; ++i) ms[i] = h->lp_ms[i];
+    return 0;
+}
+
+// ---- binary classification: expectation propagation (GPML sections 3.6 and 5.5.2) ---------------
+// The vectors of an EP handle in lp_vec: the sites, b (Sigma nu' = K b, where the posterior pass
+// reads Laplace's g), the marginals, nu' = nu - tau mean, the site kernel's scratch, a zero vector.
+// sW = sqrt tau is in LV_SW; LV_T, LV_C and LV_X stay the scratch of the solve.
+enum { EV_TAU = LV_A, EV_NU = LV_F, EV_B = LV_G, EV_SII = LV_W, EV_MU = LV_D3, EV_NUP = LV_B,
+       EV_TN = LV_AN, EV_VN = LV_FN, EV_ZERO = LV_U };
+// The weak-site rule: tau_i >= GPX_EP_FLOOR / K_ii. A site whose precision underflows (z beyond
+// 38) keeps a divisor for Sigma_ii = (1 - (B^-1)_ii) / tau_i; at the floor that quotient has lost
+// eps / (tau_i Sigma_ii) <= eps / GPX_EP_FLOOR = 2e-6 of itself, in a site whose whole influence
+// on every result is of the floor's size.
+#define GPX_EP_FLOOR 1e-10
+
+int gpx_ep_update(gpx_t *h, const gpx_kspec *k, double mean, double tol, int max_iter,
+                  double damping, int *iters, int *info)
+{
+    CHECK_H(h);
+    GPX_TRY(require_state(h, ST_LAPLACE, "gpx_ep_update"));
+    if (!std::isfinite(mean) || !(tol > 0) || !std::isfinite(tol) || max_iter < 1 ||
+        !(damping > 0 && damping <= 1)) {
+        gpx_set_error("gpx_ep_update: bad arguments (a finite mean, tol > 0, max_iter >= 1, "
+                      "0 < damping <= 1)");
+        return -1;
+    }
+    if (iters) *iters = 0;
+    if (info) *info = 0;
+    GPX_TRY(gpx_flatten_kspec(k, h->d, &h->kp));
+    h->have_factor = h->have_inverse = false;
+    h->lp_mode = false;
+    h->lp_approx = LP_NONE;
+    h->lp_dlz.clear();
+    h->mean = mean;
+    h->lp_lik = GPX_LIK_PROBIT;
+    GPX_TRY(laplace_reserve(h));
+    hipStream_t s = h->stream;
+    const int n = h->n, np = h->np;
+    double *tau = lpv(h, EV_TAU), *nu = lpv(h, EV_NU), *sW = lpv(h, LV_SW), *nup = lpv(h, EV_NUP);
+    double *Sii = lpv(h, EV_SII), *mu = lpv(h, EV_MU), *b = lpv(h, EV_B);
+    double *t = lpv(h, LV_T), *x = lpv(h, LV_X);
+    double *out = h->lp_sc.as<double>();
+    const double prior = gpx_kernel_prior(h->kp), tfloor = GPX_EP_FLOOR / prior;
+    hipEvent_t *ev = h->ep_ev;
+    if (h->timing) {
+        for (hipEvent_t &e : h->ep_ev)
+            if (!e) GPX_HIP(hipEventCreate(&e));
+        for (double &m : h->ep_ms) m = 0.0;
+        GPX_HIP(hipEventRecord(ev[0], s));
+    }
+    // before the first sweep: no sites, the prior's marginals
+    GPX_TRY(gpx_laplace_fill(s, 0.0, n, np, tau));
+    GPX_TRY(gpx_laplace_fill(s, 0.0, n, np, nu));
+    GPX_TRY(gpx_laplace_fill(s, prior, n, np, Sii));
+    GPX_TRY(gpx_laplace_fill(s, mean, n, np, mu));
+    int it = 0;
+    for (;;) {
+        // the site pass on the marginals of sweep `it`, and the one read of the sweep: its nine
+        // doubles and, behind a factorisation, sum log R_ii and the status word
+        GPX_TRY(gpx_ep_site(s, h->y.as<double>(), Sii, mu, mean, damping, tol, tfloor, it == 0, n,
+                            np, tau, nu, sW, nup, lpv(h, EV_TN), lpv(h, EV_VN), out));
+        if (h->timing && it == 1) GPX_HIP(hipEventRecord(ev[7], s));
+        GPX_HIP(hipMemcpyAsync(h->hres, out, 9 * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (it > 0)
+            GPX_HIP(hipMemcpyAsync(h->hres + 12, h->scalars.p, 4 * sizeof(double),
+                                   hipMemcpyDeviceToHost, s));
+        GPX_HIP(hipStreamSynchronize(s));
+        if (it > 0) {
+            const int st = laplace_status(h, (int)h->hres[15], info);
+            if (st != 0) return st;
+        }
+        if (!std::isfinite(h->hres[0]) || !std::isfinite(h->hres[1])) {
+            gpx_set_error("gpx_ep_update: the sites left the numbers at sweep %d", it);
+            return -1;
+        }
+        if (h->hres[8] != 0.0) break;
+        if (it == max_iter) {
+            if (iters) *iters = it;
+            gpx_set_error("gpx_ep_update: no convergence in %d sweeps (max_iter)", it);
+            return -1;
+        }
+        ++it;
+        // the marginals of the new sites: B = R^T R and all of R^-1, b = nu' - sW o B^-1 (sW o K
+        // nu'), mu = mean + K b, Sigma_ii from the rows of R^-1
+        const bool first = h->timing && it == 1;
+        if (first) GPX_HIP(hipEventRecord(ev[1], s));
+        GPX_TRY(laplace_factor(h, true, first ? ev[2] : nullptr));
+        GPX_TRY(gpx_lz_terms(s, h->A.as<double>(), h->ld, n, nup, nullptr, h->scalars.as<double>(),
+                             1, 0, 0, 0, h->info.as<int>()));
+        if (first) GPX_HIP(hipEventRecord(ev[3], s));
+        GPX_TRY(laplace_kv(h, nup, 0.0, x));
+        if (first) GPX_HIP(hipEventRecord(ev[4], s));
+        GPX_TRY(gpx_laplace_mul(s, sW, x, n, np, t));
+        GPX_TRY(laplace_solve(h, t, x));
+        GPX_TRY(gpx_laplace_nmulsub(s, nup, sW, x, n, np, b));
+        if (first) GPX_HIP(hipEventRecord(ev[5], s));
+        GPX_TRY(laplace_kv(h, b, mean, mu));
+        if (first) GPX_HIP(hipEventRecord(ev[6], s));     // (ev[7]: behind the next site pass)
+        GPX_TRY(gpx_ep_rownorm(s, h->W.as<double>(), h->ld, n, np, tau, Sii));
+    }
+    if (iters) *iters = it;
+    h->lp_iters = it;
+    // at the fixed point: lZ = -sum log R_ii + the four sums of the last site pass
+    h->lZ = -h->hres[13] + h->hres[4] + h->hres[5] + h->hres[6] + h->hres[7];
+    if (h->timing) {
+        GPX_HIP(hipEventRecord(ev[8], s));
+        GPX_HIP(hipEventSynchronize(ev[8]));
+        auto span = [&](int e0, int e1) {
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, ev[e0], ev[e1]);
+            return (double)ms;
+        };
+        h->ep_ms[0] = span(0, 8);
+        h->ep_ms[1] = span(1, 2);
+        h->ep_ms[2] = span(2, 3);
+        h->ep_ms[3] = span(3, 4) + span(5, 6);
+        h->ep_ms[4] = span(4, 5);
+        h->ep_ms[5] = span(6, 7);
+    }
+    h->have_factor = true;
+    h->lp_approx = LP_EP;
+    return 0;
+}
+
+int gpx_ep_loglik(gpx_t *h, double *lZ, double *dlZ)
+{
+    CHECK_H(h);
+    GPX_TRY(require_state(h, ST_LAPLACE, "gpx_ep_loglik"));
+    if (!h->have_factor || h->lp_approx != LP_EP) {
+        gpx_set_error("gpx_ep_loglik: no fixed point (call gpx_ep_update)");
+        return -1;
+    }
+    if (lZ) *lZ = h->lZ;
+    if (!dlZ) return 0;
+    const int nh = h->kp.nhyper;
+    if (h->lp_dlz.empty()) {
+        // lZ is stationary in the sites at the fixed point, so the gradient has the explicit term
+        // only: B^-1's buffer becomes Wt = sW sW^T o B^-1 (Laplace's weight with u = 0), the trace
+        // pass takes it with b; computed once per update
+        hipStream_t s = h->stream;
+        const DenseWs w = h->ws();
+        const int n = h->n, np = h->np;
+        double *b = lpv(h, EV_B), *zero = lpv(h, EV_ZERO);
+        GPX_TRY(gpx_lauum(s, w));                                   // B^-1 (upper)
+        GPX_TRY(gpx_laplace_fill(s, 0.0, n, np, zero));
+        GPX_TRY(gpx_laplace_sums(s, b, zero, n, h->lp_sc.as<double>() + 10));
+        GPX_TRY(gpx_laplace_weight(s, w.Kinv, h->ld, n, lpv(h, LV_SW), zero, zero));
+        GPX_TRY(gpx_trace_grad(s, h->kp, h->X.as<double>(), n, np, h->d, w.Kinv, h->ld, b,
+                               h->partial.as<double>(), h->acc));
+        GPX_HIP(hipMemcpyAsync(h->hres, h->acc, (1 + nh) * sizeof(double), hipMemcpyDeviceToHost,
+                               s));
+        GPX_HIP(hipMemcpyAsync(h->hres + 1 + nh, h->lp_sc.as<double>() + 10, sizeof(double),
+                               hipMemcpyDeviceToHost, s));
+        GPX_HIP(hipStreamSynchronize(s));
+        // d lZ / d theta = 1/2 sum_ij (b_i b_j - Wt_ij) dK_ij; d lZ / d mean = sum b
+        h->lp_dlz.resize(nh + 1);
+        for (int i = 0; i < nh; ++i) h->lp_dlz[i] = -0.5 * h->hres[1 + i];
+        h->lp_dlz[nh] = h->hres[1 + nh];
+        h->have_inverse = true;
+    }
+    for (int i = 0; i <= nh; ++i) dlZ[i] = h->lp_dlz[i];
+    return 0;
+}
+
+int gpx_ep_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2)
+{
+    return posterior_impl(h, Xs, m, mu, s2, nullptr, nullptr, ST_LAPLACE, "gpx_ep_posterior",
+                          LP_EP);
+}
+
+int gpx_ep_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma)
+{
+    return posterior_full_impl(h, Xs, m, mu, Sigma, ST_LAPLACE, "gpx_ep_posterior_full", LP_EP);
+}
+
+int gpx_ep_get_sites(gpx_t *h, int64_t n, double *tau, double *nu, double *mu, double *s2)
+{
+    CHECK_H(h);
+    GPX_TRY(require_state(h, ST_LAPLACE, "gpx_ep_get_sites"));
+    if (!h->have_factor || h->lp_approx != LP_EP || n != h->n) {
+        gpx_set_error("gpx_ep_get_sites: no fixed point for %lld points (call gpx_ep_update)",
+                      (long long)n);
+        return -1;
+    }
+    const int slot[4] = {EV_TAU, EV_NU, EV_MU, EV_SII};
+    double *dst[4] = {tau, nu, mu, s2};
+    for (int i = 0; i < 4; ++i)
+        if (dst[i])
+            GPX_HIP(hipMemcpyAsync(dst[i], lpv(h, slot[i]), (size_t)n * 8, hipMemcpyDeviceToHost,
+                                   h->stream));
+    GPX_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int gpx_ep_timings(gpx_t *h, double *ms)
+{
+    CHECK_H(h);
+    if (!ms) {
+        gpx_set_error("gpx_ep_timings: null output");
+        return -1;
+    }
+    for (int i = 0; i < 6; ++i) ms[i] = h->ep_ms[i];
     return 0;
 }
 

@@ -685,3 +685,15 @@ int gpx_laplace_sums(hipStream_t s, const double *g, const double *u, int n, dou
 // mu[j] = mean + Ks[:, j].g (j < mcp) from the unscaled Ks (np x ldk), then row i of Ks times sW_i
 int gpx_laplace_cross(hipStream_t s, double *Ks, int ldk, int n, int mcp, const double *g,
                       const double *sW, double mean, double *mu);
+
+// ---- expectation propagation for classification (ep.hip; driver in gpx_api.hip) ----------------
+// one pass over the sites: cavity, Probit moments, new sites; out[0..3] the stopping quantities,
+// out[4..7] the sums of lZ at the sites that came in, out[8] = 1 if they are a fixed point to tol
+// (never when `first`); otherwise the damped update of tau, nu and sW = sqrt tau,
+// nup = nu - tau mean (np doubles, zero beyond n). tn, vn: scratch of n doubles.
+int gpx_ep_site(hipStream_t s, const double *y, const double *Sii, const double *mu, double mean,
+                double eta, double tol, double tfloor, int first, int n, int np, double *tau,
+                double *nu, double *sW, double *nup, double *tn, double *vn, double *out);
+// Sii_i = (1 - sum_j W_ij^2) / tau_i from the rows of W = R^-1 as gpx_trtri leaves it
+int gpx_ep_rownorm(hipStream_t s, const double *W, int ld, int n, int np, const double *tau,
+                   double *Sii);

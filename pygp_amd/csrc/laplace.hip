@@ -1,81 +1,11 @@
 // GP classification by Laplace's approximation (GPML algorithms 3.1, 3.2, 5.1): the pointwise
-// likelihood terms, the O(N^2) / O(N) kernels around the exact path's factorisation, and the
+// likelihood terms (lik_dev.h, shared with ep.hip), the O(N^2) / O(N) kernels around the exact path's factorisation, and the
 // vector steps of the Newton iteration. The driver is in gpx_api.hip (gpx_laplace_*); K v comes
 // from kmatvec_kernel (kmat.hip). Every reduction here has a fixed order: one workgroup, a
 // strided sum per thread, a tree over LDS.
 
 #include "gpx_internal.h"
-
-// ---- the likelihoods on one point ------------------------------------------------------------
-// y in {-1, +1}, z = y f. lp = log p(y | f), g = d lp / d f, W = -d2 lp / d f2 > 0,
-// d3 = d3 lp / d f3.
-struct LikTerms {
-    double lp, g, W, d3;
-};
-
-__device__ __forceinline__ LikTerms lik_point(int lik, double y, double f)
-{
-    LikTerms t;
-    const double z = y * f;
-    if (lik == GPX_LIK_LOGISTIC) {
-        // e = exp(-|z|) never overflows; 1 - sigma(z) and sigma(z) (1 - sigma(z)) through it
-        const double e = exp(-fabs(z));
-        const double q = 1.0 / (1.0 + e);
-        t.lp = (z >= 0 ? 0.0 : z) - log1p(e);
-        const double om = z >= 0 ? e * q : q;                 // sigma(-z)
-        t.g = y * om;
-        t.W = e * q * q;
-        // d3 = y W tanh(z / 2), tanh(|z| / 2) = -expm1(-|z|) / (1 + e)
-        const double th = -expm1(-fabs(z)) * q;
-        t.d3 = y * t.W * (z >= 0 ? th : -th);
-    } else {
-        // r = N(z) / Phi(z): sqrt(2 / pi) / erfcx(-z / sqrt 2) where Phi is small, the plain
-        // quotient where Phi >= 1/2 (erfcx of a negative argument overflows beyond z = 37)
-        const double s = z * M_SQRT1_2;
-        double r;
-        if (z < 0) {
-            const double ex = erfcx(-s);
-            r = 0.7978845608028654 / ex;
-            t.lp = log(0.5 * ex) - s * s;
-        } else {
-            const double c = 0.5 * erfc(s);
-            r = 0.3989422804014327 * exp(-s * s) / (1.0 - c);
-            t.lp = log1p(-c);
-        }
-        t.g = y * r;
-        t.W = r * (r + z);
-        t.d3 = y * (t.W * (2.0 * r + z) - r);
-    }
-    return t;
-}
-
-__device__ __forceinline__ double block_sum_1024(double v, double *red)
-{
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int off = 512; off > 0; off >>= 1) {
-        if (tid < off) red[tid] += red[tid + off];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ double block_max_1024(double v, double *red)
-{
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int off = 512; off > 0; off >>= 1) {
-        if (tid < off) red[tid] = fmax(red[tid], red[tid + off]);
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
+#include "lik_dev.h"
 
 // g, W, sW = sqrt W, d3 and b = W (f - mean) + g at f (zero in the padding up to np);
 // sums[0] = sum_i log p(y_i | f_i)

@@ -3,10 +3,11 @@ from .basic import BasicGP
 from .gradobs import GradientGP
 from .multiout import MultiOutputGP
 from .laplace import LaplaceGP
+from .ep import EPGP
 from .fitc import FITC
 from .dtc import DTC
 from .vfe import VFE
 from .select import select_pseudoinputs
 
-__all__ = ['GP', 'ExactGP', 'BasicGP', 'GradientGP', 'MultiOutputGP', 'LaplaceGP', 'FITC', 'DTC', 'VFE',
-           'select_pseudoinputs']
+__all__ = ['GP', 'ExactGP', 'BasicGP', 'GradientGP', 'MultiOutputGP', 'LaplaceGP', 'EPGP', 'FITC',
+           'DTC', 'VFE', 'select_pseudoinputs']

@@ -1,7 +1,7 @@
 """Gaussian observation noise, the only likelihood exact inference admits
 (/root/reference/pygp/likelihoods/gaussian.py:23-49, _base.py:41-46), and the two
 likelihoods of binary labels y in {-1, +1} that `LaplaceGP` takes: p(y | f) = sigma(y f)
-(Logistic) and Phi(y f) (Probit). Neither has a hyperparameter."""
+(Logistic) and Phi(y f) (Probit, which `EPGP` takes too). Neither has a hyperparameter."""
 
 import numpy as np
 

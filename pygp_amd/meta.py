@@ -44,8 +44,8 @@ class HyperEnsemble(object):
             # sparse model's
             raise TypeError('HyperEnsemble runs exact GPs only; %s is a sparse model'
                             % type(model).__name__)
-        from .inference.laplace import LaplaceGP
-        if isinstance(model, LaplaceGP):
+        from .inference._labels import LabelsGP
+        if isinstance(model, LabelsGP):
             # ... with Gaussian noise: a classifier's hypers have no noise slot
             raise TypeError('HyperEnsemble runs exact GPs only; %s is a classifier'
                             % type(model).__name__)
