@@ -212,6 +212,20 @@ def _f64(a, ndim=None):
     return a
 
 
+def _pair(X1, X2, dtype=np.float64):
+    """The inputs of a kernel entry as (X1, n1, X2, n2, d); X2 None: X1 against itself."""
+    X1 = np.ascontiguousarray(X1, dtype=dtype)
+    if X1.ndim != 2:
+        raise ValueError('expected a 2-d array')
+    n1, d = X1.shape
+    if X2 is None:
+        return X1, n1, None, n1, d
+    X2 = np.ascontiguousarray(X2, dtype=dtype)
+    if X2.ndim != 2 or X2.shape[1] != d:
+        raise ValueError('X1 and X2 have different dimensions')
+    return X1, n1, X2, X2.shape[0], d
+
+
 def check(code):
     """Map a C return code to the reference's exceptions: >0 is the LinAlgError
     scipy.linalg.cholesky raises at pygp/inference/exact.py:54."""
@@ -334,18 +348,39 @@ class Handle(object):
         except Exception:
             pass
 
+    # -- what the families' result entries share; `entry` is the family's own C function --
+    def _posterior(self, entry, Xs, full, lead=None):
+        """Xs -> (mu, s2), or (mu, Sigma) when full; lead: the mean comes back from the
+        device as (lead, m) and goes to the caller as (m, lead)."""
+        Xs = _f64(Xs, 2)
+        m = Xs.shape[0]
+        mu = np.empty(m) if lead is None else np.empty((lead, m))
+        cov = np.empty((m, m)) if full else np.empty(m)
+        check(entry(self._h, _ptr(Xs), m, _ptr(mu), _ptr(cov)))
+        return (mu if lead is None else np.ascontiguousarray(mu.T)), cov
+
+    def _loglik(self, entry, ngrad, grad):
+        """lZ, or (lZ, dlZ) with ngrad entries."""
+        lZ = C.c_double(0)
+        dlZ = np.empty(ngrad) if grad else None
+        check(entry(self._h, C.byref(lZ), _ptr(dlZ)))
+        return (lZ.value, dlZ) if grad else lZ.value
+
+    def _append(self, entry, Xnew, ynew):
+        Xnew, ynew = _f64(Xnew, 2), _f64(ynew, 1)
+        if Xnew.shape[0] != ynew.shape[0]:
+            raise ValueError('X and y disagree')
+        info = C.c_int(0)
+        code = entry(self._h, _ptr(Xnew), _ptr(ynew), Xnew.shape[0], C.byref(info))
+        if code == -3:
+            return False
+        check(code)
+        return True
+
     # -- kernels --
     def kernel_get(self, spec, X1, X2=None, dtype=np.float64):
         dt = F32 if np.dtype(dtype) == np.float32 else F64
-        X1 = np.ascontiguousarray(X1, dtype=dtype)
-        n1, d = X1.shape
-        if X2 is not None:
-            X2 = np.ascontiguousarray(X2, dtype=dtype)
-            if X2.shape[1] != d:
-                raise ValueError('X1 and X2 have different dimensions')
-            n2 = X2.shape[0]
-        else:
-            n2 = n1
+        X1, n1, X2, n2, d = _pair(X1, X2, dtype)
         out = np.empty((n1, n2), dtype=dtype)
         if out.size == 0:
             return out
@@ -354,13 +389,7 @@ class Handle(object):
         return out
 
     def kernel_grad(self, spec, X1, X2=None):
-        X1 = _f64(X1, 2)
-        n1, d = X1.shape
-        if X2 is not None:
-            X2 = _f64(X2, 2)
-            n2 = X2.shape[0]
-        else:
-            n2 = n1
+        X1, n1, X2, n2, d = _pair(X1, X2)
         out = np.empty((spec.c.nhyper, n1, n2))
         if out.size == 0:
             return out
@@ -404,20 +433,10 @@ class Handle(object):
     def exact_append(self, Xnew, ynew):
         """True if the factor was extended in place, False if the caller has to
         refactorise (the points do not fit / nothing to extend)."""
-        Xnew, ynew = _f64(Xnew, 2), _f64(ynew, 1)
-        info = C.c_int(0)
-        code = self._L.gpx_exact_append(self._h, _ptr(Xnew), _ptr(ynew), Xnew.shape[0],
-                                        C.byref(info))
-        if code == -3:
-            return False
-        check(code)
-        return True
+        return self._append(self._L.gpx_exact_append, Xnew, ynew)
 
     def exact_loglik(self, nhyper_kernel, grad=False):
-        lZ = C.c_double(0)
-        dlZ = np.empty(nhyper_kernel + 2) if grad else None
-        check(self._L.gpx_exact_loglik(self._h, C.byref(lZ), _ptr(dlZ)))
-        return (lZ.value, dlZ) if grad else lZ.value
+        return self._loglik(self._L.gpx_exact_loglik, nhyper_kernel + 2, grad)
 
     def exact_loo(self, nhyper_kernel, n, grad=False, points=False):
         """Leave-one-out log predictive probability L of the last update; grad: (L, dL);
@@ -440,19 +459,10 @@ class Handle(object):
         return (lZ.value, dlZ) if grad else lZ.value
 
     def exact_posterior(self, Xs):
-        Xs = _f64(Xs, 2)
-        m = Xs.shape[0]
-        mu, s2 = np.empty(m), np.empty(m)
-        check(self._L.gpx_exact_posterior(self._h, _ptr(Xs), m, _ptr(mu),
-                                          _ptr(s2)))
-        return mu, s2
+        return self._posterior(self._L.gpx_exact_posterior, Xs, False)
 
     def exact_posterior_full(self, Xs):
-        Xs = _f64(Xs, 2)
-        m = Xs.shape[0]
-        mu, Sigma = np.empty(m), np.empty((m, m))
-        check(self._L.gpx_exact_posterior_full(self._h, _ptr(Xs), m, _ptr(mu), _ptr(Sigma)))
-        return mu, Sigma
+        return self._posterior(self._L.gpx_exact_posterior_full, Xs, True)
 
     # -- exact GP with gradient observations --
     def gradobs_set_data(self, X, y, Xg, G):
@@ -481,18 +491,10 @@ class Handle(object):
         return lZ.value
 
     def gradobs_posterior(self, Xs):
-        Xs = _f64(Xs, 2)
-        m = Xs.shape[0]
-        mu, s2 = np.empty(m), np.empty(m)
-        check(self._L.gpx_gradobs_posterior(self._h, _ptr(Xs), m, _ptr(mu), _ptr(s2)))
-        return mu, s2
+        return self._posterior(self._L.gpx_gradobs_posterior, Xs, False)
 
     def gradobs_posterior_full(self, Xs):
-        Xs = _f64(Xs, 2)
-        m = Xs.shape[0]
-        mu, Sigma = np.empty(m), np.empty((m, m))
-        check(self._L.gpx_gradobs_posterior_full(self._h, _ptr(Xs), m, _ptr(mu), _ptr(Sigma)))
-        return mu, Sigma
+        return self._posterior(self._L.gpx_gradobs_posterior_full, Xs, True)
 
     # -- binary classification by Laplace's approximation (LaplaceGP) --
     def laplace_set_data(self, X, y):
@@ -511,24 +513,13 @@ class Handle(object):
         return iters.value
 
     def laplace_loglik(self, nhyper_kernel, grad=False):
-        lZ = C.c_double(0)
-        dlZ = np.empty(nhyper_kernel + 1) if grad else None
-        check(self._L.gpx_laplace_loglik(self._h, C.byref(lZ), _ptr(dlZ)))
-        return (lZ.value, dlZ) if grad else lZ.value
+        return self._loglik(self._L.gpx_laplace_loglik, nhyper_kernel + 1, grad)
 
     def laplace_posterior(self, Xs):
-        Xs = _f64(Xs, 2)
-        m = Xs.shape[0]
-        mu, s2 = np.empty(m), np.empty(m)
-        check(self._L.gpx_laplace_posterior(self._h, _ptr(Xs), m, _ptr(mu), _ptr(s2)))
-        return mu, s2
+        return self._posterior(self._L.gpx_laplace_posterior, Xs, False)
 
     def laplace_posterior_full(self, Xs):
-        Xs = _f64(Xs, 2)
-        m = Xs.shape[0]
-        mu, Sigma = np.empty(m), np.empty((m, m))
-        check(self._L.gpx_laplace_posterior_full(self._h, _ptr(Xs), m, _ptr(mu), _ptr(Sigma)))
-        return mu, Sigma
+        return self._posterior(self._L.gpx_laplace_posterior_full, Xs, True)
 
     def laplace_get_mode(self, n):
         """(f, g): the mode and the gradient of log p(y | f) there."""
@@ -554,24 +545,13 @@ class Handle(object):
         return iters.value
 
     def ep_loglik(self, nhyper_kernel, grad=False):
-        lZ = C.c_double(0)
-        dlZ = np.empty(nhyper_kernel + 1) if grad else None
-        check(self._L.gpx_ep_loglik(self._h, C.byref(lZ), _ptr(dlZ)))
-        return (lZ.value, dlZ) if grad else lZ.value
+        return self._loglik(self._L.gpx_ep_loglik, nhyper_kernel + 1, grad)
 
     def ep_posterior(self, Xs):
-        Xs = _f64(Xs, 2)
-        m = Xs.shape[0]
-        mu, s2 = np.empty(m), np.empty(m)
-        check(self._L.gpx_ep_posterior(self._h, _ptr(Xs), m, _ptr(mu), _ptr(s2)))
-        return mu, s2
+        return self._posterior(self._L.gpx_ep_posterior, Xs, False)
 
     def ep_posterior_full(self, Xs):
-        Xs = _f64(Xs, 2)
-        m = Xs.shape[0]
-        mu, Sigma = np.empty(m), np.empty((m, m))
-        check(self._L.gpx_ep_posterior_full(self._h, _ptr(Xs), m, _ptr(mu), _ptr(Sigma)))
-        return mu, Sigma
+        return self._posterior(self._L.gpx_ep_posterior_full, Xs, True)
 
     def ep_get_sites(self, n):
         """(tau, nu, mu, s2): the sites and the marginals of the latent at the data."""
@@ -604,24 +584,13 @@ class Handle(object):
                                     C.byref(info)))
 
     def mo_loglik(self, nhyper_kernel, grad=False):
-        lZ = C.c_double(0)
-        dlZ = np.empty(nhyper_kernel + 2) if grad else None
-        check(self._L.gpx_mo_loglik(self._h, C.byref(lZ), _ptr(dlZ)))
-        return (lZ.value, dlZ) if grad else lZ.value
+        return self._loglik(self._L.gpx_mo_loglik, nhyper_kernel + 2, grad)
 
     def mo_posterior(self, Xs):
-        Xs = _f64(Xs, 2)
-        m = Xs.shape[0]
-        mu, s2 = np.empty((self._mo_T, m)), np.empty(m)
-        check(self._L.gpx_mo_posterior(self._h, _ptr(Xs), m, _ptr(mu), _ptr(s2)))
-        return np.ascontiguousarray(mu.T), s2
+        return self._posterior(self._L.gpx_mo_posterior, Xs, False, self._mo_T)
 
     def mo_posterior_full(self, Xs):
-        Xs = _f64(Xs, 2)
-        m = Xs.shape[0]
-        mu, Sigma = np.empty((self._mo_T, m)), np.empty((m, m))
-        check(self._L.gpx_mo_posterior_full(self._h, _ptr(Xs), m, _ptr(mu), _ptr(Sigma)))
-        return np.ascontiguousarray(mu.T), Sigma
+        return self._posterior(self._L.gpx_mo_posterior_full, Xs, True, self._mo_T)
 
     # -- sparse pseudo-input models (FITC / DTC / VFE) on the resident data --
     def sparse_update(self, spec, method, U, log_sn, mean):
@@ -633,22 +602,10 @@ class Handle(object):
     def sparse_append(self, Xnew, ynew):
         """True if the sparse model took the new observations in place, False if the caller
         has to upload everything and refactor (no current model / they do not fit)."""
-        Xnew, ynew = _f64(Xnew, 2), _f64(ynew, 1)
-        if Xnew.shape[0] != ynew.shape[0]:
-            raise ValueError('X and y disagree')
-        info = C.c_int(0)
-        code = self._L.gpx_sparse_append(self._h, _ptr(Xnew), _ptr(ynew), Xnew.shape[0],
-                                         C.byref(info))
-        if code == -3:
-            return False
-        check(code)
-        return True
+        return self._append(self._L.gpx_sparse_append, Xnew, ynew)
 
     def sparse_loglik(self, nhyper_kernel, grad=False):
-        lZ = C.c_double(0)
-        dlZ = np.empty(nhyper_kernel + 2) if grad else None
-        check(self._L.gpx_sparse_loglik(self._h, C.byref(lZ), _ptr(dlZ)))
-        return (lZ.value, dlZ) if grad else lZ.value
+        return self._loglik(self._L.gpx_sparse_loglik, nhyper_kernel + 2, grad)
 
     def sparse_posterior(self, Xs, grad=False):
         Xs = _f64(Xs, 2)
@@ -661,11 +618,7 @@ class Handle(object):
         return (mu, s2, dmu, ds2) if grad else (mu, s2)
 
     def sparse_posterior_full(self, Xs):
-        Xs = _f64(Xs, 2)
-        m = Xs.shape[0]
-        mu, Sigma = np.empty(m), np.empty((m, m))
-        check(self._L.gpx_sparse_posterior_full(self._h, _ptr(Xs), m, _ptr(mu), _ptr(Sigma)))
-        return mu, Sigma
+        return self._posterior(self._L.gpx_sparse_posterior_full, Xs, True)
 
     def sparse_timings(self):
         """HIP-event ms of the last [update, gradient stage, contraction pass]."""
@@ -727,13 +680,7 @@ class Handle(object):
         return mu, s2, dmu, ds2
 
     def kernel_gradx(self, spec, X1, X2=None, wrt=1):
-        X1 = _f64(X1, 2)
-        n1, d = X1.shape
-        if X2 is not None:
-            X2 = _f64(X2, 2)
-            n2 = X2.shape[0]
-        else:
-            n2 = n1
+        X1, n1, X2, n2, d = _pair(X1, X2)
         out = np.empty((n1, n2, d))
         if out.size:
             check(self._L.gpx_kernel_gradx(self._h, spec.ref(), _ptr(X1), n1, _ptr(X2),
@@ -741,13 +688,7 @@ class Handle(object):
         return out
 
     def kernel_gradxy(self, spec, X1, X2=None):
-        X1 = _f64(X1, 2)
-        n1, d = X1.shape
-        if X2 is not None:
-            X2 = _f64(X2, 2)
-            n2 = X2.shape[0]
-        else:
-            n2 = n1
+        X1, n1, X2, n2, d = _pair(X1, X2)
         out = np.empty((n1, n2, d, d))
         if out.size:
             check(self._L.gpx_kernel_gradxy(self._h, spec.ref(), _ptr(X1), n1, _ptr(X2), n2, d,

@@ -73,9 +73,8 @@ struct gpx_ctx {
     int lp_iters = 0;
     DevBuf lp_vec, lp_kmv, lp_sc, lp_mu;
     std::vector<double> lp_dlz;    // the gradient of the last update, once computed
-    hipEvent_t lp_ev[8] = {};
-    double lp_ms[5] = {};
-    hipEvent_t ep_ev[9] = {};
+    hipEvent_t lb_ev[9] = {};      // the timed update's events, whichever approximation ran it
+    double lp_ms[5] = {};          // ... and each approximation's own last timed update
     double ep_ms[6] = {};
     // factorisation state
     DevBuf A, W, Kinv, r, a, alpha, scalars, partial, info, gv_part, pctl;
@@ -574,9 +573,7 @@ int gpx_destroy(gpx_t *h)
     DLOG("events");
     for (int i = 0; i <= GPX_NTIMERS; ++i)
         if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-    for (hipEvent_t e : h->lp_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->ep_ev)
+    for (hipEvent_t e : h->lb_ev)
         if (e) (void)hipEventDestroy(e);
     DLOG("host buffers");
     if (h->hres) (void)hipHostFree(h->hres);
@@ -2198,6 +2195,126 @@ static int laplace_status(gpx_ctx *h, int inf, int *info)
     return 0;
 }
 
+// ---- what Laplace and EP share on a handle of labels -------------------------------------------
+// behind either update's argument check: the kernel, no result of either approximation any more
+static int labels_begin(gpx_ctx *h, const gpx_kspec *k, int lik, double mean)
+{
+    GPX_TRY(gpx_flatten_kspec(k, h->d, &h->kp));
+    h->have_factor = h->have_inverse = false;
+    h->lp_mode = false;
+    h->lp_approx = LP_NONE;
+    h->lp_dlz.clear();
+    h->mean = mean;
+    h->lp_lik = lik;
+    return laplace_reserve(h);
+}
+
+// a = v - sW o B^-1 (sW o K v), f = mean + K a behind a factorisation of B (Newton: b -> a_new,
+// f_new; EP: nu' -> b, mu); ev: lb_ev in a timed step (4, 5, 6: behind K v, the solve, K a)
+static int labels_marginals(gpx_ctx *h, const double *v, double *a, double *f, hipEvent_t *ev)
+{
+    hipStream_t s = h->stream;
+    const int n = h->n, np = h->np;
+    double *sW = lpv(h, LV_SW), *t = lpv(h, LV_T), *x = lpv(h, LV_X);
+    GPX_TRY(laplace_kv(h, v, 0.0, x));
+    if (ev) GPX_HIP(hipEventRecord(ev[4], s));
+    GPX_TRY(gpx_laplace_mul(s, sW, x, n, np, t));
+    GPX_TRY(laplace_solve(h, t, x));
+    GPX_TRY(gpx_laplace_nmulsub(s, v, sW, x, n, np, a));
+    if (ev) GPX_HIP(hipEventRecord(ev[5], s));
+    GPX_TRY(laplace_kv(h, a, h->mean, f));
+    if (ev) GPX_HIP(hipEventRecord(ev[6], s));
+    return 0;
+}
+
+// a timed update begins: the events (created on first use), the caller's ms zeroed, event 0
+static int labels_timer_start(gpx_ctx *h, double *ms, int count)
+{
+    for (hipEvent_t &e : h->lb_ev)
+        if (!e) GPX_HIP(hipEventCreate(&e));
+    for (int i = 0; i < count; ++i) ms[i] = 0.0;
+    GPX_HIP(hipEventRecord(h->lb_ev[0], h->stream));
+    return 0;
+}
+
+static double labels_span(const gpx_ctx *h, int e0, int e1)
+{
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, h->lb_ev[e0], h->lb_ev[e1]);
+    return (double)ms;
+}
+
+// the five spans both updates report: the whole (to event `last`), the build, the factorisation,
+// the two products with K, the solve
+static void labels_spans(const gpx_ctx *h, double *ms, int last)
+{
+    ms[0] = labels_span(h, 0, last);
+    ms[1] = labels_span(h, 1, 2);
+    ms[2] = labels_span(h, 2, 3);
+    ms[3] = labels_span(h, 3, 4) + labels_span(h, 5, 6);
+    ms[4] = labels_span(h, 4, 5);
+}
+
+static int labels_timings(gpx_t *h, int approx, double *ms)
+{
+    const bool ep = approx == LP_EP;
+    CHECK_H(h);
+    if (!ms) {
+        gpx_set_error("%s: null output", ep ? "gpx_ep_timings" : "gpx_laplace_timings");
+        return -1;
+    }
+    for (int i = 0; i < (ep ? 6 : 5); ++i) ms[i] = ep ? h->ep_ms[i] : h->lp_ms[i];
+    return 0;
+}
+
+// the handle holds labels and a finished update of `approx`; n, if given: for *n points
+static int labels_ready(const gpx_ctx *h, int approx, const char *what, const int64_t *n = nullptr)
+{
+    const char *result = approx == LP_EP ? "fixed point" : "mode";
+    const char *update = approx == LP_EP ? "gpx_ep_update" : "gpx_laplace_update";
+    GPX_TRY(require_state(h, ST_LAPLACE, what));
+    if (h->have_factor && h->lp_approx == approx && (!n || *n == h->n)) return 0;
+    if (!n)
+        gpx_set_error("%s: no %s (call %s)", what, result, update);
+    else
+        gpx_set_error("%s: no %s for %lld points (call %s)", what, result, (long long)*n, update);
+    return -1;
+}
+
+// the tail of both gradients, with B^-1 (upper) in Kinv: Wt = sW sW^T o B^-1 - u lead^T - lead u^T,
+// d lZ / d theta = 1/2 sum_ij (lead_i lead_j - Wt_ij) dK_ij, d lZ / d mean = the nsum sums at
+// lp_sc + slot. Laplace: lead = g; EP: lead = b, u = 0 (lZ is stationary in the sites).
+static int labels_grad_tail(gpx_ctx *h, const double *lead, const double *u, int nsum, int slot)
+{
+    hipStream_t s = h->stream;
+    const DenseWs w = h->ws();
+    const int nh = h->kp.nhyper;
+    GPX_TRY(gpx_laplace_weight(s, w.Kinv, h->ld, h->n, lpv(h, LV_SW), lead, u));
+    GPX_TRY(gpx_trace_grad(s, h->kp, h->X.as<double>(), h->n, h->np, h->d, w.Kinv, h->ld, lead,
+                           h->partial.as<double>(), h->acc));
+    GPX_HIP(hipMemcpyAsync(h->hres, h->acc, (1 + nh) * sizeof(double), hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipMemcpyAsync(h->hres + 1 + nh, h->lp_sc.as<double>() + slot, nsum * sizeof(double),
+                           hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipStreamSynchronize(s));
+    h->lp_dlz.resize(nh + 1);
+    for (int i = 0; i < nh; ++i) h->lp_dlz[i] = -0.5 * h->hres[1 + i];
+    h->lp_dlz[nh] = h->hres[1 + nh];
+    for (int i = 1; i < nsum; ++i) h->lp_dlz[nh] += h->hres[1 + nh + i];
+    h->have_inverse = true;
+    return 0;
+}
+
+// `count` of lp_vec's vectors (n doubles each) to the host, those with a destination; one sync
+static int labels_copy_out(gpx_ctx *h, const int *slot, double *const *dst, int count, int64_t n)
+{
+    for (int i = 0; i < count; ++i)
+        if (dst[i])
+            GPX_HIP(hipMemcpyAsync(dst[i], lpv(h, slot[i]), (size_t)n * 8, hipMemcpyDeviceToHost,
+                                   h->stream));
+    GPX_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
 int gpx_laplace_update(gpx_t *h, const gpx_kspec *k, int lik, double mean, double tol,
                        int max_iter, int warm, int *iters, int *info)
 {
@@ -2211,28 +2328,17 @@ int gpx_laplace_update(gpx_t *h, const gpx_kspec *k, int lik, double mean, doubl
     }
     if (iters) *iters = 0;
     if (info) *info = 0;
-    GPX_TRY(gpx_flatten_kspec(k, h->d, &h->kp));
-    const bool use_warm = warm && h->lp_mode;
-    h->have_factor = h->have_inverse = false;
-    h->lp_mode = false;
-    h->lp_approx = LP_NONE;
-    h->lp_dlz.clear();
-    h->mean = mean;
-    h->lp_lik = lik;
-    GPX_TRY(laplace_reserve(h));
+    const bool use_warm = warm && h->lp_mode;       // (read before labels_begin drops the mode)
+    GPX_TRY(labels_begin(h, k, lik, mean));
     hipStream_t s = h->stream;
     const int n = h->n, np = h->np;
     const double *y = h->y.as<double>();
     double *a = lpv(h, LV_A), *f = lpv(h, LV_F), *an = lpv(h, LV_AN), *fn = lpv(h, LV_FN);
-    double *t = lpv(h, LV_T), *c = lpv(h, LV_C), *x = lpv(h, LV_X);
+    double *t = lpv(h, LV_T), *c = lpv(h, LV_C);
     double *g = lpv(h, LV_G), *W = lpv(h, LV_W), *sW = lpv(h, LV_SW), *d3 = lpv(h, LV_D3);
     double *b = lpv(h, LV_B);
-    if (h->timing) {
-        for (hipEvent_t &e : h->lp_ev)
-            if (!e) GPX_HIP(hipEventCreate(&e));
-        for (double &m : h->lp_ms) m = 0.0;
-        GPX_HIP(hipEventRecord(h->lp_ev[0], s));
-    }
+    hipEvent_t *ev = h->lb_ev;
+    if (h->timing) GPX_TRY(labels_timer_start(h, h->lp_ms, 5));
     if (use_warm) {
         GPX_TRY(laplace_kv(h, a, mean, f));
     } else {
@@ -2247,18 +2353,11 @@ int gpx_laplace_update(gpx_t *h, const gpx_kspec *k, int lik, double mean, doubl
         ++it;
         const bool timed = h->timing && it == 1;
         GPX_TRY(gpx_lik_terms(s, lik, y, f, mean, n, np, g, W, sW, d3, b, h->lp_sc.as<double>() + 4));
-        if (timed) GPX_HIP(hipEventRecord(h->lp_ev[1], s));
-        GPX_TRY(laplace_factor(h, true, timed ? h->lp_ev[2] : nullptr));
-        if (timed) GPX_HIP(hipEventRecord(h->lp_ev[3], s));
+        if (timed) GPX_HIP(hipEventRecord(ev[1], s));
+        GPX_TRY(laplace_factor(h, true, timed ? ev[2] : nullptr));
+        if (timed) GPX_HIP(hipEventRecord(ev[3], s));
         // a_new = b - sW o B^-1 (sW o K b), f_new = mean + K a_new
-        GPX_TRY(laplace_kv(h, b, 0.0, x));
-        if (timed) GPX_HIP(hipEventRecord(h->lp_ev[4], s));
-        GPX_TRY(gpx_laplace_mul(s, sW, x, n, np, t));
-        GPX_TRY(laplace_solve(h, t, x));
-        GPX_TRY(gpx_laplace_nmulsub(s, b, sW, x, n, np, an));
-        if (timed) GPX_HIP(hipEventRecord(h->lp_ev[5], s));
-        GPX_TRY(laplace_kv(h, an, mean, fn));
-        if (timed) GPX_HIP(hipEventRecord(h->lp_ev[6], s));
+        GPX_TRY(labels_marginals(h, b, an, fn, timed ? ev : nullptr));
         GPX_TRY(laplace_read(h, an, fn, f, true));
         const int st = laplace_status(h, *h->hinfo, info);
         if (st != 0) return st;
@@ -2303,23 +2402,12 @@ int gpx_laplace_update(gpx_t *h, const gpx_kspec *k, int lik, double mean, doubl
     GPX_TRY(gpx_laplace_psi(s, lik, y, a, f, f, mean, n, h->lp_sc.as<double>()));
     GPX_HIP(hipMemcpyAsync(h->hres, h->scalars.p, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
     GPX_HIP(hipMemcpyAsync(h->hres + 4, h->lp_sc.p, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (h->timing) GPX_HIP(hipEventRecord(h->lp_ev[7], s));
+    if (h->timing) GPX_HIP(hipEventRecord(ev[7], s));
     GPX_HIP(hipStreamSynchronize(s));
     const int st = laplace_status(h, (int)h->hres[3], info);
     if (st != 0) return st;
     h->lZ = h->hres[4] - h->hres[1];
-    if (h->timing) {
-        auto span = [&](int e0, int e1) {
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, h->lp_ev[e0], h->lp_ev[e1]);
-            return (double)ms;
-        };
-        h->lp_ms[0] = span(0, 7);
-        h->lp_ms[1] = span(1, 2);
-        h->lp_ms[2] = span(2, 3);
-        h->lp_ms[3] = span(3, 4) + span(5, 6);
-        h->lp_ms[4] = span(4, 5);
-    }
+    if (h->timing) labels_spans(h, h->lp_ms, 7);
     h->have_factor = true;
     h->lp_mode = true;
     h->lp_approx = LP_LAPLACE;
@@ -2329,11 +2417,7 @@ int gpx_laplace_update(gpx_t *h, const gpx_kspec *k, int lik, double mean, doubl
 int gpx_laplace_loglik(gpx_t *h, double *lZ, double *dlZ)
 {
     CHECK_H(h);
-    GPX_TRY(require_state(h, ST_LAPLACE, "gpx_laplace_loglik"));
-    if (!h->have_factor || h->lp_approx != LP_LAPLACE) {
-        gpx_set_error("gpx_laplace_loglik: no mode (call gpx_laplace_update)");
-        return -1;
-    }
+    GPX_TRY(labels_ready(h, LP_LAPLACE, "gpx_laplace_loglik"));
     if (lZ) *lZ = h->lZ;
     if (!dlZ) return 0;
     const int nh = h->kp.nhyper;
@@ -2355,20 +2439,9 @@ int gpx_laplace_loglik(gpx_t *h, double *lZ, double *dlZ)
         GPX_TRY(gpx_laplace_mul(s, sW, x, n, np, t));
         GPX_TRY(gpx_laplace_symv(s, w.Kinv, h->ld, n, t, c));
         GPX_TRY(gpx_laplace_nmulsub(s, s2, sW, c, n, np, u));
+        // d lZ / d mean = sum g + sum u
         GPX_TRY(gpx_laplace_sums(s, g, u, n, h->lp_sc.as<double>() + 8));
-        GPX_TRY(gpx_laplace_weight(s, w.Kinv, h->ld, n, sW, g, u));
-        GPX_TRY(gpx_trace_grad(s, h->kp, h->X.as<double>(), n, np, h->d, w.Kinv, h->ld, g,
-                               h->partial.as<double>(), h->acc));
-        GPX_HIP(hipMemcpyAsync(h->hres, h->acc, (1 + nh) * sizeof(double), hipMemcpyDeviceToHost,
-                               s));
-        GPX_HIP(hipMemcpyAsync(h->hres + 1 + nh, h->lp_sc.as<double>() + 8, 2 * sizeof(double),
-                               hipMemcpyDeviceToHost, s));
-        GPX_HIP(hipStreamSynchronize(s));
-        // d lZ / d theta = 1/2 sum_ij (g_i g_j - Wt_ij) dK_ij; d lZ / d mean = sum g + sum u
-        h->lp_dlz.resize(nh + 1);
-        for (int i = 0; i < nh; ++i) h->lp_dlz[i] = -0.5 * h->hres[1 + i];
-        h->lp_dlz[nh] = h->hres[1 + nh] + h->hres[2 + nh];
-        h->have_inverse = true;
+        GPX_TRY(labels_grad_tail(h, g, u, 2, 8));
     }
     for (int i = 0; i <= nh; ++i) dlZ[i] = h->lp_dlz[i];
     return 0;
@@ -2389,27 +2462,15 @@ int gpx_laplace_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu
 int gpx_laplace_get_mode(gpx_t *h, int64_t n, double *f, double *g)
 {
     CHECK_H(h);
-    GPX_TRY(require_state(h, ST_LAPLACE, "gpx_laplace_get_mode"));
-    if (!h->have_factor || h->lp_approx != LP_LAPLACE || n != h->n) {
-        gpx_set_error("gpx_laplace_get_mode: no mode for %lld points (call gpx_laplace_update)",
-                      (long long)n);
-        return -1;
-    }
-    if (f) GPX_HIP(hipMemcpyAsync(f, lpv(h, LV_F), (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
-    if (g) GPX_HIP(hipMemcpyAsync(g, lpv(h, LV_G), (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
-    GPX_HIP(hipStreamSynchronize(h->stream));
-    return 0;
+    GPX_TRY(labels_ready(h, LP_LAPLACE, "gpx_laplace_get_mode", &n));
+    const int slot[2] = {LV_F, LV_G};
+    double *dst[2] = {f, g};
+    return labels_copy_out(h, slot, dst, 2, n);
 }
 
 int gpx_laplace_timings(gpx_t *h, double *ms)
 {
-    CHECK_H(h);
-    if (!ms) {
-        gpx_set_error("gpx_laplace_timings: null output");
-        return -1;
-    }
-    for (int i = 0; i < 5; ++i) ms[i] = h->lp_ms[i];
-    return 0;
+    return labels_timings(h, LP_LAPLACE, ms);
 }
 
 // ---- binary classification: expectation propagation (GPML sections 3.6 and 5.5.2) ---------------
@@ -2437,28 +2498,15 @@ int gpx_ep_update(gpx_t *h, const gpx_kspec *k, double mean, double tol, int max
     }
     if (iters) *iters = 0;
     if (info) *info = 0;
-    GPX_TRY(gpx_flatten_kspec(k, h->d, &h->kp));
-    h->have_factor = h->have_inverse = false;
-    h->lp_mode = false;
-    h->lp_approx = LP_NONE;
-    h->lp_dlz.clear();
-    h->mean = mean;
-    h->lp_lik = GPX_LIK_PROBIT;
-    GPX_TRY(laplace_reserve(h));
+    GPX_TRY(labels_begin(h, k, GPX_LIK_PROBIT, mean));
     hipStream_t s = h->stream;
     const int n = h->n, np = h->np;
     double *tau = lpv(h, EV_TAU), *nu = lpv(h, EV_NU), *sW = lpv(h, LV_SW), *nup = lpv(h, EV_NUP);
     double *Sii = lpv(h, EV_SII), *mu = lpv(h, EV_MU), *b = lpv(h, EV_B);
-    double *t = lpv(h, LV_T), *x = lpv(h, LV_X);
     double *out = h->lp_sc.as<double>();
     const double prior = gpx_kernel_prior(h->kp), tfloor = GPX_EP_FLOOR / prior;
-    hipEvent_t *ev = h->ep_ev;
-    if (h->timing) {
-        for (hipEvent_t &e : h->ep_ev)
-            if (!e) GPX_HIP(hipEventCreate(&e));
-        for (double &m : h->ep_ms) m = 0.0;
-        GPX_HIP(hipEventRecord(ev[0], s));
-    }
+    hipEvent_t *ev = h->lb_ev;
+    if (h->timing) GPX_TRY(labels_timer_start(h, h->ep_ms, 6));
     // before the first sweep: no sites, the prior's marginals
     GPX_TRY(gpx_laplace_fill(s, 0.0, n, np, tau));
     GPX_TRY(gpx_laplace_fill(s, 0.0, n, np, nu));
@@ -2499,14 +2547,7 @@ int gpx_ep_update(gpx_t *h, const gpx_kspec *k, double mean, double tol, int max
         GPX_TRY(gpx_lz_terms(s, h->A.as<double>(), h->ld, n, nup, nullptr, h->scalars.as<double>(),
                              1, 0, 0, 0, h->info.as<int>()));
         if (first) GPX_HIP(hipEventRecord(ev[3], s));
-        GPX_TRY(laplace_kv(h, nup, 0.0, x));
-        if (first) GPX_HIP(hipEventRecord(ev[4], s));
-        GPX_TRY(gpx_laplace_mul(s, sW, x, n, np, t));
-        GPX_TRY(laplace_solve(h, t, x));
-        GPX_TRY(gpx_laplace_nmulsub(s, nup, sW, x, n, np, b));
-        if (first) GPX_HIP(hipEventRecord(ev[5], s));
-        GPX_TRY(laplace_kv(h, b, mean, mu));
-        if (first) GPX_HIP(hipEventRecord(ev[6], s));     // (ev[7]: behind the next site pass)
+        GPX_TRY(labels_marginals(h, nup, b, mu, first ? ev : nullptr));    // (ev[7]: next site pass)
         GPX_TRY(gpx_ep_rownorm(s, h->W.as<double>(), h->ld, n, np, tau, Sii));
     }
     if (iters) *iters = it;
@@ -2516,17 +2557,8 @@ int gpx_ep_update(gpx_t *h, const gpx_kspec *k, double mean, double tol, int max
     if (h->timing) {
         GPX_HIP(hipEventRecord(ev[8], s));
         GPX_HIP(hipEventSynchronize(ev[8]));
-        auto span = [&](int e0, int e1) {
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, ev[e0], ev[e1]);
-            return (double)ms;
-        };
-        h->ep_ms[0] = span(0, 8);
-        h->ep_ms[1] = span(1, 2);
-        h->ep_ms[2] = span(2, 3);
-        h->ep_ms[3] = span(3, 4) + span(5, 6);
-        h->ep_ms[4] = span(4, 5);
-        h->ep_ms[5] = span(6, 7);
+        labels_spans(h, h->ep_ms, 8);
+        h->ep_ms[5] = labels_span(h, 6, 7);
     }
     h->have_factor = true;
     h->lp_approx = LP_EP;
@@ -2536,38 +2568,20 @@ int gpx_ep_update(gpx_t *h, const gpx_kspec *k, double mean, double tol, int max
 int gpx_ep_loglik(gpx_t *h, double *lZ, double *dlZ)
 {
     CHECK_H(h);
-    GPX_TRY(require_state(h, ST_LAPLACE, "gpx_ep_loglik"));
-    if (!h->have_factor || h->lp_approx != LP_EP) {
-        gpx_set_error("gpx_ep_loglik: no fixed point (call gpx_ep_update)");
-        return -1;
-    }
+    GPX_TRY(labels_ready(h, LP_EP, "gpx_ep_loglik"));
     if (lZ) *lZ = h->lZ;
     if (!dlZ) return 0;
     const int nh = h->kp.nhyper;
     if (h->lp_dlz.empty()) {
-        // lZ is stationary in the sites at the fixed point, so the gradient has the explicit term
-        // only: B^-1's buffer becomes Wt = sW sW^T o B^-1 (Laplace's weight with u = 0), the trace
-        // pass takes it with b; computed once per update
+        // B^-1's buffer becomes Wt = sW sW^T o B^-1 (Laplace's weight with u = 0), the trace pass
+        // takes it with b; computed once per update. d lZ / d mean = sum b
         hipStream_t s = h->stream;
-        const DenseWs w = h->ws();
         const int n = h->n, np = h->np;
         double *b = lpv(h, EV_B), *zero = lpv(h, EV_ZERO);
-        GPX_TRY(gpx_lauum(s, w));                                   // B^-1 (upper)
+        GPX_TRY(gpx_lauum(s, h->ws()));                             // B^-1 (upper)
         GPX_TRY(gpx_laplace_fill(s, 0.0, n, np, zero));
         GPX_TRY(gpx_laplace_sums(s, b, zero, n, h->lp_sc.as<double>() + 10));
-        GPX_TRY(gpx_laplace_weight(s, w.Kinv, h->ld, n, lpv(h, LV_SW), zero, zero));
-        GPX_TRY(gpx_trace_grad(s, h->kp, h->X.as<double>(), n, np, h->d, w.Kinv, h->ld, b,
-                               h->partial.as<double>(), h->acc));
-        GPX_HIP(hipMemcpyAsync(h->hres, h->acc, (1 + nh) * sizeof(double), hipMemcpyDeviceToHost,
-                               s));
-        GPX_HIP(hipMemcpyAsync(h->hres + 1 + nh, h->lp_sc.as<double>() + 10, sizeof(double),
-                               hipMemcpyDeviceToHost, s));
-        GPX_HIP(hipStreamSynchronize(s));
-        // d lZ / d theta = 1/2 sum_ij (b_i b_j - Wt_ij) dK_ij; d lZ / d mean = sum b
-        h->lp_dlz.resize(nh + 1);
-        for (int i = 0; i < nh; ++i) h->lp_dlz[i] = -0.5 * h->hres[1 + i];
-        h->lp_dlz[nh] = h->hres[1 + nh];
-        h->have_inverse = true;
+        GPX_TRY(labels_grad_tail(h, b, zero, 1, 10));
     }
     for (int i = 0; i <= nh; ++i) dlZ[i] = h->lp_dlz[i];
     return 0;
@@ -2587,31 +2601,15 @@ int gpx_ep_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, dou
 int gpx_ep_get_sites(gpx_t *h, int64_t n, double *tau, double *nu, double *mu, double *s2)
 {
     CHECK_H(h);
-    GPX_TRY(require_state(h, ST_LAPLACE, "gpx_ep_get_sites"));
-    if (!h->have_factor || h->lp_approx != LP_EP || n != h->n) {
-        gpx_set_error("gpx_ep_get_sites: no fixed point for %lld points (call gpx_ep_update)",
-                      (long long)n);
-        return -1;
-    }
+    GPX_TRY(labels_ready(h, LP_EP, "gpx_ep_get_sites", &n));
     const int slot[4] = {EV_TAU, EV_NU, EV_MU, EV_SII};
     double *dst[4] = {tau, nu, mu, s2};
-    for (int i = 0; i < 4; ++i)
-        if (dst[i])
-            GPX_HIP(hipMemcpyAsync(dst[i], lpv(h, slot[i]), (size_t)n * 8, hipMemcpyDeviceToHost,
-                                   h->stream));
-    GPX_HIP(hipStreamSynchronize(h->stream));
-    return 0;
+    return labels_copy_out(h, slot, dst, 4, n);
 }
 
 int gpx_ep_timings(gpx_t *h, double *ms)
 {
-    CHECK_H(h);
-    if (!ms) {
-        gpx_set_error("gpx_ep_timings: null output");
-        return -1;
-    }
-    for (int i = 0; i < 6; ++i) ms[i] = h->ep_ms[i];
-    return 0;
+    return labels_timings(h, LP_EP, ms);
 }
 
 // ---- multi-output data: T outputs at the same inputs, one kernel, one factorisation --------

@@ -8,13 +8,12 @@ its own iteration in `_iterate`.
 
 import numpy as np
 
-from .. import _lib
-from .exact import GP
+from ._device import DeviceGP
 
 __all__ = ['LabelsGP']
 
 
-class LabelsGP(GP):
+class LabelsGP(DeviceGP):
     """Hyper layout [kernel | mean]: the likelihoods have no hyperparameter."""
 
     _what = None               # 'Laplace', 'EP': "... is not built for <what> inference"
@@ -28,36 +27,7 @@ class LabelsGP(GP):
         super(LabelsGP, self).__init__(likelihood, kernel, mean)
         self._tol = tol
         self._max_iter = max_iter
-        self._dev_ = None          # _lib.Handle, created on first use
-        self._resident = False     # X, y uploaded to this handle
-        self._factored = False     # device holds the approximation for the current hypers
         self._iters = 0
-
-    # -- device state (as ExactGP) ---------------------------------------------
-    def _dev(self):
-        if self._dev_ is None:
-            self._dev_ = _lib.Handle()
-            self._resident = False
-        return self._dev_
-
-    def _data_changed(self):
-        self._resident = False
-        self._factored = False
-
-    def __deepcopy__(self, memo):
-        import copy
-        clone = type(self).__new__(type(self))
-        memo[id(self)] = clone
-        for key, val in self.__dict__.items():
-            if key not in ('_dev_', '_resident', '_factored'):
-                setattr(clone, key, copy.deepcopy(val, memo))
-        clone._dev_, clone._resident, clone._factored = None, False, False
-        return clone
-
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state['_dev_'], state['_resident'], state['_factored'] = None, False, False
-        return state
 
     @classmethod
     def from_gp(cls, gp, likelihood=None, **kwargs):
@@ -75,10 +45,6 @@ class LabelsGP(GP):
             new.add_data(*gp.data)
         return new
 
-    def reset(self):
-        super(LabelsGP, self).reset()
-        self._data_changed()
-
     def set_hyper(self, hyper):
         self._factored = False
         super(LabelsGP, self).set_hyper(hyper)
@@ -90,21 +56,10 @@ class LabelsGP(GP):
         raise NotImplementedError
 
     def _update(self):
-        if not (np.all(np.isfinite(self.get_hyper())) and
-                (self._resident or np.all(np.isfinite(self._X)))):
-            self._factored = False
-            raise ValueError('array must not contain infs or NaNs')
-        dev = self._dev()
-        if not self._resident:
-            dev.laplace_set_data(self._X, self._y)
-            self._resident = True
-        self._factored = False
+        # (the labels are checked by laplace_set_data itself: -1 or +1)
+        dev = self._upload('laplace_set_data', (self._X, self._y), check=(self._X,))
         self._iters = self._iterate(dev)
         self._factored = True
-
-    def _ensure(self):
-        if self.ndata > 0 and not self._factored:
-            self._update()
 
     def _call(self, name, *args):
         return getattr(self._dev(), self._entry + '_' + name)(*args)
@@ -122,19 +77,17 @@ class LabelsGP(GP):
             raise NotImplementedError('input gradients of the %s posterior are not built'
                                       % self._what)
         if self._X is None:
-            return np.full(X.shape[0], self._mean), self._kernel.dget(X)
+            return self._prior(X)
         self._ensure()
-        if X.shape[1] != self._X.shape[1]:
-            raise ValueError('test inputs have the wrong dimension')
+        self._check_width(X)
         return self._call('posterior', X)
 
     def _full_posterior(self, X):
         """Mean vector and full covariance of the latent f; `sample` draws from it."""
         if self._X is None:
-            return np.full(X.shape[0], self._mean), self._kernel.get(X)
+            return self._prior(X, full=True)
         self._ensure()
-        if X.shape[1] != self._X.shape[1]:
-            raise ValueError('test inputs have the wrong dimension')
+        self._check_width(X)
         return self._call('posterior_full', X)
 
     def predict_proba(self, X):

@@ -14,57 +14,24 @@ add_data's to rounding, not bit for bit, which is why it is a method of its own.
 import numpy as np
 
 from ..likelihoods import Gaussian
-from .. import _lib
-from .exact import GP
+from ._device import DeviceGP
 from .select import select_pseudoinputs, _check as select_check
 
 __all__ = ['SparseGP']
 
 
-class SparseGP(GP):
+class SparseGP(DeviceGP):
     """Base of FITC, DTC and VFE: a Gaussian likelihood and p pseudo-inputs U."""
 
     _method = None          # _lib.GPX_FITC / GPX_DTC / GPX_VFE
+    # (_appends_in_place: append_data calls served by gpx_sparse_append)
+    _transient = dict(DeviceGP._transient, _appends_in_place=0)
 
     def __init__(self, likelihood, kernel, mean, U):
         if not isinstance(likelihood, Gaussian):
             raise ValueError('sparse inference requires a Gaussian likelihood')
         super(SparseGP, self).__init__(likelihood, kernel, mean)
         self._U = np.array(U, ndmin=2, dtype=float, copy=True)
-        self._dev_ = None
-        self._resident = False
-        self._factored = False
-        self._appends_in_place = 0  # append_data calls served by gpx_sparse_append
-
-    # -- device state -------------------------------------------------------
-    def _dev(self):
-        if self._dev_ is None:
-            self._dev_ = _lib.Handle()
-            self._resident = False
-        return self._dev_
-
-    def _data_changed(self):
-        self._resident = False
-        self._factored = False
-
-    def __deepcopy__(self, memo):
-        """A copy gets hypers, pseudo-inputs and host data, never the device handle; it
-        uploads and refactors lazily (as ExactGP.__deepcopy__)."""
-        import copy
-        clone = type(self).__new__(type(self))
-        memo[id(self)] = clone
-        for key, val in self.__dict__.items():
-            if key not in ('_dev_', '_resident', '_factored', '_appends_in_place'):
-                setattr(clone, key, copy.deepcopy(val, memo))
-        clone._dev_, clone._resident, clone._factored = None, False, False
-        clone._appends_in_place = 0
-        return clone
-
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state['_dev_'], state['_resident'], state['_factored'] = None, False, False
-        state['_appends_in_place'] = 0
-        return state
 
     @property
     def pseudoinputs(self):
@@ -113,37 +80,16 @@ class SparseGP(GP):
             raise ValueError('no data')
         p = self._U.shape[0] if p is None else p
         select_check(self._X.shape[0], self._X.shape[1], p, tol)
-        if not np.all(np.isfinite(self._kernel.get_hyper())):
-            raise ValueError('array must not contain infs or NaNs')
-        dev = self._dev()
-        if not self._resident:
-            if not (np.all(np.isfinite(self._X)) and np.all(np.isfinite(self._y))):
-                raise ValueError('array must not contain infs or NaNs')
-            dev.set_data(self._X, self._y)
-            self._resident = True
-            self._factored = False
+        dev = self._upload('set_data', (self._X, self._y))
         idx, _, trace = dev.select_pivots(self._kernel._kspec(), None, int(p), tol)
         self.set_pseudoinputs(self._X[idx])
         return idx, trace
 
-    def reset(self):
-        super(SparseGP, self).reset()
-        self._data_changed()
-
     # -- the hot path -------------------------------------------------------
     def _update(self):
-        if not (np.all(np.isfinite(self.get_hyper())) and
-                (self._resident or (np.all(np.isfinite(self._X)) and
-                                    np.all(np.isfinite(self._y))))):
-            self._factored = False
-            raise ValueError('array must not contain infs or NaNs')
         if self._U.shape[1] != self._X.shape[1]:
             raise ValueError('pseudo-inputs have the wrong dimension')
-        dev = self._dev()
-        if not self._resident:
-            dev.set_data(self._X, self._y)
-            self._resident = True
-        self._factored = False
+        dev = self._upload('set_data', (self._X, self._y))
         dev.sparse_update(self._kernel._kspec(), self._method, self._U,
                           self._likelihood.get_hyper()[0], self._mean)
         self._factored = True
@@ -180,10 +126,6 @@ class SparseGP(GP):
         self._y = np.r_[self._y, y]
         self._appends_in_place += 1
 
-    def _ensure(self):
-        if self.ndata > 0 and not self._factored:
-            self._update()
-
     def loglikelihood(self, grad=False, pseudoinputs=False):
         """lZ (and dlZ with grad); with pseudoinputs, (lZ, dlZ, dU) where dU = d lZ / d U
         has the shape of the pseudo-inputs."""
@@ -196,12 +138,9 @@ class SparseGP(GP):
 
     def _marg_posterior(self, X, grad=False):
         if self._X is None:
-            prior = (np.full(X.shape[0], self._mean), self._kernel.dget(X))
-            # constant mean, stationary kernel: flat prior gradients
-            return prior + (np.zeros_like(X), np.zeros_like(X)) if grad else prior
+            return self._prior(X, grad=grad)
         self._ensure()
-        if X.shape[1] != self._X.shape[1]:
-            raise ValueError('test inputs have the wrong dimension')
+        self._check_width(X)
         return self._dev().sparse_posterior(X, grad)
 
     def _full_posterior(self, X):
@@ -210,10 +149,9 @@ class SparseGP(GP):
             raise ValueError('the full posterior covers at most 8192 points (got %d)'
                              % X.shape[0])
         if self._X is None:
-            return np.full(X.shape[0], self._mean), self._kernel.get(X)
+            return self._prior(X, full=True)
         self._ensure()
-        if X.shape[1] != self._X.shape[1]:
-            raise ValueError('test inputs have the wrong dimension')
+        self._check_width(X)
         return self._dev().sparse_posterior_full(X)
 
     def _state(self, i):

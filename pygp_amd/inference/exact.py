@@ -14,163 +14,22 @@ add_data, and sends only hyperparameters down and a few doubles back up.
 
 import numpy as np
 
-from ..utils.models import Parameterized
 from ..likelihoods import Gaussian
-from .. import _lib
+from ._device import GP, DeviceGP
 
 __all__ = ['GP', 'ExactGP']
 
 
-class GP(Parameterized):
-    """State machine of a GP model: hypers, data, and when to refactorise."""
-
-    def __init__(self, likelihood, kernel, mean):
-        self._likelihood = likelihood
-        self._kernel = kernel
-        self._mean = float(mean)
-        self._X = None
-        self._y = None
-        self.nhyper = likelihood.nhyper + kernel.nhyper + 1
-
-    # -- bookkeeping ------------------------------------------------------
-    def reset(self):
-        """Forget all data."""
-        self._X = None
-        self._y = None
-
-    def __repr__(self):
-        def hang(prefix, text):
-            return prefix + ('\n' + ' ' * len(prefix)).join(text.splitlines())
-        inner = ',\n'.join([hang('likelihood=', repr(self._likelihood)),
-                            hang('kernel=', repr(self._kernel)),
-                            hang('mean=', str(self._mean))])
-        return hang(type(self).__name__ + '(', inner + ')')
-
-    def _params(self):
-        out = [('like.' + p[0],) + tuple(p[1:]) for p in self._likelihood._params()]
-        out += [('kern.' + p[0],) + tuple(p[1:]) for p in self._kernel._params()]
-        return out + [('mean', 1, False)]
-
-    def get_hyper(self):
-        return np.r_[self._likelihood.get_hyper(), self._kernel.get_hyper(),
-                     self._mean]
-
-    def set_hyper(self, hyper):
-        nl, nk = self._likelihood.nhyper, self._kernel.nhyper
-        self._likelihood.set_hyper(hyper[:nl])
-        self._kernel.set_hyper(hyper[nl:nl + nk])
-        self._mean = hyper[-1]
-        if self.ndata > 0:
-            self._update()
-
-    @property
-    def ndata(self):
-        return 0 if self._X is None else self._X.shape[0]
-
-    @property
-    def data(self):
-        return (self._X, self._y)
-
-    def add_data(self, X, y):
-        X = self._kernel.transform(X)
-        y = self._likelihood.transform(y)
-        if self._X is None:
-            self._X, self._y = X.copy(), y.copy()
-            self._data_changed()
-            self._update()
-            return
-        # same flow as the reference (_base.py:132-141): try the incremental
-        # update, refactorise from scratch if it is not available
-        try:
-            self._updateinc(X, y)
-            self._X = np.r_[self._X, X]
-            self._y = np.r_[self._y, y]
-        except NotImplementedError:
-            self._X = np.r_[self._X, X]
-            self._y = np.r_[self._y, y]
-            self._data_changed()
-            self._update()
-
-    def _updateinc(self, X, y):
-        raise NotImplementedError
-
-    def posterior(self, X, grad=False):
-        return self._marg_posterior(self._kernel.transform(X), grad)
-
-    def sample(self, X, m=None, latent=True, rng=None):
-        """Joint samples of the posterior at X (_base.py:143-178): an n-vector, or an
-        (m, n) array when m is given; latent=False adds the observation noise. rng:
-        None -> NumPy's global state, an int seed or a RandomState."""
-        import scipy.linalg as sla
-        X = self._kernel.transform(X)
-        flatten = m is None
-        m = 1 if flatten else m
-        n = len(X)
-        if rng is None:
-            rng = np.random.mtrand._rand
-        elif not isinstance(rng, np.random.RandomState):
-            rng = np.random.RandomState(rng)
-        mu, Sigma = self._full_posterior(X)
-        Sigma = Sigma + 1e-10 * np.eye(n)
-        f = mu[None] + np.dot(rng.normal(size=(m, n)), sla.cholesky(Sigma))
-        if not latent:
-            f = self._likelihood.sample(f.ravel(), rng).reshape(m, n)
-        return f.ravel() if flatten else f
-
-    def sample_fourier(self, N, rng=None):
-        raise NotImplementedError(
-            'Fourier-basis function samples are outside the accelerated path')
-
-    def _full_posterior(self, X):
-        raise NotImplementedError
-
-    def gradient_posterior(self, X):
-        """(mu, S): mean (m, d) and covariance (m, d, d) of grad f at the rows of X."""
-        raise NotImplementedError(
-            'the posterior of the gradient is provided by exact inference only')
-
-
-class ExactGP(GP):
+class ExactGP(DeviceGP):
     """Exact inference; the likelihood must be Gaussian (exact.py:28-35)."""
+
+    # (_appends_in_place: add_data calls served by gpx_exact_append)
+    _transient = dict(DeviceGP._transient, _appends_in_place=0)
 
     def __init__(self, likelihood, kernel, mean):
         if not isinstance(likelihood, Gaussian):
             raise ValueError('exact inference requires a Gaussian likelihood')
         super(ExactGP, self).__init__(likelihood, kernel, mean)
-        self._dev_ = None          # _lib.Handle, created on first use
-        self._resident = False     # X, y uploaded to this handle
-        self._factored = False     # device holds R, a for the current hypers
-        self._appends_in_place = 0  # add_data calls served by gpx_exact_append
-
-    # -- device state -------------------------------------------------------
-    def _dev(self):
-        if self._dev_ is None:
-            self._dev_ = _lib.Handle()
-            self._resident = False
-        return self._dev_
-
-    def _data_changed(self):
-        self._resident = False
-        self._factored = False
-
-    def __deepcopy__(self, memo):
-        """copy.deepcopy (Parameterized.copy, models.py:47-55) must not share a
-        device handle: the clone gets hypers + host data and re-uploads and
-        refactorises lazily."""
-        import copy
-        clone = type(self).__new__(type(self))
-        memo[id(self)] = clone
-        for key, val in self.__dict__.items():
-            if key not in ('_dev_', '_resident', '_factored', '_appends_in_place'):
-                setattr(clone, key, copy.deepcopy(val, memo))
-        clone._dev_, clone._resident, clone._factored = None, False, False
-        clone._appends_in_place = 0
-        return clone
-
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state['_dev_'], state['_resident'], state['_factored'] = None, False, False
-        return state
 
     @classmethod
     def from_gp(cls, gp):
@@ -179,25 +38,10 @@ class ExactGP(GP):
             new.add_data(*gp.data)
         return new
 
-    def reset(self):
-        super(ExactGP, self).reset()
-        self._data_changed()
-
     # -- the hot path -------------------------------------------------------
     def _update(self):
         """K + sn^2 I -> R -> a on the device (exact.py:50-55)."""
-        # scipy.linalg.cholesky(check_finite=True) at exact.py:54 refuses a matrix
-        # with NaN/inf entries; they can only come from the data or the hypers
-        if not (np.all(np.isfinite(self.get_hyper())) and
-                (self._resident or (np.all(np.isfinite(self._X)) and
-                                    np.all(np.isfinite(self._y))))):
-            self._factored = False
-            raise ValueError('array must not contain infs or NaNs')
-        dev = self._dev()
-        if not self._resident:
-            dev.set_data(self._X, self._y)
-            self._resident = True
-        self._factored = False
+        dev = self._upload('set_data', (self._X, self._y))
         dev.exact_update(self._kernel._kspec(),
                          self._likelihood.get_hyper()[0], self._mean)
         self._factored = True
@@ -207,6 +51,8 @@ class ExactGP(GP):
         (exact.py:57-62) when the current factor can be extended in place."""
         if not (self._factored and self._resident):
             raise NotImplementedError
+        if X.shape[0] != y.shape[0]:                 # (as SparseGP.append_data, and exact_append)
+            raise ValueError('X and y disagree')
         if X.shape[1] != self._X.shape[1]:
             raise ValueError('new inputs have the wrong dimension')
         if not (np.all(np.isfinite(X)) and np.all(np.isfinite(y))):
@@ -224,10 +70,6 @@ class ExactGP(GP):
         if not extended:
             raise NotImplementedError
         self._appends_in_place += 1
-
-    def _ensure(self):
-        if self.ndata > 0 and not self._factored:
-            self._update()
 
     def loglikelihood(self, grad=False):
         """log marginal likelihood (and d/d hyper) (exact.py:118-143)."""
@@ -256,12 +98,9 @@ class ExactGP(GP):
     def _marg_posterior(self, X, grad=False):
         """Predictive mean and variance (exact.py:81-97)."""
         if self._X is None:
-            prior = (np.full(X.shape[0], self._mean), self._kernel.dget(X))
-            # constant mean, stationary kernel: flat prior gradients (exact.py:99-101)
-            return prior + (np.zeros_like(X), np.zeros_like(X)) if grad else prior
+            return self._prior(X, grad=grad)
         self._ensure()
-        if X.shape[1] != self._X.shape[1]:
-            raise ValueError('test inputs have the wrong dimension')
+        self._check_width(X)
         if grad:                       # exact.py:99-116
             return self._dev().exact_posterior_grad(X)
         return self._dev().exact_posterior(X)
@@ -269,10 +108,9 @@ class ExactGP(GP):
     def _full_posterior(self, X):
         """Mean vector and full covariance (exact.py:64-79)."""
         if self._X is None:
-            return np.full(X.shape[0], self._mean), self._kernel.get(X)
+            return self._prior(X, full=True)
         self._ensure()
-        if X.shape[1] != self._X.shape[1]:
-            raise ValueError('test inputs have the wrong dimension')
+        self._check_width(X)
         return self._dev().exact_posterior_full(X)
 
     def gradient_posterior(self, X):
@@ -292,8 +130,7 @@ class ExactGP(GP):
                 S[:] = self._kernel.gradxy(X[:1])[0, 0]
             return np.zeros_like(X), S
         self._ensure()
-        if X.shape[1] != self._X.shape[1]:
-            raise ValueError('test inputs have the wrong dimension')
+        self._check_width(X)
         return self._dev().exact_posterior_gradient(X)
 
     # gp._R / gp._a as the reference exposes them (upper factor, R^-T (y-m))

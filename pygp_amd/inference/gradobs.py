@@ -113,17 +113,9 @@ class GradientGP(ExactGP):
         if self.ngrad == 0:
             return super(GradientGP, self)._update()
         self._kernel._check_gradxy()
-        finite = np.all(np.isfinite(self.get_hyper()))
-        if finite and not self._resident and self._X is not None:
-            finite = np.all(np.isfinite(self._X)) and np.all(np.isfinite(self._y))
-        if not finite:
-            self._factored = False
-            raise ValueError('array must not contain infs or NaNs')
-        dev = self._dev()
-        if not self._resident:
-            dev.gradobs_set_data(self._X, self._y, self._Xg, self._G)
-            self._resident = True
-        self._factored = False
+        # (the gradients were checked on their way in, add_gradient_data)
+        dev = self._upload('gradobs_set_data', (self._X, self._y, self._Xg, self._G),
+                           check=() if self._X is None else (self._X, self._y))
         dev.gradobs_update(self._kernel._kspec(), self._likelihood.get_hyper()[0],
                            self._grad_noise, self._mean)
         self._factored = True
@@ -149,8 +141,7 @@ class GradientGP(ExactGP):
         if grad:
             raise NotImplementedError('input gradients of the posterior under derivative '
                                       'observations are not built')
-        if X.shape[1] != self._Xg.shape[1]:
-            raise ValueError('test inputs have the wrong dimension')
+        self._check_width(X, self._Xg)
         self._ensure()
         return self._dev().gradobs_posterior(X)
 
@@ -158,8 +149,7 @@ class GradientGP(ExactGP):
         """Mean vector and full covariance of f; `sample` draws from it."""
         if self.ngrad == 0:
             return super(GradientGP, self)._full_posterior(X)
-        if X.shape[1] != self._Xg.shape[1]:
-            raise ValueError('test inputs have the wrong dimension')
+        self._check_width(X, self._Xg)
         self._ensure()
         return self._dev().gradobs_posterior_full(X)
 

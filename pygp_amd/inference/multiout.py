@@ -82,16 +82,7 @@ class MultiOutputGP(ExactGP):
     # -- device ---------------------------------------------------------------
     def _update(self):
         """K + sn^2 I -> R -> a_1 .. a_T on the device."""
-        if not (np.all(np.isfinite(self.get_hyper())) and
-                (self._resident or (np.all(np.isfinite(self._X)) and
-                                    np.all(np.isfinite(self._y))))):
-            self._factored = False
-            raise ValueError('array must not contain infs or NaNs')
-        dev = self._dev()
-        if not self._resident:
-            dev.mo_set_data(self._X, self._y)
-            self._resident = True
-        self._factored = False
+        dev = self._upload('mo_set_data', (self._X, self._y))
         dev.mo_update(self._kernel._kspec(), self._likelihood.get_hyper()[0], self._mean)
         self._factored = True
 
@@ -109,8 +100,7 @@ class MultiOutputGP(ExactGP):
                                       'several outputs')
         if self._X is None:
             raise ValueError('no data: the number of outputs is not known yet')
-        if X.shape[1] != self._X.shape[1]:
-            raise ValueError('test inputs have the wrong dimension')
+        self._check_width(X)
         self._ensure()
         return self._dev().mo_posterior(X)
 
@@ -118,8 +108,7 @@ class MultiOutputGP(ExactGP):
         """(mu (m, T), Sigma (m, m)): Sigma is the covariance of every output."""
         if self._X is None:
             raise ValueError('no data: the number of outputs is not known yet')
-        if X.shape[1] != self._X.shape[1]:
-            raise ValueError('test inputs have the wrong dimension')
+        self._check_width(X)
         self._ensure()
         return self._dev().mo_posterior_full(X)
 

@@ -358,3 +358,143 @@ def test_the_switch_to_safe_mode_is_opt_in_and_visible():
     f.switched.clear()
     with pytest.raises(_lib.GpxError, match='timed out waiting'):
         f.work()
+
+
+# -- the shared bindings of _lib.Handle and the device state of the models, without a device --
+
+class StubLib(object):
+    """Stands in for the loaded libgpx.so: every gpx_* entry records its name and returns 0."""
+
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        if not name.startswith('gpx_'):
+            raise AttributeError(name)
+
+        def entry(*args):
+            self.calls.append(name)
+            return 0
+        return entry
+
+
+from pygp_amd._lib import Handle as REAL_HANDLE           # noqa: E402  (tests below replace the name)
+
+
+def stub_handle():
+    """A real _lib.Handle around a StubLib: the bindings run, nothing native does."""
+    import threading
+    h = REAL_HANDLE.__new__(REAL_HANDLE)
+    h._L, h._h, h._lock = StubLib(), object(), threading.RLock()
+    return h
+
+
+def _device_models():
+    from pygp_amd.inference import (ExactGP, MultiOutputGP, GradientGP, FITC, DTC, VFE,
+                                    LaplaceGP, EPGP)
+    from pygp_amd.likelihoods import Gaussian, Logistic, Probit
+    k = lambda: pk.SE(1.3, [0.5, 1.5])                                        # noqa: E731
+    U = np.arange(6.0).reshape(3, 2)
+    return [
+        (ExactGP(Gaussian(0.1), k(), 0.3), {}),
+        (MultiOutputGP(Gaussian(0.1), k(), 0.3), {}),
+        (GradientGP(Gaussian(0.1), k(), 0.3, grad_noise=0.25), {'_grad_noise': 0.25}),
+        (FITC(Gaussian(0.1), k(), 0.3, U), {'_U': U}),
+        (DTC(Gaussian(0.1), k(), 0.3, U), {'_U': U}),
+        (VFE(Gaussian(0.1), k(), 0.3, U), {'_U': U}),
+        (LaplaceGP(Logistic(), k(), 0.3, tol=1e-6, max_iter=17, warm_start=True),
+         {'_tol': 1e-6, '_max_iter': 17, '_warm_start': True}),
+        (EPGP(Probit(), k(), 0.3, tol=1e-7, max_iter=19, damping=0.5),
+         {'_tol': 1e-7, '_max_iter': 19, '_damping': 0.5}),
+    ]
+
+
+@pytest.mark.parametrize('index', range(8))
+def test_copies_and_pickles_carry_no_device_state(index):
+    """deepcopy, copy() and a pickle agree: no handle, nothing resident or factored, the count
+    of in-place appends back at 0; the hypers and the family's own options come along."""
+    import copy
+    import pickle
+    m, options = _device_models()[index]
+    counted = hasattr(m, '_appends_in_place')
+    assert counted == (type(m).__name__ in ('ExactGP', 'MultiOutputGP', 'GradientGP', 'FITC',
+                                            'DTC', 'VFE'))
+    if counted:
+        m._appends_in_place = 3
+    m._resident = m._factored = True
+    for clone in (copy.deepcopy(m), m.copy(), pickle.loads(pickle.dumps(m))):
+        assert type(clone) is type(m)
+        assert clone._dev_ is None
+        assert clone._resident is False and clone._factored is False
+        if counted:
+            assert clone._appends_in_place == 0
+        nt.assert_array_equal(clone.get_hyper(), m.get_hyper())
+        for name, value in options.items():
+            nt.assert_array_equal(getattr(clone, name), value)
+            assert type(getattr(clone, name)) is type(getattr(m, name))
+    # the original keeps what it had
+    assert m._resident is True and m._factored is True
+    assert not counted or m._appends_in_place == 3
+
+
+@pytest.mark.parametrize('entry', ['exact_append', 'sparse_append'])
+def test_append_compares_the_lengths_before_any_native_call(entry):
+    h = stub_handle()
+    X, y = np.random.RandomState(1).rand(4, 2), np.arange(4.0)
+    with pytest.raises(ValueError, match='X and y disagree'):
+        getattr(h, entry)(X[:3], y[:2])
+    assert h._L.calls == []
+    assert getattr(h, entry)(X[:3], y[:3]) is True
+    assert h._L.calls == ['gpx_' + entry]
+
+
+def test_exact_gp_refuses_an_append_of_unequal_lengths(monkeypatch):
+    from pygp_amd import _lib
+    from pygp_amd.inference import ExactGP
+    from pygp_amd.likelihoods import Gaussian
+    monkeypatch.setattr(_lib, 'Handle', stub_handle)
+    X, y = np.random.RandomState(2).rand(4, 2), np.arange(4.0)
+    gp = ExactGP(Gaussian(0.1), pk.SE(1.0, [1.0, 2.0]), 0.0)
+    gp.add_data(X, y)
+    assert gp._dev_._L.calls == ['gpx_set_data', 'gpx_exact_update'] and gp._factored
+    with pytest.raises(ValueError, match='X and y disagree'):
+        gp.add_data(X[:3], y[:2])
+    assert gp.ndata == 4 and gp.data[1].shape == (4,)
+    assert gp._dev_._L.calls == ['gpx_set_data', 'gpx_exact_update']
+    assert gp._resident and gp._factored and gp._appends_in_place == 0
+    gp.add_data(X[:3], y[:3])                                # the lengths agree: in place
+    assert gp.ndata == 7 and gp._appends_in_place == 1
+    assert gp._dev_._L.calls[-1] == 'gpx_exact_append'
+
+
+FOLDED = [
+    # a posterior at Xs (5, 2): the shapes of its results (three outputs under mo_*); a
+    # likelihood: how many entries its gradient has beyond the kernel's
+    ('exact_posterior', [(5,), (5,)]), ('exact_posterior_full', [(5,), (5, 5)]),
+    ('gradobs_posterior', [(5,), (5,)]), ('gradobs_posterior_full', [(5,), (5, 5)]),
+    ('laplace_posterior', [(5,), (5,)]), ('laplace_posterior_full', [(5,), (5, 5)]),
+    ('ep_posterior', [(5,), (5,)]), ('ep_posterior_full', [(5,), (5, 5)]),
+    ('mo_posterior', [(5, 3), (5,)]), ('mo_posterior_full', [(5, 3), (5, 5)]),
+    ('sparse_posterior_full', [(5,), (5, 5)]),
+    ('exact_loglik', 2), ('mo_loglik', 2), ('sparse_loglik', 2), ('laplace_loglik', 1),
+    ('ep_loglik', 1),
+]
+
+
+@pytest.mark.parametrize('method,want', FOLDED, ids=[f[0] for f in FOLDED])
+def test_folded_bindings_keep_their_shapes_and_their_own_entries(method, want):
+    h = stub_handle()
+    h._mo_T = 3                                   # (what mo_set_data leaves on the handle)
+    if isinstance(want, list):
+        Xs = np.asfortranarray(np.random.RandomState(3).rand(5, 2))
+        out = getattr(h, method)(Xs)
+        assert isinstance(out, tuple) and [a.shape for a in out] == want
+        assert all(a.dtype == np.float64 and a.flags.c_contiguous for a in out)
+    else:
+        nhyper = 4
+        value = getattr(h, method)(nhyper)
+        assert type(value) is float
+        assert type(getattr(h, method)(nhyper, grad=False)) is float
+        lZ, dlZ = getattr(h, method)(nhyper, True)
+        assert type(lZ) is float and dlZ.shape == (nhyper + want,) and dlZ.dtype == np.float64
+    assert set(h._L.calls) == {'gpx_' + method}
