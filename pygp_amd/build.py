@@ -17,11 +17,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(CSRC, '_obj')
 LIB = os.path.join(HERE, 'libgpx.so')
-SOURCES = ['gpx_api.hip', 'kmat.hip', 'gemm_f64.hip', 'chol.hip', 'leaf.hip', 'panel.hip', 'vec.hip',
-           'multi.hip', 'group.hip', 'sparse.hip', 'loo.hip', 'select.hip', 'laplace.hip', 'ep.hip']
+SOURCES = ['gpx_api.hip', 'kmat.hip', 'kgrad.hip', 'kderiv.hip', 'gemm_f64.hip', 'chol.hip', 'leaf.hip',
+           'panel.hip', 'vec.hip', 'multi.hip', 'group.hip', 'sparse.hip', 'loo.hip', 'select.hip',
+           'laplace.hip', 'ep.hip']
 HEADERS = [os.path.join(CSRC, 'gpx_internal.h'), os.path.join(CSRC, 'gpx_env.h'),
            os.path.join(CSRC, 'gemm_tile.h'), os.path.join(CSRC, 'leaf_dev.h'),
-           os.path.join(CSRC, 'lik_dev.h'),
+           os.path.join(CSRC, 'lik_dev.h'), os.path.join(CSRC, 'kmat_dev.h'),
            os.path.join(HERE, '..', 'include', 'gpx.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall',
          '-Wno-unused-function']

@@ -119,6 +119,17 @@ struct MemberBatch {
     long long mstride = 0;                   // between the members' np x ld matrices
     long long vstride = 0;                   // between the members' vectors of np
 };
+// what a launch takes from its `const MemberBatch *` (null: one member, kp by value)
+struct MemberView {
+    int members;
+    const MemberParams *mp;
+    long long mstride, vstride;
+    explicit MemberView(const MemberBatch *mb)
+        : members(mb ? mb->count : 1), mp(mb ? mb->params : nullptr),
+          mstride(mb ? mb->mstride : 0), vstride(mb ? mb->vstride : 0)
+    {
+    }
+};
 int gpx_kspec_with_hyper(const gpx_kspec *k, const double *hyper,
                          std::vector<gpx_kspec> &store, gpx_kspec *out);
 

@@ -1,6 +1,6 @@
 """ExactGP.gradient_posterior on the GPU (gpx_exact_posterior_gradient: gradpost_build_kernel,
 the R^-T solve of the full posterior, gradpost_contract_kernel / gradpost_final_kernel in
-pygp_amd/csrc/kmat.hip) against scipy.linalg on K + sn^2 I (tests/gradpost_ref.py)."""
+pygp_amd/csrc/kderiv.hip) against scipy.linalg on K + sn^2 I (tests/gradpost_ref.py)."""
 
 import numpy as np
 import numpy.testing as nt

@@ -1,5 +1,5 @@
 """GradientGP on the GPU (gpx_gradobs_*: kaug_build_kernel and kaug_cross_kernel in
-pygp_amd/csrc/kmat.hip, then the exact path's factorisation, solves and reductions) against the
+pygp_amd/csrc/kderiv.hip, then the exact path's factorisation, solves and reductions) against the
 float64 NumPy / SciPy reference of tests/gradobs_ref.py, which tests/test_gradobs_host.py holds
 to longdouble a hundred times tighter than the tolerances here."""
 

@@ -1,5 +1,5 @@
 """GPU parity of the mixed second derivative RealKernel.gradxy (kgradxy_kernel in
-pygp_amd/csrc/kmat.hip): against the reference's own gradxy (tests/golden/g_gradxy.npz) for SE
+pygp_amd/csrc/kderiv.hip): against the reference's own gradxy (tests/golden/g_gradxy.npz) for SE
 and its sum and product, and against the longdouble closed forms of tests/gradxy_ref.py for
 every family and combination."""
 

@@ -1,6 +1,6 @@
 """MultiOutputGP on the GPU (gpx_mo_*: the mo_gemvt_*, mo_trmv_upper, mo_lz_terms and
 mo_posterior_* kernels in pygp_amd/csrc/vec.hip, mo_trace_grad_rows_kernel and
-mo_trace_grad_kernel in kmat.hip, around the exact path's build, factorisation and inverse)
+mo_trace_grad_kernel in kgrad.hip, around the exact path's build, factorisation and inverse)
 against the float64 NumPy / SciPy reference of tests/multiout_ref.py, which
 tests/test_multiout_host.py holds to longdouble a hundred times tighter than the tolerances here,
 and against T runs of ExactGP on the columns."""

@@ -1,5 +1,5 @@
 """The pseudo-input gradient dlZ/dU of FITC and DTC on the device (pair_gradx_kernel,
-kmat.hip; gpx_sparse_loglik_pseudo) against the host restatement of
+kderiv.hip; gpx_sparse_loglik_pseudo) against the host restatement of
 tests/sparse_pseudo_ref.py, the device's own finite differences, and central differences
 of the reference's objective (g_sparse_pseudo.npz); every DMAX instance and odd shapes,
 bitwise repeatability (also under GPX_TEST_JITTER), a longdouble accuracy ratio, the life

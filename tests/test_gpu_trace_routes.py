@@ -1,4 +1,4 @@
-"""Routes of the trace pass (pygp_amd/csrc/kmat.hip) that the other GPU tests do not take.
+"""Routes of the trace pass (pygp_amd/csrc/kgrad.hip) that the other GPU tests do not take.
 
 GPX_TRACE_ROWS=0 sends sums of SE / Matern parts through the one-workgroup-per-tile kernels
 (trace_grad_kernel and mo_trace_grad_kernel, MODE 1) instead of the row-persistent ones. The

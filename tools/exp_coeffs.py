@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Coefficients of the exp() used by the trace-gradient kernel (kmat.hip, gpx_exp):
+"""Coefficients of the exp() used by the trace-gradient kernel (kmat_dev.h, gpx_exp):
 exp(r) ~ 1 + r + r^2 q(r) on |r| <= ln2/2, q of degree 9 interpolated at Chebyshev nodes
 in 50-digit arithmetic (near-minimax), rounded to double; prints the coefficients of
 1, r, ..., r^11 and the worst relative error over a fine grid."""
