@@ -1,13 +1,23 @@
 // fp64 tile engine for gfx950: C = alpha * op(A) * op(B) + beta * C on
 // v_mfma_f64_16x16x4_f64.
 //
-// One 256-thread workgroup (4 waves, 2x2) owns a TILE x TILE block of C,
-// TILE = 128 (each wave 64x64 = 4x4 MFMA tiles, 128 accumulator VGPRs) or, for
-// launches that would leave most of the 256 CUs idle, TILE = 64 (each wave
-// 32x32 = 2x2 MFMA tiles; 4x the workgroups, 1/4 of the serial K-loop latency
-// per workgroup). The K loop walks BK=16 slices: global -> registers (16-B
-// loads, one slice ahead, issued before the MFMAs of the current slice) -> LDS
-// (double buffered) -> one ds_read_b64 per fragment -> MFMA.
+// One workgroup owns a TILE x TILE block of C. The default shapes have 512
+// threads (8 waves, 2x4), two workgroups per CU (128 VGPRs): TILE = 128 (each
+// wave 64x32 = 4x2 MFMA tiles, 64 accumulator VGPRs) or, for launches that would
+// leave most of the 256 CUs idle, TILE = 64 (each wave 32x16 = 2x1 MFMA tiles;
+// 4x the workgroups, 1/4 of the serial K-loop latency per workgroup); 256-thread
+// shapes (4 waves, 2x2, wave 64x64 or 32x32) exist for comparison. The K loop
+// walks BK=16 slices: global -> registers (16-B loads, two slices ahead, issued
+// before the MFMAs of the current slice) -> LDS (double buffered) -> one
+// ds_read_b64 per fragment (paired into ds_read2_b64 in a k-major image) -> MFMA.
+//
+// A slice is 4 k-steps of 8 MFMAs per wave (TILE = 128, 8 waves). The fragments of
+// k-step t+1 are requested while the MFMAs of step t issue (pipe_step below), also
+// across the slice boundary, and the waits in front of the MFMAs are counted, not
+// drained; the slice addresses of the global loads advance on the scalar unit.
+// MFMA utilisation of the group-of-six launches at N = 16384: 0.94 (0.90 with the
+// earlier body, which read, drained and then issued; GPX_GEMM_PIPE=0 still selects
+// it, same bits). profiles/gemm_pipe_*.txt.
 //
 // LDS images keep the operand's own storage order so that the staging writes
 // are 16-B and conflict-free either way:
@@ -17,9 +27,11 @@
 // disjoint banks (ds_read_b64 banks = (addr/4) % 64).
 //
 // The f64 MFMA is slow in wall-clock terms (~30 ns per instruction per SIMD,
-// tools/probe_mfma.hip), so a slice costs a wave 64 MFMAs = 1.9 us at TILE=128;
-// LDS and global traffic are far off the critical path. What matters is that
-// all four SIMDs of every CU always have an MFMA to issue.
+// tools/probe_mfma.hip), so a slice costs a wave 32 MFMAs = 0.9 us at TILE=128
+// (four waves share a SIMD); LDS and global bandwidth are far off the critical
+// path. What matters is that all four SIMDs of every CU always have an MFMA to
+// issue: a wave that waits out an LDS round trip leaves its SIMD to the other
+// three, which are often in the same state.
 //
 // Triangular structure is exploited at tile granularity: per-tile k-ranges
 // (GEMM_KLO_* / GEMM_KHI_*) skip slices that are structurally zero, and
@@ -34,7 +46,123 @@
 
 #include "gemm_tile.h"
 
-template <int TA, int TB, typename G>
+// ---- the pipelined k-loop (PIPE = 1, the default; GPX_GEMM_PIPE=0 selects the old body) ----
+// Per-thread byte offsets of the NLOAD 16-B loads of one operand slice, relative to the
+// slice's first element: computed once in front of the k-loop. The slice itself moves on
+// the scalar unit (uniform 64-bit base + fixed 32-bit vector offset), so the loop holds no
+// 64-bit vector arithmetic. Offsets stay far below 4 GB: at most TILE rows of ld doubles.
+template <typename G, bool KMAJOR>
+__device__ __forceinline__ void slice_offsets(int ld, int tid, unsigned (&off)[G::NLOAD])
+{
+#pragma unroll
+    for (int c = 0; c < G::NLOAD; ++c) {
+        const int idx = tid + G::NTH * c;
+        if (KMAJOR) {
+            const int row = idx / (G::TILE / 2), c2 = idx % (G::TILE / 2);
+            off[c] = ((unsigned)row * (unsigned)ld + 2u * c2) * 8u;
+        } else {
+            const int row = idx >> 3, k2 = idx & 7;
+            off[c] = ((unsigned)row * (unsigned)ld + 2u * k2) * 8u;
+        }
+    }
+}
+
+// first element of the slice at k0 of the tile at mn0 (uniform, 64-bit)
+template <bool KMAJOR>
+__device__ __forceinline__ const double *slice_base(const double *__restrict__ P, int ld, int mn0,
+                                                    int k0)
+{
+    return KMAJOR ? P + ((long long)k0 * ld + mn0) : P + ((long long)mn0 * ld + k0);
+}
+
+template <typename G>
+__device__ __forceinline__ Regs<G::NLOAD> load_slice_at(const double *base,
+                                                        unsigned (&off)[G::NLOAD])
+{
+    Regs<G::NLOAD> out;
+#pragma unroll
+    for (int c = 0; c < G::NLOAD; ++c) {
+        // (an empty statement on the offset's own register.) It keeps the widening to 64 bits
+        // HERE, next to the load, where it folds into the load's address mode; widened once in
+        // front of the loop the offset would live in a register pair and every load would
+        // need a 64-bit vector add again
+        asm volatile("" : "+v"(off[c]));
+        out.v[c] = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(base) +
+                                                      (size_t)off[c]);
+    }
+    return out;
+}
+
+// the fragments of one k-step (4 of k): one double per MFMA tile and operand
+template <int WTM, int WTN, int AT, int BT>
+__device__ __forceinline__ void pipe_read(const double *__restrict__ ap,
+                                          const double *__restrict__ bp, double (&a)[WTM],
+                                          double (&b)[WTN])
+{
+#pragma unroll
+    for (int t = 0; t < WTN; ++t) b[t] = bp[t * BT];
+#pragma unroll
+    for (int t = 0; t < WTM; ++t) a[t] = ap[t * AT];
+}
+
+// Nothing but vector and scalar ALU instructions (address adds) may be scheduled across
+// this: it pins LDS reads, MFMAs, global loads and LDS writes to their source order. Left
+// alone the scheduler gathers the reads of two k-steps in front of the MFMAs and pays for
+// the registers with scratch.
+#define PIPE_FENCE() __builtin_amdgcn_sched_barrier(0x2 | 0x4)
+
+// The MFMAs of one k-step on the fragments in a / b, with the reads of the NEXT k-step (at
+// apn / bpn) in flight under them; s_waitcnt then counts the reads an MFMA consumes and
+// does not drain the queue. Every acc[i][j] sees the k-steps in the order of mfma_slice, so
+// results keep their bits.
+//   4 rows of MFMA tiles: a[i] is dead after the last MFMA of row i, so the successors of
+//   a pair of rows are read straight into their registers behind that pair (in pairs: one
+//   ds_read2_b64 in a k-major image). The b fragments live to the end of the step; their
+//   successors go to registers of their own, requested first. The last pair is read behind
+//   the last MFMA and has the first two rows of the next step to arrive.
+//   2 rows (64-tiles): too few MFMAs for that; a second set of fragments, requested first.
+template <int WTM, int WTN, int AT, int BT, bool READ_NEXT = true>
+__device__ __forceinline__ void pipe_step(const double *__restrict__ apn,
+                                          const double *__restrict__ bpn, double (&a)[WTM],
+                                          double (&b)[WTN], v4d (&acc)[WTM][WTN])
+{
+    static_assert(WTM % 2 == 0, "rows are taken in pairs");
+    constexpr bool INPLACE = WTM >= 4;
+    double an[WTM], bn[WTN];
+    if (READ_NEXT) {
+#pragma unroll
+        for (int t = 0; t < WTN; ++t) bn[t] = bpn[t * BT];
+        if (!INPLACE) {
+#pragma unroll
+            for (int t = 0; t < WTM; ++t) an[t] = apn[t * AT];
+        }
+    }
+    PIPE_FENCE();
+#pragma unroll
+    for (int i = 0; i < WTM; i += 2) {
+#pragma unroll
+        for (int r = i; r < i + 2; ++r)
+#pragma unroll
+            for (int j = 0; j < WTN; ++j)
+                acc[r][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[r], b[j], acc[r][j], 0, 0, 0);
+        PIPE_FENCE();
+        if (READ_NEXT && INPLACE) {
+            a[i] = apn[i * AT];
+            a[i + 1] = apn[(i + 1) * AT];
+            PIPE_FENCE();
+        }
+    }
+    if (READ_NEXT) {
+#pragma unroll
+        for (int t = 0; t < WTN; ++t) b[t] = bn[t];
+        if (!INPLACE) {
+#pragma unroll
+            for (int t = 0; t < WTM; ++t) a[t] = an[t];
+        }
+    }
+}
+
+template <int TA, int TB, typename G, int PIPE>
 __global__ __launch_bounds__(G::NTH, G::MINW) void gemm_f64_kernel(GemmArgs g)
 {
     constexpr int TILE = G::TILE, WTM = G::WTM, WTN = G::WTN;
@@ -161,7 +289,89 @@ __global__ __launch_bounds__(G::NTH, G::MINW) void gemm_f64_kernel(GemmArgs g)
         const int amn = wm * (TILE / G::WM) + lr, bmn = wn * (TILE / G::WN) + lr;
         const double *ap0 = As + (AKM ? lk * G::KSTR + amn : amn * MNSTR + lk);
         const double *bp0 = Bs + (BKM ? lk * G::KSTR + bmn : bmn * MNSTR + lk);
-        if constexpr (!G::DEEP) {
+        if constexpr (PIPE) {
+            unsigned aoff[G::NLOAD], boff[G::NLOAD];
+            slice_offsets<G, AKM>(g.lda, tid, aoff);
+            slice_offsets<G, BKM>(g.ldb, tid, boff);
+            const int last = nslice - 1;
+            auto a_at = [&](int s) {
+                return load_slice_at<G>(slice_base<AKM>(A, g.lda, m0, kfirst + s * kstep), aoff);
+            };
+            auto b_at = [&](int s) {
+                return load_slice_at<G>(slice_base<BKM>(B, g.ldb, n0, kfirst + s * kstep), boff);
+            };
+            const double *ap1 = ap0 + G::OPER, *bp1 = bp0 + G::OPER;
+            double fa[WTM], fb[WTN];
+            if constexpr (!G::DEEP) {
+                Regs<G::NLOAD> ra = a_at(0), rb = b_at(0);
+                store_slice<G, AKM>(As, tid, ra);
+                store_slice<G, BKM>(Bs, tid, rb);
+                __syncthreads();
+                pipe_read<WTM, WTN, AT, BT>(ap0, bp0, fa, fb);
+                // slice s sits in LDS[s & 1] and its first fragments in fa / fb; slice s+1
+                // is requested before the MFMAs and published behind the third k-step
+                for (int s = 0; s < last; ++s) {
+                    const double *ap = (s & 1) ? ap1 : ap0, *bp = (s & 1) ? bp1 : bp0;
+                    const double *apx = (s & 1) ? ap0 : ap1, *bpx = (s & 1) ? bp0 : bp1;
+                    ra = a_at(s + 1);
+                    rb = b_at(s + 1);
+#pragma unroll
+                    for (int ks = 1; ks < BK / 4; ++ks)
+                        pipe_step<WTM, WTN, AT, BT>(ap + ks * AK, bp + ks * BKS, fa, fb, acc);
+                    const int nxt = (s & 1) ^ 1;
+                    store_slice<G, AKM>(As + nxt * G::OPER, tid, ra);
+                    store_slice<G, BKM>(Bs + nxt * G::OPER, tid, rb);
+                    __syncthreads();
+                    pipe_step<WTM, WTN, AT, BT>(apx, bpx, fa, fb, acc);
+                }
+                const double *ap = (last & 1) ? ap1 : ap0, *bp = (last & 1) ? bp1 : bp0;
+#pragma unroll
+                for (int ks = 1; ks < BK / 4; ++ks)
+                    pipe_step<WTM, WTN, AT, BT>(ap + ks * AK, bp + ks * BKS, fa, fb, acc);
+                pipe_step<WTM, WTN, AT, BT, false>(ap, bp, fa, fb, acc);
+            } else {
+                // two slices in flight, as in the body below; nslice is even
+                Regs<G::NLOAD> ra0 = a_at(0), rb0 = b_at(0);
+                Regs<G::NLOAD> ra1 = a_at(min(1, last)), rb1 = b_at(min(1, last));
+                store_slice<G, AKM>(As, tid, ra0);
+                store_slice<G, BKM>(Bs, tid, rb0);
+                __syncthreads();
+                pipe_read<WTM, WTN, AT, BT>(ap0, bp0, fa, fb);
+                for (int s = 0; s < nslice; s += 2) {
+                    {   // LDS[0] = slice s (first fragments in fa / fb), r1 = slice s+1
+                        ra0 = a_at(min(s + 2, last));
+                        rb0 = b_at(min(s + 2, last));
+#pragma unroll
+                        for (int ks = 1; ks < BK / 4 - 1; ++ks)
+                            pipe_step<WTM, WTN, AT, BT>(ap0 + ks * AK, bp0 + ks * BKS, fa, fb,
+                                                        acc);
+                        // published one k-step ahead of the barrier: it finds them retired
+                        store_slice<G, AKM>(As + G::OPER, tid, ra1);
+                        store_slice<G, BKM>(Bs + G::OPER, tid, rb1);
+                        pipe_step<WTM, WTN, AT, BT>(ap0 + (BK / 4 - 1) * AK,
+                                                    bp0 + (BK / 4 - 1) * BKS, fa, fb, acc);
+                        __syncthreads();
+                        pipe_step<WTM, WTN, AT, BT>(ap1, bp1, fa, fb, acc);
+                    }
+                    {   // LDS[1] = slice s+1, r0 = slice s+2
+                        ra1 = a_at(min(s + 3, last));
+                        rb1 = b_at(min(s + 3, last));
+#pragma unroll
+                        for (int ks = 1; ks < BK / 4 - 1; ++ks)
+                            pipe_step<WTM, WTN, AT, BT>(ap1 + ks * AK, bp1 + ks * BKS, fa, fb,
+                                                        acc);
+                        // published one k-step ahead of the barrier: it finds them retired
+                        store_slice<G, AKM>(As, tid, ra0);
+                        store_slice<G, BKM>(Bs, tid, rb0);
+                        pipe_step<WTM, WTN, AT, BT>(ap1 + (BK / 4 - 1) * AK,
+                                                    bp1 + (BK / 4 - 1) * BKS, fa, fb, acc);
+                        __syncthreads();
+                        // (behind the last slice this reads fragments nobody uses)
+                        pipe_step<WTM, WTN, AT, BT>(ap0, bp0, fa, fb, acc);
+                    }
+                }
+            }
+        } else if constexpr (!G::DEEP) {
             Regs<G::NLOAD> ra, rb;
             ra = load_slice<G, AKM>(A, g.lda, m0, kfirst, tid);
             rb = load_slice<G, BKM>(B, g.ldb, n0, kfirst, tid);
@@ -467,8 +677,18 @@ static int launch(hipStream_t s, const GemmArgs &g0, const LaunchCtx &lc, int pa
         grid = dim3(tl.count, 1, g.batch > 0 ? g.batch : 1);
     }
     log_launch(s, TA, TB, G::TILE, g, part, (int)(grid.x * grid.y * grid.z));
-    hipLaunchKernelGGL((gemm_f64_kernel<TA, TB, G>), grid, dim3(G::NTH), G::LDS_BYTES, s,
-                       g);
+    // GPX_GEMM_PIPE=0: the k-loop without fragment reads under the MFMAs (kept for A/B runs).
+    // Where the caller leaves the shape to the engine, 128-tiles with K <= 512 keep that body
+    // too: the 256-member launches of K^-1 = W W^T at N = 512 (k-ranges of 8 to 32 slices)
+    // measured 35 us a launch slower with the pipelined one, N = 1024 none (same bits either
+    // way; profiles/gemm_pipe_ab.txt section 5)
+    const bool short_k = G::TILE == 128 && g.tile == 0 && g.waves == 0 && g.K <= 512;
+    if (gpx_env().gemm_pipe && !short_k)
+        hipLaunchKernelGGL((gemm_f64_kernel<TA, TB, G, 1>), grid, dim3(G::NTH), G::LDS_BYTES, s,
+                           g);
+    else
+        hipLaunchKernelGGL((gemm_f64_kernel<TA, TB, G, 0>), grid, dim3(G::NTH), G::LDS_BYTES, s,
+                           g);
     GPX_HIP(hipGetLastError());
     return 0;
 }
@@ -476,7 +696,9 @@ static int launch(hipStream_t s, const GemmArgs &g0, const LaunchCtx &lc, int pa
 template <int TA, int TB, typename G>
 static int set_attr()
 {
-    GPX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_f64_kernel<TA, TB, G>),
+    GPX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_f64_kernel<TA, TB, G, 0>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));
+    GPX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_f64_kernel<TA, TB, G, 1>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));
     return 0;
 }

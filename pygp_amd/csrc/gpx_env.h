@@ -39,6 +39,7 @@
     X(int, gemm_small_below, "GPX_GEMM_SMALL_BELOW", 0)                         \
     X(int, gemm_nobalance, "GPX_GEMM_NOBALANCE", 0)                             \
     X(int, gemm_nosplit, "GPX_GEMM_NOSPLIT", 0)                                 \
+    X(int, gemm_pipe, "GPX_GEMM_PIPE", 1)                                       \
     X(const char *, gemm_log, "GPX_GEMM_LOG", nullptr)                          \
     X(int, ldpad, "GPX_LDPAD", 32)                                              \
     X(int, bench_ldpad, "GPX_BENCH_LDPAD", 0)                                   \
