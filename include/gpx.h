@@ -236,6 +236,39 @@ int gpx_mo_loglik(gpx_t *h, double *lZ, double *dlZ);
 int gpx_mo_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2);
 /* mu as above and the full covariance Sigma[m][m] the outputs share; 1 <= m <= 8192. */
 int gpx_mo_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma);
+/* ---- correlated outputs at their own inputs: intrinsic coregionalisation (own design; Bonilla,
+ * Chai & Williams 2008; GPML section 9.1) ----
+ * Observation i is (x_i, task[i] in [0, T), y_i), 1 <= T <= GPX_ICM_TMAX:
+ *   K_ij = B[t_i][t_j] k(x_i, x_j) + delta_ij sn[t_i]^2,  r_i = y_i - mean[t_i],
+ * B a symmetric positive semi-definite T x T matrix (row-major, any parameterisation: the device
+ * knows it only as a matrix), noise and constant mean per task. K is one dense matrix of order
+ * n in the workspace of the exact path; factorisation, inverse and lZ are that path's.
+ * Upload: replaces whatever data the handle held; a task index outside [0, T) is refused. While
+ * a handle holds these data every entry of every other family but the set_data entries returns
+ * < 0 with an error text and touches nothing; any set_data returns it to its own family. The
+ * gpx_icm_* entries below refuse a handle in another state. */
+#define GPX_ICM_TMAX 8
+int gpx_icm_set_data(gpx_t *h, const double *X, int64_t n, int64_t d, const double *y,
+                     const int32_t *task, int64_t T);
+/* K, R = chol(K), a = R^-T r. log_sn[T], B[T*T], mean[T]; non-finite values and an asymmetric B
+ * are refused before any launch. *info as gpx_exact_update. */
+int gpx_icm_update(gpx_t *h, const gpx_kspec *k, const double *log_sn, const double *B,
+                   const double *mean, int *info);
+/* lZ of the last update. dlZ == NULL: the value only, no inverse is formed. Else dlZ holds
+ * T + nhyper(k) + T*T + T doubles, with Q = K^-1 - alpha alpha^T:
+ *   [ d lZ / d log sn_t = -sn_t^2 sum_{t_i = t} Q_ii | d lZ / d theta_h = -1/2 sum_ij Q_ij
+ *     B[t_i][t_j] dk_ij/dtheta_h | S_st = sum_{t_i = s} sum_{t_j = t} Q_ij k(x_i, x_j), row-major,
+ *     so that dlZ = -1/2 sum_st S_st dB_st | d lZ / d mean_t = sum_{t_i = t} alpha_i ]
+ * Every sum runs in an order fixed by the shape: the same call returns the same bits. */
+int gpx_icm_loglik(gpx_t *h, double *lZ, double *dlZ);
+/* predictive mean and variance of f_{ts[j]} at Xs[j], j < m: k*_i = B[t_i][ts_j] k(x_i, xs_j),
+ * mu = mean[ts_j] + (R^-T k*).a, s2 = B[ts_j][ts_j] k(xs_j, xs_j) - |R^-T k*|^2. Passes of test
+ * points as gpx_exact_posterior. */
+int gpx_icm_posterior(gpx_t *h, const double *Xs, const int32_t *ts, int64_t m, double *mu,
+                      double *s2);
+/* mu[m] and Sigma[m][m], Sigma_ab = B[ts_a][ts_b] k(xs_a, xs_b) - (V^T V)_ab; 1 <= m <= 8192. */
+int gpx_icm_posterior_full(gpx_t *h, const double *Xs, const int32_t *ts, int64_t m, double *mu,
+                           double *Sigma);
 /* ---- binary classification by Laplace's approximation (own design; GPML algorithms 3.1, 3.2,
  * 5.1 with a constant mean) ----
  * Labels y in {-1, +1} at X under a Logistic or Probit likelihood; the latent is f = mean + K a.
@@ -455,7 +488,7 @@ int gpx_select_timing(gpx_t *h, double *ms);
 /* ---- instrumentation ---------------------------------------------------- */
 /* per-stage GPU times (ms) of the last gpx_exact_eval / update+loglik measured
  * with HIP events on the handle's stream. names via gpx_timing_name(i). */
-#define GPX_NTIMERS 10
+#define GPX_NTIMERS 11
 int gpx_enable_timing(gpx_t *h, int on);
 int gpx_get_timings(gpx_t *h, double *ms, int n);
 /* batches that ran as groups (gpx_loglik_batch) since timing was last switched on: the sum of

@@ -26,7 +26,7 @@ KIND_SUM = 6
 KIND_RQ = 7
 KIND_PRODUCT = 8
 F64, F32 = 0, 1
-NTIMERS = 10
+NTIMERS = 11
 
 
 class GpxError(RuntimeError):
@@ -119,6 +119,11 @@ SIGNATURES = {
     'gpx_mo_loglik': (C.c_int, [_vp, _dp, _vp]),
     'gpx_mo_posterior': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     'gpx_mo_posterior_full': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    'gpx_icm_set_data': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64]),
+    'gpx_icm_update': (C.c_int, [_vp, C.POINTER(_KSpec), _vp, _vp, _vp, _ip]),
+    'gpx_icm_loglik': (C.c_int, [_vp, _dp, _vp]),
+    'gpx_icm_posterior': (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    'gpx_icm_posterior_full': (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
     'gpx_exact_get_factor': (C.c_int, [_vp, _i64, _vp, _vp]),
     'gpx_sparse_update': (C.c_int, [_vp, C.POINTER(_KSpec), C.c_int, _vp, _i64, C.c_double,
                                     C.c_double, _ip]),
@@ -591,6 +596,51 @@ class Handle(object):
 
     def mo_posterior_full(self, Xs):
         return self._posterior(self._L.gpx_mo_posterior_full, Xs, True, self._mo_T)
+
+    # -- correlated outputs at their own inputs (CoregionalGP) --
+    ICM_TMAX = 8                                     # GPX_ICM_TMAX
+
+    def icm_set_data(self, X, y, task, T):
+        """X (n, d), y (n,) and task (n,) ints in [0, T), 1 <= T <= 8."""
+        X, y = _f64(X, 2), _f64(y, 1)
+        task = np.ascontiguousarray(task, dtype=np.int32)
+        if not X.shape[0] == y.shape[0] == task.shape[0] or task.ndim != 1:
+            raise ValueError('X, y and task disagree')
+        check(self._L.gpx_icm_set_data(self._h, _ptr(X), X.shape[0], X.shape[1], _ptr(y),
+                                       _ptr(task), int(T)))
+        self._icm_T = int(T)
+
+    def icm_update(self, spec, log_sn, B, mean):
+        """log_sn (T,), B (T, T) symmetric, mean (T,)."""
+        T = self._icm_T
+        log_sn, B, mean = _f64(log_sn, 1), _f64(B, 2), _f64(mean, 1)
+        if log_sn.shape != (T,) or B.shape != (T, T) or mean.shape != (T,):
+            raise ValueError('log_sn, B and mean must have T = %d entries a side' % T)
+        info = C.c_int(0)
+        check(self._L.gpx_icm_update(self._h, spec.ref(), _ptr(log_sn), _ptr(B), _ptr(mean),
+                                     C.byref(info)))
+
+    def icm_loglik(self, nhyper_kernel, grad=False):
+        """lZ, or (lZ, dlZ): dlZ = [noise (T) | kernel | S (T*T) | mean sums (T)]."""
+        T = self._icm_T
+        return self._loglik(self._L.gpx_icm_loglik, 2 * T + T * T + nhyper_kernel, grad)
+
+    def _icm_posterior(self, entry, Xs, ts, full):
+        Xs = _f64(Xs, 2)
+        ts = np.ascontiguousarray(ts, dtype=np.int32)
+        m = Xs.shape[0]
+        if ts.shape != (m,):
+            raise ValueError('one task per test point')
+        mu = np.empty(m)
+        cov = np.empty((m, m)) if full else np.empty(m)
+        check(entry(self._h, _ptr(Xs), _ptr(ts), m, _ptr(mu), _ptr(cov)))
+        return mu, cov
+
+    def icm_posterior(self, Xs, ts):
+        return self._icm_posterior(self._L.gpx_icm_posterior, Xs, ts, False)
+
+    def icm_posterior_full(self, Xs, ts):
+        return self._icm_posterior(self._L.gpx_icm_posterior_full, Xs, ts, True)
 
     # -- sparse pseudo-input models (FITC / DTC / VFE) on the resident data --
     def sparse_update(self, spec, method, U, log_sn, mean):

@@ -27,15 +27,16 @@ void gpx_set_error(const char *fmt, ...)
 }
 
 // ---- handle ------------------------------------------------------------------
+#define HRES_ICM (GPX_MAX_HYPER + 8)     // where the pinned result block holds ICM's task sums
 enum { T_BUILD = 0, T_POTRF, T_TRSV, T_TRTRI, T_TRMV, T_LAUUM, T_TRACE, T_SCALARS,
-       T_POST_BUILD, T_POST_SOLVE };
+       T_POST_BUILD, T_POST_SOLVE, T_TASK_SUMS };
 static const char *kTimerNames[GPX_NTIMERS] = {
     "kernel_build", "potrf", "trsv", "trtri", "trmv", "lauum", "trace_grad",
-    "scalars", "posterior_build", "posterior_solve"};
+    "scalars", "posterior_build", "posterior_solve", "task_sums"};
 
 // What the resident data of a handle is: set by the family's set_data (commit_data), asked for
 // by every entry that reads the data (require_state).
-enum { ST_PLAIN = 0, ST_GRADOBS, ST_MO, ST_LAPLACE };
+enum { ST_PLAIN = 0, ST_GRADOBS, ST_MO, ST_LAPLACE, ST_ICM };
 // ... and which approximation filled a handle that holds labels
 enum { LP_NONE = 0, LP_LAPLACE, LP_EP };
 
@@ -59,6 +60,14 @@ struct gpx_ctx {
     // (0 in every other state). y, r, a and alpha then hold mo_T columns, column t at + t * cap;
     // the factorisation is that of plain data on X.
     int mo_T = 0;
+    // ST_ICM, correlated outputs at their own inputs (gpx_icm_set_data): row i of X observes
+    // output icm_task[i] < icm_T (0 in every other state); icm_par holds B, the noise variances
+    // and the means of the last update (ICM_* in gpx_internal.h) and icm_host the host's copy of
+    // them; the factorisation is that of K_ij = B[t_i][t_j] k_ij + delta_ij sn2[t_i].
+    // icm_ts: the tasks of a posterior pass's test points; icm_acc: the sums by task.
+    int icm_T = 0;
+    double icm_host[ICM_NPAR] = {};
+    DevBuf icm_task, icm_par, icm_ts, icm_acc, icm_part;
     // ST_LAPLACE, binary labels under a Logistic / Probit likelihood (gpx_laplace_set_data): y
     // holds the n labels, the factorisation below is that of B = I + sW K sW^T at the mode, lp_vec
     // the vectors of the Newton iteration (LV_* in the Laplace section, cap doubles each).
@@ -181,10 +190,11 @@ static int ld_for(int np)
 // the one refusal of a handle in another state than the calling entry's family (`what`) needs
 static int require_state(const gpx_ctx *h, int want, const char *what)
 {
-    static const char *holds[4] = {"plain data (gpx_set_data)",
+    static const char *holds[5] = {"plain data (gpx_set_data)",
                                    "gradient observations (gpx_gradobs_*)",
                                    "multi-output data (gpx_mo_*)",
-                                   "classification labels (gpx_laplace_*)"};
+                                   "classification labels (gpx_laplace_*)",
+                                   "coregionalised outputs (gpx_icm_*)"};
     if (h->state == want) return 0;
     gpx_set_error("%s: the handle holds %s%s", what, holds[h->state],
                   want == ST_PLAIN ? "; gpx_set_data returns it to plain data" : "");
@@ -201,6 +211,7 @@ static void drop_data(gpx_ctx *h)
     h->state = ST_PLAIN;
     h->go_n = h->go_ng = 0;
     h->mo_T = 0;
+    h->icm_T = 0;
     h->lp_mode = false;
     h->lp_approx = LP_NONE;
     h->data_version++;
@@ -529,7 +540,8 @@ int gpx_create(int device, gpx_t **out)
     // [0..2] scalar terms, [3] status word, [4..] trace accumulators: one result copy
     GPX_TRY(h->scalars.reserve((4 + GPX_MAX_HYPER + 2) * sizeof(double)));
     h->acc = h->scalars.as<double>() + 4;
-    GPX_HIP(hipHostMalloc((void **)&h->hres, (GPX_MAX_HYPER + 8) * sizeof(double)));
+    // (behind them, at HRES_ICM, the sums by task of gpx_icm_loglik)
+    GPX_HIP(hipHostMalloc((void **)&h->hres, (HRES_ICM + ICM_NACC) * sizeof(double)));
     GPX_HIP(hipHostMalloc((void **)&h->hinfo, 64));
     *out = h;
     return 0;
@@ -901,7 +913,8 @@ static int enqueue_update(gpx_ctx *h, StageClock &clk, int mode, bool grad_follo
     const GpxBlocks lb(h->np, mode == GPX_POTRF_KINV);
     const int lead_rows = lb.count >= 2 && lb.len(1) <= GPX_PANEL_MAX ? lb.off(2) : lb.len(0);
     hipEvent_t lead_ev = gpx_potrf_lead_event(w);
-    const bool lead = h->state != ST_GRADOBS && lead_on && lead_ev && w.crit && lead_rows < h->np;
+    const bool per_pair = h->state == ST_GRADOBS || h->state == ST_ICM;   // whole, no lead rows
+    const bool lead = !per_pair && lead_on && lead_ev && w.crit && lead_rows < h->np;
     if (lead) {
         GPX_TRY(gpx_kbuild<double>(h->stream, h->kp, h->X.as<double>(), h->n, h->np,
                                    h->X.as<double>(), h->n, h->np, h->d, w.A, h->ld, true,
@@ -924,6 +937,10 @@ static int enqueue_update(gpx_ctx *h, StageClock &clk, int mode, bool grad_follo
         GPX_TRY(gpx_kaug_build(h->stream, h->kp, h->X.as<double>(), h->go_n, h->Xg.as<double>(),
                                h->go_ng, h->d, sn2, h->grad_noise * h->grad_noise, w.A, w.Kinv,
                                h->ld, h->np));
+    } else if (h->state == ST_ICM) {
+        // the task-weighted matrix in the same places, whole before the factorisation starts
+        GPX_TRY(gpx_kicm_build(h->stream, h->kp, h->X.as<double>(), h->icm_task.as<int>(), h->n,
+                               h->d, h->icm_par.d(), w.A, w.Kinv, h->ld, h->np));
     } else {
         GPX_TRY(gpx_kbuild<double>(h->stream, h->kp, h->X.as<double>(), h->n, h->np,
                                    h->X.as<double>(), h->n, h->np, h->d, w.A, h->ld, true,
@@ -951,6 +968,9 @@ static int enqueue_update(gpx_ctx *h, StageClock &clk, int mode, bool grad_follo
         if (h->state == ST_GRADOBS)
             GPX_TRY(gpx_gradobs_residual(h->stream, h->y.as<double>(), h->go_n, h->n, h->np,
                                          h->mean, nullptr, w.Kinv, h->ld));
+        else if (h->state == ST_ICM)
+            GPX_TRY(gpx_icm_residual(h->stream, h->y.as<double>(), h->icm_task.as<int>(), h->n,
+                                     h->np, h->icm_par.d(), nullptr, w.Kinv, h->ld));
         else
             GPX_TRY(gpx_residual_rhs(h->stream, h->y.as<double>(), h->mean, h->n, h->np, nullptr,
                                      w.Kinv, h->ld));
@@ -973,6 +993,9 @@ static int enqueue_update(gpx_ctx *h, StageClock &clk, int mode, bool grad_follo
         if (h->state == ST_GRADOBS)
             GPX_TRY(gpx_gradobs_residual(h->stream, h->y.as<double>(), h->go_n, h->n, h->np,
                                          h->mean, h->r.as<double>(), nullptr, h->ld));
+        else if (h->state == ST_ICM)
+            GPX_TRY(gpx_icm_residual(h->stream, h->y.as<double>(), h->icm_task.as<int>(), h->n,
+                                     h->np, h->icm_par.d(), h->r.as<double>(), nullptr, h->ld));
         else
             GPX_TRY(gpx_residual(h->stream, h->y.as<double>(), h->mean, h->n, h->np,
                                  h->r.as<double>()));
@@ -1031,6 +1054,10 @@ static int enqueue_grad(gpx_ctx *h, StageClock &clk)
         GPX_TRY(gpx_mo_trace_grad(h->stream, h->kp, h->X.as<double>(), h->n, h->np, h->d, w.Kinv,
                                   h->ld, h->alpha.as<double>(), h->mo_T, h->cap,
                                   h->partial.as<double>(), h->acc));
+    else if (h->state == ST_ICM)
+        GPX_TRY(gpx_icm_trace_grad(h->stream, h->kp, h->X.as<double>(), h->n, h->np, h->d, w.Kinv,
+                                   h->ld, h->alpha.as<double>(), h->icm_task.as<int>(),
+                                   h->icm_par.d(), h->partial.as<double>(), h->acc));
     else
         GPX_TRY(gpx_trace_grad(h->stream, h->kp, h->X.as<double>(), h->n, h->np, h->d, w.Kinv,
                                h->ld, h->alpha.as<double>(), h->partial.as<double>(),
@@ -1584,6 +1611,10 @@ static int build_cross(gpx_ctx *h, int mc, int mcp)
         return gpx_kaug_cross(h->stream, h->kp, h->X.as<double>(), h->go_n, h->Xg.as<double>(),
                               h->go_ng, h->d, h->np, h->Xs.as<double>(), mc, h->Ks.as<double>(),
                               mcp);
+    if (h->state == ST_ICM)       // (the caller put the test points' tasks into icm_ts)
+        return gpx_kicm_cross(h->stream, h->kp, h->X.as<double>(), h->icm_task.as<int>(), h->n,
+                              h->np, h->Xs.as<double>(), h->icm_ts.as<int>(), mc, h->d,
+                              h->icm_par.d(), h->Ks.as<double>(), mcp);
     return gpx_kbuild<double>(h->stream, h->kp, h->X.as<double>(), h->n, h->np,
                               h->Xs.as<double>(), mc, mcp, h->d, h->Ks.as<double>(), mcp, false,
                               false, 0.0);
@@ -1607,12 +1638,12 @@ static int laplace_cross(gpx_ctx *h, int mcp)
 // `approx`) asks of the handle first
 static int posterior_ready(const gpx_ctx *h, int state, int approx, const char *what)
 {
-    static const char *update[5] = {"gpx_exact_update", "gpx_gradobs_update", "gpx_mo_update",
-                                    "gpx_laplace_update", "gpx_ep_update"};
+    static const char *update[6] = {"gpx_exact_update", "gpx_gradobs_update", "gpx_mo_update",
+                                    "gpx_laplace_update", "gpx_icm_update", "gpx_ep_update"};
     GPX_TRY(require_state(h, state, what));
     if (!h->have_factor || h->lp_approx != approx) {
         gpx_set_error("%s: no factorisation (call %s)", what,
-                      update[approx == LP_EP ? 4 : state]);
+                      update[approx == LP_EP ? 5 : state]);
         return -1;
     }
     return 0;
@@ -1684,18 +1715,49 @@ static int copy_mean(gpx_ctx *h, double *mu, size_t stride, int mc, int mcp)
     return 0;
 }
 
+// ST_ICM: the tasks ts[0 .. m) of the test points (host memory) are checked before any launch
+static int icm_check_tasks(const gpx_ctx *h, const int32_t *ts, int64_t m, const char *what)
+{
+    for (int64_t j = 0; j < m; ++j)
+        if (ts[j] < 0 || ts[j] >= h->icm_T) {
+            gpx_set_error("%s: task %d of test point %lld is outside [0, %d)", what, (int)ts[j],
+                          (long long)j, h->icm_T);
+            return -1;
+        }
+    return 0;
+}
+
+// ... and those of a pass put where build_cross and icm_tail read them, before the pass
+static int icm_stage_tasks(gpx_ctx *h, const int32_t *ts, int mc)
+{
+    GPX_TRY(h->icm_ts.reserve((size_t)mc * sizeof(int32_t)));
+    GPX_HIP(hipMemcpyAsync(h->icm_ts.p, ts, (size_t)mc * sizeof(int32_t), hipMemcpyHostToDevice,
+                           h->stream));
+    return 0;
+}
+
+// ... and behind the pass, which reduced with mean = prior = 0: every test point's own task mean
+// and, with s2, B[t][t] times the kernel's prior variance
+static int icm_tail(gpx_ctx *h, int mc, bool with_s2)
+{
+    return gpx_icm_posterior_tail(h->stream, h->icm_ts.as<int>(), mc, h->icm_par.d(),
+                                  gpx_kernel_prior(h->kp), h->mu.as<double>(),
+                                  with_s2 ? h->s2.as<double>() : nullptr);
+}
+
 // what: the calling entry, of the family `state`; the handle must be in that state. ST_MO: mu is
-// mo_T rows of m doubles.
+// mo_T rows of m doubles. ST_ICM: ts holds the m test points' tasks.
 static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2,
                           double *dmu, double *ds2, int state, const char *what,
-                          int approx = LP_NONE)
+                          int approx = LP_NONE, const int32_t *ts = nullptr)
 {
     CHECK_H(h);
     GPX_TRY(posterior_ready(h, state, approx, what));
-    if (!Xs || !mu || !s2 || m < 0) {
+    if (!Xs || !mu || !s2 || m < 0 || (state == ST_ICM && !ts)) {
         gpx_set_error("%s: bad arguments", what);
         return -1;
     }
+    if (ts) GPX_TRY(icm_check_tasks(h, ts, m, what));
     // test points per pass: as many as keep the two np x CH panels within ~2 GB
     // (one pass = one host synchronisation)
     const int CH = h->np <= 8192 ? 8192 : (h->np <= 16384 ? 4096 : 2048);
@@ -1703,13 +1765,15 @@ static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, dou
     ++h->posterior_calls;
     GPX_TRY(complete_w(h));
     if (grads) GPX_TRY(solve_alpha(h));
-    const double prior = gpx_kernel_prior(h->kp);
+    const double prior = ts ? 0.0 : gpx_kernel_prior(h->kp);
     StageClock clk(h);
     for (int64_t c0 = 0; c0 < m; c0 += CH) {
         const int mc = (int)std::min<int64_t>(CH, m - c0);
         const int mcp = round_up(mc, GPX_TILE);
         double *V;
+        if (ts) GPX_TRY(icm_stage_tasks(h, ts + c0, mc));
         GPX_TRY(posterior_pass(h, Xs + c0 * h->d, mc, mcp, prior, &V, &clk));
+        if (ts) GPX_TRY(icm_tail(h, mc, true));
         clk.tick(T_POST_SOLVE);
         if (grads) {
             // beta = W V (V = R^-T K*): W upper -> k >= row tile
@@ -1740,23 +1804,33 @@ static int posterior_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, dou
 // Sigma = K(Xs, Xs) - V^T V, V = R^-T K(X, Xs); GP.sample draws from it
 // (_base.py:143-178). One pass, m <= 8192.
 static int posterior_full_impl(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma,
-                               int state, const char *what, int approx = LP_NONE)
+                               int state, const char *what, int approx = LP_NONE,
+                               const int32_t *ts = nullptr)
 {
     CHECK_H(h);
     GPX_TRY(posterior_ready(h, state, approx, what));
-    if (!Xs || !mu || !Sigma || m < 1 || m > 8192) {
+    if (!Xs || !mu || !Sigma || m < 1 || m > 8192 || (state == ST_ICM && !ts)) {
         gpx_set_error("%s: bad arguments (1 <= m <= 8192)", what);
         return -1;
     }
+    if (ts) GPX_TRY(icm_check_tasks(h, ts, m, what));
     GPX_TRY(complete_w(h));
     const int mc = (int)m, mcp = round_up(mc, GPX_TILE);
     GPX_TRY(h->t2.reserve((size_t)mcp * mcp * 8));
     double *V;
+    if (ts) GPX_TRY(icm_stage_tasks(h, ts, mc));
     GPX_TRY(posterior_pass(h, Xs, mc, mcp, 0.0, &V));
-    // Sigma = K(Xs, Xs) - V^T V on the padded mcp x mcp block
-    GPX_TRY(gpx_kbuild<double>(h->stream, h->kp, h->Xs.as<double>(), mc, mcp,
-                               h->Xs.as<double>(), mc, mcp, h->d, h->t2.as<double>(), mcp,
-                               false, false, 0.0));
+    // Sigma = K(Xs, Xs) - V^T V on the padded mcp x mcp block (ICM: the prior block carries
+    // B[ts_a][ts_b], the mean its task's constant)
+    if (ts) {
+        GPX_TRY(icm_tail(h, mc, false));
+        GPX_TRY(gpx_kicm_cross(h->stream, h->kp, h->Xs.as<double>(), h->icm_ts.as<int>(), mc, mcp,
+                               h->Xs.as<double>(), h->icm_ts.as<int>(), mc, h->d, h->icm_par.d(),
+                               h->t2.as<double>(), mcp));
+    } else
+        GPX_TRY(gpx_kbuild<double>(h->stream, h->kp, h->Xs.as<double>(), mc, mcp,
+                                   h->Xs.as<double>(), mc, mcp, h->d, h->t2.as<double>(), mcp,
+                                   false, false, 0.0));
     GemmArgs g;
     g.A = V; g.B = V; g.C = h->t2.as<double>();
     g.lda = mcp; g.ldb = mcp; g.ldc = mcp;
@@ -2692,6 +2766,134 @@ int gpx_mo_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *
 int gpx_mo_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma)
 {
     return posterior_full_impl(h, Xs, m, mu, Sigma, ST_MO, "gpx_mo_posterior_full");
+}
+
+// ---- correlated outputs at their own inputs: intrinsic coregionalisation -------------------
+int gpx_icm_set_data(gpx_t *h, const double *X, int64_t n, int64_t d, const double *y,
+                     const int32_t *task, int64_t T)
+{
+    CHECK_H(h);
+    if (!X || !y || !task || n < 1 || d < 1 || d > GPX_MAX_DIM || n > (1 << 20) || T < 1 ||
+        T > GPX_ICM_TMAX) {
+        gpx_set_error("gpx_icm_set_data: bad shape n=%lld T=%lld d=%lld (1 <= T <= %d, d <= %d)",
+                      (long long)n, (long long)T, (long long)d, GPX_ICM_TMAX, GPX_MAX_DIM);
+        return -1;
+    }
+    for (int64_t i = 0; i < n; ++i)
+        if (task[i] < 0 || task[i] >= T) {
+            gpx_set_error("gpx_icm_set_data: task %d of row %lld is outside [0, %lld)",
+                          (int)task[i], (long long)i, (long long)T);
+            return -1;
+        }
+    const size_t cap = (size_t)round_up(n + 256, 1024);      // as gpx_set_data
+    GPX_TRY(h->X.reserve(cap * d * 8));
+    GPX_TRY(h->y.reserve(cap * 8));
+    GPX_TRY(h->icm_task.reserve(cap * sizeof(int32_t)));
+    GPX_TRY(h->icm_par.reserve(ICM_NPAR * sizeof(double)));
+    GPX_TRY(h->icm_acc.reserve(ICM_NACC * sizeof(double)));
+    drop_data(h);
+    GPX_HIP(hipMemcpyAsync(h->X.p, X, (size_t)n * d * 8, hipMemcpyHostToDevice, h->stream));
+    GPX_HIP(hipMemcpyAsync(h->y.p, y, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+    GPX_HIP(hipMemcpyAsync(h->icm_task.p, task, (size_t)n * sizeof(int32_t),
+                           hipMemcpyHostToDevice, h->stream));
+    GPX_HIP(hipStreamSynchronize(h->stream));
+    commit_data(h, ST_ICM, n, d, cap);
+    h->icm_T = (int)T;
+    return 0;
+}
+
+int gpx_icm_update(gpx_t *h, const gpx_kspec *k, const double *log_sn, const double *B,
+                   const double *mean, int *info)
+{
+    CHECK_H(h);
+    GPX_TRY(require_state(h, ST_ICM, "gpx_icm_update"));
+    const int T = h->icm_T;
+    bool ok = k && log_sn && B && mean;
+    for (int s = 0; ok && s < T; ++s) {
+        ok = std::isfinite(log_sn[s]) && std::isfinite(mean[s]);
+        for (int t = 0; ok && t < T; ++t)
+            ok = std::isfinite(B[s * T + t]) && B[s * T + t] == B[t * T + s];
+    }
+    if (!ok) {
+        gpx_set_error("gpx_icm_update: null or non-finite hyperparameters, or B is not symmetric");
+        return -1;
+    }
+    h->have_factor = h->have_inverse = false;
+    GPX_TRY(gpx_flatten_kspec(k, h->d, &h->kp));
+    memset(h->icm_host, 0, sizeof h->icm_host);
+    for (int s = 0; s < T; ++s) {
+        for (int t = 0; t < T; ++t) h->icm_host[ICM_B + s * GPX_ICM_TMAX + t] = B[s * T + t];
+        h->icm_host[ICM_SN2 + s] = exp(log_sn[s] * 2);           // gaussian.py:36-39
+        h->icm_host[ICM_MEAN + s] = mean[s];
+    }
+    // (the shared posterior pass adds h->mean: the task means are added behind it, icm_tail)
+    h->log_sn = 0;
+    h->mean = 0;
+    GPX_TRY(reserve_factor(h, false));
+    GPX_HIP(hipMemcpyAsync(h->icm_par.p, h->icm_host, sizeof h->icm_host, hipMemcpyHostToDevice,
+                           h->stream));
+    StageClock clk(h);
+    GPX_TRY(enqueue_update(h, clk, GPX_POTRF_R));
+    int r = finish(h, clk, false, nullptr, nullptr, info);
+    if (r == 0) h->have_factor = true;
+    return r;
+}
+
+int gpx_icm_loglik(gpx_t *h, double *lZ, double *dlZ)
+{
+    CHECK_H(h);
+    GPX_TRY(require_state(h, ST_ICM, "gpx_icm_loglik"));
+    if (!h->have_factor) {
+        gpx_set_error("gpx_icm_loglik: no factorisation (call gpx_icm_update)");
+        return -1;
+    }
+    if (!dlZ) {
+        if (lZ) *lZ = h->lZ;
+        return 0;
+    }
+    GPX_TRY(reserve_factor(h, true));
+    GPX_TRY(h->icm_part.reserve(gpx_icm_task_scratch(h->np) * 8));
+    StageClock clk(h);
+    GPX_TRY(enqueue_grad(h, clk));
+    GPX_TRY(gpx_icm_task_sums(h->stream, h->kp, h->X.as<double>(), h->icm_task.as<int>(), h->n,
+                              h->np, h->d, h->icm_T, h->Kinv.as<double>(), h->ld,
+                              h->alpha.as<double>(), h->icm_part.d(), h->icm_acc.d()));
+    clk.tick(T_TASK_SUMS);
+    GPX_HIP(hipMemcpyAsync(h->hres + HRES_ICM, h->icm_acc.p, ICM_NACC * sizeof(double),
+                           hipMemcpyDeviceToHost, h->stream));
+    GPX_TRY(enqueue_finish(h, clk, true));
+    int r = collect(h, clk, lZ, nullptr, nullptr);
+    if (r != 0) return r;
+    h->have_inverse = true;
+    // [noise (T) | kernel | S (T x T) | mean sums (T)]; the slots of gpx_lz_terms and of the trace
+    // pass for sum alpha and tr Q run over all rows and are not read
+    const int T = h->icm_T, nh = h->kp.nhyper;
+    const double *acc = h->hres + 4, *ta = h->hres + HRES_ICM;
+    for (int t = 0; t < T; ++t) dlZ[t] = -h->icm_host[ICM_SN2 + t] * ta[ICM_ACC_DQ + t];
+    for (int i = 0; i < nh; ++i) dlZ[T + i] = -0.5 * acc[1 + i];
+    // S = P + P^T - diag(sum_i Q_ii k_ii): the pass met the pairs i <= j only
+    for (int s = 0; s < T; ++s)
+        for (int t = 0; t < T; ++t) {
+            const double p = ta[ICM_ACC_P + s * GPX_ICM_TMAX + t],
+                         pt = ta[ICM_ACC_P + t * GPX_ICM_TMAX + s];
+            dlZ[T + nh + s * T + t] = s == t ? p + pt - ta[ICM_ACC_DK + s] : p + pt;
+        }
+    for (int t = 0; t < T; ++t) dlZ[T + nh + T * T + t] = ta[ICM_ACC_ALPHA + t];
+    return 0;
+}
+
+int gpx_icm_posterior(gpx_t *h, const double *Xs, const int32_t *ts, int64_t m, double *mu,
+                      double *s2)
+{
+    return posterior_impl(h, Xs, m, mu, s2, nullptr, nullptr, ST_ICM, "gpx_icm_posterior",
+                          LP_NONE, ts);
+}
+
+int gpx_icm_posterior_full(gpx_t *h, const double *Xs, const int32_t *ts, int64_t m, double *mu,
+                           double *Sigma)
+{
+    return posterior_full_impl(h, Xs, m, mu, Sigma, ST_ICM, "gpx_icm_posterior_full", LP_NONE,
+                               ts);
 }
 
 static int sparse_ready(gpx_ctx *h, const char *what)

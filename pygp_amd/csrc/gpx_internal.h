@@ -655,6 +655,47 @@ int gpx_kaug_cross(hipStream_t s, const KParams &kp, const double *X, int n, con
 int gpx_gradobs_residual(hipStream_t s, const double *obs, int n, int M, int np, double mean,
                          double *r, double *aug, int ld);
 
+// ---- correlated outputs at their own inputs (gpx_icm_*, gpx_api.hip) ----------------------
+// task[i] in [0, T), T <= GPX_ICM_TMAX, is the output that row i observes. par: the model's
+// numbers in device memory, the same for every kernel of the family:
+//   par[ICM_B + s * GPX_ICM_TMAX + t] = B[s][t]   par[ICM_SN2 + t] = sn_t^2   par[ICM_MEAN + t]
+enum { ICM_B = 0, ICM_SN2 = GPX_ICM_TMAX * GPX_ICM_TMAX, ICM_MEAN = ICM_SN2 + GPX_ICM_TMAX,
+       ICM_NPAR = ICM_MEAN + GPX_ICM_TMAX };
+// K_ij = B[t_i][t_j] k(x_i, x_j) + delta_ij sn2[t_i] where gpx_kbuild (sym, upper_only,
+// out_offdiag) leaves K + sn2 I for gpx_potrf: the diagonal 128-tiles (both triangles, same
+// bits) in A, the other upper tiles in S, identity in the padding n .. np (kmat.hip)
+int gpx_kicm_build(hipStream_t s, const KParams &kp, const double *X, const int *task, int n,
+                   int d, const double *par, double *A, double *S, int ld, int np);
+// out[a][j] = B[t1_a][t2_j] k(x1_a, x2_j) for a < n1, j < n2 and 0 up to np1 x ldo: the
+// right-hand side of the posterior solve and the prior block of the full posterior
+int gpx_kicm_cross(hipStream_t s, const KParams &kp, const double *X1, const int *task1, int n1,
+                   int np1, const double *X2, const int *task2, int n2, int d, const double *par,
+                   double *out, int ldo);
+// r_i = y_i - mean[t_i], zero up to np: into r (may be null) and, with aug, into column np of
+// the staging matrix as gpx_residual_rhs does
+int gpx_icm_residual(hipStream_t s, const double *y, const int *task, int n, int np,
+                     const double *par, double *r, double *aug, int ld);
+// mu_j += mean[ts_j] (mu may be null) and s2_j += B[ts_j][ts_j] prior, j < m: behind
+// gpx_posterior_reduce called with mean = prior = 0
+int gpx_icm_posterior_tail(hipStream_t s, const int *ts, int m, const double *par, double prior,
+                           double *mu, double *s2);
+// The trace pass with the weight q_ij = (Kinv_ij - alpha_i alpha_j) B[t_i][t_j]: acc[1 + h] =
+// sum_ij q_ij dk_ij/dtheta_h (slot 0 is not this model's tr Q). partial: gpx_trace_scratch(np).
+int gpx_icm_trace_grad(hipStream_t s, const KParams &kp, const double *X, int n, int np, int d,
+                       const double *Kinv, int ld, const double *alpha, const int *task,
+                       const double *par, double *partial, double *acc);
+// One pass over the stored (upper) triangle of K^-1, with Q = K^-1 - alpha alpha^T, into
+// acc[ICM_NACC]: P[s][t] = sum_{i <= j, t_i = s, t_j = t} Q_ij k(x_i, x_j) at s * TMAX + t, then
+// per task t the sums over its rows of Q_ii k_ii, Q_ii and alpha_i. partial:
+// gpx_icm_task_scratch(np) doubles.
+enum { ICM_ACC_P = 0, ICM_ACC_DK = GPX_ICM_TMAX * GPX_ICM_TMAX,
+       ICM_ACC_DQ = ICM_ACC_DK + GPX_ICM_TMAX, ICM_ACC_ALPHA = ICM_ACC_DQ + GPX_ICM_TMAX,
+       ICM_NACC = ICM_ACC_ALPHA + GPX_ICM_TMAX };
+size_t gpx_icm_task_scratch(int np);
+int gpx_icm_task_sums(hipStream_t s, const KParams &kp, const double *X, const int *task, int n,
+                      int np, int d, int T, const double *Kinv, int ld, const double *alpha,
+                      double *partial, double *acc);
+
 // column strip [j0, j0+npc) of K + diag_add I for an appended block of observations
 // (j0 a multiple of 128); out_offdiag: the off-diagonal 128-tiles go there instead
 int gpx_kbuild_strip(hipStream_t s, const KParams &kp, const double *X, int n, int np,

@@ -540,21 +540,8 @@ int gpx_gradpost_contract(hipStream_t s, const KParams &kp, const double *B, int
 // written where kbuild_kernel (sym, upper_only, out_offdiag) leaves K + sn2 I for gpx_potrf:
 // only the 128-tiles with column tile >= row tile, diagonal tiles (both triangles) in A, the
 // others in the staging matrix S, identity in the padding M .. np. Every entry is computed
-// once, for row entity <= column entity, and offered to both places (kaug_put2): the two
-// triangles of a diagonal tile hold the same bits.
-__device__ __forceinline__ void kaug_put(double *__restrict__ A, double *__restrict__ S, int ld,
-                                         int gi, int gj, double v)
-{
-    const int ti = gi / GPX_TILE, tj = gj / GPX_TILE;
-    if (tj < ti) return;
-    (ti == tj ? A : S)[(size_t)gi * ld + gj] = v;
-}
-__device__ __forceinline__ void kaug_put2(double *__restrict__ A, double *__restrict__ S, int ld,
-                                          int gi, int gj, double v)
-{
-    kaug_put(A, S, ld, gi, gj, v);
-    if (gi != gj) kaug_put(A, S, ld, gj, gi, v);
-}
+// once, for row entity <= column entity, and offered to both places (kaug_put2, kmat_dev.h): the
+// two triangles of a diagonal tile hold the same bits.
 
 // Three launches, one per kind of block, so that the f-f and f-g threads do not carry the
 // registers and LDS of the g-g rows:

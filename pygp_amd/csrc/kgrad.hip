@@ -10,6 +10,8 @@
 //               reductions. No N x N temporaries (the reference makes ~4 per
 //               hyperparameter).
 //   pair_grad   the same sums over a rectangular pair set with given weights (sparse.hip).
+//   icm_task_sums  sum(Q o K) by pair of tasks and the per-task sums of Q_ii and alpha_i
+//               (gpx_icm_*): one more pass over the upper triangle of K^-1.
 //
 // All paths are relative to the reference's pygp/.
 
@@ -141,6 +143,42 @@ struct TraceWeightT {
     __device__ __forceinline__ double q(const double (*)[KT], int, int ii, int, double kinv) const
     {
         return (double)T * kinv - aa[ii];
+    }
+};
+// Correlated outputs (gpx_icm_*): q_ij = (Kinv_ij - alpha_i alpha_j) B[t_i][t_j]. The row side
+// staged once per workgroup is alpha_i (ai_s[0]) and, for every task t, the factor of the row
+// against a column of task t: ai_s[1 + t][r] = B[t_r][t]. What depends on the column is its
+// alpha_j and where its factors start, &ai_s[1 + t_j][ig * 16]: two registers, and q() reads the
+// factor of row ii at a compile-time offset from there (a wave's lanes read at most TMAX
+// addresses). Sixteen gathered factors held in registers beside the tile's operands cost the
+// D = 16 Matern row instances 24 bytes of scratch; an array of B's rows indexed by a run-time
+// task number would live in scratch altogether.
+struct TraceWeightTask {
+    static constexpr int NT = 1 + GPX_ICM_TMAX;
+    static constexpr bool STAGED = true;
+    const double *__restrict__ alpha;
+    const int *__restrict__ task;
+    const double *__restrict__ par;
+    double aj;
+    const double *brow;
+    __device__ __forceinline__ void stage(double (*ai_s)[KT], int i0, int n) const
+    {
+        const int tid = threadIdx.x;
+        if (tid < KT) ai_s[0][tid] = alpha[min(i0 + tid, n - 1)];
+        for (int e = tid; e < GPX_ICM_TMAX * KT; e += 256) {
+            const int t = e / KT, r = e - t * KT;
+            ai_s[1 + t][r] = par[ICM_B + task[min(i0 + r, n - 1)] * GPX_ICM_TMAX + t];
+        }
+    }
+    __device__ __forceinline__ void column(const double (*ai_s)[KT], int ig, int cj)
+    {
+        aj = alpha[cj];
+        brow = &ai_s[1 + task[cj]][ig * 16];
+    }
+    __device__ __forceinline__ double q(const double (*ai_s)[KT], int ig, int ii, int,
+                                        double kinv) const
+    {
+        return (kinv - ai_s[0][ig * 16 + ii] * aj) * brow[ii];
     }
 };
 
@@ -336,6 +374,16 @@ __global__ __launch_bounds__(256) void mo_trace_grad_kernel(
     int nacc)
 {
     trace_tile_body<DMAX, MODE>(kp, X, n, d, Kinv, ld, TraceWeightT{A, T, vs, {}}, partial, nacc);
+}
+
+template <int DMAX, int MODE>
+__global__ __launch_bounds__(256) void icm_trace_grad_kernel(
+    KParams kp, const double *__restrict__ X, int n, int d, const double *__restrict__ Kinv,
+    int ld, const double *__restrict__ alpha, const int *__restrict__ task,
+    const double *__restrict__ par, double *__restrict__ partial, int nacc)
+{
+    trace_tile_body<DMAX, MODE>(kp, X, n, d, Kinv, ld, TraceWeightTask{alpha, task, par, 0.0, nullptr},
+                                partial, nacc);
 }
 
 // ---- trace_grad, row-persistent form (sums of SE / Matern parts) ---------------
@@ -585,6 +633,16 @@ __global__ __launch_bounds__(256, (DMAX == 16 ? 2 : 1)) void mo_trace_grad_rows_
                                 do_trq);
 }
 
+template <int DMAX, int KIND>
+__global__ __launch_bounds__(256, (DMAX == 16 ? 2 : 1)) void icm_trace_grad_rows_kernel(
+    KParams kp, const double *__restrict__ Xs, int n, const double *__restrict__ Kinv, int ld,
+    const double *__restrict__ alpha, const int *__restrict__ task,
+    const double *__restrict__ par, double *__restrict__ partial, int nacc, int do_trq)
+{
+    trace_rows_body<DMAX, KIND>(kp, Xs, n, Kinv, ld, TraceWeightTask{alpha, task, par, 0.0, nullptr},
+                                partial, nacc, do_trq);
+}
+
 // deterministic second stage: acc[h] = sum over blocks of partial[b][h]
 __global__ __launch_bounds__(256) void trace_reduce_kernel(
     const double *__restrict__ partial, int nblocks, int nacc, double *__restrict__ acc,
@@ -627,10 +685,12 @@ template <typename F> static int with_family(int kind, F &&f)
 // then only describes the STRUCTURE the members share: parts, kinds, iso flags, slots; every
 // member's scratch is gpx_trace_scratch(np) doubles, its accumulators astride doubles behind
 // those of the member before). nout >= 1: a = A, its columns vs apart (never member-batched).
+// task != null: one output per row, a = alpha, the weight times B[t_i][t_j] from par (never
+// member-batched either).
 static int trace_grad_launch(hipStream_t s, const KParams &kp, const double *X, int n, int np,
                              int d, const double *Kinv, int ld, const double *a, int nout,
                              long long vs, double *partial, double *acc, const MemberBatch *mb,
-                             int astride)
+                             int astride, const int *task = nullptr, const double *par = nullptr)
 {
     const int T = np / KT;
     const int nacc = 1 + kp.nhyper;
@@ -665,6 +725,11 @@ static int trace_grad_launch(hipStream_t s, const KParams &kp, const double *X, 
             GPX_TRY(with_dmax(d, [&](auto dm) {
                 return with_family(kind, [&](auto kd) {
                     constexpr int DM = decltype(dm)::value, KD = decltype(kd)::value;
+                    if (task) {
+                        GPX_LAUNCH((icm_trace_grad_rows_kernel<DM, KD>), grid, dim3(256), 0, s, kp,
+                                   Xs, n, Kinv, ld, a, task, par, partial, nacc, do_trq);
+                        return 0;
+                    }
                     if (nout) {
                         GPX_LAUNCH((mo_trace_grad_rows_kernel<DM, KD>), grid, dim3(256), 0, s, kp,
                                    Xs, n, Kinv, ld, a, nout, vs, partial, nacc, do_trq);
@@ -683,6 +748,11 @@ static int trace_grad_launch(hipStream_t s, const KParams &kp, const double *X, 
         GPX_TRY(with_dmax(d, [&](auto dm) {
             return with_bool(simple, [&](auto plain) {       // MODE of GPX_GRAD_PAIR
                 constexpr int DM = decltype(dm)::value, MODE = decltype(plain)::value ? 1 : 0;
+                if (task) {
+                    GPX_LAUNCH((icm_trace_grad_kernel<DM, MODE>), grid, dim3(256), 0, s, kp, X, n,
+                               d, Kinv, ld, a, task, par, partial, nacc);
+                    return 0;
+                }
                 if (nout) {
                     GPX_LAUNCH((mo_trace_grad_kernel<DM, MODE>), grid, dim3(256), 0, s, kp, X, n, d,
                                Kinv, ld, a, nout, vs, partial, nacc);
@@ -721,6 +791,119 @@ int gpx_mo_trace_grad(hipStream_t s, const KParams &kp, const double *X, int n, 
         return -1;
     }
     return trace_grad_launch(s, kp, X, n, np, d, Kinv, ld, A, T, vs, partial, acc, nullptr, 0);
+}
+
+// ---- correlated outputs at their own inputs (gpx_icm_*) -----------------------------------
+int gpx_icm_trace_grad(hipStream_t s, const KParams &kp, const double *X, int n, int np, int d,
+                       const double *Kinv, int ld, const double *alpha, const int *task,
+                       const double *par, double *partial, double *acc)
+{
+    if (!task || !par) {
+        gpx_set_error("gpx_icm_trace_grad: bad arguments");
+        return -1;
+    }
+    return trace_grad_launch(s, kp, X, n, np, d, Kinv, ld, alpha, 0, 0, partial, acc, nullptr, 0,
+                             task, par);
+}
+
+// The sums of Q = K^-1 - alpha alpha^T by task: S for d lZ / d B, and per task the sums over its
+// rows of Q_ii (noise) and alpha_i (mean). One pass over the stored (upper) triangle of K^-1. A
+// workgroup owns the 64 columns of column block blockIdx.y and walks the row tiles bi = c0, c0 +
+// C, .. <= its own; wave ig takes rows ig*16 .. +15 of a tile. So a lane's column, and with it
+// t_j, is fixed and the task of a row is the same for the whole wave: the lane keeps one sum per
+// row task s in acc[s], indexed at compile time (a select per s, no array indexed by a task
+// number). k_ij is the per-pair value code of kcolumn_kernel. Per workgroup: for every (s, t) the
+// wavefront sum of acc[s] over the lanes with t_j = t, the four waves added in order; a second
+// launch (trace_reduce_kernel) adds the workgroups in order. No atomics.
+// Only pairs i <= j are met: P[s][t] = sum_{i <= j} Q_ij k_ij [t_i = s][t_j = t]; the caller
+// forms S = P + P^T - diag(sum_i Q_ii k_ii [t_i = s]) (the mirrored pairs, i = j once).
+#define ICM_SUM_CHUNKS 16
+__global__ __launch_bounds__(256) void icm_task_sums_kernel(
+    KParams kp, const double *__restrict__ X, const int *__restrict__ task, int n, int d, int T,
+    const double *__restrict__ Kinv, int ld, const double *__restrict__ alpha,
+    double *__restrict__ partial)
+{
+    __shared__ double red[4][ICM_NACC];
+    const int C = gridDim.x, c0 = blockIdx.x, bj = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, ig = tid >> 6;
+    double *pout = partial + ((size_t)bj * C + c0) * ICM_NACC;
+    const int gj = bj * KT + lane;
+    const bool livej = gj < n;
+    const int cj = min(gj, n - 1);
+    const int tj = task[cj];
+    const double aj = alpha[cj];
+    const double *xj = X + (size_t)cj * d;
+    double acc[GPX_ICM_TMAX];
+#pragma unroll
+    for (int s = 0; s < GPX_ICM_TMAX; ++s) acc[s] = 0.0;
+    double dk = 0.0, dq = 0.0;
+    for (int bi = c0; bi <= bj; bi += C) {
+        for (int ii = 0; ii < 16; ++ii) {
+            const int gi = bi * KT + ig * 16 + ii;
+            if (gi >= n) break;                            // (the same for the whole wave)
+            const int ti = task[gi];
+            double u = 0.0;
+            if (livej && gi <= gj) {
+                const double *xi = X + (size_t)gi * d;
+                double v = 0.0;
+                for (int p = 0; p < kp.nparts; ++p) {
+                    if (p > 0 && kp.part[p].group == kp.part[p - 1].group) continue;
+                    v += part_value_pair(kp.part[p], xi, xj, d) * group_factor(kp, p, xi, xj, d);
+                }
+                const double q = Kinv[(size_t)gi * ld + gj] - alpha[gi] * aj;
+                u = q * v;
+                if (gi == gj) {
+                    dk = u;
+                    dq = q;
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < GPX_ICM_TMAX; ++s) acc[s] += s == ti ? u : 0.0;
+        }
+    }
+    // every column's alpha once: the workgroup that holds its diagonal entry, in that lane
+    const double da = (livej && c0 == bj % C && ig == lane / 16) ? aj : 0.0;
+    for (int t = 0; t < GPX_ICM_TMAX; ++t) {
+        const bool mine = t < T && tj == t;
+#pragma unroll
+        for (int s = 0; s < GPX_ICM_TMAX; ++s) {
+            const double v = wave_sum(mine ? acc[s] : 0.0);
+            if (lane == 0) red[ig][ICM_ACC_P + s * GPX_ICM_TMAX + t] = v;
+        }
+        const double v1 = wave_sum(mine ? dk : 0.0);
+        const double v2 = wave_sum(mine ? dq : 0.0);
+        const double v3 = wave_sum(mine ? da : 0.0);
+        if (lane == 0) {
+            red[ig][ICM_ACC_DK + t] = v1;
+            red[ig][ICM_ACC_DQ + t] = v2;
+            red[ig][ICM_ACC_ALPHA + t] = v3;
+        }
+    }
+    __syncthreads();
+    if (tid < ICM_NACC) pout[tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+}
+
+static int icm_sum_chunks(int np) { return std::min(np / KT, ICM_SUM_CHUNKS); }
+
+size_t gpx_icm_task_scratch(int np)
+{
+    return (size_t)(np / KT) * icm_sum_chunks(np) * ICM_NACC;
+}
+
+int gpx_icm_task_sums(hipStream_t s, const KParams &kp, const double *X, const int *task, int n,
+                      int np, int d, int T, const double *Kinv, int ld, const double *alpha,
+                      double *partial, double *acc)
+{
+    if (n < 1 || n > np || np % KT || T < 1 || T > GPX_ICM_TMAX || !task || !partial || !acc) {
+        gpx_set_error("gpx_icm_task_sums: bad arguments (n = %d, np = %d, T = %d)", n, np, T);
+        return -1;
+    }
+    const int TB = np / KT, C = icm_sum_chunks(np);
+    GPX_LAUNCH(icm_task_sums_kernel, dim3(C, TB), dim3(256), 0, s, kp, X, task, n, d, T, Kinv, ld,
+               alpha, partial);
+    GPX_LAUNCH(trace_reduce_kernel, dim3(ICM_NACC, 1, 1), dim3(256), 0, s, partial, TB * C,
+               ICM_NACC, acc, 0LL, 0);
+    return 0;
 }
 
 // ---- weighted gradient over a rectangular pair set (sparse models, sparse.hip) -------

@@ -696,6 +696,85 @@ int gpx_kcolumn(hipStream_t s, const KParams &kp, const double *X, int n, int np
     return 0;
 }
 
+// ---- correlated outputs at their own inputs (gpx_icm_*) -----------------------------------
+// K_ij = B[t_i][t_j] k(x_i, x_j) + delta_ij sn2[t_i], written per pair the way K_aug is
+// (kaug_build_kernel<8, KAUG_FF>, kderiv.hip): blockIdx.x = row a < n, threads over the columns
+// b >= a, the value by the per-pair code of kcolumn_kernel, offered to both places of the pair
+// (kaug_put2). Behind the n rows one block row per padding column q in [n, np), threads over the
+// rows t <= q: the identity. Writes stay inside rows and columns < np.
+__global__ __launch_bounds__(256) void kicm_build_kernel(
+    KParams kp, const double *__restrict__ X, const int *__restrict__ task, int n, int d,
+    const double *__restrict__ par, double *__restrict__ A, double *__restrict__ S, int ld, int np)
+{
+    const int t = blockIdx.y * 256 + threadIdx.x;
+    const int a = blockIdx.x;
+    if (a >= n) {
+        if (a < np && t <= a) kaug_put2(A, S, ld, t, a, t == a ? 1.0 : 0.0);
+        return;
+    }
+    if (t < a || t >= n) return;
+    const double *xa = X + (size_t)a * d, *xb = X + (size_t)t * d;
+    double v = 0.0;
+    for (int p = 0; p < kp.nparts; ++p) {
+        if (p > 0 && kp.part[p].group == kp.part[p - 1].group) continue;
+        v += part_value_pair(kp.part[p], xa, xb, d) * group_factor(kp, p, xa, xb, d);
+    }
+    const int ta = task[a];
+    v *= par[ICM_B + ta * GPX_ICM_TMAX + task[t]];
+    kaug_put2(A, S, ld, a, t, t == a ? v + par[ICM_SN2 + ta] : v);
+}
+
+int gpx_kicm_build(hipStream_t s, const KParams &kp, const double *X, const int *task, int n,
+                   int d, const double *par, double *A, double *S, int ld, int np)
+{
+    if (n < 1 || d < 1 || d > GPX_MAX_DIM || n > np || np % GPX_TILE || np - n >= GPX_TILE ||
+        ld < np || !X || !task || !par || !A || !S) {
+        gpx_set_error("kicm_build: bad shape n=%d d=%d np=%d ld=%d", n, d, np, ld);
+        return -1;
+    }
+    GPX_TRY(gpx_test_jitter(s));
+    GPX_LAUNCH(kicm_build_kernel, dim3(np, (np + 255) / 256), dim3(256), 0, s, kp, X, task, n, d,
+               par, A, S, ld, np);
+    return 0;
+}
+
+// out[a][j] = B[t1_a][t2_j] k(x1_a, x2_j), np1 x ldo: blockIdx.x = row a, threads over the
+// columns; rows >= n1 and columns >= n2 are zero
+__global__ __launch_bounds__(256) void kicm_cross_kernel(
+    KParams kp, const double *__restrict__ X1, const int *__restrict__ task1, int n1,
+    const double *__restrict__ X2, const int *__restrict__ task2, int n2, int d,
+    const double *__restrict__ par, double *__restrict__ out, int ldo)
+{
+    const int a = blockIdx.x;
+    const int j = blockIdx.y * 256 + threadIdx.x;
+    if (j >= ldo) return;
+    double v = 0.0;
+    if (a < n1 && j < n2) {
+        const double *xa = X1 + (size_t)a * d, *xb = X2 + (size_t)j * d;
+        for (int p = 0; p < kp.nparts; ++p) {
+            if (p > 0 && kp.part[p].group == kp.part[p - 1].group) continue;
+            v += part_value_pair(kp.part[p], xa, xb, d) * group_factor(kp, p, xa, xb, d);
+        }
+        v *= par[ICM_B + task1[a] * GPX_ICM_TMAX + task2[j]];
+    }
+    out[(size_t)a * ldo + j] = v;
+}
+
+int gpx_kicm_cross(hipStream_t s, const KParams &kp, const double *X1, const int *task1, int n1,
+                   int np1, const double *X2, const int *task2, int n2, int d, const double *par,
+                   double *out, int ldo)
+{
+    if (n1 < 1 || n1 > np1 || n2 < 1 || n2 > ldo || d < 1 || d > GPX_MAX_DIM || !X1 || !task1 ||
+        !X2 || !task2 || !par || !out) {
+        gpx_set_error("kicm_cross: bad shape n1=%d np1=%d n2=%d ldo=%d d=%d", n1, np1, n2, ldo, d);
+        return -1;
+    }
+    GPX_TRY(gpx_test_jitter(s));
+    GPX_LAUNCH(kicm_cross_kernel, dim3(np1, (ldo + 255) / 256), dim3(256), 0, s, kp, X1, task1, n1,
+               X2, task2, n2, d, par, out, ldo);
+    return 0;
+}
+
 // ---- K(X, X) V without K (gpx_kernel_matvec, the Newton steps of gpx_laplace_update) ----------
 // out[j][c] = bias + sum_i k(x_j, x_i) V[i][c] for nv <= 4 columns: N^2 kernel values (one exp,
 // pow or sin per part and pair) against N nv 8 bytes of traffic. The layout of

@@ -245,6 +245,24 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
+// ---- a matrix built per pair for gpx_potrf (K_aug in kderiv.hip, the ICM matrix in kmat.hip) ---
+// Entry (gi, gj) where kbuild_kernel (sym, upper_only, out_offdiag) leaves it: only the
+// 128-tiles with column tile >= row tile, diagonal tiles in A, the others in the staging matrix
+// S. kaug_put2 offers a value computed once to both places of the pair.
+__device__ __forceinline__ void kaug_put(double *__restrict__ A, double *__restrict__ S, int ld,
+                                         int gi, int gj, double v)
+{
+    const int ti = gi / GPX_TILE, tj = gj / GPX_TILE;
+    if (tj < ti) return;
+    (ti == tj ? A : S)[(size_t)gi * ld + gj] = v;
+}
+__device__ __forceinline__ void kaug_put2(double *__restrict__ A, double *__restrict__ S, int ld,
+                                          int gi, int gj, double v)
+{
+    kaug_put(A, S, ld, gi, gj, v);
+    if (gi != gj) kaug_put(A, S, ld, gj, gi, v);
+}
+
 // ---- input gradients -----------------------------------------------------------
 // d k(x1, x2) / d x2 ("grady"; gradx is its negative) for one part, accumulated
 // into g[0..d). SE: K (u1-u2)/ell (se.py:76-86); Matern: M (u1-u2)/ell with

@@ -830,3 +830,52 @@ int gpx_mo_posterior_reduce(hipStream_t s, const double *V, int ldv, int np, int
     GPX_HIP(hipGetLastError());
     return 0;
 }
+
+// ---- correlated outputs at their own inputs (gpx_icm_*): per-task mean, noise and prior ------
+// r_i = y_i - mean[t_i] where residual_members_kernel leaves y - mean: r (may be null) and, with
+// aug, column np of the staging matrix with the 127 columns right of it zero. With aug one
+// thread per (row, pair of columns) of the strip, without it one thread per row, as
+// residual_kernel.
+__global__ void icm_residual_kernel(const double *__restrict__ y, const int *__restrict__ task,
+                                    int n, int np, const double *__restrict__ par,
+                                    double *__restrict__ r, double *__restrict__ aug, int ld)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    const int i = aug ? e >> 6 : e, c = aug ? e & 63 : 0;
+    if (i >= np) return;
+    const double v = i < n ? y[i] - par[ICM_MEAN + task[i]] : 0.0;
+    if (r && c == 0) r[i] = v;
+    if (aug)
+        reinterpret_cast<double2 *>(aug + (size_t)i * ld + np)[c] =
+            make_double2(c == 0 ? v : 0.0, 0.0);
+}
+
+int gpx_icm_residual(hipStream_t s, const double *y, const int *task, int n, int np,
+                     const double *par, double *r, double *aug, int ld)
+{
+    hipLaunchKernelGGL(icm_residual_kernel, dim3(((aug ? np * 64 : np) + 255) / 256), dim3(256), 0,
+                       s, y, task, n, np, par, r, aug, ld);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// behind gpx_posterior_reduce with mean = prior = 0: the test point's own task mean and prior
+__global__ void icm_posterior_tail_kernel(const int *__restrict__ ts, int m,
+                                          const double *__restrict__ par, double prior,
+                                          double *__restrict__ mu, double *__restrict__ s2)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    const int t = ts[j];
+    if (mu) mu[j] += par[ICM_MEAN + t];
+    if (s2) s2[j] += par[ICM_B + t * GPX_ICM_TMAX + t] * prior;
+}
+
+int gpx_icm_posterior_tail(hipStream_t s, const int *ts, int m, const double *par, double prior,
+                           double *mu, double *s2)
+{
+    hipLaunchKernelGGL(icm_posterior_tail_kernel, dim3((m + 255) / 256), dim3(256), 0, s, ts, m,
+                       par, prior, mu, s2);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}

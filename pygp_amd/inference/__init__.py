@@ -2,6 +2,7 @@ from .exact import GP, ExactGP
 from .basic import BasicGP
 from .gradobs import GradientGP
 from .multiout import MultiOutputGP
+from .coreg import CoregionalGP
 from .laplace import LaplaceGP
 from .ep import EPGP
 from .fitc import FITC
@@ -9,5 +10,5 @@ from .dtc import DTC
 from .vfe import VFE
 from .select import select_pseudoinputs
 
-__all__ = ['GP', 'ExactGP', 'BasicGP', 'GradientGP', 'MultiOutputGP', 'LaplaceGP', 'EPGP', 'FITC',
-           'DTC', 'VFE', 'select_pseudoinputs']
+__all__ = ['GP', 'ExactGP', 'BasicGP', 'GradientGP', 'MultiOutputGP', 'CoregionalGP', 'LaplaceGP',
+           'EPGP', 'FITC', 'DTC', 'VFE', 'select_pseudoinputs']

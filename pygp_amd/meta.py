@@ -57,6 +57,10 @@ class HyperEnsemble(object):
             # ... with one observation vector: the batch entries know nothing of Y's columns
             raise TypeError('HyperEnsemble runs GPs with one output only; this %s holds %d'
                             % (type(model).__name__, model.nout))
+        if getattr(model, 'ntask', 0) > 0:
+            # ... and one noise level and mean: the batch entries know nothing of tasks or B
+            raise TypeError('HyperEnsemble runs GPs with one output only; this %s holds %d '
+                            'coregionalised ones' % (type(model).__name__, model.ntask))
         self._model = model.copy()
         self._hypers = np.array(hypers, dtype=float, ndmin=2)
         if self._hypers.shape[1] != self._model.nhyper:
