@@ -1,6 +1,6 @@
 // Binary GP classification by expectation propagation (GPML section 3.6, the parallel form with
 // damping, Probit likelihood): the two kernels of a sweep that Laplace's Newton step does not
-// have. The driver is in gpx_api.hip (gpx_ep_*); B = I + sW K sW^T, its factorisation, the solve
+// have. The driver is in gpx_labels.hip (gpx_ep_*); B = I + sW K sW^T, its factorisation, the solve
 // and the products with K are the code of the Laplace path. Every reduction here has a fixed
 // order and no floating-point atomics.
 

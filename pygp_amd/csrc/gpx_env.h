@@ -85,7 +85,7 @@
     X(int, solo_max_np, "GPX_SOLO_MAX_NP", 0)                                   \
     X(int, solo_min_members, "GPX_SOLO_MIN_MEMBERS", 16)                        \
     X(int, xs_debug, "GPX_XS_DEBUG", 0)                                         \
-    /* per-member contexts of a batch, multi-device calls (gpx_api.hip, multi.hip) */ \
+    /* per-member contexts of a batch, multi-device calls (gpx_batch.hip, multi.hip) */ \
     X(int, batch_inflight, "GPX_BATCH_INFLIGHT", 3)                             \
     X(int, batch_lookahead, "GPX_BATCH_LOOKAHEAD", -1)                          \
     X(int, twin_probe, "GPX_TWIN_PROBE", 1)                                     \

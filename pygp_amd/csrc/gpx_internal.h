@@ -655,7 +655,7 @@ int gpx_kaug_cross(hipStream_t s, const KParams &kp, const double *X, int n, con
 int gpx_gradobs_residual(hipStream_t s, const double *obs, int n, int M, int np, double mean,
                          double *r, double *aug, int ld);
 
-// ---- correlated outputs at their own inputs (gpx_icm_*, gpx_api.hip) ----------------------
+// ---- correlated outputs at their own inputs (gpx_icm_*, gpx_exact.hip) --------------------
 // task[i] in [0, T), T <= GPX_ICM_TMAX, is the output that row i observes. par: the model's
 // numbers in device memory, the same for every kernel of the family:
 //   par[ICM_B + s * GPX_ICM_TMAX + t] = B[s][t]   par[ICM_SN2 + t] = sn_t^2   par[ICM_MEAN + t]
@@ -709,7 +709,7 @@ size_t gpx_kmatvec_scratch(int n);
 int gpx_kmatvec(hipStream_t s, const KParams &kp, const double *X, int n, int d, const double *V,
                 long long vs, int nv, double bias, double *scratch, double *out, long long os);
 
-// ---- Laplace's approximation for classification (laplace.hip; driver in gpx_api.hip) ----------
+// ---- Laplace's approximation for classification (laplace.hip; driver in gpx_labels.hip) -------
 // g, W, sW, d3, b = W (f - mean) + g at f (zero in the padding), sums[0] = sum log p(y | f)
 int gpx_lik_terms(hipStream_t s, int lik, const double *y, const double *f, double mean, int n,
                   int np, double *g, double *W, double *sW, double *d3, double *b, double *sums);
@@ -738,7 +738,7 @@ int gpx_laplace_sums(hipStream_t s, const double *g, const double *u, int n, dou
 int gpx_laplace_cross(hipStream_t s, double *Ks, int ldk, int n, int mcp, const double *g,
                       const double *sW, double mean, double *mu);
 
-// ---- expectation propagation for classification (ep.hip; driver in gpx_api.hip) ----------------
+// ---- expectation propagation for classification (ep.hip; driver in gpx_labels.hip) -------------
 // one pass over the sites: cavity, Probit moments, new sites; out[0..3] the stopping quantities,
 // out[4..7] the sums of lZ at the sites that came in, out[8] = 1 if they are a fixed point to tol
 // (never when `first`); otherwise the damped update of tau, nu and sW = sqrt tau,

@@ -1,0 +1,251 @@
+// C ABI of libgpx.so, the wrappers of the sparse models (gpx_sparse_*: FITC, DTC, VFE) and of
+// the greedy pseudo-input selection (gpx_select_*): argument checks and the handle's book-keeping
+// (which data the sparse model belongs to) around the entry points of sparse.hip and select.hip,
+// which own their buffers and kernels.
+
+#include "gpx_ctx.h"
+
+#include <cmath>
+
+using namespace gpxh;
+
+extern "C" {
+
+static int sparse_ready(gpx_ctx *h, const char *what)
+{
+    if (!h->sparse || h->sparse_version < 0) {
+        gpx_set_error("%s: no sparse model (call gpx_sparse_update)", what);
+        return -1;
+    }
+    if (h->sparse_version != h->data_version) {
+        gpx_set_error("%s: the data changed since gpx_sparse_update (stale model)", what);
+        return -1;
+    }
+    return 0;
+}
+
+int gpx_sparse_update(gpx_t *h, const gpx_kspec *k, int method, const double *U, int64_t p,
+                      double log_sn, double mean, int *info)
+{
+    CHECK_H(h);
+    GPX_TRY(require_state(h, ST_PLAIN, "gpx_sparse_update"));
+    if (info) *info = 0;
+    h->sparse_version = -1;
+    if (h->n <= 0) {
+        gpx_set_error("gpx_sparse_update: no data: call gpx_set_data first");
+        return -1;
+    }
+    if (method != GPX_FITC && method != GPX_DTC && method != GPX_VFE) {
+        gpx_set_error("gpx_sparse_update: method must be GPX_FITC, GPX_DTC or GPX_VFE (got %d)",
+                      method);
+        return -1;
+    }
+    if (!U || p < 1 || p > GPX_SPARSE_MAX_P) {
+        gpx_set_error("gpx_sparse_update: need 1 <= p <= %d pseudo-inputs (got %lld)",
+                      GPX_SPARSE_MAX_P, (long long)p);
+        return -1;
+    }
+    const long long pp = round_up(p, GPX_TILE), np = round_up(h->n, GPX_TILE);
+    if (pp * np >= (1LL << 31)) {
+        gpx_set_error("gpx_sparse_update: p_pad * N_pad = %lld x %lld must stay below 2^31", pp,
+                      np);
+        return -1;
+    }
+    if (!std::isfinite(log_sn) || !std::isfinite(mean)) {
+        gpx_set_error("gpx_sparse_update: non-finite hyperparameters");
+        return -1;
+    }
+    for (int64_t i = 0; i < p * h->d; ++i)
+        if (!std::isfinite(U[i])) {
+            gpx_set_error("gpx_sparse_update: non-finite pseudo-inputs");
+            return -1;
+        }
+    KParams kp;
+    GPX_TRY(gpx_flatten_kspec(k, h->d, &kp));
+    const int r = gpx_sparse_run_update(&h->sparse, h->stream, kp, method, U, (int)p, log_sn,
+                                        mean, h->X.as<double>(), h->y.as<double>(), h->n, h->d,
+                                        h->cap, info);
+    if (r == 0) h->sparse_version = h->data_version;
+    return r;
+}
+
+// m observations behind the resident data and into the current sparse model, in
+// O(p^2 m + p^3) whatever N is (sparse.hip, gpx_sparse_run_append). -3 (no error text) when
+// that is not possible; nothing has been touched then.
+int gpx_sparse_append(gpx_t *h, const double *Xnew, const double *ynew, int64_t m, int *info)
+{
+    CHECK_H(h);
+    GPX_TRY(require_state(h, ST_PLAIN, "gpx_sparse_append"));
+    if (info) *info = 0;
+    if (!Xnew || !ynew || m < 1) {
+        gpx_set_error("gpx_sparse_append: bad arguments");
+        return -1;
+    }
+    if (!h->sparse || h->sparse_version < 0 || h->sparse_version != h->data_version ||
+        h->n <= 0 || h->n + m > h->cap)
+        return -3;
+    const int n_old = h->n;
+    const size_t xrow = (size_t)h->d * 8;
+    if (h->X.bytes < (size_t)(n_old + m) * xrow || h->y.bytes < (size_t)(n_old + m) * 8 ||
+        !gpx_sparse_can_append(h->sparse, n_old, (int)m))
+        return -3;
+    double *Xd = h->X.as<double>() + (size_t)n_old * h->d, *yd = h->y.as<double>() + n_old;
+    GPX_HIP(hipMemcpyAsync(Xd, Xnew, (size_t)m * xrow, hipMemcpyHostToDevice, h->stream));
+    GPX_HIP(hipMemcpyAsync(yd, ynew, (size_t)m * 8, hipMemcpyHostToDevice, h->stream));
+    const int r = gpx_sparse_run_append(h->sparse, h->stream, Xd, yd, n_old, (int)m, info);
+    if (r != 0) {
+        // the rows behind n are never read and the old data stand (h->n, h->np), but the
+        // model's sums and factor are gone: every sparse call fails until gpx_sparse_update
+        (void)hipStreamSynchronize(h->stream);
+        h->sparse_version = -1;
+        return r;
+    }
+    // the data changed: an exact factorisation of this handle is stale as after gpx_set_data
+    h->n = n_old + (int)m;
+    h->np = round_up(h->n, GPX_TILE);
+    h->data_version++;
+    h->sparse_version = h->data_version;
+    h->have_factor = h->have_inverse = false;
+    h->kinv_ready = false;
+    h->posterior_calls = 0;
+    return 0;
+}
+
+int gpx_sparse_loglik(gpx_t *h, double *lZ, double *dlZ)
+{
+    CHECK_H(h);
+    GPX_TRY(sparse_ready(h, "gpx_sparse_loglik"));
+    if (!lZ) {
+        gpx_set_error("gpx_sparse_loglik: lZ is null");
+        return -1;
+    }
+    return gpx_sparse_run_loglik(h->sparse, h->stream, h->X.as<double>(), lZ, dlZ);
+}
+
+int gpx_sparse_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2,
+                         double *dmu, double *ds2)
+{
+    CHECK_H(h);
+    GPX_TRY(sparse_ready(h, "gpx_sparse_posterior"));
+    if (!Xs || !mu || !s2 || m < 0 || (!dmu) != (!ds2)) {
+        gpx_set_error("gpx_sparse_posterior: bad arguments");
+        return -1;
+    }
+    if (m == 0) return 0;
+    return gpx_sparse_run_posterior(h->sparse, h->stream, Xs, m, mu, s2, dmu, ds2, nullptr);
+}
+
+int gpx_sparse_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma)
+{
+    CHECK_H(h);
+    GPX_TRY(sparse_ready(h, "gpx_sparse_posterior_full"));
+    if (!Xs || !mu || !Sigma || m < 1 || m > 8192) {
+        gpx_set_error("gpx_sparse_posterior_full: bad arguments (1 <= m <= 8192)");
+        return -1;
+    }
+    return gpx_sparse_run_posterior(h->sparse, h->stream, Xs, m, mu, nullptr, nullptr, nullptr,
+                                    Sigma);
+}
+
+int gpx_sparse_get_state(gpx_t *h, double *F1, double *F2, double *v)
+{
+    CHECK_H(h);
+    GPX_TRY(sparse_ready(h, "gpx_sparse_get_state"));
+    return gpx_sparse_run_state(h->sparse, h->stream, F1, F2, v);
+}
+
+int gpx_sparse_timings(gpx_t *h, double *ms)
+{
+    CHECK_H(h);
+    if (!ms) {
+        gpx_set_error("gpx_sparse_timings: ms is null");
+        return -1;
+    }
+    return gpx_sparse_run_timings(h->sparse, ms);
+}
+
+int gpx_sparse_loglik_pseudo(gpx_t *h, double *lZ, double *dlZ, double *dU)
+{
+    CHECK_H(h);
+    GPX_TRY(sparse_ready(h, "gpx_sparse_loglik_pseudo"));
+    if (!lZ || !dlZ || !dU) {
+        gpx_set_error("gpx_sparse_loglik_pseudo: lZ, dlZ and dU must not be null");
+        return -1;
+    }
+    return gpx_sparse_run_loglik_pseudo(h->sparse, h->stream, h->X.as<double>(), lZ, dlZ, dU);
+}
+
+int gpx_sparse_pseudo_timing(gpx_t *h, double *ms)
+{
+    CHECK_H(h);
+    if (!ms) {
+        gpx_set_error("gpx_sparse_pseudo_timing: ms is null");
+        return -1;
+    }
+    return gpx_sparse_run_pseudo_timing(h->sparse, ms);
+}
+
+// ---- greedy pseudo-input selection (select.hip) ---------------------------------------
+int gpx_select_pivots(gpx_t *h, const gpx_kspec *k, const double *X, int64_t n, int64_t d,
+                      int64_t p, double tol, int64_t *idx, double *piv, double *trace,
+                      int64_t *count)
+{
+    CHECK_H(h);
+    GPX_TRY(require_state(h, ST_PLAIN, "gpx_select_pivots"));
+    if (!k || !idx || !count) {
+        gpx_set_error("gpx_select_pivots: k, idx and count must not be null");
+        return -1;
+    }
+    if (!X) {
+        if (h->n <= 0) {
+            gpx_set_error("gpx_select_pivots: X is null and the handle has no data "
+                          "(gpx_set_data)");
+            return -1;
+        }
+        n = h->n;
+        d = h->d;
+    }
+    if (n < 1 || n > (1 << 20) || d < 1 || d > GPX_MAX_DIM) {
+        gpx_set_error("gpx_select_pivots: bad shape n=%lld d=%lld (1 <= n <= 2^20, d <= %d)",
+                      (long long)n, (long long)d, GPX_MAX_DIM);
+        return -1;
+    }
+    if (p < 1 || p > n || p > GPX_SPARSE_MAX_P) {
+        gpx_set_error("gpx_select_pivots: need 1 <= p <= min(n, %d) (got p=%lld, n=%lld)",
+                      GPX_SPARSE_MAX_P, (long long)p, (long long)n);
+        return -1;
+    }
+    const long long pp = round_up(p, GPX_TILE), np = round_up(n, GPX_TILE);
+    if (pp * np >= (1LL << 31)) {
+        gpx_set_error("gpx_select_pivots: p_pad * N_pad = %lld x %lld must stay below 2^31", pp,
+                      np);
+        return -1;
+    }
+    if (!(tol >= 0.0) || !std::isfinite(tol)) {
+        gpx_set_error("gpx_select_pivots: tol must be finite and >= 0");
+        return -1;
+    }
+    if (X)
+        for (int64_t i = 0; i < n * d; ++i)
+            if (!std::isfinite(X[i])) {
+                gpx_set_error("gpx_select_pivots: non-finite X");
+                return -1;
+            }
+    KParams kp;
+    GPX_TRY(gpx_flatten_kspec(k, d, &kp));
+    return gpx_select_run(&h->select, h->stream, kp, X ? nullptr : h->X.as<double>(), X, (int)n,
+                          (int)d, (int)p, tol, idx, piv, trace, count);
+}
+
+int gpx_select_timing(gpx_t *h, double *ms)
+{
+    CHECK_H(h);
+    if (!ms) {
+        gpx_set_error("gpx_select_timing: ms is null");
+        return -1;
+    }
+    *ms = gpx_select_ms(h->select);
+    return 0;
+}
+
+}  // extern "C"

@@ -107,7 +107,7 @@ namespace {
 int ld_for_group(int np)
 {
     // room for the right-hand-side tile column of a whole-matrix launch, plus the padding
-    // that keeps consecutive rows off one HBM channel (gpx_api.hip: ld_for)
+    // that keeps consecutive rows off one HBM channel (gpx_ctx.h: ld_for)
     return np + 128 + 32;
 }
 
@@ -296,7 +296,7 @@ static int group_update(Slot &s, const double *X, const double *y, int n, int d,
         GPX_HIP(hipMemsetAsync(s.info.p, 0, sizeof(int) * count, st));
     }
     w.whole = whole;
-    w.full_w = grad_eval && gpx_grad_full_w(w, mode);   // (as the single evaluation, gpx_api.hip)
+    w.full_w = grad_eval && gpx_grad_full_w(w, mode);   // (as the single evaluation, gpx_exact.hip)
     if (s.timed) GPX_HIP(hipEventRecord(s.ev[0], st));
     GPX_TRY(gpx_potrf(st, w, mode, true));
     if (s.timed) GPX_HIP(hipEventRecord(s.ev[1], st));
@@ -563,7 +563,7 @@ int gpx_groups_loglik(GpxGroups **state, int device, const double *X, const doub
 
 // ---- posteriors of a batch of models (meta/mcmc.py:75-77, meta/smc.py:128-130) -----------
 // C (np x mcp) = op(W) B for every member, W = R^-1 triangular (ta = 1: W^T, k < m0 + tile;
-// ta = 0: W, k >= m0) -- gpx_api.hip's tri_product with the member dimension: with few
+// ta = 0: W, k >= m0) -- gpx_posterior.hip's tri_product with the member dimension: with few
 // columns the k range is cut into chunks whose partial products are summed in a fixed
 // order, the cut depending on (np, mcp) only, as for a single model.
 static int group_tri_product(Slot &s, const DenseWs &w, int count, int ta, const double *B,
@@ -599,7 +599,7 @@ static int group_tri_product(Slot &s, const DenseWs &w, int count, int ta, const
                             (long long)nsplit * pstride, pstride);
 }
 
-// test points per pass (gpx_api.hip: posterior_impl; the cut decides the split-K of the
+// test points per pass (gpx_posterior.hip: posterior_impl; the cut decides the split-K of the
 // products, so it is the same function of np here)
 static int posterior_chunk(int np) { return np <= 8192 ? 8192 : (np <= 16384 ? 4096 : 2048); }
 
@@ -619,7 +619,7 @@ static int group_posterior(Slot &s, const double *X, const double *y, int n, int
     const int ld = s.ld;
     GPX_HIP(hipMemcpyAsync(s.hinfo.p, s.info.p, sizeof(int) * count, hipMemcpyDeviceToHost, st));
     // V = R^-T K* is a triangle-aware product with W^T and one step of refinement, as for a
-    // single model (gpx_api.hip, solve_rt_refined): W = R^-1 is completed first
+    // single model (gpx_posterior.hip, solve_rt_refined): W = R^-1 is completed first
     if (!gc.full_inverse)
         GPX_TRY(gpx_trtri(st, w));
     double *a = s.a.as<double>();

@@ -1,6 +1,6 @@
 // GP classification by Laplace's approximation (GPML algorithms 3.1, 3.2, 5.1): the pointwise
 // likelihood terms (lik_dev.h, shared with ep.hip), the O(N^2) / O(N) kernels around the exact path's factorisation, and the
-// vector steps of the Newton iteration. The driver is in gpx_api.hip (gpx_laplace_*); K v comes
+// vector steps of the Newton iteration. The driver is in gpx_labels.hip (gpx_laplace_*); K v comes
 // from kmatvec_kernel (kmat.hip). Every reduction here has a fixed order: one workgroup, a
 // strided sum per thread, a tree over LDS.
 

@@ -193,7 +193,7 @@ __global__ __launch_bounds__(SEL_PT) void sel_pivot_kernel(
     if ((int)threadIdx.x < d) xs[threadIdx.x] = X[(size_t)pv * d + threadIdx.x];
 }
 
-// ---- entry points (called by gpx_api.hip with the handle's stream) ---------------------
+// ---- entry points (called by gpx_sparse.hip with the handle's stream) ---------------------
 void gpx_select_destroy(GpxSelect *st)
 {
     if (!st) return;

@@ -514,7 +514,7 @@ static int sp_abt_split(GpxSparse *st, hipStream_t s, const double *A, const dou
 // V (pp x mp, ld) = L^-T K(U, X) for the m rows X on the device, zero outside p x m, with one
 // step of refinement, V += L^-T (K - L^T V): the product with the explicit inverse alone has
 // the forward error of the inverse, and ell (FITC) takes kxx + sn2 - |V_j|^2, which cancels
-// (the exact path's posterior does the same, solve_rt_refined in gpx_api.hip). T1 and T2 are
+// (the exact path's posterior does the same, solve_rt_refined in gpx_posterior.hip). T1 and T2 are
 // scratch of V's shape. The update's panel, the append's strip and the posterior's test
 // columns all come through here.
 static int sp_refined_v0(GpxSparse *st, hipStream_t s, const double *X, int m, int mp, double *V,
@@ -580,7 +580,7 @@ static int sp_factor(GpxSparse *st, hipStream_t s, double *F, double *Fw, double
     return 0;
 }
 
-// ---- entry points (called by gpx_api.hip with the handle's stream and data) ----------
+// ---- entry points (called by gpx_sparse.hip with the handle's stream and data) ----------
 int gpx_sparse_nhyper(const GpxSparse *st) { return st ? st->kp.nhyper : -1; }
 
 void gpx_sparse_destroy(GpxSparse *st)

@@ -53,7 +53,7 @@ from oracle import gp_oracle as orc
 LD = np.longdouble
 MEAN = lr.MEAN
 MS = (4, 130)                    # test-point counts of the GPU checks
-FLOOR = 1e-10                    # GPX_EP_FLOOR of pygp_amd/csrc/gpx_api.hip
+FLOOR = 1e-10                    # GPX_EP_FLOOR of pygp_amd/csrc/gpx_labels.hip
 TOL, MAX_ITER, DAMPING = 1e-10, 200, 0.8
 
 

@@ -1,4 +1,4 @@
-"""The C entries that ask what a handle holds (require_state in pygp_amd/csrc/gpx_api.hip), each
+"""The C entries that ask what a handle holds (require_state in pygp_amd/csrc/gpx_handle.hip), each
 with valid arguments: the one table of the refusal tests (helpers.assert_refused)."""
 
 import ctypes as C

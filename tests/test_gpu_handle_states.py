@@ -1,4 +1,4 @@
-"""The four states of a handle (ST_* in pygp_amd/csrc/gpx_api.hip): every set_data enters its
+"""The five states of a handle (ST_* in pygp_amd/csrc/gpx_ctx.h): every set_data enters its
 state from every other, the entries of the other families then refuse the handle, and its own
 return the bits of a fresh handle; and the posterior pass the states share, across the boundary
 between two passes. The families themselves are held to the oracle by tests/test_gpu_gp.py,

@@ -1,7 +1,7 @@
 // Probe (round 3): which streams of a process share a hardware queue, and which share
 // something coarser (a dispatcher pipe)? Ten plain streams, created and touched in order,
 // beside a high- and a low-priority one (as a handle's look-ahead streams are). For every
-// pair: (1) the serialisation test of gpx_api.hip (a 0.3-ms spinner on one, an empty kernel
+// pair: (1) the serialisation test of gpx_batch.hip (a 0.3-ms spinner on one, an empty kernel
 // on the other: does the empty one queue behind it?), (2) a dispatch-bound kernel (8192
 // one-wave workgroups that do nothing) on both at once: time of the pair over time of one.
 // Build: hipcc --offload-arch=gfx950 -O3 tools/probe_queues.hip -o tools/bin/probe_queues
