@@ -535,7 +535,7 @@ int gpx_grad_mode(const DenseWs &w)
 // ... and on that route (up to np = GPX_GRAD_FULL_W, 4096) the factorisation -- one launch, or one
 // lock-step sweep, over the whole matrix -- assembles ALL of R^-1 beside R instead of leaving
 // the completion to gpx_trtri: the columns of the inverse as chunked sums on the launch's
-// workers (panel.hip, Graph::build). One evaluation with gradients, off -> on: N = 1280
+// workers (panel_graph.hip, Graph::build). One evaluation with gradients, off -> on: N = 1280
 // 0.604 -> 0.549 ms, 2048 0.893 -> 0.83, 2560 1.228 -> 1.127, 3072 1.51 -> 1.45, 3584
 // 1.94 -> 1.80, 4096 2.39 -> 2.285. Groups of 8 members in ONE launch share its workers and
 // lose: -1 % at 1536, -9 % at 2048, -10 % at 3072, -13 % at 4096; lock-step sweeps (the sums

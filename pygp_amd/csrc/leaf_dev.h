@@ -403,7 +403,7 @@ __device__ __forceinline__ void leaf_stream_signal(int *stream, int lane, int st
 // follows the factorisation. Row panel p
 // of R (16 rows, final) and the inverse of its diagonal 16-block go out as soon as they
 // exist and the counter then moves to p + 1, so that the workgroups solving the tiles
-// to the right of this one (xs_run, panel.hip) work alongside the pivot chain instead
+// to the right of this one (xs_run, panel_dev.h) work alongside the pivot chain instead
 // of after it; strict: release fence before the counter moves.
 template <bool AGENT = false>
 __device__ __forceinline__ void leaf2_run(double *__restrict__ A, int lda,
@@ -449,7 +449,7 @@ __device__ __forceinline__ void leaf2_run(double *__restrict__ A, int lda,
     // of 16 cost 6 us more per leaf; reading only the upper 16-blocks changes nothing:
     // the phase is latency-, not byte-bound)
     // (preloaded: the block is in S already, left there by the task that applied its last
-    // update -- xs_run, panel.hip)
+    // update -- xs_run, panel_dev.h)
     if (!preloaded) {
         double2 tmp[32];
 #pragma unroll

@@ -141,7 +141,8 @@ def test_multi_device_pack_and_scatter(libpath, ndev, B, width):
 
 @pytest.mark.parametrize('stream', [True, False])
 def test_panel_task_graph_is_a_valid_schedule(stream):
-    """The diagonal-panel kernel (pygp_amd/csrc/panel.hip) runs a host-built task list:
+    """The diagonal-panel kernel (pygp_amd/csrc/panel.hip) runs a task list built on the host
+    (panel_graph.hip):
     workgroups claim tasks in list order and wait on device counters, so the list must
     be a topological order of those counter dependencies or the launch would stall
     until its timeout. gpx_panel_graph_check replays the list on the host for every

@@ -9,7 +9,14 @@ smallest order that takes the blocked driver with lead rows, the look-ahead stre
 split-k route of the posterior's products. Run it from two trees (it imports the package of the
 tree it lies in) on the same device: the outputs must not differ. The last line counts the
 arrays and the doubles.
-usage: units_digest.py > out.txt"""
+The routes of the task-queue launches (pygp_amd/csrc/panel.hip, panel_graph.hip) at the smallest
+shapes that take them: a whole matrix in one launch with its right-hand side, without and with
+the whole inverse (N = 300, three tiles, one panel; N = 1100, nine tiles); the member-batched
+launch (6 thetas) and the lock-step sweep (16 and 33 thetas), value-only and with gradients; the
+blocked driver's wide panels in the N = 2100 pass. `panel` runs these alone, for a pass per
+developer switch (GPX_PANEL_STRICT, GPX_PANEL_SPLIT, GPX_PANEL_STREAM, GPX_SWEEP_LITE,
+GPX_SOLO_MAX_NP / GPX_SOLO_MIN_MEMBERS).
+usage: units_digest.py [panel] > out.txt"""
 import hashlib
 import os
 import sys
@@ -138,8 +145,32 @@ def refusals(h, t, spec, nh, X, y, labels, Xs):
     put(t('exact_append on coregional'), lambda: h.exact_append(X[:2], y[:2]))
 
 
+def panel_routes(h):
+    d = 3
+    k = K.SE(1.1, 0.5 * np.sqrt(d) * (1.0 + 0.1 * np.arange(d)))
+    spec, hyp, nh = k._kspec(), k.get_hyper(), k.nhyper
+    for n in (300, 1100):
+        rng = np.random.RandomState(500 + n)
+        X = rng.rand(n, d)
+        y = np.sin(3 * X.sum(axis=1)) + 0.1 * rng.randn(n)
+        t = lambda what: 'N=%-4d panel    %s' % (n, what)
+        h.set_data(X, y)
+        put(t('exact_eval value'), lambda: h.exact_eval(spec, LSN, MEAN, False))
+        put(t('exact_eval grad'), lambda: h.exact_eval(spec, LSN, MEAN, True))
+        for B in (6, 16, 33):
+            base = np.r_[LSN, hyp, MEAN]
+            thetas = base + 0.1 * np.cos(np.arange(B * (nh + 2)).reshape(B, nh + 2))
+            for grad in (False, True):              # (the plan of the batch names its route)
+                plan = h.batch_plan(B, grad)
+                put(t('loglik_batch B=%d %s, %s x %d' % (B, 'grad' if grad else 'value', plan['arrangement'],
+                                                         plan['members_per_group'])),
+                    lambda: h.loglik_batch(spec, thetas, grad=grad))
+
+
+ONLY_PANEL = sys.argv[1:] == ['panel']
 h = _lib.Handle(0)
-for d in WIDTHS:
+panel_routes(h)
+for d in () if ONLY_PANEL else WIDTHS:
     rng = np.random.RandomState(1000 + d)
     X, X2 = rng.rand(N1, d), rng.rand(N2, d)
     Xs = {m: rng.rand(m, d) for m in MS}
