@@ -552,11 +552,21 @@ int gpx_panel_graph_check(int T, int workers, int stream, int *ntasks);
 /* the sizing rule of a MEMBER-BATCHED panel launch over nmem members on a device of ncu CUs
  * (host only; the function the launch itself calls): every workgroup of the launch holds a
  * whole CU, and all spine workgroups plus at least one worker must be resident together for
- * the launch to make progress. *nspwg = spine workgroups per member (3 / 2 / 1 by members, or
- * GPX_PANEL_MSPINE; fewer if they would not fit), *workers = the shared pool (250 workgroups in
- * all, or GPX_PANEL_MWG); < 0: even one spine workgroup per member does not fit. A launch
- * over a single matrix sizes itself separately (9 / 5 / 3 spine workgroups by split and fold,
- * workers by the size of the matrix). */
+ * the launch to make progress. The rule is one of (members, graph, kind of launch): tiles =
+ * tiles of the block (more than 8: a launch over a whole matrix), split / fold = the graph has
+ * the split spine / its solves fold their tile's last update in (the defaults; 0 / 0: the fused
+ * spine task). *nspwg = spine workgroups per member: as many as the graph keeps busy (9 / 5 / 3
+ * by split and fold) while the spines of all members together stay within 40 workgroups (a
+ * whole matrix: 20), never fewer than 3 / 2 / 1 up to 16 / 40 / more members, or
+ * GPX_PANEL_MSPINE; fewer if they would not fit the device. *workers = the shared pool (250
+ * workgroups in all, or GPX_PANEL_MWG). < 0: even one spine workgroup per member does not fit.
+ * A launch over a single matrix sizes itself separately (9 / 5 / 3 spine workgroups by split
+ * and fold, workers by the size of the matrix). */
+int gpx_panel_grid_rule(int nmem, int ncu, int tiles, int split, int fold, int *nspwg,
+                        int *workers);
+/* ... for the graph with the fused spine task (split = fold = 0): 3 / 2 / 1 spine workgroups by
+ * members, the fewest the rule gives any graph -- the co-residency every launch over nmem
+ * members needs at least */
 int gpx_panel_grid_check(int nmem, int ncu, int *nspwg, int *workers);
 /* the same for a wide panel launch: the block's T tiles plus E (0..8) tile columns to its
  * right, whose row-panel tiles and whose E x E diagonal block's update run inside the launch */

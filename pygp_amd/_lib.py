@@ -166,6 +166,7 @@ SIGNATURES = {
     'gpx_multi_enable_timing': (C.c_int, [C.c_int, C.c_int]),
     'gpx_multi_batch_info': (C.c_int, [C.c_int, _i64, C.c_int, _dp, C.POINTER(_i64), _ip]),
     'gpx_panel_grid_check': (C.c_int, [C.c_int, C.c_int, _ip, _ip]),
+    'gpx_panel_grid_rule': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip]),
     'gpx_la_gemm_ex': (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]),
     'gpx_la_potrf': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _ip]),
     'gpx_la_gemm_bench': (C.c_int, [_vp, C.c_int, C.c_int, _i64, C.c_int, _dp]),
@@ -1033,10 +1034,21 @@ def multi_batch_info(ndev, B_per_dev, grad=False):
 
 def panel_grid_check(nmem, ncu=256):
     """(spine workgroups per member, workers) of a panel launch over nmem members on a device
-    of ncu CUs, or RuntimeError if even one spine workgroup per member does not fit
+    of ncu CUs for the graph with the fused spine task -- the fewest spines any graph gets --,
+    or RuntimeError if even one spine workgroup per member does not fit
     (gpx_panel_grid_check; host only)."""
     sp, wk = C.c_int(0), C.c_int(0)
     check(lib().gpx_panel_grid_check(int(nmem), int(ncu), C.byref(sp), C.byref(wk)))
+    return sp.value, wk.value
+
+
+def panel_grid_rule(nmem, ncu=256, tiles=8, split=True, fold=True):
+    """(spine workgroups per member, workers) of a member-batched panel launch over `tiles`
+    tiles (more than 8: a whole matrix) of the graph with / without the split spine and the
+    fold, or RuntimeError if it cannot fit (gpx_panel_grid_rule; host only)."""
+    sp, wk = C.c_int(0), C.c_int(0)
+    check(lib().gpx_panel_grid_rule(int(nmem), int(ncu), int(tiles), int(split), int(fold),
+                                    C.byref(sp), C.byref(wk)))
     return sp.value, wk.value
 
 

@@ -737,9 +737,25 @@ int gpx_potrf(hipStream_t s, const DenseWs &w, int mode, bool offdiag_staged)
                 g.order = gpx_env().ord_r12;
                 GPX_TRY(gpx_gemm(bulk, 1, 0, g));
             }
-            // update k of the next diagonal block first: F_k+1 can start
             const size_t o11 = (size_t)o1 * ld + o1;
-            if (!wide)
+            // No look-ahead above np = 8192 (a group -- ONE is in flight there --, a single
+            // evaluation in safe mode or without streams): nothing can start early and nothing
+            // else runs, so update k is ONE launch over the upper tiles of the whole trailing
+            // matrix. The three launches of the look-ahead order are a partition of exactly
+            // these tiles -- same operand panel, same K, same k order, diagonal tiles in A and
+            // the others in the staging area -- so every tile gets the same bits; what goes are
+            // partly empty last rounds and two launch boundaries a step (a group of six at
+            // N = 16384: 126 -> 112 launches, TN 128-tiles 126.2 -> 124.6 ms a step).
+            // Up to np = 8192 TWO groups are in flight and take turns launch by launch: 64
+            // thetas at N = 8192 ran 0.8 % (value-only) / 0.3 % (with gradients) SLOWER with
+            // the one launch (profiles/group_step_ab.txt), and their 32 members leave no
+            // partly empty round to win. GPX_TRAIL_ONE=0: three launches everywhere (A/B
+            // runs, the bit test).
+            const bool one = !ahead && !wide && w.np > 8192 && gpx_env().trail_one;
+            if (one)
+                GPX_TRY(syrk_upper(bulk, w.A + ok1, ld, w.A + o11, ld, rest, nk, w.Kinv + o11));
+            // otherwise update k of the next diagonal block first: F_k+1 can start
+            else if (!wide)
                 GPX_TRY(syrk_upper(bulk, w.A + ok1, ld, w.A + o11, ld, n1, nk, w.Kinv + o11));
             if (ahead) GPX_EV(hipEventRecord(D[k + 1], bulk));
             if (k + 2 < nb) {
@@ -748,14 +764,16 @@ int gpx_potrf(hipStream_t s, const DenseWs &w, int mode, bool offdiag_staged)
                              o22 = (size_t)o2 * ld + o2;
                 // ... then the off-diagonal tiles of row k+1 (they stay in the staging
                 // area) ...
-                {
+                if (!one) {
                     GemmArgs g = mk(w.A + ok1, ld, w.A + ok2, ld, w.Kinv + o12, ld, n1, rest2,
                                     nk, -1.0, 1.0, 0);
                     GPX_TRY(gpx_gemm(bulk, 1, 0, g));
                 }
                 GPX_TRY(gate_bump(bulk, w, 0));
                 // ... and the trailing blocks: diagonal tiles in A, the others in Kinv
-                GPX_TRY(syrk_upper(bulk, w.A + ok2, ld, w.A + o22, ld, rest2, nk, w.Kinv + o22));
+                if (!one)
+                    GPX_TRY(syrk_upper(bulk, w.A + ok2, ld, w.A + o22, ld, rest2, nk,
+                                       w.Kinv + o22));
                 GPX_TRY(gate_bump(bulk, w, 1));
             }
         }

@@ -1036,7 +1036,8 @@ int gpx_panel(hipStream_t s, const DenseWs &w, int off, int n, int extra, int ga
         // error instead of a launch that would wait out its 2-s bound.
         int ncu = 0;
         GPX_TRY(device_cus(&ncu));
-        if (!(nmem > 1 ? panel_grid_members(nmem, ncu, &nspwg, &workers)
+        if (!(nmem > 1 ? panel_grid_members(nmem, ncu, whole, split, panel_fold(), &nspwg,
+                                            &workers)
                        : panel_grid_single(w.np, T, E, whole, split, ncu, &nspwg, &workers))) {
             gpx_set_error("panel: %d members need %d spine workgroups, the device has %d CUs "
                           "(run such groups through the lock-step sweep)", nmem, nmem, ncu);

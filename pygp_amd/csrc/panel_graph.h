@@ -43,6 +43,7 @@ bool panel_split(bool stream, int E, bool aug);
 bool panel_fold();
 
 bool gpx_panel_grid_fits(int nmem, int nspwg, int ncu);
-bool panel_grid_members(int nmem, int ncu, int *nspwg, int *workers);
+bool panel_grid_members(int nmem, int ncu, bool whole, bool split, bool fold, int *nspwg,
+                        int *workers);
 bool panel_grid_single(int np, int T, int E, bool whole, bool split, int ncu, int *nspwg,
                        int *workers);

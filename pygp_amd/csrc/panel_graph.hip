@@ -683,29 +683,46 @@ bool gpx_panel_grid_fits(int nmem, int nspwg, int ncu)
 {
     return nmem >= 1 && nspwg >= 1 && (long long)nmem * nspwg + 1 <= ncu;
 }
-// Member-batched launch: the same graph for every member of the workspace. The chain of
-// a member keeps 1-3 spine workgroups busy and its products a handful of workers, so the
-// members share one pool of workers (the interleaved queue) and the launch is sized to
-// the GPU: about 250 workgroups in all -- each holds a whole CU -- of which the spines
-// take 3 per member up to 16 members, 2 up to 40, 1 beyond (the chain of a member then
-// runs solve, diagonal update and leaf one after the other on one CU: 70 instead of 42 us
-// per tile, for a third of the CUs), fewer until the launch fits a device of ncu CUs.
+// spine workgroups the chain of ONE matrix can keep busy, by its graph (round 5, split spine:
+// per tile a solving and a following task -- nine, five without the fold, so that solve,
+// follower + leaf and the leaf's inverse tail of neighbouring tiles never wait for each other's
+// workgroup; three for the fused spine task)
+static int graph_spines(bool split, bool fold) { return split ? (fold ? 9 : 5) : 3; }
+// Member-batched launch: the same graph for every member of the workspace. The members share
+// one pool of workers (the interleaved queue) and the launch is sized to the GPU: about 250
+// workgroups in all, each of which holds a whole CU. Spine workgroups per member, a rule of
+// (members, graph, kind of launch):
+//   - never fewer than 3 up to 16 members, 2 up to 40, 1 beyond (the chain of a member then
+//     runs solve, diagonal update and leaf one after the other on one CU: 70 instead of 42 us
+//     per tile, for a third of the CUs) -- all the fused spine task can use;
+//   - with the split spine as many as the graph can keep busy (graph_spines) while the spines
+//     of ALL members stay within a share of the launch: 40 workgroups for a block of at most
+//     1024 rows, whose launch is as long as its chain, 20 for a whole-matrix launch, which is
+//     bound by its workers from about six members on. Measured, ms per call with 3 / 5 / 6 / 9
+//     spine workgroups a member (profiles/group_panel_spines.txt): N = 1024 value-only, 3
+//     members 0.57 / 0.42 / 0.40 / 0.39, 6: 0.63 / 0.49 / 0.47 / 0.50, 8: 0.66 / 0.56 / 0.58 /
+//     0.61, 12: 0.78 / 0.82 / 0.83 / 0.96; N = 2048 (whole), 3 members 1.15 / 0.80 / 0.76 /
+//     0.80, 6: 1.28 / 1.25 / 1.25 / 1.35, 8: 1.56 / 1.69 / 1.71 / 1.89; the 1024-blocks of the
+//     N = 16384 group of six 543 / 415 / 394 / 409 us a launch.
+//   - fewer until the launch fits a device of ncu CUs (gpx_panel_grid_fits).
 // GPX_PANEL_MSPINE / GPX_PANEL_MWG override. false: it cannot fit.
-bool panel_grid_members(int nmem, int ncu, int *nspwg, int *workers)
+bool panel_grid_members(int nmem, int ncu, bool whole, bool split, bool fold, int *nspwg,
+                        int *workers)
 {
     const int mspine = gpx_env().panel_mspine, mwg = gpx_env().panel_mwg;   // (-1: the rule)
-    int sp = mspine > 0 ? mspine : (nmem <= 16 ? 3 : (nmem <= 40 ? 2 : 1));
+    const int least = nmem <= 16 ? 3 : (nmem <= 40 ? 2 : 1);
+    const int share = whole ? 20 : 40;
+    int sp = std::max(least, std::min(graph_spines(split, fold), share / std::max(1, nmem)));
+    if (mspine > 0) sp = mspine;
     while (sp > 1 && !gpx_panel_grid_fits(nmem, sp, ncu)) --sp;
     if (!gpx_panel_grid_fits(nmem, sp, ncu)) return false;
     *nspwg = sp;
     *workers = std::max(8, (mwg > 0 ? mwg : 250) - nmem * sp);
     return true;
 }
-// A single-matrix launch sizes itself by the matrix: spine workgroups by the graph (round 5,
-// split spine: per tile a solving and a following task -- nine spine workgroups, five without
-// the fold, so that solve, follower + leaf and the leaf's inverse tail of neighbouring tiles
-// never wait for each other's workgroup; three for the fused spine task), fewer if the
-// device is smaller than that, and workers beside them: the row-panel tasks hold up to
+// A single-matrix launch sizes itself by the matrix: spine workgroups by the graph
+// (graph_spines), fewer if the device is smaller than that, and workers beside them: the
+// row-panel tasks hold up to
 // seven of them for the length of a leaf and a workgroup that has claimed a task waits for
 // it, whatever else is ready (32 -> 64 -> 128: 450 / 412 / 370 us per 1024-block; N = 4096
 // evaluation 3.08 -> 2.96 ms with 128); above N = 4096 the chain hides under the products of
@@ -722,7 +739,7 @@ bool panel_grid_single(int np, int T, int E, bool whole, bool split, int ncu, in
                        int *workers)
 {
     const GpxEnv &e = gpx_env();                       // (-1: the rule)
-    int sp = e.panel_nspine > 0 ? e.panel_nspine : (split ? (panel_fold() ? 9 : 5) : 3);
+    int sp = e.panel_nspine > 0 ? e.panel_nspine : graph_spines(split, panel_fold());
     while (sp > 1 && !gpx_panel_grid_fits(1, sp, ncu)) --sp;
     if (!gpx_panel_grid_fits(1, sp, ncu)) return false;
     *nspwg = sp;
@@ -732,23 +749,34 @@ bool panel_grid_single(int np, int T, int E, bool whole, bool split, int ncu, in
                : np <= 4096 ? 128 : 32;
     return true;
 }
-// the rule of a MEMBER-BATCHED launch (panel_grid_members, which gpx_panel applies) as a
-// host check: spine workgroups per member and workers for nmem members on ncu CUs; -1: the
-// launch cannot fit. (A single-matrix launch sizes itself separately: panel_grid_single.)
-extern "C" int gpx_panel_grid_check(int nmem, int ncu, int *nspwg, int *workers)
+// the rule of a MEMBER-BATCHED launch (panel_grid_members, which gpx_panel applies) as a host
+// check: spine workgroups per member and workers for nmem members on ncu CUs, for a launch over
+// `tiles` tiles (more than 8: a whole matrix) of the graph with / without the split spine and
+// the fold; -1: the launch cannot fit. (A single-matrix launch sizes itself separately:
+// panel_grid_single.)
+extern "C" int gpx_panel_grid_rule(int nmem, int ncu, int tiles, int split, int fold, int *nspwg,
+                                   int *workers)
 {
-    if (nmem < 1 || ncu < 1) {
+    if (nmem < 1 || ncu < 1 || tiles < 2 || tiles > PCTL_TMAX) {
         gpx_set_error("panel grid check: bad arguments");
         return -1;
     }
     int sp = 0, wk = 0;
-    if (!panel_grid_members(nmem, ncu, &sp, &wk)) {
+    if (!panel_grid_members(nmem, ncu, tiles > GPX_PANEL_MAX / 128, split != 0, split && fold, &sp,
+                            &wk)) {
         gpx_set_error("panel grid check: %d members do not fit %d CUs", nmem, ncu);
         return -1;
     }
     if (nspwg) *nspwg = sp;
     if (workers) *workers = wk;
     return 0;
+}
+// ... for the graph with the fused spine task (GPX_PANEL_SPLIT=0, the round-1 graph): the
+// fewest spine workgroups the rule gives any graph, and so the co-residency every launch over
+// nmem members needs at least
+extern "C" int gpx_panel_grid_check(int nmem, int ncu, int *nspwg, int *workers)
+{
+    return gpx_panel_grid_rule(nmem, ncu, GPX_PANEL_MAX / 128, 0, 0, nspwg, workers);
 }
 // Host-side self-check of the task graph of one panel launch (no GPU needed): the
 // schedule is a permutation and a topological order of the counter dependencies (every
