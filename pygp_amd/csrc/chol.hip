@@ -16,7 +16,8 @@
 //          With GPX_POTRF_W / _KINV the sweep also builds R^-1 and (R^T R)^-1 block
 //          column by block column (inverse_column, on a third stream): the
 //          shrinking trailing update and the growing inverse work add up to about
-//          the same amount of products in every step.
+//          the same amount of products in every step. (Without look-ahead above
+//          np = 8192 only R^-1 is built that way; (R^T R)^-1 is one lauum behind the sweep.)
 //   inside a diagonal block: recursive -- factor the leading half AND invert its
 //          factor, R12 = W11^T A12, SYRK the trailing half, recurse, extend the
 //          inverse W12 = -W11 (R12 W22). Blocks of <= 1024 rows are one task-queue
@@ -441,6 +442,10 @@ static int trtri_blocks(hipStream_t s, const DenseWs &w, const Blocks &bl, int b
 // Summed over k these are the N^3/3 + N^3/3 flops of trtri + lauum as rank-NB products
 // that only trail the factorisation by one block, so they fill the GPU while the last
 // diagonal blocks (a latency-bound chain with little trailing matrix left) are factored.
+// That holds with look-ahead; K^-1 accumulates here (`kinv`) on every look-ahead path and,
+// without look-ahead, up to np = 8192. Without look-ahead above np = 8192 nothing is hidden
+// by the early updates: gpx_potrf asks for the columns of W only and forms K^-1 as one
+// product behind its block loop (same bits; the reasons are written there).
 // Round 3 reassociated the column: rounds 1-2 formed T = R[:k, k] W_kk first and then
 // -W[:k, :k] T, so the large product (k^2 nk flops) waited for the diagonal block's
 // inverse. P needs only rows < k of R (final when row panel k-1 is: `early`) and runs
@@ -625,6 +630,19 @@ int gpx_potrf(hipStream_t s, const DenseWs &w, int mode, bool offdiag_staged)
     // the caller goes on (vector kernels that need R and R^-1 only) while the last K^-1
     // update is still running
     const bool defer = ahead && w.defer_kinv && mode == GPX_POTRF_KINV && aux != bulk;
+    // No look-ahead above np = 8192 (the bound and the cases of the one trailing update, see
+    // the block loop): nothing runs beside the K^-1 updates of inverse_column, so having them
+    // early hides nothing, and each of them ramps up, drains, and reads and writes again every
+    // K^-1 tile it touches. There the columns form R^-1 only and K^-1 = W W^T is ONE launch
+    // behind the loop (gpx_lauum; N = 16384: nine launches -> one). A tile's k-range is the
+    // same in both forms -- klo = max(m0, n0) either way, beta C as the initial accumulator
+    // with beta / alpha = 1, k walked upwards -- so cutting it at block boundaries or walking
+    // it once is the same chain of MFMAs: same bits (tests/test_gpu_group_kinv.py). Up to
+    // np = 8192 two groups are in flight and interleave their launches (the one trailing
+    // update measured slower there), and with look-ahead the updates run under the chain of
+    // diagonal blocks: both keep the accumulating form. GPX_KINV_ONE=0: accumulating
+    // everywhere (A/B runs, the bit test).
+    const bool kinv_one = mode == GPX_POTRF_KINV && !ahead && w.np > 8192 && gpx_env().kinv_one;
     // The diagonal blocks are (part of) the critical path, and on `bulk` the two small
     // products between F_k and F_k+1 -- the block column of the row panel that the next
     // diagonal block needs and that block's update -- queued behind the far trailing update
@@ -777,13 +795,19 @@ int gpx_potrf(hipStream_t s, const DenseWs &w, int mode, bool offdiag_staged)
                 GPX_TRY(gate_bump(bulk, w, 1));
             }
         }
-        // the inverse follows one block behind, on its own stream
+        // the inverse follows one block behind, on its own stream. K^-1 with it, update by
+        // update, wherever there is look-ahead (it fills the device under the chain of
+        // diagonal blocks) and up to np = 8192 (two groups take turns launch by launch);
+        // kinv_one: R^-1 only, K^-1 is one product behind the loop
         if (mode != GPX_POTRF_R)
-            GPX_TRY(inverse_column(aux, w, bl, k, mode == GPX_POTRF_KINV,
+            GPX_TRY(inverse_column(aux, w, bl, k, mode == GPX_POTRF_KINV && !kinv_one,
                                    defer && k == nb - 1 ? evW : nullptr,
                                    ahead && aux != bulk && k > 0 ? D[k] : nullptr,
                                    ahead && aux != bulk ? F[k] : nullptr));
     }
+    // (the T / P scratch of the columns in Kinv[:k, k] was last read by the second product of
+    // its own column; this launch writes every upper tile from zero)
+    if (kinv_one) return gpx_lauum(s, w, true);
     if (ahead) {                                       // back on the caller's stream
         GPX_EV(hipEventRecord(evJoin, bulk));
         GPX_EV(hipStreamWaitEvent(s, evJoin, 0));
@@ -861,14 +885,14 @@ int gpx_trsm_rt(hipStream_t s, const DenseWs &w, double *B, double *T, int ldb, 
     return 0;
 }
 
-int gpx_lauum(hipStream_t s, const DenseWs &w)
+int gpx_lauum(hipStream_t s, const DenseWs &w, bool k_up)
 {
     // Kinv[i][j] = sum_{k >= max(i,j)} W[i][k] W[j][k], tiles with j >= i
     const BatchScope batch_scope(w);
     const int n = w.np, ld = w.ld;
     GemmArgs g = mk(w.W, ld, w.W, ld, w.Kinv, ld, n, n, n, 1.0, 0.0,
                     GEMM_UPPER_ONLY | GEMM_KLO_M | GEMM_KLO_N |
-                        (gpx_env().krev ? GEMM_KREV : 0));
+                        (gpx_env().krev && !k_up ? GEMM_KREV : 0));
     g.order = gpx_env().ord_lauum;
     return gpx_gemm(s, 0, 1, g);
 }

@@ -24,6 +24,7 @@
     X(int, invcol_early, "GPX_INVCOL_EARLY", -1)                                \
     X(int, overlap_nosplit, "GPX_OVERLAP_NOSPLIT", 1)                           \
     X(int, trail_one, "GPX_TRAIL_ONE", 1)                                       \
+    X(int, kinv_one, "GPX_KINV_ONE", 1)                                         \
     X(int, grad_whole, "GPX_GRAD_WHOLE", 4096)                                  \
     X(int, grad_full_w, "GPX_GRAD_FULL_W", 4096)                                \
     /* products of the drivers on the tile engine (chol.hip, gemm_f64.hip) */   \

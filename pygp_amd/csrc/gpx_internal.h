@@ -303,7 +303,8 @@ int gpx_potrf_join(hipStream_t s, const DenseWs &w);
 hipEvent_t gpx_potrf_lead_event(const DenseWs &w);
 // complete W = R^-1 after a gpx_potrf(..., false)
 int gpx_trtri(hipStream_t s, const DenseWs &w);
-int gpx_lauum(hipStream_t s, const DenseWs &w);            // Kinv = W W^T
+// Kinv = W W^T (k_up: k walked upwards whatever GPX_KREV says)
+int gpx_lauum(hipStream_t s, const DenseWs &w, bool k_up = false);
 // C = S S^T on the tiles with column >= row, S a full np x np matrix (ld w.ld, like C)
 int gpx_aat_upper(hipStream_t s, const DenseWs &w, const double *S, double *C);
 // X = R^-T B for B (np x m, ld ldb) in place, m multiple of GPX_TILE; T is a
