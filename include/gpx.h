@@ -485,6 +485,35 @@ int gpx_select_pivots(gpx_t *h, const gpx_kspec *k, const double *X, int64_t n, 
 /* HIP-event ms around the launches of the last gpx_select_pivots on this handle (0: none) */
 int gpx_select_timing(gpx_t *h, double *ms);
 
+/* ---- Fourier-feature function samples (pygp/inference/_fourier.py) -------- */
+/* A sample f(x) = mean + a sum_j cos(w_j.x + b_j) theta_j over M random features: W[M*d], b[M]
+ * and a come from the caller (the kernel's spectrum is drawn on the host), theta from the
+ * posterior of the weights given n observations. gpx_fourier_fit forms Phi = a cos(X W^T + b),
+ * A = Phi^T Phi + sn^2 I = R^T R and, for each of the S rows p_s of P[S*M] (standard normal
+ * draws), theta_s = A^-1 Phi^T (y - mean) + sn R^-1 p_s; theta[S*M] is written back and stays
+ * on the device. X == NULL (with n != 0): the handle's resident data (gpx_set_data; n is then
+ * taken from them); n == 0: no data, theta = P. A non-positive pivot of A returns > 0, also in
+ * *info. Limits: 1 <= M <= GPX_FOURIER_MAX_M, d <= GPX_MAX_DIM, n <= 2^20,
+ * round_up(M, 128) * round_up(n, 128) < 2^31, 1 <= S <= GPX_FOURIER_MAX_S.
+ * The sample lives in buffers of its own: no gpx_fourier_* call touches the resident data, an
+ * exact factorisation or a sparse model of the handle, and gpx_set_data leaves the sample as
+ * it is. Every sum has a fixed order: the same call returns the same bits. */
+#define GPX_FOURIER_MAX_M 4096
+#define GPX_FOURIER_MAX_S 32
+int gpx_fourier_fit(gpx_t *h, const double *W, int64_t M, int64_t d, const double *b, double a,
+                    double log_sn, double mean, const double *X, int64_t n, const double *y,
+                    const double *P, int64_t S, double *theta, int *info);
+/* installs a given sample (theta[S*M]) without fitting: what a copy or a pickle restores */
+int gpx_fourier_set(gpx_t *h, const double *W, int64_t M, int64_t d, const double *b, double a,
+                    double mean, const double *theta, int64_t S);
+/* F[S*n] = f_s(Xs_i) and, G != NULL, G[S*n*d] with G[s][i][c] = d f_s / d x_c at Xs_i, for the
+ * n rows of Xs[n*d], 1 <= n <= 2^20: one fused pass, one sincos per point and feature, the
+ * features are never stored */
+int gpx_fourier_eval(gpx_t *h, const double *Xs, int64_t n, double *F, double *G);
+/* HIP-event ms of the last gpx_fourier_fit (ms[0]) and of the kernels of the last
+ * gpx_fourier_eval (ms[1]) on this handle (0: none) */
+int gpx_fourier_timings(gpx_t *h, double *ms);
+
 /* ---- instrumentation ---------------------------------------------------- */
 /* per-stage GPU times (ms) of the last gpx_exact_eval / update+loglik measured
  * with HIP events on the handle's stream. names via gpx_timing_name(i). */

@@ -5,7 +5,8 @@ Only the path named in BASELINE.json is here: pairwise kernel evaluation
 (SE / Matern / Periodic / RQ, sums of products), ExactGP update /
 log-likelihood (+gradient) / posterior, the sparse FITC / DTC / VFE models and binary
 classification by Laplace's approximation (LaplaceGP) and by expectation propagation (EPGP),
-and correlated outputs at their own inputs (CoregionalGP), executed by hand-written HIP kernels in libgpx.so; `batch` and `meta` route the
+correlated outputs at their own inputs (CoregionalGP) and posterior function samples through
+random Fourier features (FourierSample), executed by hand-written HIP kernels in libgpx.so; `batch` and `meta` route the
 per-sample loops of the reference's meta-models through the batched entry points.
 """
 
@@ -16,9 +17,9 @@ from . import learning
 from . import batch
 from . import meta
 from .inference import (BasicGP, ExactGP, GradientGP, MultiOutputGP, CoregionalGP, LaplaceGP,
-                        EPGP, FITC, DTC, VFE, select_pseudoinputs)
+                        EPGP, FITC, DTC, VFE, select_pseudoinputs, FourierSample)
 from .learning import optimize
 
 __all__ = ['BasicGP', 'ExactGP', 'GradientGP', 'MultiOutputGP', 'CoregionalGP', 'LaplaceGP', 'EPGP',
-           'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'optimize', 'kernels', 'likelihoods', 'inference', 'learning',
+           'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'FourierSample', 'optimize', 'kernels', 'likelihoods', 'inference', 'learning',
            'batch', 'meta']

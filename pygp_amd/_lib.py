@@ -138,6 +138,11 @@ SIGNATURES = {
     'gpx_select_pivots': (C.c_int, [_vp, C.POINTER(_KSpec), _vp, _i64, _i64, _i64, C.c_double,
                                     _vp, _vp, _vp, C.POINTER(_i64)]),
     'gpx_select_timing': (C.c_int, [_vp, _vp]),
+    'gpx_fourier_fit': (C.c_int, [_vp, _vp, _i64, _i64, _vp, C.c_double, C.c_double, C.c_double,
+                                  _vp, _i64, _vp, _vp, _i64, _vp, _ip]),
+    'gpx_fourier_set': (C.c_int, [_vp, _vp, _i64, _i64, _vp, C.c_double, C.c_double, _vp, _i64]),
+    'gpx_fourier_eval': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    'gpx_fourier_timings': (C.c_int, [_vp, _vp]),
     'gpx_loglik_batch': (C.c_int, [_vp, C.POINTER(_KSpec), _vp, _i64, C.c_int,
                                    _vp, _vp, _vp]),
     'gpx_batch_plan': (C.c_int, [_vp, _i64, C.c_int, _ip]),
@@ -714,6 +719,58 @@ class Handle(object):
         ms = np.zeros(1)
         check(self._L.gpx_select_timing(self._h, _ptr(ms)))
         return float(ms[0])
+
+    # -- Fourier-feature function samples (a state of the handle's own) --
+    def fourier_fit(self, W, b, a, log_sn, mean, X, y, P):
+        """theta (S, M) of the S rows of P: the posterior weights given (X, y); X None: the
+        handle's resident data; X with no rows: theta = P."""
+        W, b, P = _f64(W, 2), _f64(b, 1), _f64(P, 2)
+        M, d = W.shape
+        if X is None:
+            n, y = -1, None
+        else:
+            X, y = _f64(X, 2), _f64(y, 1)
+            n = X.shape[0]
+            if n and X.shape[1] != d:
+                raise ValueError('X and W have different dimensions')
+        if b.shape[0] != M or P.shape[1] != M or (n > 0 and y.shape[0] != n):
+            raise ValueError('shapes of W, b, P, X and y do not agree')
+        theta = np.empty_like(P)
+        info = C.c_int(0)
+        check(self._L.gpx_fourier_fit(self._h, _ptr(W), M, d, _ptr(b), float(a), float(log_sn),
+                                      float(mean), _ptr(X), n, _ptr(y), _ptr(P), P.shape[0],
+                                      _ptr(theta), C.byref(info)))
+        self._fourier_shape = (P.shape[0], d)
+        return theta
+
+    def fourier_set(self, W, b, a, mean, theta):
+        W, b, theta = _f64(W, 2), _f64(b, 1), _f64(theta, 2)
+        M, d = W.shape
+        if b.shape[0] != M or theta.shape[1] != M:
+            raise ValueError('shapes of W, b and theta do not agree')
+        check(self._L.gpx_fourier_set(self._h, _ptr(W), M, d, _ptr(b), float(a), float(mean),
+                                      _ptr(theta), theta.shape[0]))
+        self._fourier_shape = (theta.shape[0], d)
+
+    def fourier_eval(self, Xs, grad=False):
+        """F (S, n), or (F, G) with G (S, n, d), of the installed sample at the rows of Xs."""
+        Xs = _f64(Xs, 2)
+        n, d = Xs.shape
+        S, dim = getattr(self, '_fourier_shape', (0, d))
+        if S == 0:
+            raise GpxError('fourier_eval: no sample (call fourier_fit or fourier_set)')
+        if d != dim:
+            raise ValueError('test inputs have the wrong dimension')
+        F = np.empty((S, n))
+        G = np.empty((S, n, d)) if grad else None
+        check(self._L.gpx_fourier_eval(self._h, _ptr(Xs), n, _ptr(F), _ptr(G)))
+        return (F, G) if grad else F
+
+    def fourier_timings(self):
+        """HIP-event ms of the last [fit, evaluation]."""
+        ms = np.zeros(2)
+        check(self._L.gpx_fourier_timings(self._h, _ptr(ms)))
+        return ms
 
     def sparse_get_state(self, p):
         F1, F2, v = np.empty((p, p)), np.empty((p, p)), np.empty(p)

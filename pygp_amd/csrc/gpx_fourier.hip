@@ -1,0 +1,148 @@
+// C ABI of libgpx.so, the wrappers of the Fourier-feature function samples (gpx_fourier_*):
+// argument checks around the entry points of fourier.hip, which owns its buffers and kernels.
+// The sample has a state of its own on the handle (GpxFourier): no call here touches the
+// resident data, an exact factorisation or a sparse model.
+
+#include "gpx_ctx.h"
+
+#include <cmath>
+
+using namespace gpxh;
+
+extern "C" {
+
+// the shape and the numbers of a sample, shared by gpx_fourier_fit and gpx_fourier_set
+static int fourier_check(const char *what, const double *W, int64_t M, int64_t d, const double *b,
+                         double a, double mean, int64_t S)
+{
+    if (!W || !b) {
+        gpx_set_error("%s: W and b must not be null", what);
+        return -1;
+    }
+    if (M < 1 || M > GPX_FOURIER_MAX_M || d < 1 || d > GPX_MAX_DIM) {
+        gpx_set_error("%s: bad shape M=%lld d=%lld (1 <= M <= %d, 1 <= d <= %d)", what,
+                      (long long)M, (long long)d, GPX_FOURIER_MAX_M, GPX_MAX_DIM);
+        return -1;
+    }
+    if (S < 1 || S > GPX_FOURIER_MAX_S) {
+        gpx_set_error("%s: need 1 <= S <= %d samples (got %lld)", what, GPX_FOURIER_MAX_S,
+                      (long long)S);
+        return -1;
+    }
+    if (!std::isfinite(a) || !std::isfinite(mean)) {
+        gpx_set_error("%s: non-finite a or mean", what);
+        return -1;
+    }
+    for (int64_t i = 0; i < M * d; ++i)
+        if (!std::isfinite(W[i])) {
+            gpx_set_error("%s: non-finite W", what);
+            return -1;
+        }
+    for (int64_t i = 0; i < M; ++i)
+        if (!std::isfinite(b[i])) {
+            gpx_set_error("%s: non-finite b", what);
+            return -1;
+        }
+    return 0;
+}
+
+static int fourier_finite(const char *what, const char *name, const double *v, int64_t count)
+{
+    for (int64_t i = 0; i < count; ++i)
+        if (!std::isfinite(v[i])) {
+            gpx_set_error("%s: non-finite %s", what, name);
+            return -1;
+        }
+    return 0;
+}
+
+int gpx_fourier_fit(gpx_t *h, const double *W, int64_t M, int64_t d, const double *b, double a,
+                    double log_sn, double mean, const double *X, int64_t n, const double *y,
+                    const double *P, int64_t S, double *theta, int *info)
+{
+    CHECK_H(h);
+    if (info) *info = 0;
+    GPX_TRY(fourier_check("gpx_fourier_fit", W, M, d, b, a, mean, S));
+    if (!P || !theta || !std::isfinite(log_sn)) {
+        gpx_set_error("gpx_fourier_fit: P and theta must not be null, log_sn finite");
+        return -1;
+    }
+    GPX_TRY(fourier_finite("gpx_fourier_fit", "P", P, S * M));
+    const double *Xdev = nullptr, *ydev = nullptr;
+    if (n != 0 && !X) {
+        GPX_TRY(require_state(h, ST_PLAIN, "gpx_fourier_fit"));
+        if (h->n <= 0) {
+            gpx_set_error("gpx_fourier_fit: X is null and the handle has no data (gpx_set_data)");
+            return -1;
+        }
+        if (h->d != d) {
+            gpx_set_error("gpx_fourier_fit: W has %lld columns, the resident data %d",
+                          (long long)d, h->d);
+            return -1;
+        }
+        n = h->n;
+        Xdev = h->X.as<double>();
+        ydev = h->y.as<double>();
+    } else if (n != 0) {
+        if (!y || n < 0) {
+            gpx_set_error("gpx_fourier_fit: bad arguments (y null or n < 0)");
+            return -1;
+        }
+    }
+    if (n > (1 << 20)) {
+        gpx_set_error("gpx_fourier_fit: n = %lld observations (at most 2^20)", (long long)n);
+        return -1;
+    }
+    const long long Mp = round_up(M, GPX_TILE), np = round_up(n, GPX_TILE);
+    if (Mp * np >= (1LL << 31)) {
+        gpx_set_error("gpx_fourier_fit: M_pad * N_pad = %lld x %lld must stay below 2^31", Mp, np);
+        return -1;
+    }
+    if (n != 0 && X) {
+        GPX_TRY(fourier_finite("gpx_fourier_fit", "X", X, n * d));
+        GPX_TRY(fourier_finite("gpx_fourier_fit", "y", y, n));
+    }
+    return gpx_fourier_run_fit(&h->fourier, h->stream, W, (int)M, (int)d, b, a, log_sn, mean, Xdev,
+                               ydev, X, y, (int)n, P, (int)S, theta, info);
+}
+
+int gpx_fourier_set(gpx_t *h, const double *W, int64_t M, int64_t d, const double *b, double a,
+                    double mean, const double *theta, int64_t S)
+{
+    CHECK_H(h);
+    GPX_TRY(fourier_check("gpx_fourier_set", W, M, d, b, a, mean, S));
+    if (!theta) {
+        gpx_set_error("gpx_fourier_set: theta is null");
+        return -1;
+    }
+    GPX_TRY(fourier_finite("gpx_fourier_set", "theta", theta, S * M));
+    return gpx_fourier_run_set(&h->fourier, h->stream, W, (int)M, (int)d, b, a, mean, theta,
+                               (int)S);
+}
+
+int gpx_fourier_eval(gpx_t *h, const double *Xs, int64_t n, double *F, double *G)
+{
+    CHECK_H(h);
+    if (!gpx_fourier_ready(h->fourier)) {
+        gpx_set_error("gpx_fourier_eval: no sample (call gpx_fourier_fit or gpx_fourier_set)");
+        return -1;
+    }
+    if (!Xs || !F || n < 1 || n > (1 << 20)) {
+        gpx_set_error("gpx_fourier_eval: bad arguments (1 <= n <= 2^20)");
+        return -1;
+    }
+    GPX_TRY(fourier_finite("gpx_fourier_eval", "Xs", Xs, n * gpx_fourier_dim(h->fourier)));
+    return gpx_fourier_run_eval(h->fourier, h->stream, Xs, n, F, G);
+}
+
+int gpx_fourier_timings(gpx_t *h, double *ms)
+{
+    CHECK_H(h);
+    if (!ms) {
+        gpx_set_error("gpx_fourier_timings: ms is null");
+        return -1;
+    }
+    return gpx_fourier_run_timings(h->fourier, ms);
+}
+
+}  // extern "C"

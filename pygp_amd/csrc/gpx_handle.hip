@@ -238,6 +238,10 @@ int gpx_destroy(gpx_t *h)
         gpx_select_destroy(h->select);
         h->select = nullptr;
     }
+    if (h->fourier) {
+        gpx_fourier_destroy(h->fourier);
+        h->fourier = nullptr;
+    }
     if (h->groups) {
         DLOG("groups");
         gpx_groups_destroy(h->groups);

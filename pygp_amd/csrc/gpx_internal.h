@@ -613,6 +613,27 @@ int gpx_select_run(GpxSelect **state, hipStream_t s, const KParams &kp, const do
 double gpx_select_ms(const GpxSelect *st);   // HIP-event ms of the last run's launches
 void gpx_select_destroy(GpxSelect *st);
 
+// ---- Fourier-feature function samples (fourier.hip) -------------------------------------
+// One sample set per handle, in buffers of its own: M features (W: M x d, b, the scale a), S
+// weight vectors theta (S x M) and the mean. *state is created on first use (per handle).
+// fit: theta_s = A^-1 Phi^T (y - mean) + sn R^-1 p_s for the S rows of P on n observations at
+// Xdev / ydev (device) or, Xdev null, copies of Xhost / yhost; n == 0: theta = P. Returns the
+// pivot (> 0, also in *info) when A = sn2 I + Phi^T Phi is not positive definite.
+struct GpxFourier;
+int gpx_fourier_run_fit(GpxFourier **state, hipStream_t s, const double *W, int M, int d,
+                        const double *b, double a, double log_sn, double mean, const double *Xdev,
+                        const double *ydev, const double *Xhost, const double *yhost, int n,
+                        const double *P, int S, double *theta, int *info);
+int gpx_fourier_run_set(GpxFourier **state, hipStream_t s, const double *W, int M, int d,
+                        const double *b, double a, double mean, const double *theta, int S);
+bool gpx_fourier_ready(const GpxFourier *st);
+int gpx_fourier_dim(const GpxFourier *st);
+// F[S][n] and G[S][n][d] (or null) at the n host points Xs
+int gpx_fourier_run_eval(GpxFourier *st, hipStream_t s, const double *Xs, int64_t n, double *F,
+                         double *G);
+int gpx_fourier_run_timings(const GpxFourier *st, double *ms);
+void gpx_fourier_destroy(GpxFourier *st);
+
 // d k / d x2 (sign = +1) or d k / d x1 (sign = -1): out[n1][n2][d]
 int gpx_kgrady(hipStream_t s, const KParams &kp, const double *X1, int n1, const double *X2,
                int n2, int d, double sign, double *out);

@@ -9,6 +9,7 @@ from .fitc import FITC
 from .dtc import DTC
 from .vfe import VFE
 from .select import select_pseudoinputs
+from .fourier import FourierSample
 
 __all__ = ['GP', 'ExactGP', 'BasicGP', 'GradientGP', 'MultiOutputGP', 'CoregionalGP', 'LaplaceGP',
-           'EPGP', 'FITC', 'DTC', 'VFE', 'select_pseudoinputs']
+           'EPGP', 'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'FourierSample']

@@ -15,7 +15,16 @@ from ._base import RealKernel
 from ..utils.models import printable
 from .. import _lib
 
-__all__ = ['SE', 'Matern', 'Periodic', 'RQ']
+__all__ = ['SE', 'Matern', 'Periodic', 'RQ', 'rstate']
+
+
+def rstate(rng=None):
+    """None -> NumPy's global state, an int seed or a RandomState (as GP.sample takes it)."""
+    if rng is None:
+        return np.random.mtrand._rand
+    if isinstance(rng, np.random.RandomState):
+        return rng
+    return np.random.RandomState(rng)
 
 
 class _ARDKernel(RealKernel):
@@ -65,6 +74,12 @@ class SE(_ARDKernel):
         return _lib.KSpecHolder(_lib.KIND_SE, self._iso, self.ndim,
                                 self.get_hyper())
 
+    def sample_spectrum(self, N, rng=None):
+        """(W, sf^2): N frequencies (N, ndim) drawn from the spectral density, a Gaussian of
+        scale 1 / ell (se.py:101-106; host arithmetic, the reference's draws in its order)."""
+        normal = rstate(rng).randn(N, self.ndim)
+        return normal / np.exp(self._logell), np.exp(self._logsf * 2)
+
 
 @printable
 class Matern(_ARDKernel):
@@ -79,6 +94,16 @@ class Matern(_ARDKernel):
     def _kspec(self):
         return _lib.KSpecHolder(_lib.KIND_MATERN[self._d], self._iso, self.ndim,
                                 self.get_hyper())
+
+    def sample_spectrum(self, N, rng=None):
+        """(W, sf^2): N frequencies (N, ndim) drawn from the spectral density, a Student-t with
+        d degrees of freedom as a Gaussian scale mixture: the gamma draws first, then the normal
+        ones (matern.py:119-126; host arithmetic, the reference's draws in its order)."""
+        rng = rstate(rng)
+        nu = self._d / 2.
+        mix = rng.gamma(nu, 1 / nu, N)
+        normal = rng.randn(N, self.ndim)
+        return normal / np.exp(self._logell) / np.sqrt(mix)[:, None], np.exp(self._logsf * 2)
 
     def _check_gradxy(self):
         if self._d == 1:
