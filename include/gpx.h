@@ -514,6 +514,39 @@ int gpx_fourier_eval(gpx_t *h, const double *Xs, int64_t n, double *F, double *G
  * gpx_fourier_eval (ms[1]) on this handle (0: none) */
 int gpx_fourier_timings(gpx_t *h, double *ms);
 
+/* ---- sparse-spectrum GP regression on those features (own design) --------- */
+/* The regression model of the features above, f(x) = mean + a sum_j cos(w_j.x + b_j) theta_j with
+ * theta ~ N(0, I), on the handle's resident data (gpx_set_data), as gpx_fourier_fit(X == NULL)
+ * reads them. With r = y - mean, A = Phi^T Phi + sn^2 I = R^T R, beta = A^-1 Phi^T r and
+ * e = r - Phi beta:
+ *   lZ = -e.e / (2 sn^2) - beta.beta / 2 - sum_j log R_jj + (M - n) log sn - (n / 2) log 2 pi.
+ * gpx_ssgp_update forms all of that (one host synchronisation) and returns lZ; a non-positive
+ * pivot of A returns > 0, also in *info. Limits: those of gpx_fourier_fit. The model lives in a
+ * state of its own: no gpx_ssgp_* call touches the resident data, an exact factorisation, a
+ * sparse model or a Fourier sample of the handle; after gpx_set_data the entries below ask for
+ * a new update. Every sum has a fixed order: the same call returns the same bits. */
+int gpx_ssgp_update(gpx_t *h, const double *W, int64_t M, int64_t d, const double *b, double a,
+                    double log_sn, double mean, double *lZ, int *info);
+/* lZ of the last update. dlZ3 != NULL: also dlZ3[3] = d lZ / d (log sn, log sf, mean) with
+ * a = sqrt(2 sf^2 / M), and with D = d lZ / d W (M x d): dW_W[d], dW_W[c] = -sum_j D_jc W_jc
+ * (d lZ / d log ell_c when W_jc = S_jc / ell_c); dW[M*d] = D and db[M] = d lZ / d b, each or
+ * NULL */
+int gpx_ssgp_loglik(gpx_t *h, double *lZ, double *dlZ3, double *dW_W, double *dW, double *db);
+/* the posterior of f at m test points, 1 <= m <= 2^20: mu[m], s2[m] = sn^2 phi*^T A^-1 phi*;
+ * dmu, ds2 [m*d] (both or neither): their input gradients. A point's results do not depend on
+ * the other points of the call. */
+int gpx_ssgp_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2, double *dmu,
+                       double *ds2);
+/* mu[m], Sigma[m][m] = sn^2 Phi* A^-1 Phi*^T, 1 <= m <= 8192 */
+int gpx_ssgp_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma);
+/* beta[M], the posterior mean of the weights */
+int gpx_ssgp_get(gpx_t *h, double *beta);
+/* HIP-event ms[7] of the last calls on this handle: ms[0..2] the update's panel, Gram matrix
+ * with v, and factorisation; ms[3] the product A^-1 Phi^T and ms[4] the contraction of the last
+ * gpx_ssgp_loglik with dlZ3 (0: none since the update); ms[5] the last gpx_ssgp_posterior;
+ * ms[6] A^-1 with its trace, when a gpx_ssgp_loglik formed it (0: none, or a posterior did) */
+int gpx_ssgp_timings(gpx_t *h, double *ms);
+
 /* ---- instrumentation ---------------------------------------------------- */
 /* per-stage GPU times (ms) of the last gpx_exact_eval / update+loglik measured
  * with HIP events on the handle's stream. names via gpx_timing_name(i). */

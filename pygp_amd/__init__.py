@@ -6,7 +6,7 @@ Only the path named in BASELINE.json is here: pairwise kernel evaluation
 log-likelihood (+gradient) / posterior, the sparse FITC / DTC / VFE models and binary
 classification by Laplace's approximation (LaplaceGP) and by expectation propagation (EPGP),
 correlated outputs at their own inputs (CoregionalGP) and posterior function samples through
-random Fourier features (FourierSample), executed by hand-written HIP kernels in libgpx.so; `batch` and `meta` route the
+random Fourier features (FourierSample) with their regression model (SSGP), executed by hand-written HIP kernels in libgpx.so; `batch` and `meta` route the
 per-sample loops of the reference's meta-models through the batched entry points.
 """
 
@@ -17,9 +17,9 @@ from . import learning
 from . import batch
 from . import meta
 from .inference import (BasicGP, ExactGP, GradientGP, MultiOutputGP, CoregionalGP, LaplaceGP,
-                        EPGP, FITC, DTC, VFE, select_pseudoinputs, FourierSample)
+                        EPGP, FITC, DTC, VFE, select_pseudoinputs, FourierSample, SSGP)
 from .learning import optimize
 
 __all__ = ['BasicGP', 'ExactGP', 'GradientGP', 'MultiOutputGP', 'CoregionalGP', 'LaplaceGP', 'EPGP',
-           'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'FourierSample', 'optimize', 'kernels', 'likelihoods', 'inference', 'learning',
+           'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'FourierSample', 'SSGP', 'optimize', 'kernels', 'likelihoods', 'inference', 'learning',
            'batch', 'meta']

@@ -143,6 +143,13 @@ SIGNATURES = {
     'gpx_fourier_set': (C.c_int, [_vp, _vp, _i64, _i64, _vp, C.c_double, C.c_double, _vp, _i64]),
     'gpx_fourier_eval': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     'gpx_fourier_timings': (C.c_int, [_vp, _vp]),
+    'gpx_ssgp_update': (C.c_int, [_vp, _vp, _i64, _i64, _vp, C.c_double, C.c_double, C.c_double,
+                                  _dp, _ip]),
+    'gpx_ssgp_loglik': (C.c_int, [_vp, _dp, _vp, _vp, _vp, _vp]),
+    'gpx_ssgp_posterior': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    'gpx_ssgp_posterior_full': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    'gpx_ssgp_get': (C.c_int, [_vp, _vp]),
+    'gpx_ssgp_timings': (C.c_int, [_vp, _vp]),
     'gpx_loglik_batch': (C.c_int, [_vp, C.POINTER(_KSpec), _vp, _i64, C.c_int,
                                    _vp, _vp, _vp]),
     'gpx_batch_plan': (C.c_int, [_vp, _i64, C.c_int, _ip]),
@@ -770,6 +777,74 @@ class Handle(object):
         """HIP-event ms of the last [fit, evaluation]."""
         ms = np.zeros(2)
         check(self._L.gpx_fourier_timings(self._h, _ptr(ms)))
+        return ms
+
+    # -- sparse-spectrum GP on the resident data (a state of the handle's own) --
+    _ssgp_shape = (0, 0)        # (M, d) of the last ssgp_update of this handle
+    def ssgp_update(self, W, b, a, log_sn, mean):
+        """Factor the feature model of the resident data; returns lZ."""
+        W, b = _f64(W, 2), _f64(b, 1)
+        M, d = W.shape
+        if b.shape[0] != M:
+            raise ValueError('shapes of W and b do not agree')
+        lZ, info = C.c_double(0), C.c_int(0)
+        check(self._L.gpx_ssgp_update(self._h, _ptr(W), M, d, _ptr(b), float(a), float(log_sn),
+                                      float(mean), C.byref(lZ), C.byref(info)))
+        self._ssgp_shape = (M, d)
+        return lZ.value
+
+    def ssgp_loglik(self, grad=False, spectrum=False):
+        """lZ; with grad (lZ, dlZ3, dW_W): d lZ / d (log sn, log sf, mean) and -sum_j D_jc W_jc
+        per column c; with spectrum also D = d lZ / d W (M, d) and d lZ / d b (M)."""
+        lZ = C.c_double(0)
+        if not (grad or spectrum):
+            check(self._L.gpx_ssgp_loglik(self._h, C.byref(lZ), None, None, None, None))
+            return lZ.value
+        M, d = self._ssgp_shape
+        if M == 0:
+            raise GpxError('ssgp_loglik: no model (call ssgp_update)')
+        dlZ3, dW_W = np.empty(3), np.empty(d)
+        dW, db = (np.empty((M, d)), np.empty(M)) if spectrum else (None, None)
+        check(self._L.gpx_ssgp_loglik(self._h, C.byref(lZ), _ptr(dlZ3), _ptr(dW_W), _ptr(dW),
+                                      _ptr(db)))
+        return (lZ.value, dlZ3, dW_W, dW, db) if spectrum else (lZ.value, dlZ3, dW_W)
+
+    def _ssgp_points(self, Xs):
+        """Xs as the entries read it: m rows of the model's width."""
+        Xs = _f64(Xs, 2)
+        if self._ssgp_shape[0] == 0:
+            raise GpxError('no sparse-spectrum model (call ssgp_update)')
+        if Xs.shape[1] != self._ssgp_shape[1]:
+            raise ValueError('test inputs have the wrong dimension')
+        return Xs
+
+    def ssgp_posterior(self, Xs, grad=False):
+        Xs = self._ssgp_points(Xs)
+        m, d = Xs.shape
+        mu, s2 = np.empty(m), np.empty(m)
+        dmu, ds2 = (np.empty((m, d)), np.empty((m, d))) if grad else (None, None)
+        if m:
+            check(self._L.gpx_ssgp_posterior(self._h, _ptr(Xs), m, _ptr(mu), _ptr(s2), _ptr(dmu),
+                                             _ptr(ds2)))
+        return (mu, s2, dmu, ds2) if grad else (mu, s2)
+
+    def ssgp_posterior_full(self, Xs):
+        return self._posterior(self._L.gpx_ssgp_posterior_full, self._ssgp_points(Xs), True)
+
+    def ssgp_get(self):
+        """beta (M,), the posterior mean of the weights."""
+        M = self._ssgp_shape[0]
+        if M == 0:
+            raise GpxError('ssgp_get: no model (call ssgp_update)')
+        beta = np.empty(M)
+        check(self._L.gpx_ssgp_get(self._h, _ptr(beta)))
+        return beta
+
+    def ssgp_timings(self):
+        """HIP-event ms of the last [panel, Gram, factorisation, A^-1 Phi^T, contraction,
+        posterior, A^-1]."""
+        ms = np.zeros(7)
+        check(self._L.gpx_ssgp_timings(self._h, _ptr(ms)))
         return ms
 
     def sparse_get_state(self, p):

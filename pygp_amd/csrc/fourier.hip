@@ -8,6 +8,8 @@
 //   F[s][i] = mean + a sum_j cos(z_ij) theta_sj,  G[s][i][c] = -a sum_j sin(z_ij) theta_sj w_jc.
 // Every sum has a fixed order (per lane, waves in order, slabs in order): the same call gives
 // the same bits. Arguments of cos / sincos are not small: the full-range fp64 functions.
+// The second half of the file is the regression model of the same features, the
+// sparse-spectrum GP: it shares the fit's launches and the evaluation.
 #include "kmat_dev.h"
 #include <cmath>
 #include <cstring>
@@ -511,6 +513,77 @@ static int fr_gram(GpxFourier *st, hipStream_t s, int np, double sn2)
     return 0;
 }
 
+// ---- the launches of a fit, shared with the sparse-spectrum model below ----------------------
+// the buffers of a fit of the installed features to n observations
+static int fr_fit_reserve(GpxFourier *st, hipStream_t s, int n)
+{
+    const int Mp = st->Mp, np = round_up(n, GPX_TILE);
+    const size_t mat = (size_t)Mp * st->ldp * 8;
+    GPX_TRY(st->Phi.reserve((size_t)Mp * np * 8));
+    GPX_TRY(st->A.reserve(mat));
+    GPX_TRY(st->Aw.reserve(mat));
+    GPX_TRY(st->Ak.reserve(mat));
+    GPX_TRY(st->v.reserve((size_t)Mp * 8));
+    GPX_TRY(st->t.reserve((size_t)Mp * 8));
+    GPX_TRY(st->P.reserve((size_t)st->S * st->M * 8));
+    if (!st->pctl.p) {
+        GPX_TRY(st->info.reserve(64));
+        GPX_TRY(st->pctl.reserve(gpx_panel_ctl_bytes()));
+        GPX_HIP(hipMemsetAsync(st->pctl.p, 0, gpx_panel_ctl_bytes(), s));
+    }
+    return 0;
+}
+
+static DenseWs fr_ws(GpxFourier *st)
+{
+    DenseWs w;
+    w.A = st->A.d();
+    w.W = st->Aw.d();
+    w.Kinv = st->Ak.d();
+    w.np = st->Mp;
+    w.ld = st->ldp;
+    w.info = st->info.as<int>();
+    w.pctl = st->pctl.as<int>();
+    w.gate_total = st->gates;
+    return w;
+}
+
+// The panel, A and v = Phi^T (y - mean), then A = R^T R with W = R^-1 and the pivot in
+// st->info: enqueued, nothing waited for. marks (or null): three events, recorded behind the
+// panel, behind A and v, and behind the factorisation.
+static int fr_fit_factor(GpxFourier *st, hipStream_t s, const double *X, const double *y, int n,
+                         double sn2, hipEvent_t *marks)
+{
+    const int M = st->M, Mp = st->Mp, d = st->d, np = round_up(n, GPX_TILE);
+    GPX_TRY(fr_with_width(d, [&](auto w) {
+        GPX_LAUNCH(fr_panel_kernel<decltype(w)::value>, dim3((np + FR_T - 1) / FR_T, Mp / FR_FT),
+                   dim3(FR_T), 0, s, X, n, np, d, st->W.d(), st->b.d(), M, st->a, st->Phi.d());
+        return 0;
+    }));
+    if (marks) GPX_HIP(hipEventRecord(marks[0], s));
+    GPX_TRY(fr_gram(st, s, np, sn2));
+    GPX_LAUNCH(fr_gemv_rows_kernel, dim3(Mp), dim3(FR_T), 0, s, st->Phi.d(), np, n, y, st->mean,
+               st->v.d());
+    if (marks) GPX_HIP(hipEventRecord(marks[1], s));
+    DenseWs w = fr_ws(st);
+    GPX_HIP(hipMemsetAsync(w.info, 0, sizeof(int), s));
+    w.whole = gpx_potrf_whole(w, GPX_POTRF_W);
+    GPX_TRY(gpx_potrf(s, w, GPX_POTRF_W, false));
+    if (marks) GPX_HIP(hipEventRecord(marks[2], s));
+    return 0;
+}
+
+// theta_s = W (W^T v + sn p_s) for the S rows of st->P, and its coefficient matrix
+static int fr_fit_theta(GpxFourier *st, hipStream_t s, double sn)
+{
+    const int M = st->M, ldp = st->ldp;
+    GPX_LAUNCH(fr_wt_v_kernel, dim3((M + FR_T - 1) / FR_T), dim3(FR_T), 0, s, st->Aw.d(), ldp, M,
+               st->v.d(), st->t.d());
+    GPX_LAUNCH(fr_theta_kernel, dim3(M, st->S), dim3(FR_T), 0, s, st->Aw.d(), ldp, M, st->t.d(),
+               st->P.d(), sn, st->theta.d());
+    return fr_build_coef(st, s);
+}
+
 // Xdev, ydev: the handle's resident data (device), or null: Xhost, yhost are copied to the
 // state's own buffers. n == 0: theta = P. Returns the pivot (> 0, also in *info) when A is
 // not positive definite.
@@ -534,20 +607,7 @@ int gpx_fourier_run_fit(GpxFourier **state, hipStream_t s, const double *W, int 
         return 0;
     }
     GPX_TRY(fr_install(st, s, W, M, d, b, a, mean, nullptr, S));
-    const int Mp = st->Mp, ldp = st->ldp, np = round_up(n, GPX_TILE);
-    const size_t mat = (size_t)Mp * ldp * 8;
-    GPX_TRY(st->Phi.reserve((size_t)Mp * np * 8));
-    GPX_TRY(st->A.reserve(mat));
-    GPX_TRY(st->Aw.reserve(mat));
-    GPX_TRY(st->Ak.reserve(mat));
-    GPX_TRY(st->v.reserve((size_t)Mp * 8));
-    GPX_TRY(st->t.reserve((size_t)Mp * 8));
-    GPX_TRY(st->P.reserve((size_t)S * M * 8));
-    if (!st->pctl.p) {
-        GPX_TRY(st->info.reserve(64));
-        GPX_TRY(st->pctl.reserve(gpx_panel_ctl_bytes()));
-        GPX_HIP(hipMemsetAsync(st->pctl.p, 0, gpx_panel_ctl_bytes(), s));
-    }
+    GPX_TRY(fr_fit_reserve(st, s, n));
     const double *X = Xdev, *y = ydev;
     if (!X) {
         GPX_TRY(st->X.reserve((size_t)n * d * 8));
@@ -560,39 +620,16 @@ int gpx_fourier_run_fit(GpxFourier **state, hipStream_t s, const double *W, int 
     GPX_HIP(hipMemcpyAsync(st->P.p, P, (size_t)S * M * 8, hipMemcpyHostToDevice, s));
     const double sn = exp(log_sn), sn2 = exp(2 * log_sn);            // gaussian.py
     GPX_TRY(fr_event(st, s, 0));
-    GPX_TRY(fr_with_width(d, [&](auto w) {
-        GPX_LAUNCH(fr_panel_kernel<decltype(w)::value>, dim3((np + FR_T - 1) / FR_T, Mp / FR_FT),
-                   dim3(FR_T), 0, s, X, n, np, d, st->W.d(), st->b.d(), M, a, st->Phi.d());
-        return 0;
-    }));
-    GPX_TRY(fr_gram(st, s, np, sn2));
-    GPX_LAUNCH(fr_gemv_rows_kernel, dim3(Mp), dim3(FR_T), 0, s, st->Phi.d(), np, n, y, mean,
-               st->v.d());
-    DenseWs w;
-    w.A = st->A.d();
-    w.W = st->Aw.d();
-    w.Kinv = st->Ak.d();
-    w.np = Mp;
-    w.ld = ldp;
-    w.info = st->info.as<int>();
-    w.pctl = st->pctl.as<int>();
-    w.gate_total = st->gates;
-    GPX_HIP(hipMemsetAsync(w.info, 0, sizeof(int), s));
-    w.whole = gpx_potrf_whole(w, GPX_POTRF_W);
-    GPX_TRY(gpx_potrf(s, w, GPX_POTRF_W, false));
+    GPX_TRY(fr_fit_factor(st, s, X, y, n, sn2, nullptr));
     int inf = 0;
-    GPX_HIP(hipMemcpyAsync(&inf, w.info, sizeof(int), hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipMemcpyAsync(&inf, st->info.p, sizeof(int), hipMemcpyDeviceToHost, s));
     GPX_HIP(hipStreamSynchronize(s));
     if (inf) {
         gpx_set_error("gpx_fourier_fit: matrix is not positive definite: pivot %d", inf);
         if (info) *info = inf;
         return inf;
     }
-    GPX_LAUNCH(fr_wt_v_kernel, dim3((M + FR_T - 1) / FR_T), dim3(FR_T), 0, s, st->Aw.d(), ldp, M,
-               st->v.d(), st->t.d());
-    GPX_LAUNCH(fr_theta_kernel, dim3(M, S), dim3(FR_T), 0, s, st->Aw.d(), ldp, M, st->t.d(),
-               st->P.d(), sn, st->theta.d());
-    GPX_TRY(fr_build_coef(st, s));
+    GPX_TRY(fr_fit_theta(st, s, sn));
     GPX_TRY(fr_event(st, s, 1));
     GPX_HIP(hipMemcpyAsync(theta, st->theta.p, (size_t)S * M * 8, hipMemcpyDeviceToHost, s));
     GPX_HIP(hipStreamSynchronize(s));
@@ -723,5 +760,531 @@ int gpx_fourier_run_timings(const GpxFourier *st, double *ms)
 {
     ms[0] = st ? st->ms[0] : 0.0;
     ms[1] = st ? st->ms[1] : 0.0;
+    return 0;
+}
+
+// ==== the sparse-spectrum GP ===========================================
+// The regression model of the same features, theta ~ N(0, I): with r = y - mean, A = Phi^T Phi +
+// sn2 I = R^T R, v = Phi^T r, beta = A^-1 v and e = r - Phi beta,
+//   lZ = -e.e / (2 sn2) - beta.beta / 2 - sum_j log R_jj + (M - N) log sn - (N / 2) log 2 pi.
+// The update is the fit above with P = 0 (theta = beta, S = 1) on the handle's resident data,
+// kept in a GpxFourier of the model's own; the residual, the likelihood terms, the gradient and
+// the posterior variance are the kernels here. Every sum has a fixed order.
+#define SS_CT 64              // columns of one staged tile of the contraction
+#define SS_PASS 8192          // test points of one pass of the posterior
+enum { SS_EE = 0, SS_E, SS_BB, SS_LOGR, SS_TRINV, SS_NSC };
+enum { SE_START = 0, SE_PANEL, SE_GRAM, SE_FACTOR, SE_G0, SE_INV, SE_PROD, SE_CONTRACT, SE_P0,
+       SE_P1, SE_COUNT };
+
+struct GpxSsgp {
+    GpxFourier f;             // features, panel, factorisation and beta (f.theta, S = 1)
+    int n = 0, np = 0;
+    long version = -1;        // of the resident data the update read
+    double log_sn = 0, sn2 = 0;
+    bool ready = false, have_inverse = false;
+    double sc[SS_NSC] = {};
+    // e (np), the scalars, B = A^-1 Phi^T (Mp x np), slabs and results of the contraction
+    DevBuf e, scal, B, slab, Dw, db, dww;
+    // a pass of the posterior: test points, their panel, T = A^-1 Phi* or V = W^T Phi*, results
+    DevBuf Xs, PhiS, T, s2, ds2, Sig;
+    hipEvent_t ev[SE_COUNT] = {};
+    double ms[7] = {0, 0, 0, 0, 0, 0, 0};
+};
+
+// e_i = y_i - mean - sum_j Phi^T[j][i] beta_j, zero in the padding: one lane per column, beta
+// as LDS broadcast
+__global__ __launch_bounds__(FR_T) void ss_resid_kernel(const double *__restrict__ Phi, int np,
+                                                       int n, int M, const double *__restrict__ y,
+                                                       double mean, const double *__restrict__ beta,
+                                                       double *__restrict__ e)
+{
+    __shared__ double b_s[FR_T];
+    const int i = blockIdx.x * FR_T + threadIdx.x;
+    double s = 0.0;
+    for (int j0 = 0; j0 < M; j0 += FR_T) {
+        __syncthreads();
+        b_s[threadIdx.x] = j0 + threadIdx.x < M ? beta[j0 + threadIdx.x] : 0.0;
+        __syncthreads();
+        const int jn = min(FR_T, M - j0);
+        if (i < n)
+            for (int r = 0; r < jn; ++r) s = fma(Phi[(size_t)(j0 + r) * np + i], b_s[r], s);
+    }
+    if (i < np) e[i] = i < n ? (y[i] - mean) - s : 0.0;
+}
+
+// out[q], q = first + blockIdx.x: e.e, sum e, beta.beta, sum_j log R_jj, tr A^-1 (SS_*)
+__global__ __launch_bounds__(FR_T) void ss_terms_kernel(const double *__restrict__ e, int n,
+                                                       const double *__restrict__ beta, int M,
+                                                       const double *__restrict__ R,
+                                                       const double *__restrict__ Ainv, int ld,
+                                                       int first, double *__restrict__ out)
+{
+    __shared__ double red[FR_T];
+    const int q = first + blockIdx.x;
+    const int count = q <= SS_E ? n : M;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < count; i += FR_T) {
+        double v;
+        if (q == SS_EE)
+            v = e[i] * e[i];
+        else if (q == SS_E)
+            v = e[i];
+        else if (q == SS_BB)
+            v = beta[i] * beta[i];
+        else if (q == SS_LOGR)
+            v = log(R[(size_t)i * ld + i]);
+        else
+            v = Ainv[(size_t)i * ld + i];
+        s += v;
+    }
+    s = fr_block_sum(s, red);
+    if (threadIdx.x == 0) out[q] = s;
+}
+
+// the lower triangle of A^-1 from the upper one gpx_lauum leaves
+__global__ __launch_bounds__(FR_T) void ss_mirror_kernel(double *__restrict__ A, int ld, int Mp)
+{
+    const int j = blockIdx.x * FR_T + threadIdx.x, i = blockIdx.y;
+    if (j < i && i < Mp) A[(size_t)i * ld + j] = A[(size_t)j * ld + i];
+}
+
+// ---- the gradient's contraction ---------------------------------------------------------------
+// fr_eval_kernel's mirror: a lane owns feature j = 64 blockIdx.x + lane, keeps w_j (D values),
+// b_j, beta_j / sn2 and its 1 + D sums in registers and walks the columns i of slab blockIdx.y,
+//   g = (beta_j e_i / sn2 - B[j][i]) sin z_ij,   db_j += g,   D_jc += g x_ic,
+// the factor -a behind the sums; G^T = beta e^T / sn2 - B is never stored. x_i and e_i arrive as
+// LDS broadcasts and the 64 x SS_CT tile of B through LDS, read along i. The four waves take 16
+// columns of a tile each and add their sums in wave order; ss_reduce_kernel adds the slabs in
+// order. Columns >= n and features >= M carry e = B = 0 and contribute exact zeros.
+template <int D>
+__global__ __launch_bounds__(FR_T) void ss_contract_kernel(
+    const double *__restrict__ X, int n, int np, int d, const double *__restrict__ W,
+    const double *__restrict__ b, const double *__restrict__ beta, int M, int Mp,
+    const double *__restrict__ e, const double *__restrict__ B, double a, double inv_sn2, int cols,
+    double *__restrict__ slab)
+{
+    constexpr int NA = 1 + D;
+    static_assert(NA + 1 <= SS_CT + 1, "the waves' sums reuse the tile of B");
+    __shared__ double x_s[SS_CT][D];
+    __shared__ double e_s[SS_CT];
+    __shared__ double bt[FR_FT][SS_CT + 1];
+    const int tid = threadIdx.x, lane = tid & 63, ig = tid >> 6;
+    const int j0 = blockIdx.x * FR_FT, j = j0 + lane;
+    const int i_lo = blockIdx.y * cols, i_hi = min(np, i_lo + cols);
+    double w[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) w[c] = (j < M && c < d) ? W[(size_t)j * d + c] : 0.0;
+    const double bj = j < M ? b[j] : 0.0;
+    const double be = j < M ? beta[j] * inv_sn2 : 0.0;
+    double acc[NA];
+#pragma unroll
+    for (int k = 0; k < NA; ++k) acc[k] = 0.0;
+    for (int i0 = i_lo; i0 < i_hi; i0 += SS_CT) {
+        __syncthreads();
+        for (int q = tid; q < SS_CT * D; q += FR_T) {
+            const int r = q / D, c = q - r * D;
+            x_s[r][c] = (i0 + r < n && c < d) ? X[(size_t)(i0 + r) * d + c] : 0.0;
+        }
+        if (tid < SS_CT) e_s[tid] = e[i0 + tid];
+        for (int q = tid; q < FR_FT * SS_CT; q += FR_T) {
+            const int r = q / SS_CT, c = q - r * SS_CT;
+            bt[r][c] = B[(size_t)(j0 + r) * np + i0 + c];
+        }
+        __syncthreads();
+        for (int rr = 0; rr < SS_CT / 4; ++rr) {
+            const int cc = ig * (SS_CT / 4) + rr;
+            double z = 0.0;
+#pragma unroll
+            for (int c = 0; c < D; ++c) z = fma(x_s[cc][c], w[c], z);
+            const double g = (be * e_s[cc] - bt[lane][cc]) * sin(z + bj);
+            acc[0] += g;
+#pragma unroll
+            for (int c = 0; c < D; ++c) acc[1 + c] = fma(g, x_s[cc][c], acc[1 + c]);
+        }
+    }
+    // the waves' sums in wave order, in the storage of the tile
+    double(*red)[NA + 1] = reinterpret_cast<double(*)[NA + 1]>(&bt[0][0]);
+    for (int wv = 0; wv < 4; ++wv) {
+        __syncthreads();
+        if (ig == wv) {
+#pragma unroll
+            for (int k = 0; k < NA; ++k) red[lane][k] = wv == 0 ? acc[k] : red[lane][k] + acc[k];
+        }
+    }
+    __syncthreads();
+    for (int q = tid; q < FR_FT * (1 + d); q += FR_T) {
+        const int ft = q % FR_FT, k = q / FR_FT;
+        slab[((size_t)blockIdx.y * (1 + d) + k) * Mp + j0 + ft] = -a * red[ft][k];
+    }
+}
+
+// the slabs in order: db[j] (k == 0) and D[j][k - 1]
+__global__ __launch_bounds__(FR_T) void ss_reduce_kernel(const double *__restrict__ slab, int C,
+                                                        int d, int M, int Mp,
+                                                        double *__restrict__ db,
+                                                        double *__restrict__ Dw)
+{
+    const int q = blockIdx.x * FR_T + threadIdx.x;
+    if (q >= (1 + d) * M) return;
+    const int k = q / M, j = q - k * M;
+    double sum = 0.0;
+    for (int c0 = 0; c0 < C; ++c0) sum += slab[((size_t)c0 * (1 + d) + k) * Mp + j];
+    if (k == 0)
+        db[j] = sum;
+    else
+        Dw[(size_t)j * d + (k - 1)] = sum;
+}
+
+// out[c] = -sum_j D[j][c] W[j][c], one block per column c
+__global__ __launch_bounds__(FR_T) void ss_dot_w_kernel(const double *__restrict__ Dw,
+                                                       const double *__restrict__ W, int M, int d,
+                                                       double *__restrict__ out)
+{
+    __shared__ double red[FR_T];
+    const int c = blockIdx.x;
+    double s = 0.0;
+    for (int j = threadIdx.x; j < M; j += FR_T) s += Dw[(size_t)j * d + c] * W[(size_t)j * d + c];
+    s = fr_block_sum(s, red);
+    if (threadIdx.x == 0) out[c] = -s;
+}
+
+// ---- the posterior variance -------------------------------------------------------------------
+// fr_eval_kernel<D, 1, GRAD> with the coefficient of feature j read per point from T[j][i] =
+// (A^-1 Phi*)_ji, along i, instead of theta_j:
+//   s2_i = sn2 a sum_j cos(z_ij) T_ji,   ds2_ic = -2 sn2 a sum_j sin(z_ij) w_jc T_ji.
+// One workgroup walks every feature of its 64 points, so a point's sums are those of its own
+// column whatever the pass holds.
+template <int D, bool GRAD>
+__global__ __launch_bounds__(FR_T) void ss_var_kernel(
+    const double *__restrict__ Xs, int m, int d, const double *__restrict__ W,
+    const double *__restrict__ b, const double *__restrict__ T, int ldt, int M, double a,
+    double sn2, double *__restrict__ s2, double *__restrict__ ds2)
+{
+    constexpr int NA = GRAD ? 1 + D : 1;
+    __shared__ double w_s[FR_FT][D];
+    __shared__ double b_s[FR_FT];
+    __shared__ double red[FR_PT][NA + 1];
+    const int tid = threadIdx.x, lane = tid & 63, ig = tid >> 6;
+    const int i = blockIdx.x * FR_PT + lane;            // < ldt = round_up(m, 128)
+    const int nt = (M + FR_FT - 1) / FR_FT;
+    double x[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) x[c] = (i < m && c < d) ? Xs[(size_t)i * d + c] : 0.0;
+    double acc[NA];
+#pragma unroll
+    for (int k = 0; k < NA; ++k) acc[k] = 0.0;
+    for (int bt = 0; bt < nt; ++bt) {
+        const int j0 = bt * FR_FT;
+        __syncthreads();
+        for (int q = tid; q < FR_FT * D; q += FR_T) {
+            const int r = q / D, c = q - r * D;
+            w_s[r][c] = (j0 + r < M && c < d) ? W[(size_t)(j0 + r) * d + c] : 0.0;
+        }
+        if (tid < FR_FT) b_s[tid] = j0 + tid < M ? b[j0 + tid] : 0.0;
+        __syncthreads();
+        for (int rr = 0; rr < 16; ++rr) {
+            const int r = ig * 16 + rr;
+            const double th = T[(size_t)(j0 + r) * ldt + i];       // rows < round_up(M, 64) <= Mp
+            double z = 0.0;
+#pragma unroll
+            for (int c = 0; c < D; ++c) z = fma(x[c], w_s[r][c], z);
+            z += b_s[r];
+            if (GRAD) {
+                double sn, cs;
+                sincos(z, &sn, &cs);
+                acc[0] = fma(cs, th, acc[0]);
+                const double u = sn * th;
+#pragma unroll
+                for (int c = 0; c < D; ++c) acc[1 + c] = fma(u, w_s[r][c], acc[1 + c]);
+            } else {
+                acc[0] = fma(cos(z), th, acc[0]);
+            }
+        }
+    }
+    for (int wv = 0; wv < 4; ++wv) {
+        __syncthreads();
+        if (ig == wv) {
+#pragma unroll
+            for (int k = 0; k < NA; ++k) red[lane][k] = wv == 0 ? acc[k] : red[lane][k] + acc[k];
+        }
+    }
+    __syncthreads();
+    const int nq = GRAD ? 1 + d : 1;
+    for (int q = tid; q < FR_PT * nq; q += FR_T) {
+        const int pt = q % FR_PT, c = q / FR_PT;
+        const int gi = blockIdx.x * FR_PT + pt;
+        if (gi >= m) continue;
+        if (c == 0)
+            s2[gi] = sn2 * a * red[pt][0];
+        else
+            ds2[(size_t)gi * d + (c - 1)] = -2.0 * sn2 * a * red[pt][c];
+    }
+}
+
+// ---- host ------------------------------------------------------------------------------------
+static int ss_event(GpxSsgp *st, hipStream_t s, int i)
+{
+    if (!st->ev[i]) GPX_HIP(hipEventCreate(&st->ev[i]));
+    GPX_HIP(hipEventRecord(st->ev[i], s));
+    return 0;
+}
+
+static double ss_elapsed(GpxSsgp *st, int a, int b)
+{
+    float t = 0;
+    if (hipEventElapsedTime(&t, st->ev[a], st->ev[b]) != hipSuccess) return -1.0;
+    return t;
+}
+
+void gpx_ssgp_destroy(GpxSsgp *st)
+{
+    if (!st) return;
+    for (hipEvent_t e : st->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : st->f.ev)
+        if (e) (void)hipEventDestroy(e);
+    delete st;
+}
+
+bool gpx_ssgp_ready(const GpxSsgp *st, long version)
+{
+    return st && st->ready && st->version == version;
+}
+int gpx_ssgp_dim(const GpxSsgp *st) { return st ? st->f.d : 0; }
+
+// lZ from the sums of the update
+static double ss_lz(const GpxSsgp *st)
+{
+    const double *sc = st->sc;
+    return -0.5 * sc[SS_EE] / st->sn2 - 0.5 * sc[SS_BB] - sc[SS_LOGR] +
+           (st->f.M - st->n) * st->log_sn - 0.5 * st->n * log(2 * M_PI);
+}
+
+// X, y: the handle's resident data (device). Returns the pivot (> 0, also in *info) when A is
+// not positive definite. One host synchronisation.
+int gpx_ssgp_run_update(GpxSsgp **state, hipStream_t s, const double *W, int M, int d,
+                        const double *b, double a, double log_sn, double mean, const double *X,
+                        const double *y, int n, long version, double *lZ, int *info)
+{
+    if (!*state) *state = new GpxSsgp();
+    GpxSsgp *st = *state;
+    GpxFourier *f = &st->f;
+    st->ready = false;
+    st->have_inverse = false;
+    if (info) *info = 0;
+    for (int i = SE_START; i <= SE_FACTOR; ++i)
+        if (!st->ev[i]) GPX_HIP(hipEventCreate(&st->ev[i]));
+    GPX_TRY(fr_install(f, s, W, M, d, b, a, mean, nullptr, 1));
+    GPX_TRY(fr_fit_reserve(f, s, n));
+    const int np = round_up(n, GPX_TILE);
+    GPX_TRY(st->e.reserve((size_t)np * 8));
+    GPX_TRY(st->scal.reserve(SS_NSC * 8));
+    GPX_HIP(hipMemsetAsync(f->P.p, 0, (size_t)M * 8, s));
+    const double sn = exp(log_sn), sn2 = exp(2 * log_sn);
+    GPX_HIP(hipEventRecord(st->ev[SE_START], s));
+    GPX_TRY(fr_fit_factor(f, s, X, y, n, sn2, st->ev + SE_PANEL));
+    GPX_TRY(fr_fit_theta(f, s, sn));
+    GPX_LAUNCH(ss_resid_kernel, dim3((np + FR_T - 1) / FR_T), dim3(FR_T), 0, s, f->Phi.d(), np, n,
+               M, y, mean, f->theta.d(), st->e.d());
+    GPX_LAUNCH(ss_terms_kernel, dim3(SS_TRINV), dim3(FR_T), 0, s, st->e.d(), n, f->theta.d(), M,
+               f->A.d(), f->Ak.d(), f->ldp, 0, st->scal.d());
+    int inf = 0;
+    GPX_HIP(hipMemcpyAsync(&inf, f->info.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipMemcpyAsync(st->sc, st->scal.p, SS_TRINV * 8, hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipStreamSynchronize(s));
+    if (inf) {
+        gpx_set_error("gpx_ssgp_update: matrix is not positive definite: pivot %d", inf);
+        if (info) *info = inf;
+        return inf;
+    }
+    st->n = n;
+    st->np = np;
+    st->version = version;
+    st->log_sn = log_sn;
+    st->sn2 = sn2;
+    st->ms[0] = ss_elapsed(st, SE_START, SE_PANEL);
+    st->ms[1] = ss_elapsed(st, SE_PANEL, SE_GRAM);
+    st->ms[2] = ss_elapsed(st, SE_GRAM, SE_FACTOR);
+    st->ms[3] = st->ms[4] = st->ms[6] = 0.0;
+    st->sc[SS_TRINV] = 0.0;
+    f->ready = true;
+    st->ready = true;
+    if (lZ) *lZ = ss_lz(st);
+    return 0;
+}
+
+// A^-1 (full, in f.Ak) and its trace, once per factorisation
+static int ss_inverse(GpxSsgp *st, hipStream_t s)
+{
+    if (st->have_inverse) return 0;
+    GpxFourier *f = &st->f;
+    const int Mp = f->Mp, ldp = f->ldp;
+    GPX_TRY(gpx_lauum(s, fr_ws(f)));
+    GPX_LAUNCH(ss_mirror_kernel, dim3((Mp + FR_T - 1) / FR_T, Mp), dim3(FR_T), 0, s, f->Ak.d(),
+               ldp, Mp);
+    GPX_LAUNCH(ss_terms_kernel, dim3(1), dim3(FR_T), 0, s, st->e.d(), st->n, f->theta.d(), f->M,
+               f->A.d(), f->Ak.d(), ldp, (int)SS_TRINV, st->scal.d());
+    GPX_HIP(hipMemcpyAsync(st->sc + SS_TRINV, st->scal.d() + SS_TRINV, 8, hipMemcpyDeviceToHost,
+                           s));
+    st->have_inverse = true;
+    return 0;
+}
+
+// C (Mp x cols) = alpha op(A) P for the Mp x cols panel P (ld cols): A = A^-1 (ta = 0) or W^T
+// with W upper triangular (ta = 1). 64-tiles whatever cols is: a column's sums are the same in
+// every panel that holds it.
+static int ss_panel_product(hipStream_t s, int ta, const double *A, int lda, const double *P,
+                            double *C, int Mp, int cols)
+{
+    GemmArgs g;
+    g.A = A; g.B = P; g.C = C;
+    g.lda = lda; g.ldb = cols; g.ldc = cols;
+    g.M = Mp; g.N = cols; g.K = Mp;
+    g.tile = 64;
+    if (ta) g.flags = GEMM_KHI_M;
+    return gpx_gemm(s, ta, 0, g);
+}
+
+// column slabs of the contraction: about 1024 workgroups in all, a function of the shape only
+static int ss_slab_cols(int Mp, int np)
+{
+    const int C = std::max(1, std::min(np / SS_CT, 1024 / (Mp / FR_FT)));
+    return round_up((np + C - 1) / C, SS_CT);
+}
+
+// lZ; dlZ3 != null: also dlZ3 = d lZ / d (log sn, log sf, mean), dW_W[c] = -sum_j D_jc W_jc and,
+// if not null, dW = D (M x d) and db (M)
+int gpx_ssgp_run_loglik(GpxSsgp *st, hipStream_t s, const double *X, double *lZ, double *dlZ3,
+                        double *dW_W, double *dW, double *db)
+{
+    *lZ = ss_lz(st);
+    if (!dlZ3) return 0;
+    GpxFourier *f = &st->f;
+    const int M = f->M, Mp = f->Mp, d = f->d, n = st->n, np = st->np;
+    const int cols = ss_slab_cols(Mp, np), C = (np + cols - 1) / cols;
+    GPX_TRY(st->B.reserve((size_t)Mp * np * 8));
+    GPX_TRY(st->slab.reserve((size_t)C * (1 + d) * Mp * 8));
+    GPX_TRY(st->Dw.reserve((size_t)M * d * 8));
+    GPX_TRY(st->db.reserve((size_t)M * 8));
+    GPX_TRY(st->dww.reserve((size_t)d * 8));
+    const bool inverse_due = !st->have_inverse;
+    GPX_TRY(ss_event(st, s, SE_G0));
+    GPX_TRY(ss_inverse(st, s));
+    GPX_TRY(ss_event(st, s, SE_INV));
+    GPX_TRY(ss_panel_product(s, 0, f->Ak.d(), f->ldp, f->Phi.d(), st->B.d(), Mp, np));
+    GPX_TRY(ss_event(st, s, SE_PROD));
+    GPX_TRY(fr_with_width(d, [&](auto w) {
+        GPX_LAUNCH(ss_contract_kernel<decltype(w)::value>, dim3(Mp / FR_FT, C), dim3(FR_T), 0, s, X,
+                   n, np, d, f->W.d(), f->b.d(), f->theta.d(), M, Mp, st->e.d(), st->B.d(), f->a,
+                   1.0 / st->sn2, cols, st->slab.d());
+        return 0;
+    }));
+    GPX_LAUNCH(ss_reduce_kernel, dim3(((1 + d) * M + FR_T - 1) / FR_T), dim3(FR_T), 0, s,
+               st->slab.d(), C, d, M, Mp, st->db.d(), st->Dw.d());
+    GPX_LAUNCH(ss_dot_w_kernel, dim3(d), dim3(FR_T), 0, s, st->Dw.d(), f->W.d(), M, d,
+               st->dww.d());
+    GPX_TRY(ss_event(st, s, SE_CONTRACT));
+    GPX_HIP(hipMemcpyAsync(dW_W, st->dww.p, (size_t)d * 8, hipMemcpyDeviceToHost, s));
+    if (dW) GPX_HIP(hipMemcpyAsync(dW, st->Dw.p, (size_t)M * d * 8, hipMemcpyDeviceToHost, s));
+    if (db) GPX_HIP(hipMemcpyAsync(db, st->db.p, (size_t)M * 8, hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipStreamSynchronize(s));
+    if (inverse_due) st->ms[6] = ss_elapsed(st, SE_G0, SE_INV);
+    st->ms[3] = ss_elapsed(st, SE_INV, SE_PROD);
+    st->ms[4] = ss_elapsed(st, SE_PROD, SE_CONTRACT);
+    const double *sc = st->sc, sn2 = st->sn2;
+    dlZ3[0] = sc[SS_EE] / sn2 - n + M - sn2 * sc[SS_TRINV];
+    dlZ3[1] = sc[SS_BB] - M + sn2 * sc[SS_TRINV];
+    dlZ3[2] = sc[SS_E] / sn2;
+    return 0;
+}
+
+// the panel of the mc test points at st->Xs: Mp x mcp into st->PhiS
+static int ss_test_panel(GpxSsgp *st, hipStream_t s, const double *Xs, int mc, int mcp)
+{
+    GpxFourier *f = &st->f;
+    const int d = f->d;
+    GPX_TRY(st->Xs.reserve((size_t)mc * d * 8));
+    GPX_TRY(st->PhiS.reserve((size_t)f->Mp * mcp * 8));
+    GPX_TRY(st->T.reserve((size_t)f->Mp * mcp * 8));
+    GPX_HIP(hipMemcpyAsync(st->Xs.p, Xs, (size_t)mc * d * 8, hipMemcpyHostToDevice, s));
+    return fr_with_width(d, [&](auto w) {
+        GPX_LAUNCH(fr_panel_kernel<decltype(w)::value>,
+                   dim3((mcp + FR_T - 1) / FR_T, f->Mp / FR_FT), dim3(FR_T), 0, s, st->Xs.d(), mc,
+                   mcp, d, f->W.d(), f->b.d(), f->M, f->a, st->PhiS.d());
+        return 0;
+    });
+}
+
+// mu[m], s2[m] and (both or neither) dmu, ds2 [m * d] at the m host points Xs
+int gpx_ssgp_run_posterior(GpxSsgp *st, hipStream_t s, const double *Xs, int64_t m, double *mu,
+                           double *s2, double *dmu, double *ds2)
+{
+    GpxFourier *f = &st->f;
+    const int Mp = f->Mp, d = f->d;
+    GPX_TRY(ss_event(st, s, SE_P0));
+    GPX_TRY(gpx_fourier_run_eval(f, s, Xs, m, mu, dmu));
+    GPX_TRY(ss_inverse(st, s));
+    for (int64_t i0 = 0; i0 < m; i0 += SS_PASS) {
+        const int mc = (int)std::min<int64_t>(SS_PASS, m - i0), mcp = round_up(mc, GPX_TILE);
+        GPX_TRY(ss_test_panel(st, s, Xs + i0 * d, mc, mcp));
+        GPX_TRY(st->s2.reserve((size_t)mc * 8));
+        if (ds2) GPX_TRY(st->ds2.reserve((size_t)mc * d * 8));
+        GPX_TRY(ss_panel_product(s, 0, f->Ak.d(), f->ldp, st->PhiS.d(), st->T.d(), Mp, mcp));
+        GPX_TRY(fr_with_width(d, [&](auto w) {
+            constexpr int D = decltype(w)::value;
+            const dim3 grid((mc + FR_PT - 1) / FR_PT);
+            if (ds2)
+                GPX_LAUNCH((ss_var_kernel<D, true>), grid, dim3(FR_T), 0, s, st->Xs.d(), mc, d,
+                           f->W.d(), f->b.d(), st->T.d(), mcp, f->M, f->a, st->sn2, st->s2.d(),
+                           st->ds2.d());
+            else
+                GPX_LAUNCH((ss_var_kernel<D, false>), grid, dim3(FR_T), 0, s, st->Xs.d(), mc, d,
+                           f->W.d(), f->b.d(), st->T.d(), mcp, f->M, f->a, st->sn2, st->s2.d(),
+                           (double *)nullptr);
+            return 0;
+        }));
+        GPX_HIP(hipMemcpyAsync(s2 + i0, st->s2.p, (size_t)mc * 8, hipMemcpyDeviceToHost, s));
+        if (ds2)
+            GPX_HIP(hipMemcpyAsync(ds2 + i0 * d, st->ds2.p, (size_t)mc * d * 8,
+                                   hipMemcpyDeviceToHost, s));
+        if (i0 + SS_PASS >= m) GPX_TRY(ss_event(st, s, SE_P1));
+        GPX_HIP(hipStreamSynchronize(s));
+    }
+    st->ms[5] = ss_elapsed(st, SE_P0, SE_P1);
+    return 0;
+}
+
+// mu[m] and Sigma[m * m] = sn2 V^T V, V = W^T Phi*, at m <= SS_PASS host points
+int gpx_ssgp_run_posterior_full(GpxSsgp *st, hipStream_t s, const double *Xs, int m, double *mu,
+                                double *Sigma)
+{
+    GpxFourier *f = &st->f;
+    const int Mp = f->Mp, mp = round_up(m, GPX_TILE);
+    GPX_TRY(gpx_fourier_run_eval(f, s, Xs, m, mu, nullptr));
+    GPX_TRY(ss_test_panel(st, s, Xs, m, mp));
+    GPX_TRY(st->Sig.reserve((size_t)mp * mp * 8));
+    GPX_TRY(ss_panel_product(s, 1, f->Aw.d(), f->ldp, st->PhiS.d(), st->T.d(), Mp, mp));
+    GemmArgs g;
+    g.A = st->T.d(); g.B = st->T.d(); g.C = st->Sig.d();
+    g.lda = mp; g.ldb = mp; g.ldc = mp;
+    g.M = mp; g.N = mp; g.K = Mp;
+    g.alpha = st->sn2;
+    GPX_TRY(gpx_gemm(s, 1, 0, g));
+    GPX_HIP(hipMemcpy2DAsync(Sigma, (size_t)m * 8, st->Sig.p, (size_t)mp * 8, (size_t)m * 8, m,
+                             hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+int gpx_ssgp_run_get(GpxSsgp *st, hipStream_t s, double *beta)
+{
+    GPX_HIP(hipMemcpyAsync(beta, st->f.theta.p, (size_t)st->f.M * 8, hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+int gpx_ssgp_run_timings(const GpxSsgp *st, double *ms)
+{
+    for (int i = 0; i < 7; ++i) ms[i] = st ? st->ms[i] : 0.0;
     return 0;
 }

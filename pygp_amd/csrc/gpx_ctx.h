@@ -104,6 +104,9 @@ struct gpx_ctx {
     GpxSelect *select = nullptr;
     // Fourier-feature function sample (fourier.hip), created on first use; buffers of its own
     GpxFourier *fourier = nullptr;
+    // sparse-spectrum GP on the resident data (fourier.hip), created on first use; buffers of
+    // its own, valid for the data version its update read
+    GpxSsgp *ssgp = nullptr;
     // look-ahead of the factorisation (chol.hip): diagonal blocks on a high-priority
     // stream, the left half of the inverse tree on a low-priority one
     hipStream_t crit = nullptr, aux = nullptr, bulk = nullptr;

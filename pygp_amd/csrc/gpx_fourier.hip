@@ -1,7 +1,8 @@
 // C ABI of libgpx.so, the wrappers of the Fourier-feature function samples (gpx_fourier_*):
 // argument checks around the entry points of fourier.hip, which owns its buffers and kernels.
 // The sample has a state of its own on the handle (GpxFourier): no call here touches the
-// resident data, an exact factorisation or a sparse model.
+// resident data, an exact factorisation or a sparse model. The same for the sparse-spectrum GP
+// of those features (gpx_ssgp_*, GpxSsgp), which reads the resident data.
 
 #include "gpx_ctx.h"
 
@@ -143,6 +144,109 @@ int gpx_fourier_timings(gpx_t *h, double *ms)
         return -1;
     }
     return gpx_fourier_run_timings(h->fourier, ms);
+}
+
+// ---- the sparse-spectrum GP (gpx_ssgp_*): a state of its own again (GpxSsgp), which reads the
+// resident X and y as gpx_fourier_fit(X == NULL) does and writes nothing outside itself
+
+// the model of the resident data, updated: every entry behind gpx_ssgp_update asks for it
+static int ssgp_ready(const gpx_ctx *h, const char *what)
+{
+    GPX_TRY(require_state(h, ST_PLAIN, what));
+    if (!gpx_ssgp_ready(h->ssgp, h->data_version)) {
+        gpx_set_error("%s: no model of the resident data (call gpx_ssgp_update)", what);
+        return -1;
+    }
+    return 0;
+}
+
+int gpx_ssgp_update(gpx_t *h, const double *W, int64_t M, int64_t d, const double *b, double a,
+                    double log_sn, double mean, double *lZ, int *info)
+{
+    CHECK_H(h);
+    if (info) *info = 0;
+    GPX_TRY(require_state(h, ST_PLAIN, "gpx_ssgp_update"));
+    if (h->n <= 0) {
+        gpx_set_error("gpx_ssgp_update: the handle has no data (gpx_set_data)");
+        return -1;
+    }
+    GPX_TRY(fourier_check("gpx_ssgp_update", W, M, d, b, a, mean, 1));
+    if (!std::isfinite(log_sn)) {
+        gpx_set_error("gpx_ssgp_update: non-finite log_sn");
+        return -1;
+    }
+    if (h->d != d) {
+        gpx_set_error("gpx_ssgp_update: W has %lld columns, the resident data %d", (long long)d,
+                      h->d);
+        return -1;
+    }
+    const long long Mp = round_up(M, GPX_TILE), np = round_up(h->n, GPX_TILE);
+    if (h->n > (1 << 20) || Mp * np >= (1LL << 31)) {
+        gpx_set_error("gpx_ssgp_update: n = %d, M_pad * N_pad = %lld x %lld: at most 2^20 "
+                      "observations and a panel below 2^31 entries", h->n, Mp, np);
+        return -1;
+    }
+    return gpx_ssgp_run_update(&h->ssgp, h->stream, W, (int)M, (int)d, b, a, log_sn, mean,
+                               h->X.as<double>(), h->y.as<double>(), h->n, h->data_version, lZ,
+                               info);
+}
+
+int gpx_ssgp_loglik(gpx_t *h, double *lZ, double *dlZ3, double *dW_W, double *dW, double *db)
+{
+    CHECK_H(h);
+    GPX_TRY(ssgp_ready(h, "gpx_ssgp_loglik"));
+    if (!lZ || (dlZ3 && !dW_W) || (!dlZ3 && (dW_W || dW || db))) {
+        gpx_set_error("gpx_ssgp_loglik: lZ is null, or dlZ3 and dW_W do not come together");
+        return -1;
+    }
+    return gpx_ssgp_run_loglik(h->ssgp, h->stream, h->X.as<double>(), lZ, dlZ3, dW_W, dW, db);
+}
+
+int gpx_ssgp_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2, double *dmu,
+                       double *ds2)
+{
+    CHECK_H(h);
+    GPX_TRY(ssgp_ready(h, "gpx_ssgp_posterior"));
+    if (!Xs || !mu || !s2 || m < 1 || m > (1 << 20) || (dmu == nullptr) != (ds2 == nullptr)) {
+        gpx_set_error("gpx_ssgp_posterior: bad arguments (1 <= m <= 2^20; dmu and ds2 both or "
+                      "neither)");
+        return -1;
+    }
+    GPX_TRY(fourier_finite("gpx_ssgp_posterior", "Xs", Xs, m * gpx_ssgp_dim(h->ssgp)));
+    return gpx_ssgp_run_posterior(h->ssgp, h->stream, Xs, m, mu, s2, dmu, ds2);
+}
+
+int gpx_ssgp_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma)
+{
+    CHECK_H(h);
+    GPX_TRY(ssgp_ready(h, "gpx_ssgp_posterior_full"));
+    if (!Xs || !mu || !Sigma || m < 1 || m > 8192) {
+        gpx_set_error("gpx_ssgp_posterior_full: bad arguments (1 <= m <= 8192)");
+        return -1;
+    }
+    GPX_TRY(fourier_finite("gpx_ssgp_posterior_full", "Xs", Xs, m * gpx_ssgp_dim(h->ssgp)));
+    return gpx_ssgp_run_posterior_full(h->ssgp, h->stream, Xs, (int)m, mu, Sigma);
+}
+
+int gpx_ssgp_get(gpx_t *h, double *beta)
+{
+    CHECK_H(h);
+    GPX_TRY(ssgp_ready(h, "gpx_ssgp_get"));
+    if (!beta) {
+        gpx_set_error("gpx_ssgp_get: beta is null");
+        return -1;
+    }
+    return gpx_ssgp_run_get(h->ssgp, h->stream, beta);
+}
+
+int gpx_ssgp_timings(gpx_t *h, double *ms)
+{
+    CHECK_H(h);
+    if (!ms) {
+        gpx_set_error("gpx_ssgp_timings: ms is null");
+        return -1;
+    }
+    return gpx_ssgp_run_timings(h->ssgp, ms);
 }
 
 }  // extern "C"

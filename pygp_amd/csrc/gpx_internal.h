@@ -634,6 +634,26 @@ int gpx_fourier_run_eval(GpxFourier *st, hipStream_t s, const double *Xs, int64_
 int gpx_fourier_run_timings(const GpxFourier *st, double *ms);
 void gpx_fourier_destroy(GpxFourier *st);
 
+// ---- the sparse-spectrum GP of those features (fourier.hip) --------------------------------
+// One model per handle, in buffers of its own: the fit above with P = 0 on the resident data X,
+// y (device), its residual e and the terms of lZ; on demand A^-1, the gradient and the
+// posteriors. *state is created on first use (per handle). version: of the resident data.
+struct GpxSsgp;
+int gpx_ssgp_run_update(GpxSsgp **state, hipStream_t s, const double *W, int M, int d,
+                        const double *b, double a, double log_sn, double mean, const double *X,
+                        const double *y, int n, long version, double *lZ, int *info);
+bool gpx_ssgp_ready(const GpxSsgp *st, long version);
+int gpx_ssgp_dim(const GpxSsgp *st);
+int gpx_ssgp_run_loglik(GpxSsgp *st, hipStream_t s, const double *X, double *lZ, double *dlZ3,
+                        double *dW_W, double *dW, double *db);
+int gpx_ssgp_run_posterior(GpxSsgp *st, hipStream_t s, const double *Xs, int64_t m, double *mu,
+                           double *s2, double *dmu, double *ds2);
+int gpx_ssgp_run_posterior_full(GpxSsgp *st, hipStream_t s, const double *Xs, int m, double *mu,
+                                double *Sigma);
+int gpx_ssgp_run_get(GpxSsgp *st, hipStream_t s, double *beta);
+int gpx_ssgp_run_timings(const GpxSsgp *st, double *ms);
+void gpx_ssgp_destroy(GpxSsgp *st);
+
 // d k / d x2 (sign = +1) or d k / d x1 (sign = -1): out[n1][n2][d]
 int gpx_kgrady(hipStream_t s, const KParams &kp, const double *X1, int n1, const double *X2,
                int n2, int d, double sign, double *out);

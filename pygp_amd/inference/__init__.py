@@ -10,6 +10,7 @@ from .dtc import DTC
 from .vfe import VFE
 from .select import select_pseudoinputs
 from .fourier import FourierSample
+from .ssgp import SSGP
 
 __all__ = ['GP', 'ExactGP', 'BasicGP', 'GradientGP', 'MultiOutputGP', 'CoregionalGP', 'LaplaceGP',
-           'EPGP', 'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'FourierSample']
+           'EPGP', 'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'FourierSample', 'SSGP']

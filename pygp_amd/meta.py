@@ -44,6 +44,10 @@ class HyperEnsemble(object):
             # sparse model's
             raise TypeError('HyperEnsemble runs exact GPs only; %s is a sparse model'
                             % type(model).__name__)
+        from .inference.ssgp import SSGP
+        if isinstance(model, SSGP):
+            raise TypeError('HyperEnsemble runs exact GPs only; %s is a feature model'
+                            % type(model).__name__)
         from .inference._labels import LabelsGP
         if isinstance(model, LabelsGP):
             # ... with Gaussian noise: a classifier's hypers have no noise slot
