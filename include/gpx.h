@@ -514,6 +514,40 @@ int gpx_fourier_eval(gpx_t *h, const double *Xs, int64_t n, double *F, double *G
  * gpx_fourier_eval (ms[1]) on this handle (0: none) */
 int gpx_fourier_timings(gpx_t *h, double *ms);
 
+/* ---- pathwise posterior function samples (Wilson et al., ICML 2020) -------- */
+/* Matheron's rule: f_s(x) = mean + ft_s(x) + k(x, X) v_s, with the prior ft_s(x) = a sum_j
+ * cos(w_j.x + b_j) theta_sj drawn through M random features and the data entering through the
+ * exact solve v_s = (K + sn^2 I)^-1 (y - mean - ft_s(X) - sn e_s); theta_s and e_s are standard
+ * normal draws of the caller. Unlike a Fourier sample the function interpolates the data however
+ * many there are.
+ * gpx_path_fit runs on a handle with plain data and a current factorisation (gpx_exact_update):
+ * kernel, log_sn and mean are those of that update, the kernel a single SE or Matern part. It
+ * takes theta = P[S*M] and e = E[S*n] (n: the rows of the resident data), evaluates ft_s at the resident X on the device, solves the
+ * S columns behind the one factor and writes V[S*n] back. The factorisation is only read, except
+ * that R^-1 is completed as gpx_exact_posterior completes it. *info is 0 (the call factors
+ * nothing).
+ * Limits: 1 <= M <= GPX_FOURIER_MAX_M, 1 <= S <= GPX_FOURIER_MAX_S, d <= GPX_MAX_DIM and equal
+ * to the width of the resident data. The sample lives in buffers of its own, a copy of X
+ * included: gpx_set_data, exact updates, sparse models, SSGP and Fourier samples of the handle
+ * leave it as it is, and no gpx_path_* call changes what those return. Every sum has a fixed
+ * order, which does not depend on the number of points of a call: the same point returns the
+ * same bits whatever shares the call with it. */
+int gpx_path_fit(gpx_t *h, const double *W, int64_t M, int64_t d, const double *b, double a,
+                 const double *P, const double *E, int64_t n, int64_t S, double *V, int *info);
+/* installs a given sample without a factorisation: the kernel k (a single SE or Matern part of
+ * width d), the mean, X[n*d] (n == 0: the prior sample alone; X and V may be NULL), theta[S*M]
+ * and V[S*n]: what a copy or a pickle restores */
+int gpx_path_set(gpx_t *h, const gpx_kspec *k, double mean, const double *X, int64_t n, int64_t d,
+                 const double *W, int64_t M, const double *b, double a, const double *theta,
+                 const double *V, int64_t S);
+/* F[S*m] = f_s(Xs_i) and, G != NULL, G[S*m*d] with G[s][i][c] = d f_s / d x_c at Xs_i, for the
+ * m rows of Xs[m*d], 1 <= m <= 2^20: the feature term as gpx_fourier_eval, the data term added
+ * on the device without storing a cross-covariance matrix, one upload and one download */
+int gpx_path_eval(gpx_t *h, const double *Xs, int64_t m, double *F, double *G);
+/* HIP-event ms[4] of the last gpx_path_fit, of the kernels of the last gpx_path_eval, and of
+ * that evaluation's feature term and data term (0: none) */
+int gpx_path_timings(gpx_t *h, double *ms);
+
 /* ---- sparse-spectrum GP regression on those features (own design) --------- */
 /* The regression model of the features above, f(x) = mean + a sum_j cos(w_j.x + b_j) theta_j with
  * theta ~ N(0, I), on the handle's resident data (gpx_set_data), as gpx_fourier_fit(X == NULL)

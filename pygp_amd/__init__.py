@@ -6,7 +6,8 @@ Only the path named in BASELINE.json is here: pairwise kernel evaluation
 log-likelihood (+gradient) / posterior, the sparse FITC / DTC / VFE models and binary
 classification by Laplace's approximation (LaplaceGP) and by expectation propagation (EPGP),
 correlated outputs at their own inputs (CoregionalGP) and posterior function samples through
-random Fourier features (FourierSample) with their regression model (SSGP), executed by hand-written HIP kernels in libgpx.so; `batch` and `meta` route the
+random Fourier features (FourierSample) with their regression model (SSGP) and by pathwise
+conditioning on the exact solve (PathwiseSample), executed by hand-written HIP kernels in libgpx.so; `batch` and `meta` route the
 per-sample loops of the reference's meta-models through the batched entry points.
 """
 
@@ -17,9 +18,10 @@ from . import learning
 from . import batch
 from . import meta
 from .inference import (BasicGP, ExactGP, GradientGP, MultiOutputGP, CoregionalGP, LaplaceGP,
-                        EPGP, FITC, DTC, VFE, select_pseudoinputs, FourierSample, SSGP)
+                        EPGP, FITC, DTC, VFE, select_pseudoinputs, FourierSample, SSGP,
+                        PathwiseSample)
 from .learning import optimize
 
 __all__ = ['BasicGP', 'ExactGP', 'GradientGP', 'MultiOutputGP', 'CoregionalGP', 'LaplaceGP', 'EPGP',
-           'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'FourierSample', 'SSGP', 'optimize', 'kernels', 'likelihoods', 'inference', 'learning',
+           'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'FourierSample', 'SSGP', 'PathwiseSample', 'optimize', 'kernels', 'likelihoods', 'inference', 'learning',
            'batch', 'meta']

@@ -143,6 +143,12 @@ SIGNATURES = {
     'gpx_fourier_set': (C.c_int, [_vp, _vp, _i64, _i64, _vp, C.c_double, C.c_double, _vp, _i64]),
     'gpx_fourier_eval': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     'gpx_fourier_timings': (C.c_int, [_vp, _vp]),
+    'gpx_path_fit': (C.c_int, [_vp, _vp, _i64, _i64, _vp, C.c_double, _vp, _vp, _i64, _i64, _vp,
+                               _ip]),
+    'gpx_path_set': (C.c_int, [_vp, C.POINTER(_KSpec), C.c_double, _vp, _i64, _i64, _vp, _i64,
+                               _vp, C.c_double, _vp, _vp, _i64]),
+    'gpx_path_eval': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    'gpx_path_timings': (C.c_int, [_vp, _vp]),
     'gpx_ssgp_update': (C.c_int, [_vp, _vp, _i64, _i64, _vp, C.c_double, C.c_double, C.c_double,
                                   _dp, _ip]),
     'gpx_ssgp_loglik': (C.c_int, [_vp, _dp, _vp, _vp, _vp, _vp]),
@@ -777,6 +783,59 @@ class Handle(object):
         """HIP-event ms of the last [fit, evaluation]."""
         ms = np.zeros(2)
         check(self._L.gpx_fourier_timings(self._h, _ptr(ms)))
+        return ms
+
+    # -- pathwise posterior function samples (a state of the handle's own) --
+    def path_fit(self, W, b, a, P, E):
+        """V (S, n) of the pathwise sample with theta = P (S, M) and noise draws E (S, n), behind
+        the handle's exact factorisation (set_data, exact_update): its kernel, noise and mean."""
+        W, b, P, E = _f64(W, 2), _f64(b, 1), _f64(P, 2), _f64(E, 2)
+        M, d = W.shape
+        if b.shape[0] != M or P.shape[1] != M or E.shape[0] != P.shape[0]:
+            raise ValueError('shapes of W, b, P and E do not agree')
+        V = np.empty_like(E)
+        info = C.c_int(0)
+        check(self._L.gpx_path_fit(self._h, _ptr(W), M, d, _ptr(b), float(a), _ptr(P), _ptr(E),
+                                   E.shape[1], P.shape[0], _ptr(V), C.byref(info)))
+        self._path_shape = (P.shape[0], d)
+        return V
+
+    def path_set(self, spec, mean, X, W, b, a, theta, V):
+        """Install a given sample: X (n, d) or None, theta (S, M) and V (S, n)."""
+        W, b, theta = _f64(W, 2), _f64(b, 1), _f64(theta, 2)
+        M, d = W.shape
+        S = theta.shape[0]
+        if X is None or len(X) == 0:
+            X, V, n = None, None, 0
+        else:
+            X, V = _f64(X, 2), _f64(V, 2)
+            n = X.shape[0]
+            if X.shape[1] != d or V.shape != (S, n):
+                raise ValueError('shapes of X, W, theta and V do not agree')
+        if b.shape[0] != M or theta.shape[1] != M:
+            raise ValueError('shapes of W, b and theta do not agree')
+        check(self._L.gpx_path_set(self._h, spec.ref(), float(mean), _ptr(X), n, d, _ptr(W), M,
+                                   _ptr(b), float(a), _ptr(theta), _ptr(V), S))
+        self._path_shape = (S, d)
+
+    def path_eval(self, Xs, grad=False):
+        """F (S, m), or (F, G) with G (S, m, d), of the installed sample at the rows of Xs."""
+        Xs = _f64(Xs, 2)
+        m, d = Xs.shape
+        S, dim = getattr(self, '_path_shape', (0, d))
+        if S == 0:
+            raise GpxError('path_eval: no sample (call path_fit or path_set)')
+        if d != dim:
+            raise ValueError('test inputs have the wrong dimension')
+        F = np.empty((S, m))
+        G = np.empty((S, m, d)) if grad else None
+        check(self._L.gpx_path_eval(self._h, _ptr(Xs), m, _ptr(F), _ptr(G)))
+        return (F, G) if grad else F
+
+    def path_timings(self):
+        """HIP-event ms of the last [fit, evaluation, its feature term, its data term]."""
+        ms = np.zeros(4)
+        check(self._L.gpx_path_timings(self._h, _ptr(ms)))
         return ms
 
     # -- sparse-spectrum GP on the resident data (a state of the handle's own) --

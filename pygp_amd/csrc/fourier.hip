@@ -10,37 +10,14 @@
 // the same bits. Arguments of cos / sincos are not small: the full-range fp64 functions.
 // The second half of the file is the regression model of the same features, the
 // sparse-spectrum GP: it shares the fit's launches and the evaluation.
-#include "kmat_dev.h"
+#include "fourier_dev.h"
 #include <cmath>
 #include <cstring>
-
-#define FR_T 256      // threads of every kernel here
-#define FR_FT 64      // features of one staged tile
-#define FR_PT 64      // test points of one workgroup of the evaluation: one per lane
 
 #ifndef GPX_V4D
 #define GPX_V4D
 typedef double v4d __attribute__((ext_vector_type(4)));
 #endif
-
-struct GpxFourier {
-    int M = 0, Mp = 0, ldp = 0, d = 0, S = 0;
-    double a = 0, mean = 0;
-    bool ready = false;
-    // the sample: W (M x d), b (M), theta (S x M)
-    DevBuf W, b, theta;
-    // its coefficient matrix for the matrix-pipe evaluation (fr_coef_kernel): Mr x ldc
-    DevBuf Cf;
-    int Mr = 0, nbv = 0, ldc = 0;
-    // the fit: data of its own (X, y) unless the handle's are used, the panel (Mp x np), the
-    // factorisation's three Mp x ldp matrices, split-K partials, v = Phi^T r, t = W^T v, P
-    DevBuf X, y, Phi, A, Aw, Ak, split, v, t, P, info, pctl;
-    int gates[2] = {0, 0};
-    // the evaluation: test points, results, slab partials
-    DevBuf Xs, F, G, slab;
-    hipEvent_t ev[4] = {};
-    double ms[2] = {0, 0};
-};
 
 // ---- the feature panel ---------------------------------------------------------------------
 // One lane holds one x_i (D values, columns >= d zero) and walks the FR_FT features of the
@@ -386,21 +363,6 @@ __global__ __launch_bounds__(FR_T) void fr_eval_mfma_kernel(
 }
 
 // ---- host ----------------------------------------------------------------------------------
-// the widths a row of d values is kept in registers at
-template <typename Fn> static inline int fr_with_width(int d, Fn &&f)
-{
-    if (d <= 1) return f(std::integral_constant<int, 1>{});
-    if (d <= 2) return f(std::integral_constant<int, 2>{});
-    if (d <= 3) return f(std::integral_constant<int, 3>{});
-    if (d <= 4) return f(std::integral_constant<int, 4>{});
-    return with_dmax(d, f);
-}
-// samples of one pass with gradients: at most 36 sums a lane, and no more samples than stay
-// below FR_MFMA_MIN_COLS columns at that width
-template <int D> struct FrGradSamples {
-    static constexpr int value = D <= 1 ? 16 : (D <= 3 ? 8 : (D <= 8 ? 4 : 1));
-};
-
 static int fr_event(GpxFourier *st, hipStream_t s, int i)
 {
     if (!st->ev[i]) GPX_HIP(hipEventCreate(&st->ev[i]));
@@ -646,11 +608,11 @@ static int fr_slabs(int T, int PT, int passes)
 
 // one launch sequence over the points [0, n) at Xs (device): F (S x n), G (S x n x d or null)
 template <int D, int SB, bool GRAD>
-static int fr_eval_launch(GpxFourier *st, hipStream_t s, int n)
+static int fr_eval_launch(GpxFourier *st, hipStream_t s, int n, int slabs)
 {
     const int M = st->M, S = st->S, d = st->d;
     const int T = (M + FR_FT - 1) / FR_FT, PT = (n + FR_PT - 1) / FR_PT;
-    const int passes = (S + SB - 1) / SB, C = fr_slabs(T, PT, passes);
+    const int passes = (S + SB - 1) / SB, C = slabs ? slabs : fr_slabs(T, PT, passes);
     const int nq = GRAD ? 1 + d : 1;
     if (C > 1) GPX_TRY(st->slab.reserve((size_t)C * S * nq * n * 8));
     GPX_LAUNCH((fr_eval_kernel<D, SB, GRAD>), dim3(PT, C, passes), dim3(FR_T), 0, s, st->Xs.d(), n,
@@ -667,11 +629,11 @@ static int fr_eval_launch(GpxFourier *st, hipStream_t s, int n)
 
 // the same on the matrix pipe: NB column blocks a pass
 template <int D, int NB, bool GRAD>
-static int fr_eval_mfma_launch(GpxFourier *st, hipStream_t s, int n, int passes)
+static int fr_eval_mfma_launch(GpxFourier *st, hipStream_t s, int n, int passes, int slabs)
 {
     const int M = st->M, S = st->S, d = st->d;
     const int T = (M + FR_FM - 1) / FR_FM, PT = (n + FR_PT - 1) / FR_PT;
-    const int C = fr_slabs(T, PT, passes);
+    const int C = slabs ? slabs : fr_slabs(T, PT, passes);
     const int nq = GRAD ? 1 + d : 1;
     if (C > 1) GPX_TRY(st->slab.reserve((size_t)C * S * nq * n * 8));
     GPX_LAUNCH((fr_eval_mfma_kernel<D, NB, GRAD>), dim3(PT, C, passes), dim3(FR_T), 0, s,
@@ -686,22 +648,44 @@ static int fr_eval_mfma_launch(GpxFourier *st, hipStream_t s, int n, int passes)
     return 0;
 }
 
-template <int D> static int fr_eval_mfma(GpxFourier *st, hipStream_t s, int n, bool grad)
+template <int D>
+static int fr_eval_mfma(GpxFourier *st, hipStream_t s, int n, bool grad, int slabs)
 {
     int passes, nb;
     if (!grad) {
-        if (st->nbv == 1) return fr_eval_mfma_launch<D, 1, false>(st, s, n, 1);
-        return fr_eval_mfma_launch<D, 2, false>(st, s, n, 1);
+        if (st->nbv == 1) return fr_eval_mfma_launch<D, 1, false>(st, s, n, 1, slabs);
+        return fr_eval_mfma_launch<D, 2, false>(st, s, n, 1, slabs);
     }
     fr_mfma_plan(st->nbv + (st->S * st->d + 15) / 16, &passes, &nb);
     switch (nb) {
-    case 2: return fr_eval_mfma_launch<D, 2, true>(st, s, n, passes);
-    case 3: return fr_eval_mfma_launch<D, 3, true>(st, s, n, passes);
-    case 4: return fr_eval_mfma_launch<D, 4, true>(st, s, n, passes);
-    case 6: return fr_eval_mfma_launch<D, 6, true>(st, s, n, passes);
-    case 9: return fr_eval_mfma_launch<D, 9, true>(st, s, n, passes);
-    default: return fr_eval_mfma_launch<D, FR_NB_MAX, true>(st, s, n, passes);
+    case 2: return fr_eval_mfma_launch<D, 2, true>(st, s, n, passes, slabs);
+    case 3: return fr_eval_mfma_launch<D, 3, true>(st, s, n, passes, slabs);
+    case 4: return fr_eval_mfma_launch<D, 4, true>(st, s, n, passes, slabs);
+    case 6: return fr_eval_mfma_launch<D, 6, true>(st, s, n, passes, slabs);
+    case 9: return fr_eval_mfma_launch<D, 9, true>(st, s, n, passes, slabs);
+    default: return fr_eval_mfma_launch<D, FR_NB_MAX, true>(st, s, n, passes, slabs);
     }
+}
+
+// the launches of an evaluation of the m points at st->Xs (fourier_dev.h)
+int gpx_fourier_eval_resident(GpxFourier *st, hipStream_t s, int m, bool grad, int slabs)
+{
+    const int S = st->S, d = st->d;
+    // (a function of the shape alone, like every split here: the same call, the same bits)
+    if (S * (grad ? 1 + d : 1) >= FR_MFMA_MIN_COLS)
+        return with_dmax(d, [&](auto w) {
+            return fr_eval_mfma<decltype(w)::value>(st, s, m, grad, slabs);
+        });
+    return fr_with_width(d, [&](auto w) {
+        constexpr int D = decltype(w)::value;
+        if (grad) {
+            if (S == 1) return fr_eval_launch<D, 1, true>(st, s, m, slabs);
+            return fr_eval_launch<D, FrGradSamples<D>::value, true>(st, s, m, slabs);
+        }
+        if (S == 1) return fr_eval_launch<D, 1, false>(st, s, m, slabs);
+        if (S <= 4) return fr_eval_launch<D, 4, false>(st, s, m, slabs);
+        return fr_eval_launch<D, 16, false>(st, s, m, slabs);
+    });
 }
 
 bool gpx_fourier_ready(const GpxFourier *st) { return st && st->ready; }
@@ -713,9 +697,7 @@ int gpx_fourier_run_eval(GpxFourier *st, hipStream_t s, const double *Xs, int64_
                          double *G)
 {
     const int S = st->S, d = st->d;
-    const int64_t per_point = (int64_t)S * (G ? 1 + d : 1);
-    int64_t chunk = std::max<int64_t>(FR_PT, ((1LL << 25) / per_point) / FR_PT * FR_PT);
-    chunk = std::min(chunk, n);
+    const int64_t chunk = fr_eval_chunk(S, d, G != nullptr, n);
     GPX_TRY(st->Xs.reserve((size_t)chunk * d * 8));
     GPX_TRY(st->F.reserve((size_t)S * chunk * 8));
     if (G) GPX_TRY(st->G.reserve((size_t)S * chunk * d * 8));
@@ -724,23 +706,7 @@ int gpx_fourier_run_eval(GpxFourier *st, hipStream_t s, const double *Xs, int64_
         const int m = (int)std::min(chunk, n - i0);
         GPX_HIP(hipMemcpyAsync(st->Xs.p, Xs + i0 * d, (size_t)m * d * 8, hipMemcpyHostToDevice, s));
         GPX_TRY(fr_event(st, s, 2));
-        // (a function of the shape alone, like every split here: the same call, the same bits)
-        if (per_point >= FR_MFMA_MIN_COLS) {
-            GPX_TRY(with_dmax(d, [&](auto w) {
-                return fr_eval_mfma<decltype(w)::value>(st, s, m, G != nullptr);
-            }));
-        } else {
-            GPX_TRY(fr_with_width(d, [&](auto w) {
-                constexpr int D = decltype(w)::value;
-                if (G) {
-                    if (S == 1) return fr_eval_launch<D, 1, true>(st, s, m);
-                    return fr_eval_launch<D, FrGradSamples<D>::value, true>(st, s, m);
-                }
-                if (S == 1) return fr_eval_launch<D, 1, false>(st, s, m);
-                if (S <= 4) return fr_eval_launch<D, 4, false>(st, s, m);
-                return fr_eval_launch<D, 16, false>(st, s, m);
-            }));
-        }
+        GPX_TRY(gpx_fourier_eval_resident(st, s, m, G != nullptr, 0));
         GPX_TRY(fr_event(st, s, 3));
         for (int q = 0; q < S; ++q) {
             GPX_HIP(hipMemcpyAsync(F + (size_t)q * n + i0, st->F.d() + (size_t)q * m,

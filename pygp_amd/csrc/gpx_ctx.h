@@ -107,6 +107,9 @@ struct gpx_ctx {
     // sparse-spectrum GP on the resident data (fourier.hip), created on first use; buffers of
     // its own, valid for the data version its update read
     GpxSsgp *ssgp = nullptr;
+    // pathwise function sample (path.hip), created on first use; buffers of its own, a Fourier
+    // state of its own inside: what a fit read of the resident data it keeps as copies
+    GpxPath *path = nullptr;
     // look-ahead of the factorisation (chol.hip): diagonal blocks on a high-priority
     // stream, the left half of the inverse tree on a low-priority one
     hipStream_t crit = nullptr, aux = nullptr, bulk = nullptr;

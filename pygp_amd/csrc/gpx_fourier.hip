@@ -2,7 +2,8 @@
 // argument checks around the entry points of fourier.hip, which owns its buffers and kernels.
 // The sample has a state of its own on the handle (GpxFourier): no call here touches the
 // resident data, an exact factorisation or a sparse model. The same for the sparse-spectrum GP
-// of those features (gpx_ssgp_*, GpxSsgp), which reads the resident data.
+// of those features (gpx_ssgp_*, GpxSsgp), which reads the resident data, and for the pathwise
+// samples (gpx_path_*, GpxPath in path.hip), whose fit also reads the exact factorisation.
 
 #include "gpx_ctx.h"
 
@@ -247,6 +248,88 @@ int gpx_ssgp_timings(gpx_t *h, double *ms)
         return -1;
     }
     return gpx_ssgp_run_timings(h->ssgp, ms);
+}
+
+// ---- pathwise posterior function samples (gpx_path_*): a state of its own again (GpxPath, with
+// a Fourier state of its own inside). The fit reads the resident data and the exact
+// factorisation and completes R^-1 as gpx_exact_posterior does; nothing else outside the state
+// is written.
+
+int gpx_path_fit(gpx_t *h, const double *W, int64_t M, int64_t d, const double *b, double a,
+                 const double *P, const double *E, int64_t n, int64_t S, double *V, int *info)
+{
+    CHECK_H(h);
+    if (info) *info = 0;
+    GPX_TRY(require_factor(h, ST_PLAIN, LP_NONE, "gpx_path_fit"));
+    GPX_TRY(fourier_check("gpx_path_fit", W, M, d, b, a, h->mean, S));
+    if (!P || !E || !V) {
+        gpx_set_error("gpx_path_fit: P, E and V must not be null");
+        return -1;
+    }
+    if (h->d != d) {
+        gpx_set_error("gpx_path_fit: W has %lld columns, the resident data %d", (long long)d,
+                      h->d);
+        return -1;
+    }
+    if (h->n != n) {
+        gpx_set_error("gpx_path_fit: E has %lld columns, the resident data %d rows", (long long)n,
+                      h->n);
+        return -1;
+    }
+    GPX_TRY(gpx_path_kernel_check(h->kp, "gpx_path_fit"));
+    GPX_TRY(fourier_finite("gpx_path_fit", "P", P, S * M));
+    GPX_TRY(fourier_finite("gpx_path_fit", "E", E, S * h->n));
+    return gpx_path_run_fit(&h->path, h->stream, h->ws(), &h->w_complete, h->kp, h->log_sn,
+                            h->mean, h->X.as<double>(), h->y.as<double>(), h->n, h->d, W, (int)M,
+                            b, a, P, E, (int)S, V);
+}
+
+int gpx_path_set(gpx_t *h, const gpx_kspec *k, double mean, const double *X, int64_t n, int64_t d,
+                 const double *W, int64_t M, const double *b, double a, const double *theta,
+                 const double *V, int64_t S)
+{
+    CHECK_H(h);
+    GPX_TRY(fourier_check("gpx_path_set", W, M, d, b, a, mean, S));
+    if (!theta || n < 0 || n > (1 << 20) || (n > 0 && (!X || !V))) {
+        gpx_set_error("gpx_path_set: bad arguments (theta null, n outside 0 .. 2^20, or X or V "
+                      "null with n > 0)");
+        return -1;
+    }
+    KParams kp;
+    GPX_TRY(gpx_flatten_kspec(k, d, &kp));
+    GPX_TRY(gpx_path_kernel_check(kp, "gpx_path_set"));
+    GPX_TRY(fourier_finite("gpx_path_set", "theta", theta, S * M));
+    if (n > 0) {
+        GPX_TRY(fourier_finite("gpx_path_set", "X", X, n * d));
+        GPX_TRY(fourier_finite("gpx_path_set", "V", V, S * n));
+    }
+    return gpx_path_run_set(&h->path, h->stream, kp, mean, X, (int)n, (int)d, W, (int)M, b, a,
+                            theta, V, (int)S);
+}
+
+int gpx_path_eval(gpx_t *h, const double *Xs, int64_t m, double *F, double *G)
+{
+    CHECK_H(h);
+    if (!gpx_path_ready(h->path)) {
+        gpx_set_error("gpx_path_eval: no sample (call gpx_path_fit or gpx_path_set)");
+        return -1;
+    }
+    if (!Xs || !F || m < 1 || m > (1 << 20)) {
+        gpx_set_error("gpx_path_eval: bad arguments (1 <= m <= 2^20)");
+        return -1;
+    }
+    GPX_TRY(fourier_finite("gpx_path_eval", "Xs", Xs, m * gpx_path_dim(h->path)));
+    return gpx_path_run_eval(h->path, h->stream, Xs, m, F, G);
+}
+
+int gpx_path_timings(gpx_t *h, double *ms)
+{
+    CHECK_H(h);
+    if (!ms) {
+        gpx_set_error("gpx_path_timings: ms is null");
+        return -1;
+    }
+    return gpx_path_run_timings(h->path, ms);
 }
 
 }  // extern "C"

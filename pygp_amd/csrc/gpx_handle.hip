@@ -242,6 +242,10 @@ int gpx_destroy(gpx_t *h)
         gpx_fourier_destroy(h->fourier);
         h->fourier = nullptr;
     }
+    if (h->path) {
+        gpx_path_destroy(h->path);
+        h->path = nullptr;
+    }
     if (h->ssgp) {
         gpx_ssgp_destroy(h->ssgp);
         h->ssgp = nullptr;

@@ -654,6 +654,33 @@ int gpx_ssgp_run_get(GpxSsgp *st, hipStream_t s, double *beta);
 int gpx_ssgp_run_timings(const GpxSsgp *st, double *ms);
 void gpx_ssgp_destroy(GpxSsgp *st);
 
+// ---- pathwise posterior function samples (path.hip) ------------------------------------------
+// One sample set per handle, in buffers of its own: f_s(x) = mean + ft_s(x) + k(x, X) v_s with
+// the prior ft_s over M features (W, b, a, theta_s) and v_s = (K + sn2 I)^-1 (y - mean - ft_s(X)
+// - sn e_s). *state is created on first use (per handle). kp: one SE or Matern part
+// (gpx_path_kernel_check refuses every other kernel with a message).
+// fit: behind the factorisation w of K + sn2 I on Xdev, ydev (device, n x d): theta = P (S x M),
+// e = E (S x n); V (S x n) is written back. R, a and K^-1 are only read; *w_complete false: the
+// rest of R^-1 is completed first (gpx_trtri) and the flag set.
+struct GpxPath;
+int gpx_path_kernel_check(const KParams &kp, const char *what);
+int gpx_path_run_fit(GpxPath **state, hipStream_t s, const DenseWs &w, bool *w_complete,
+                     const KParams &kp, double log_sn, double mean, const double *Xdev,
+                     const double *ydev, int n, int d, const double *W, int M, const double *b,
+                     double a, const double *P, const double *E, int S, double *V_out);
+// installs a given sample: X (n x d, host; n == 0: the prior alone), theta (S x M), V (S x n)
+int gpx_path_run_set(GpxPath **state, hipStream_t s, const KParams &kp, double mean,
+                     const double *X, int n, int d, const double *W, int M, const double *b,
+                     double a, const double *theta, const double *V, int S);
+bool gpx_path_ready(const GpxPath *st);
+int gpx_path_dim(const GpxPath *st);
+// F[S][m] and G[S][m][d] (or null) at the m host points Xs
+int gpx_path_run_eval(GpxPath *st, hipStream_t s, const double *Xs, int64_t m, double *F,
+                      double *G);
+// ms[4]: the last fit, the last evaluation, its feature term, its data term
+int gpx_path_run_timings(const GpxPath *st, double *ms);
+void gpx_path_destroy(GpxPath *st);
+
 // d k / d x2 (sign = +1) or d k / d x1 (sign = -1): out[n1][n2][d]
 int gpx_kgrady(hipStream_t s, const KParams &kp, const double *X1, int n1, const double *X2,
                int n2, int d, double sign, double *out);

@@ -11,6 +11,8 @@ from .vfe import VFE
 from .select import select_pseudoinputs
 from .fourier import FourierSample
 from .ssgp import SSGP
+from .pathwise import PathwiseSample
 
 __all__ = ['GP', 'ExactGP', 'BasicGP', 'GradientGP', 'MultiOutputGP', 'CoregionalGP', 'LaplaceGP',
-           'EPGP', 'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'FourierSample', 'SSGP']
+           'EPGP', 'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'FourierSample', 'SSGP',
+           'PathwiseSample']
