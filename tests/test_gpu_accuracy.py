@@ -30,6 +30,7 @@ import recipes
 import xprec as xp
 from conftest import run_child
 from helpers import amd_kernel, oracle_spec
+from kernel_truth import _leaf_budget, _budget, _entrywise, _points   # noqa: F401
 from oracle import gp_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -387,81 +388,7 @@ def test_groups_against_the_truth(tmp_path):
 
 # -- 3e: entry-wise kernel builds ---------------------------------------------------------
 
-def _leaf_budget(spec, X1, X2):
-    """(K, B, P): the longdouble kernel value, its conditioning budget per entry in units of
-    eps * |K| (c plus the magnitude of the exp argument, and for Periodic that of the sine's
-    argument times its sensitivity), and the conditioning of the factors its gradients add
-    (Periodic only: they carry D cos D with D = pi r / p; the others' factors are
-    distances, conditioned by a few eps)."""
-    s = xp.ld_spec(spec)
-    A, Bx = xp.ld(X1), xp.ld(X2)
-    K = orc.kernel_get(s, A, Bx)
-    kind = s['kind']
-    lsf = abs(float(s['logsf'])) * 2
-    P = 0.0
-    if kind == 'se':
-        ell = np.exp(s['logell'])
-        arg = orc._sqdist(A / ell, Bx / ell) / 2
-    elif kind == 'matern':
-        ell = np.exp(s['logell']) / np.sqrt(xp.LD(s['d']))
-        arg = np.sqrt(orc._sqdist(A / ell, Bx / ell))
-    elif kind == 'rq':
-        ell, al = np.exp(s['logell']), np.exp(s['logalpha'])
-        d2 = orc._sqdist(A / ell, Bx / ell)
-        arg = al * np.log1p(d2 / 2 / al) + d2 / 2
-    elif kind == 'periodic':
-        ell, p = np.exp(s['logell']), np.exp(s['logp'])
-        Dp = np.sqrt(orc._sqdist(A, Bx)) * orc._PI_LD / p
-        arg = (2 * np.sin(Dp) ** 2 + 4 * np.abs(np.sin(Dp) * np.cos(Dp)) * Dp) / ell ** 2 + Dp
-        P = (Dp * (1 + Dp)).astype(float)
-    else:
-        raise ValueError(kind)
-    return K, (8 + lsf + 4 * np.abs(arg)).astype(float), P
-
-
-def _budget(spec, X1, X2):
-    """(K, E, P): truth, absolute error budget / eps per entry, and the gradient factors'
-    conditioning, through sums and products."""
-    if spec['kind'] in ('sum', 'product'):
-        parts = [_budget(p, X1, X2) for p in spec['parts']]
-        P = np.max(np.broadcast_arrays(*[pp for _, _, pp in parts]), axis=0)
-        if spec['kind'] == 'sum':
-            return sum(k for k, _, _ in parts), sum(e for _, e, _ in parts), P
-        K = np.prod([k for k, _, _ in parts], axis=0)
-        E = 0
-        for i, (k, e, _) in enumerate(parts):
-            others = np.prod([np.abs(kk.astype(float)) for j, (kk, _, _) in enumerate(parts)
-                              if j != i], axis=0)
-            E = E + e * others
-        return K, E, P
-    K, b, P = _leaf_budget(spec, X1, X2)
-    return K, b * np.abs(K.astype(float)), P
-
-
-def _entrywise(got, truth, budget, eps, tiny, tag):
-    """|got - truth| <= budget * eps (+ a few smallest subnormals); zeros, infs and NaNs of
-    the truth (rounded to the device type) must be matched."""
-    t = truth.astype(got.dtype)
-    assert np.array_equal(np.isnan(got), np.isnan(t)), tag
-    assert np.array_equal(np.isinf(got), np.isinf(t)), tag
-    assert np.all(got[truth == 0] == 0), tag
-    fin = np.isfinite(t)
-    d = np.abs(got[fin].astype(xp.LD) - truth[fin]).astype(float)
-    lim = budget[fin] * eps + 4 * np.broadcast_to(tiny, budget.shape)[fin]
-    bad = d > lim
-    assert not bad.any(), '%s: %d entries, worst %.3g x its budget' % (
-        tag, bad.sum(), np.max(d / lim))
-    return float(np.max(d / lim))
-
-
-def _points(D, seed):
-    """Pairs whose distances run from 0 (coincident points) past the exp underflow."""
-    rng = np.random.RandomState(seed)
-    dirs = rng.randn(64, D)
-    dirs /= np.linalg.norm(dirs, axis=1)[:, None]
-    X1 = dirs * np.r_[0, np.logspace(-4, 2.3, 63)][:, None]
-    X2 = np.r_[X1[:8], rng.randn(24, D) * 0.3, rng.randn(16, D) * 30]
-    return X1, X2
+# the budgets and the points live in tests/kernel_truth.py (shared with the kernel grid)
 
 
 @pytest.mark.parametrize('name', sorted(recipes.MID_CASES))
