@@ -581,6 +581,76 @@ int gpx_ssgp_get(gpx_t *h, double *beta);
  * ms[6] A^-1 with its trace, when a gpx_ssgp_loglik formed it (0: none, or a posterior did) */
 int gpx_ssgp_timings(gpx_t *h, double *ms);
 
+/* ---- matrix-free exact GP regression by preconditioned CG (own design) ---- */
+/* The exact model of gpx_exact_* on the handle's resident data (gpx_set_data) without an
+ * N x N matrix: with Kh = K(X, X) + sn^2 I, never stored, every product Kh V is recomputed from
+ * the inputs (O(N) memory, O(N^2) work an iteration), for n <= 2^20 and d <= GPX_MAX_DIM.
+ * The preconditioner is P = L^T L + sn^2 I with L the r x N factor panel of the pivoted partial
+ * Cholesky factorisation of K(X, X) (the selection of gpx_select_pivots, run inside the
+ * model's own state), applied as P^-1 v = (v - L^T (sn^2 I + L L^T)^-1 L v) / sn^2.
+ * Vectors cross this interface as columns: column c of an array of nb columns is the n
+ * contiguous doubles at + c * n.
+ * The model lives in a state of its own: no gpx_iter_* call touches the resident data, an exact
+ * factorisation, a sparse, sparse-spectrum, Fourier or pathwise state of the handle or the state
+ * of gpx_select_pivots, and none of those touches it; after gpx_set_data the entries below ask
+ * for a new update. Every sum has a fixed order and no column's sums depend on the other
+ * columns of a call: the same call returns the same bits. */
+#define GPX_ITER_CMAX 32       /* columns of one batched solve: 1 + probes <= GPX_ITER_CMAX */
+/* The standard-normal draws of the t probes, uploaded once and reused by every update: G1[t*rank]
+ * (probe c at + c * rank; NULL with rank = 0) and G2[t*n] for the n resident rows. An update
+ * forms z_c = L^T g1_c + sn g2_c ~ N(0, P); with fewer pivots than rank (an early stop) the
+ * leading entries of g1_c are used. 0 <= t < GPX_ITER_CMAX, 0 <= rank <= GPX_SPARSE_MAX_P.
+ * t = 0: no probes; alpha, the posterior and the solves are as with any t, gpx_iter_loglik's
+ * logdet is logdet P alone and its weight q = alpha alpha^T (IterativeGP asks for t >= 1). */
+int gpx_iter_set_probes(gpx_t *h, const double *G1, const double *G2, int64_t t, int64_t rank);
+/* Selects at most `rank` pivots (0: none, P = sn^2 I; the selection stops early as
+ * gpx_select_pivots with tol = 0 does), factors sn^2 I + L L^T on the host, and solves
+ * Kh [alpha | U] = [y - mean | Z] from zero by one batched PCG run in which every column keeps
+ * its own step lengths and is frozen once |r| <= tol |b|. The run ends when every column is
+ * frozen or after max_iter iterations: *iters is their count; *info is 0, or 1 + the column with
+ * the largest |r| / |b| among those not frozen (0: alpha). The model is usable either way and
+ * holds the last iterate. One host synchronisation per iteration (a block of 9 x 32 doubles).
+ * rank within gpx_select_pivots' limits. The r x r matrix sn^2 I + L L^T is factored and inverted
+ * on the host in every update, work of order r^3 in plain loops (about 10^11 operations at r =
+ * 4096): the preconditioner is meant for r of a few hundred. */
+int gpx_iter_update(gpx_t *h, const gpx_kspec *k, double log_sn, double mean, int64_t rank,
+                    double tol, int64_t max_iter, int64_t *iters, int *info);
+/* lZ = -(y - mean).alpha / 2 - logdet / 2 - n / 2 log 2 pi with the stochastic Lanczos estimate
+ * logdet = logdet P + 1/t sum_c (z_c^T P^-1 z_c) e1^T log(T_c) e1, T_c the tridiagonal of column
+ * c's PCG coefficients (its eigenproblem is solved on the host) and logdet P exact from the
+ * r x r factor. dlZ != NULL: dlZ[1 + nhyper + 1] in the layout [log sn | kernel | mean]: the
+ * kernel components (1/2) sum_ij q_ij dK_ij/dtheta, q = alpha alpha^T - 1/t sum_c sym(u_c
+ * v_c^T) with u_c = Kh^-1 z_c and v_c = P^-1 z_c, in one trace pass; sn^2 tr(q); sum alpha. The
+ * estimates are deterministic functions of the hypers for given draws. */
+int gpx_iter_loglik(gpx_t *h, double *lZ, double *dlZ);
+/* mu[m] = mean + k(Xs, X) alpha and s2[m] = k(x, x) - k_*^T Kh^-1 k_* at the m rows of
+ * Xs[m*d], 1 <= m <= 4096: the cross-covariance columns through the update's PCG (its tol and
+ * max_iter) in blocks of at most GPX_ITER_CMAX right-hand sides. A column that does not converge
+ * is an error. */
+int gpx_iter_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2);
+/* mu[m] and Sigma[m*m] = K(Xs, Xs) - K(Xs, X) Kh^-1 K(X, Xs): the same solves, then one product
+ * on the tile engine, symmetrised; 1 <= m <= 1024 */
+int gpx_iter_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma);
+/* out = Kh^-1 B for the nb columns of B (1 <= nb <= 4096), blocks of GPX_ITER_CMAX columns;
+ * *iters: the most iterations a block took. A column that does not converge is an error. */
+int gpx_iter_solve(gpx_t *h, const double *B, int64_t nb, double *out, int64_t *iters);
+/* out = Kh V for the nv columns of V, 1 <= nv <= GPX_ITER_CMAX: the wide product on its own
+ * (passes of 16 columns; a column's result does not depend on nv) */
+int gpx_iter_apply(gpx_t *h, const double *V, int64_t nv, double *out);
+/* what the last update left, each or NULL: alpha[n], U[t*n] = Kh^-1 Z, V[t*n] = P^-1 Z; the PCG
+ * coefficients a[iters*(t+1)] and b[iters*(t+1)] (row k: iteration k, 0 behind a column's last
+ * iteration); per column its iterations nit[t+1] and z^T P^-1 z, rz0[t+1]; *logdetP */
+int gpx_iter_get(gpx_t *h, double *alpha, double *U, double *V, double *a, double *b, double *nit,
+                 double *rz0, double *logdetP);
+/* ms[GPX_ITER_NTIMES] of the last calls on this handle (HIP events): the selection; the whole
+ * update; its iteration count; over its iterations the sums of the product, the preconditioner
+ * and the vector and coefficient work; the trace pass of the last gpx_iter_loglik with dlZ;
+ * the last posterior; the product of the last gpx_iter_apply */
+enum { GPX_ITER_MS_SELECT = 0, GPX_ITER_MS_UPDATE, GPX_ITER_MS_ITERS, GPX_ITER_MS_PRODUCT,
+       GPX_ITER_MS_PRECOND, GPX_ITER_MS_VECTOR, GPX_ITER_MS_TRACE, GPX_ITER_MS_POSTERIOR,
+       GPX_ITER_MS_APPLY, GPX_ITER_NTIMES };
+int gpx_iter_timings(gpx_t *h, double *ms);
+
 /* ---- instrumentation ---------------------------------------------------- */
 /* per-stage GPU times (ms) of the last gpx_exact_eval / update+loglik measured
  * with HIP events on the handle's stream. names via gpx_timing_name(i). */

@@ -7,7 +7,8 @@ log-likelihood (+gradient) / posterior, the sparse FITC / DTC / VFE models and b
 classification by Laplace's approximation (LaplaceGP) and by expectation propagation (EPGP),
 correlated outputs at their own inputs (CoregionalGP) and posterior function samples through
 random Fourier features (FourierSample) with their regression model (SSGP) and by pathwise
-conditioning on the exact solve (PathwiseSample), executed by hand-written HIP kernels in libgpx.so; `batch` and `meta` route the
+conditioning on the exact solve (PathwiseSample), and matrix-free exact regression by
+preconditioned conjugate gradients (IterativeGP), executed by hand-written HIP kernels in libgpx.so; `batch` and `meta` route the
 per-sample loops of the reference's meta-models through the batched entry points.
 """
 
@@ -19,9 +20,9 @@ from . import batch
 from . import meta
 from .inference import (BasicGP, ExactGP, GradientGP, MultiOutputGP, CoregionalGP, LaplaceGP,
                         EPGP, FITC, DTC, VFE, select_pseudoinputs, FourierSample, SSGP,
-                        PathwiseSample)
+                        PathwiseSample, IterativeGP)
 from .learning import optimize
 
 __all__ = ['BasicGP', 'ExactGP', 'GradientGP', 'MultiOutputGP', 'CoregionalGP', 'LaplaceGP', 'EPGP',
-           'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'FourierSample', 'SSGP', 'PathwiseSample', 'optimize', 'kernels', 'likelihoods', 'inference', 'learning',
+           'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'FourierSample', 'SSGP', 'PathwiseSample', 'IterativeGP', 'optimize', 'kernels', 'likelihoods', 'inference', 'learning',
            'batch', 'meta']

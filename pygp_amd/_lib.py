@@ -156,6 +156,16 @@ SIGNATURES = {
     'gpx_ssgp_posterior_full': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     'gpx_ssgp_get': (C.c_int, [_vp, _vp]),
     'gpx_ssgp_timings': (C.c_int, [_vp, _vp]),
+    'gpx_iter_set_probes': (C.c_int, [_vp, _vp, _vp, _i64, _i64]),
+    'gpx_iter_update': (C.c_int, [_vp, C.POINTER(_KSpec), C.c_double, C.c_double, _i64,
+                                  C.c_double, _i64, C.POINTER(_i64), _ip]),
+    'gpx_iter_loglik': (C.c_int, [_vp, _dp, _vp]),
+    'gpx_iter_posterior': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    'gpx_iter_posterior_full': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    'gpx_iter_solve': (C.c_int, [_vp, _vp, _i64, _vp, C.POINTER(_i64)]),
+    'gpx_iter_apply': (C.c_int, [_vp, _vp, _i64, _vp]),
+    'gpx_iter_get': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dp]),
+    'gpx_iter_timings': (C.c_int, [_vp, _vp]),
     'gpx_loglik_batch': (C.c_int, [_vp, C.POINTER(_KSpec), _vp, _i64, C.c_int,
                                    _vp, _vp, _vp]),
     'gpx_batch_plan': (C.c_int, [_vp, _i64, C.c_int, _ip]),
@@ -448,6 +458,7 @@ class Handle(object):
             raise ValueError('X and y disagree')
         check(self._L.gpx_set_data(self._h, _ptr(X), X.shape[0], X.shape[1],
                                    _ptr(y)))
+        self._data_shape = X.shape
 
     def exact_update(self, spec, log_sn, mean):
         info = C.c_int(0)
@@ -905,6 +916,106 @@ class Handle(object):
         ms = np.zeros(7)
         check(self._L.gpx_ssgp_timings(self._h, _ptr(ms)))
         return ms
+
+    # -- matrix-free exact regression on the resident data (a state of the handle's own) --
+    # the order of gpx.h's GPX_ITER_MS_* (tests/test_iter_host.py holds the two together)
+    ITER_TIMES = ('select', 'update', 'iters', 'product', 'precond', 'vector', 'trace',
+                  'posterior', 'apply')
+    _data_shape = (0, 0)            # (n, d) of the last set_data of this handle
+    _iter_probes = None             # probes of the last iter_set_probes, for _data_shape's rows
+    _iter_shape = (0, 0, 0, 0)      # (n, d, probes, nhyper) of the last iter_update
+    _iter_iters = 0
+
+    def iter_set_probes(self, G1, G2):
+        """The standard-normal draws g1 (probes, rank) and g2 (probes, n) of the resident rows."""
+        G1, G2 = _f64(G1, 2), _f64(G2, 2)
+        if G1.shape[0] != G2.shape[0]:
+            raise ValueError('shapes of G1 and G2 do not agree')
+        if G2.shape[1] != self._data_shape[0]:
+            raise ValueError('G2 has %d columns, the resident data %d rows'
+                             % (G2.shape[1], self._data_shape[0]))
+        self._iter_probes = None
+        self._iter_shape = (0, 0, 0, 0)
+        check(self._L.gpx_iter_set_probes(self._h, _ptr(G1) if G1.size else None,
+                                          _ptr(G2) if G2.size else None, G2.shape[0],
+                                          G1.shape[1]))
+        self._iter_probes = G2.shape[0]
+
+    def iter_update(self, spec, log_sn, mean, rank, tol, max_iter):
+        """One batched PCG run on the resident data; returns (iterations, info): info 0, or
+        1 + the worst column that did not reach tol. The sizes every later result is read with
+        are the handle's own: the rows of set_data and the probes of iter_set_probes."""
+        if self._iter_probes is None:
+            raise GpxError('iter_update: no probes (call iter_set_probes)')
+        iters, info = _i64(0), C.c_int(0)
+        self._iter_shape = (0, 0, 0, 0)
+        check(self._L.gpx_iter_update(self._h, spec.ref(), float(log_sn), float(mean), int(rank),
+                                      float(tol), int(max_iter), C.byref(iters), C.byref(info)))
+        self._iter_shape = tuple(self._data_shape) + (self._iter_probes, spec.c.nhyper)
+        self._iter_iters = int(iters.value)
+        return self._iter_iters, info.value
+
+    def iter_loglik(self, grad=False):
+        return self._loglik(self._L.gpx_iter_loglik, self._iter_shape[3] + 2, grad)
+
+    def _iter_points(self, Xs):
+        Xs = _f64(Xs, 2)
+        if self._iter_shape[0] == 0:
+            raise GpxError('no iterative model (call iter_update)')
+        if Xs.shape[1] != self._iter_shape[1]:
+            raise ValueError('test inputs have the wrong dimension')
+        return Xs
+
+    def iter_posterior(self, Xs):
+        return self._posterior(self._L.gpx_iter_posterior, self._iter_points(Xs), False)
+
+    def iter_posterior_full(self, Xs):
+        return self._posterior(self._L.gpx_iter_posterior_full, self._iter_points(Xs), True)
+
+    def _iter_columns(self, B):
+        """B (n,) or (n, nb) -> (flat, its columns as contiguous rows)."""
+        B = _f64(B)
+        n = self._iter_shape[0]
+        if n == 0:
+            raise GpxError('no iterative model (call iter_update)')
+        if B.ndim not in (1, 2) or B.shape[0] != n:
+            raise ValueError('expected %d rows' % n)
+        return B.ndim == 1, np.ascontiguousarray(B.reshape(n, -1).T)
+
+    def iter_solve(self, B):
+        """(K + sn^2 I)^-1 B for B (n,) or (n, nb)."""
+        flat, Bt = self._iter_columns(B)
+        out, iters = np.empty_like(Bt), _i64(0)
+        check(self._L.gpx_iter_solve(self._h, _ptr(Bt), Bt.shape[0], _ptr(out), C.byref(iters)))
+        return out[0].copy() if flat else np.ascontiguousarray(out.T)
+
+    def iter_apply(self, V):
+        """(K + sn^2 I) V for V (n,) or (n, nv <= 32), without storing K."""
+        flat, Vt = self._iter_columns(V)
+        out = np.empty_like(Vt)
+        check(self._L.gpx_iter_apply(self._h, _ptr(Vt), Vt.shape[0], _ptr(out)))
+        return out[0].copy() if flat else np.ascontiguousarray(out.T)
+
+    def iter_get(self):
+        """What the last update left: dict of alpha (n,), U, V (n, probes), the coefficients a, b
+        (iterations, 1 + probes), nit, rz0 (1 + probes,) and logdetP."""
+        n, _, t, _ = self._iter_shape
+        if n == 0:
+            raise GpxError('no iterative model (call iter_update)')
+        k = self._iter_iters
+        alpha, U, V = np.empty(n), np.empty((t, n)), np.empty((t, n))
+        a, b = np.zeros((k, 1 + t)), np.zeros((k, 1 + t))
+        nit, rz0, ldp = np.empty(1 + t), np.empty(1 + t), C.c_double(0)
+        check(self._L.gpx_iter_get(self._h, _ptr(alpha), _ptr(U), _ptr(V), _ptr(a), _ptr(b),
+                                   _ptr(nit), _ptr(rz0), C.byref(ldp)))
+        return dict(alpha=alpha, U=np.ascontiguousarray(U.T), V=np.ascontiguousarray(V.T), a=a,
+                    b=b, nit=nit.astype(int), rz0=rz0, logdetP=ldp.value)
+
+    def iter_timings(self):
+        """HIP-event ms of the last calls by name (ITER_TIMES; 'iters' is a count)."""
+        ms = np.zeros(len(self.ITER_TIMES))
+        check(self._L.gpx_iter_timings(self._h, _ptr(ms)))
+        return dict(zip(self.ITER_TIMES, ms))
 
     def sparse_get_state(self, p):
         F1, F2, v = np.empty((p, p)), np.empty((p, p)), np.empty(p)

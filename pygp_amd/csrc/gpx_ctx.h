@@ -1,6 +1,6 @@
 // The handle behind gpx_t and what the units of the C ABI (gpx_handle.hip, gpx_batch.hip,
 // gpx_kernels.hip, gpx_exact.hip, gpx_posterior.hip, gpx_labels.hip, gpx_sparse.hip,
-// gpx_fourier.hip, gpx_la.hip) share among themselves: the handle's state, the stage clock, and the host functions that cross
+// gpx_fourier.hip, gpx_iter.hip, gpx_la.hip) share among themselves: the handle's state, the stage clock, and the host functions that cross
 // a unit, in the namespace gpxh. Private to those units: the device-side units see
 // gpx_internal.h only.
 #pragma once
@@ -110,6 +110,9 @@ struct gpx_ctx {
     // pathwise function sample (path.hip), created on first use; buffers of its own, a Fourier
     // state of its own inside: what a fit read of the resident data it keeps as copies
     GpxPath *path = nullptr;
+    // matrix-free exact regression on the resident data (iter.hip), created on first use;
+    // buffers of its own, valid for the data version its update read
+    GpxIter *iter = nullptr;
     // look-ahead of the factorisation (chol.hip): diagonal blocks on a high-priority
     // stream, the left half of the inverse tree on a low-priority one
     hipStream_t crit = nullptr, aux = nullptr, bulk = nullptr;

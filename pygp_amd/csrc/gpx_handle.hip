@@ -250,6 +250,10 @@ int gpx_destroy(gpx_t *h)
         gpx_ssgp_destroy(h->ssgp);
         h->ssgp = nullptr;
     }
+    if (h->iter) {
+        gpx_iter_destroy(h->iter);
+        h->iter = nullptr;
+    }
     if (h->groups) {
         DLOG("groups");
         gpx_groups_destroy(h->groups);

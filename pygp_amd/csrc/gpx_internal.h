@@ -612,6 +612,44 @@ int gpx_select_run(GpxSelect **state, hipStream_t s, const KParams &kp, const do
                    double *piv, double *trace, int64_t *count);
 double gpx_select_ms(const GpxSelect *st);   // HIP-event ms of the last run's launches
 void gpx_select_destroy(GpxSelect *st);
+// the r x N factor panel of the last run, on the device (the iterative state's preconditioner)
+const double *gpx_select_panel(const GpxSelect *st, long long *ld);
+
+// ---- matrix-free exact regression by preconditioned CG (iter.hip) -----------------------------
+// One model per handle, in buffers of its own (a selection state of its own among them): the
+// pivots' panel L, the probes, alpha, U = Kh^-1 Z, V = P^-1 Z and the coefficients of the last
+// batched PCG run on the resident data X, y (device). *state is created on first use.
+struct GpxIter;
+int gpx_iter_run_set_probes(GpxIter **state, hipStream_t s, const double *G1, const double *G2,
+                            int t, int rank, long n);
+// *info: 0, or 1 + the worst column that did not reach tol within max_iter (the state is ready
+// either way and holds the last iterate)
+int gpx_iter_run_update(GpxIter **state, hipStream_t s, const KParams &kp, double log_sn,
+                        double mean, const double *X, const double *y, int n, int d, long version,
+                        int rank, double tol, int max_iter, int *iters, int *info);
+bool gpx_iter_ready(const GpxIter *st, long version);
+int gpx_iter_dim(const GpxIter *st);
+// probes are uploaded and were drawn for n rows and `rank` pivots
+bool gpx_iter_probes_match(const GpxIter *st, int n, int rank);
+int gpx_iter_run_loglik(GpxIter *st, hipStream_t s, const double *X, double *lZ, double *dlZ);
+int gpx_iter_run_apply(GpxIter *st, hipStream_t s, const double *V, int nv, double *out);
+int gpx_iter_run_solve(GpxIter *st, hipStream_t s, const double *B, int nb, double *out,
+                       int *iters, int *info);
+int gpx_iter_run_posterior(GpxIter *st, hipStream_t s, const double *X, const double *Xt, int m,
+                           double *mu, double *s2, double *Sigma, int *info);
+int gpx_iter_run_get(GpxIter *st, hipStream_t s, double *alpha, double *U, double *V, double *a,
+                     double *b, double *nit, double *rz0, double *logdetP);
+int gpx_iter_run_timings(const GpxIter *st, double *ms);
+void gpx_iter_destroy(GpxIter *st);
+// The trace pass with the low-rank pair weight q_ij = sum_c (a_ic b_jc + b_ic a_jc) / 2 and no
+// K^-1: acc[0] = tr(q), acc[1 + h] = sum_ij q_ij dK_ij/dtheta_h. A, B: C <= GPX_ITER_CMAX
+// columns, vs apart. partial: gpx_pairs_trace_scratch(kp, np) doubles (0: the per-tile form at
+// an np whose partial sums exceed 2^31 doubles); Xs: the inputs already scaled per part,
+// [nparts][np][gpx_dmax(d)] with rows >= n repeating row n - 1 (xscale_kernel's values).
+size_t gpx_pairs_trace_scratch(const KParams &kp, int np);
+int gpx_pairs_trace_grad(hipStream_t s, const KParams &kp, const double *X, int n, int np, int d,
+                         const double *A, const double *B, int C, long long vs, double *partial,
+                         const double *Xs, double *acc);
 
 // ---- Fourier-feature function samples (fourier.hip) -------------------------------------
 // One sample set per handle, in buffers of its own: M features (W: M x d, b, the scale a), S

@@ -86,6 +86,8 @@ int gpx_kgrad(hipStream_t s, const KParams &kp, const double *X1, int n1,
 // alpha_it alpha_jt with A = [alpha_1 .. alpha_T], column t at A + t vs. Everything else of the
 // pass is the same, so the kernels below are written once over a weight W:
 //   W::NT                      rows of LDS the row side takes: ai_s[NT][KT]
+//   W::KINV                    the weight reads K^-1 (false: its loads are compiled out and q()
+//                              gets 0)
 //   stage(ai_s, i0, n)         the row side of the workgroup's 64 rows into LDS (if W::STAGED:
 //                              the caller's barrier follows)
 //   column(ai_s, ig, cj)       the column side of a tile: this lane's column cj, held in
@@ -98,6 +100,7 @@ template <bool LDS>
 struct TraceWeight1 {
     static constexpr int NT = 1;
     static constexpr bool STAGED = LDS;
+    static constexpr bool KINV = true;
     const double *__restrict__ alpha;
     double aj;
     __device__ __forceinline__ void stage(double (*ai_s)[KT], int i0, int n) const
@@ -119,6 +122,7 @@ struct TraceWeight1 {
 struct TraceWeightT {
     static constexpr int NT = GPX_MO_TMAX;
     static constexpr bool STAGED = true;
+    static constexpr bool KINV = true;
     const double *__restrict__ A;
     int T;
     long long vs;
@@ -156,6 +160,7 @@ struct TraceWeightT {
 struct TraceWeightTask {
     static constexpr int NT = 1 + GPX_ICM_TMAX;
     static constexpr bool STAGED = true;
+    static constexpr bool KINV = true;
     const double *__restrict__ alpha;
     const int *__restrict__ task;
     const double *__restrict__ par;
@@ -179,6 +184,46 @@ struct TraceWeightTask {
                                         double kinv) const
     {
         return (kinv - ai_s[0][ig * 16 + ii] * aj) * brow[ii];
+    }
+};
+// A low-rank weight that reads no K^-1 (the iterative model, iter.hip): q_ij = sum_c (a_ic b_jc +
+// b_ic a_jc) / 2 for the C <= GPX_ITER_CMAX columns of A and B (column c at + c vs). Staged like
+// TraceWeightT: the 64 x 2C block of the row side once per workgroup (ai_s[c] = a, ai_s[C + c] =
+// b), the column side two loads per lane and c, one FMA chain over c per pair. KINV = false
+// compiles the loads of K^-1 out of both trace bodies.
+struct TraceWeightPairs {
+    static constexpr int NT = 2 * GPX_ITER_CMAX;
+    static constexpr bool STAGED = true;
+    static constexpr bool KINV = false;
+    const double *__restrict__ A;
+    const double *__restrict__ B;
+    int C;
+    long long vs;
+    double qq[16];
+    __device__ __forceinline__ void stage(double (*ai_s)[KT], int i0, int n) const
+    {
+        for (int e = threadIdx.x; e < 2 * C * KT; e += 256) {
+            const int t = e / KT, r = e - t * KT;
+            const double *src = t < C ? A + t * vs : B + (t - C) * vs;
+            ai_s[t][r] = src[min(i0 + r, n - 1)];
+        }
+    }
+    __device__ __forceinline__ void column(const double (*ai_s)[KT], int ig, int cj)
+    {
+#pragma unroll
+        for (int ii = 0; ii < 16; ++ii) qq[ii] = 0.0;
+        for (int c = 0; c < C; ++c) {
+            const double aj = A[c * vs + cj], bj = B[c * vs + cj];
+#pragma unroll
+            for (int ii = 0; ii < 16; ++ii) {
+                qq[ii] = fma(ai_s[c][ig * 16 + ii], bj, qq[ii]);
+                qq[ii] = fma(ai_s[C + c][ig * 16 + ii], aj, qq[ii]);
+            }
+        }
+    }
+    __device__ __forceinline__ double q(const double (*)[KT], int, int ii, int, double) const
+    {
+        return 0.5 * qq[ii];
     }
 };
 
@@ -306,7 +351,7 @@ __device__ __forceinline__ void trace_tile_body(const KParams &kp, const double 
         if (gi < n && gj < n) wt = gi < gj ? 2.0 : (gi == gj ? 1.0 : 0.0);
         double q = 0.0;
         if (wt != 0.0) {
-            q = w.q(ai_s, ig, ii, gi, Kinv[(size_t)gi * ld + gj]);
+            q = w.q(ai_s, ig, ii, gi, W::KINV ? Kinv[(size_t)gi * ld + gj] : 0.0);
             if (gi == gj) trq += q;
         }
         wq[ii] = wt * q;
@@ -384,6 +429,15 @@ __global__ __launch_bounds__(256) void icm_trace_grad_kernel(
 {
     trace_tile_body<DMAX, MODE>(kp, X, n, d, Kinv, ld, TraceWeightTask{alpha, task, par, 0.0, nullptr},
                                 partial, nacc);
+}
+
+template <int DMAX, int MODE>
+__global__ __launch_bounds__(256) void pairs_trace_grad_kernel(
+    KParams kp, const double *__restrict__ X, int n, int d, const double *__restrict__ A,
+    const double *__restrict__ B, int C, long long vs, double *__restrict__ partial, int nacc)
+{
+    trace_tile_body<DMAX, MODE>(kp, X, n, d, nullptr, 0, TraceWeightPairs{A, B, C, vs, {}}, partial,
+                                nacc);
 }
 
 // ---- trace_grad, row-persistent form (sums of SE / Matern parts) ---------------
@@ -538,8 +592,9 @@ __device__ __forceinline__ void trace_rows_body(const KParams &kp, const double 
             } o;
 #pragma unroll
             for (int ii = 0; ii < 16; ++ii)
-                o.q[ii] = __builtin_bit_cast(
-                    double, __builtin_amdgcn_raw_buffer_load_b64(rK, gj * 8, rowoff + ii * ld * 8, 0));
+                o.q[ii] = W::KINV ? __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(
+                                                                   rK, gj * 8, rowoff + ii * ld * 8, 0))
+                                  : 0.0;
             w.column(ai_s, ig, min(gj, n - 1));
             const double2 *__restrict__ xp =
                 reinterpret_cast<const double2 *>(xs + (size_t)gj * DMAX);
@@ -643,6 +698,16 @@ __global__ __launch_bounds__(256, (DMAX == 16 ? 2 : 1)) void icm_trace_grad_rows
                                 partial, nacc, do_trq);
 }
 
+template <int DMAX, int KIND>
+__global__ __launch_bounds__(256, (DMAX == 16 ? 2 : 1)) void pairs_trace_grad_rows_kernel(
+    KParams kp, const double *__restrict__ Xs, int n, const double *__restrict__ A,
+    const double *__restrict__ B, int C, long long vs, double *__restrict__ partial, int nacc,
+    int do_trq)
+{
+    trace_rows_body<DMAX, KIND>(kp, Xs, n, nullptr, 0, TraceWeightPairs{A, B, C, vs, {}}, partial,
+                                nacc, do_trq);
+}
+
 // deterministic second stage: acc[h] = sum over blocks of partial[b][h]
 __global__ __launch_bounds__(256) void trace_reduce_kernel(
     const double *__restrict__ partial, int nblocks, int nacc, double *__restrict__ acc,
@@ -690,8 +755,11 @@ template <typename F> static int with_family(int kind, F &&f)
 static int trace_grad_launch(hipStream_t s, const KParams &kp, const double *X, int n, int np,
                              int d, const double *Kinv, int ld, const double *a, int nout,
                              long long vs, double *partial, double *acc, const MemberBatch *mb,
-                             int astride, const int *task = nullptr, const double *par = nullptr)
+                             int astride, const int *task = nullptr, const double *par = nullptr,
+                             const double *b2 = nullptr, const double *Xs_ready = nullptr)
 {
+    // b2 != null: the low-rank pair weight (a = A, b2 = B, nout = C columns, no K^-1); Xs_ready:
+    // the caller's scaled inputs, xscale_kernel's values in its layout: read, not formed again
     const int T = np / KT;
     const int nacc = 1 + kp.nhyper;
     const MemberView mv(mb);
@@ -707,13 +775,15 @@ static int trace_grad_launch(hipStream_t s, const KParams &kp, const double *X, 
     const dim3 grid(C, T, mv.members);
     if (rows) {
         const int dmax = gpx_dmax(d);
-        double *Xs = partial + (size_t)T * T * TG_MAXACC;
+        double *Xs_mine = partial + (size_t)T * T * TG_MAXACC;
+        const double *Xs = Xs_ready ? Xs_ready : Xs_mine;
         const dim3 xgrid((np * dmax + 255) / 256, kp.nparts, mv.members);
-        GPX_TRY(with_bool(mv.mp != nullptr, [&](auto batched) {
-            GPX_LAUNCH(xscale_kernel<decltype(batched)::value>, xgrid, dim3(256), 0, s, kp, X, n, d,
-                       np, dmax, Xs, mv.mp, pstride);
-            return 0;
-        }));
+        if (!Xs_ready)
+            GPX_TRY(with_bool(mv.mp != nullptr, [&](auto batched) {
+                GPX_LAUNCH(xscale_kernel<decltype(batched)::value>, xgrid, dim3(256), 0, s, kp, X,
+                           n, d, np, dmax, Xs_mine, mv.mp, pstride);
+                return 0;
+            }));
         bool trq_done = false;
         const int kinds[4] = {GPX_SE, GPX_MATERN1, GPX_MATERN3, GPX_MATERN5};
         for (int kind : kinds) {
@@ -725,6 +795,11 @@ static int trace_grad_launch(hipStream_t s, const KParams &kp, const double *X, 
             GPX_TRY(with_dmax(d, [&](auto dm) {
                 return with_family(kind, [&](auto kd) {
                     constexpr int DM = decltype(dm)::value, KD = decltype(kd)::value;
+                    if (b2) {
+                        GPX_LAUNCH((pairs_trace_grad_rows_kernel<DM, KD>), grid, dim3(256), 0, s,
+                                   kp, Xs, n, a, b2, nout, vs, partial, nacc, do_trq);
+                        return 0;
+                    }
                     if (task) {
                         GPX_LAUNCH((icm_trace_grad_rows_kernel<DM, KD>), grid, dim3(256), 0, s, kp,
                                    Xs, n, Kinv, ld, a, task, par, partial, nacc, do_trq);
@@ -748,6 +823,11 @@ static int trace_grad_launch(hipStream_t s, const KParams &kp, const double *X, 
         GPX_TRY(with_dmax(d, [&](auto dm) {
             return with_bool(simple, [&](auto plain) {       // MODE of GPX_GRAD_PAIR
                 constexpr int DM = decltype(dm)::value, MODE = decltype(plain)::value ? 1 : 0;
+                if (b2) {
+                    GPX_LAUNCH((pairs_trace_grad_kernel<DM, MODE>), grid, dim3(256), 0, s, kp, X, n,
+                               d, a, b2, nout, vs, partial, nacc);
+                    return 0;
+                }
                 if (task) {
                     GPX_LAUNCH((icm_trace_grad_kernel<DM, MODE>), grid, dim3(256), 0, s, kp, X, n,
                                d, Kinv, ld, a, task, par, partial, nacc);
@@ -791,6 +871,38 @@ int gpx_mo_trace_grad(hipStream_t s, const KParams &kp, const double *X, int n, 
         return -1;
     }
     return trace_grad_launch(s, kp, X, n, np, d, Kinv, ld, A, T, vs, partial, acc, nullptr, 0);
+}
+
+// The low-rank pair weight of the iterative model (TraceWeightPairs): no K^-1. The partial sums
+// are one slot row per workgroup: T x C of them in the row form, T x T in the per-tile form.
+static bool trace_simple(const KParams &kp)
+{
+    bool simple = kp.nprod == 0;
+    for (int p = 0; p < kp.nparts; ++p)
+        simple = simple && (kp.part[p].kind == GPX_SE || kp.part[p].kind == GPX_MATERN1 ||
+                            kp.part[p].kind == GPX_MATERN3 || kp.part[p].kind == GPX_MATERN5);
+    return simple;
+}
+
+size_t gpx_pairs_trace_scratch(const KParams &kp, int np)
+{
+    const size_t T = np / KT;
+    const int rows_env = gpx_env().trace_rows;
+    const size_t C = trace_simple(kp) && rows_env > 0 ? std::min<size_t>(T, rows_env) : T;
+    const size_t need = T * C * (size_t)(1 + kp.nhyper);
+    return need >= ((size_t)1 << 31) ? 0 : need;
+}
+
+int gpx_pairs_trace_grad(hipStream_t s, const KParams &kp, const double *X, int n, int np, int d,
+                         const double *A, const double *B, int C, long long vs, double *partial,
+                         const double *Xs, double *acc)
+{
+    if (C < 1 || C > GPX_ITER_CMAX || !A || !B || !Xs) {
+        gpx_set_error("gpx_pairs_trace_grad: bad arguments (C = %d)", C);
+        return -1;
+    }
+    return trace_grad_launch(s, kp, X, n, np, d, nullptr, 0, A, C, vs, partial, acc, nullptr, 0,
+                             nullptr, nullptr, B, Xs);
 }
 
 // ---- correlated outputs at their own inputs (gpx_icm_*) -----------------------------------

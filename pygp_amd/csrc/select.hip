@@ -36,6 +36,7 @@ struct GpxSelect {
     size_t host_bytes = 0;
     hipEvent_t ev[2] = {};
     double ms = 0;
+    long long ld = 0;               // row stride of L in the last run
 };
 
 // ---- reductions ----------------------------------------------------------------------
@@ -205,6 +206,14 @@ void gpx_select_destroy(GpxSelect *st)
 
 double gpx_select_ms(const GpxSelect *st) { return st ? st->ms : 0.0; }
 
+// the factor panel the last run left on the device (row j contiguous, *ld doubles apart; rows
+// behind the last pivot are not written)
+const double *gpx_select_panel(const GpxSelect *st, long long *ld)
+{
+    *ld = st ? st->ld : 0;
+    return st ? st->L.d() : nullptr;
+}
+
 // Xdev: device data (n x d) to select on, or null: Xhost is copied to the call's own buffer
 int gpx_select_run(GpxSelect **state, hipStream_t s, const KParams &kp, const double *Xdev,
                    const double *Xhost, int n, int d, int p, double tol, int64_t *idx,
@@ -214,6 +223,7 @@ int gpx_select_run(GpxSelect **state, hipStream_t s, const KParams &kp, const do
     GpxSelect *st = *state;
     const int pp = round_up(p, GPX_TILE), np = round_up(n, GPX_TILE);
     const long long ld = np;
+    st->ld = ld;
     const int nb = (np + SEL_T - 1) / SEL_T;
     const size_t off_piv = C_WORDS * sizeof(int), off_trace = off_piv + (size_t)p * 8,
                  off_idx = off_trace + (size_t)p * 8, res_bytes = off_idx + (size_t)p * 4;

@@ -12,7 +12,8 @@ from .select import select_pseudoinputs
 from .fourier import FourierSample
 from .ssgp import SSGP
 from .pathwise import PathwiseSample
+from .iterative import IterativeGP
 
 __all__ = ['GP', 'ExactGP', 'BasicGP', 'GradientGP', 'MultiOutputGP', 'CoregionalGP', 'LaplaceGP',
            'EPGP', 'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'FourierSample', 'SSGP',
-           'PathwiseSample']
+           'PathwiseSample', 'IterativeGP']

@@ -48,6 +48,11 @@ class HyperEnsemble(object):
         if isinstance(model, SSGP):
             raise TypeError('HyperEnsemble runs exact GPs only; %s is a feature model'
                             % type(model).__name__)
+        from .inference.iterative import IterativeGP
+        if isinstance(model, IterativeGP):
+            # its lZ is a stochastic estimate from its own probes: the batch would not return it
+            raise TypeError('HyperEnsemble runs exact GPs by factorisation only; %s is an '
+                            'iterative model' % type(model).__name__)
         from .inference._labels import LabelsGP
         if isinstance(model, LabelsGP):
             # ... with Gaussian noise: a classifier's hypers have no noise slot
