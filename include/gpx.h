@@ -651,6 +651,48 @@ enum { GPX_ITER_MS_SELECT = 0, GPX_ITER_MS_UPDATE, GPX_ITER_MS_ITERS, GPX_ITER_M
        GPX_ITER_MS_APPLY, GPX_ITER_NTIMES };
 int gpx_iter_timings(gpx_t *h, double *ms);
 
+/* ---- the variance cache of the iterative model (own design) ---- */
+/* Posterior means and variances at many test points, and their input gradients, without a solve
+ * a point. With Q (k_eff x n) an orthonormal basis of span{k(., x_p)} over the pivots x_p of the
+ * pivoted partial Cholesky factorisation of K(X, X), H = Q Kh Q^T = Lh Lh^T and C = Lh^-1 Q,
+ *   mu(x) = mean + k_*^T alpha (alpha of the update, exact to its tol),
+ *   s2_k(x) = k(x, x) - |C k_*|^2,   k_* = K(X, x):
+ * the Galerkin approximation of k_*^T Kh^-1 k_* on the subspace. Q^T (Q Kh Q^T)^-1 Q <= Kh^-1
+ * in the Loewner order, so s2_k never underestimates gpx_iter_posterior's s2 (the latent
+ * variance, same prior term, a slightly negative value is returned as it is); it does not grow
+ * with k and is exact once k_eff = n.
+ * gpx_icache_build, after gpx_iter_update: a selection of the cache's own with at most k
+ * pivots (1 <= k <= min(n, GPX_ITER_CACHE_KMAX), gpx_select_pivots' limits) and tol = 1e-10, so
+ * that float64 stops where extended precision would; *k_eff is the count. The rows of its panel
+ * are orthonormalised in order (Gram-Schmidt, twice against all earlier rows), Kh Q^T goes
+ * through the wide product of gpx_iter_apply, H through the tile engine; H is factored and its
+ * factor inverted on the host (work of order k^3 in plain loops), C is one product. The cache is
+ * dropped by gpx_iter_update, gpx_iter_set_probes and gpx_set_data; gpx_iter_solve,
+ * gpx_iter_posterior*, gpx_iter_apply and gpx_iter_loglik leave it valid.
+ * The entries carry a prefix of their own, gpx_icache_: gpx_iter_* stays the solver's set. */
+#define GPX_ITER_CACHE_KMAX 1024
+int gpx_icache_build(gpx_t *h, int64_t k, int64_t *k_eff);
+/* mu[m], s2[m] at the m rows of Xs[m*d], 1 <= m <= 2^20, as one product K(Xs, X) [alpha; C]^T
+ * on the matrix cores that never stores K(Xs, X); dmu and ds2 (both or neither, m*d each): the
+ * gradients of mu and s2 in the test inputs, row i at + i * d. A point's results do not depend
+ * on m or on the points that share its call. */
+int gpx_icache_eval(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2, double *dmu,
+                        double *ds2);
+/* out[m*nw] = K(Xs, X) W^T for the caller's W[nw*n] (row j at + j * n), 1 <= nw <= 1 +
+ * GPX_ITER_CACHE_KMAX, 1 <= m <= 2^20: the product of gpx_icache_eval on its own. Needs the
+ * model (gpx_iter_update), not the cache. */
+int gpx_icache_cross_apply(gpx_t *h, const double *Xs, int64_t m, const double *W, int64_t nw,
+                         double *out);
+/* the cache, each or NULL: pivots[k_eff], Q[k_eff*n], H[k_eff*k_eff], C[k_eff*n] (rows) */
+int gpx_icache_get(gpx_t *h, int64_t *pivots, double *Q, double *H, double *C);
+/* ms[GPX_ITER_CACHE_NTIMES]: of the last build the selection, the orthonormalisation, Kh Q^T,
+ * H with its factor (the host's share by the wall clock), C; of the last gpx_icache_eval or
+ * gpx_icache_cross_apply the product, and of the last eval the finish and the gradient pass */
+enum { GPX_ITER_CACHE_MS_SELECT = 0, GPX_ITER_CACHE_MS_ORTH, GPX_ITER_CACHE_MS_KQ,
+       GPX_ITER_CACHE_MS_H, GPX_ITER_CACHE_MS_C, GPX_ITER_CACHE_MS_CROSS,
+       GPX_ITER_CACHE_MS_FINISH, GPX_ITER_CACHE_MS_GRAD, GPX_ITER_CACHE_NTIMES };
+int gpx_icache_timings(gpx_t *h, double *ms);
+
 /* ---- instrumentation ---------------------------------------------------- */
 /* per-stage GPU times (ms) of the last gpx_exact_eval / update+loglik measured
  * with HIP events on the handle's stream. names via gpx_timing_name(i). */

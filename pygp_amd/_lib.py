@@ -166,6 +166,11 @@ SIGNATURES = {
     'gpx_iter_apply': (C.c_int, [_vp, _vp, _i64, _vp]),
     'gpx_iter_get': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dp]),
     'gpx_iter_timings': (C.c_int, [_vp, _vp]),
+    'gpx_icache_build': (C.c_int, [_vp, _i64, C.POINTER(_i64)]),
+    'gpx_icache_eval': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    'gpx_icache_cross_apply': (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp]),
+    'gpx_icache_get': (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    'gpx_icache_timings': (C.c_int, [_vp, _vp]),
     'gpx_loglik_batch': (C.c_int, [_vp, C.POINTER(_KSpec), _vp, _i64, C.c_int,
                                    _vp, _vp, _vp]),
     'gpx_batch_plan': (C.c_int, [_vp, _i64, C.c_int, _ip]),
@@ -459,6 +464,7 @@ class Handle(object):
         check(self._L.gpx_set_data(self._h, _ptr(X), X.shape[0], X.shape[1],
                                    _ptr(y)))
         self._data_shape = X.shape
+        self._iter_cache_rank = 0
 
     def exact_update(self, spec, log_sn, mean):
         info = C.c_int(0)
@@ -936,6 +942,7 @@ class Handle(object):
                              % (G2.shape[1], self._data_shape[0]))
         self._iter_probes = None
         self._iter_shape = (0, 0, 0, 0)
+        self._iter_cache_rank = 0
         check(self._L.gpx_iter_set_probes(self._h, _ptr(G1) if G1.size else None,
                                           _ptr(G2) if G2.size else None, G2.shape[0],
                                           G1.shape[1]))
@@ -949,6 +956,7 @@ class Handle(object):
             raise GpxError('iter_update: no probes (call iter_set_probes)')
         iters, info = _i64(0), C.c_int(0)
         self._iter_shape = (0, 0, 0, 0)
+        self._iter_cache_rank = 0
         check(self._L.gpx_iter_update(self._h, spec.ref(), float(log_sn), float(mean), int(rank),
                                       float(tol), int(max_iter), C.byref(iters), C.byref(info)))
         self._iter_shape = tuple(self._data_shape) + (self._iter_probes, spec.c.nhyper)
@@ -1016,6 +1024,74 @@ class Handle(object):
         ms = np.zeros(len(self.ITER_TIMES))
         check(self._L.gpx_iter_timings(self._h, _ptr(ms)))
         return dict(zip(self.ITER_TIMES, ms))
+
+    # -- the variance cache of the iterative model --
+    # the order of gpx.h's GPX_ITER_CACHE_MS_*
+    ITER_CACHE_TIMES = ('select', 'orth', 'kq', 'h', 'c', 'cross', 'finish', 'grad')
+    ITER_CACHE_KMAX = 1024
+    ITER_CACHE_POINTS = 1 << 20
+    _iter_cache_rank = 0            # pivots of the last iter_cache_build (0: no cache)
+
+    def iter_cache_build(self, k):
+        """The cache of the last iter_update with at most k pivots; returns their count."""
+        n = self._iter_shape[0]
+        if n == 0:
+            raise GpxError('no iterative model (call iter_update)')
+        k = int(k)
+        if not 1 <= k <= min(n, self.ITER_CACHE_KMAX):
+            raise ValueError('need 1 <= k <= min(n, %d) (got %d)' % (self.ITER_CACHE_KMAX, k))
+        self._iter_cache_rank = 0
+        keff = _i64(0)
+        check(self._L.gpx_icache_build(self._h, k, C.byref(keff)))
+        # (the rank every later result is sized with: at most k, whatever the entry reports)
+        self._iter_cache_rank = max(1, min(int(keff.value), k))
+        return self._iter_cache_rank
+
+    def _iter_cache_points(self, Xs):
+        Xs = self._iter_points(Xs)
+        if not 1 <= Xs.shape[0] <= self.ITER_CACHE_POINTS:
+            raise ValueError('one call covers 1 .. %d points (got %d)'
+                             % (self.ITER_CACHE_POINTS, Xs.shape[0]))
+        return Xs
+
+    def iter_cache_eval(self, Xs, grad=False):
+        """(mu, s2), with grad (mu, s2, dmu, ds2), at the rows of Xs from the cache."""
+        Xs = self._iter_cache_points(Xs)
+        if self._iter_cache_rank == 0:
+            raise GpxError('no cache (call iter_cache_build)')
+        m, d = Xs.shape
+        mu, s2 = np.empty(m), np.empty(m)
+        dmu, ds2 = (np.empty((m, d)), np.empty((m, d))) if grad else (None, None)
+        check(self._L.gpx_icache_eval(self._h, _ptr(Xs), m, _ptr(mu), _ptr(s2), _ptr(dmu),
+                                          _ptr(ds2)))
+        return (mu, s2, dmu, ds2) if grad else (mu, s2)
+
+    def iter_cross_apply(self, Xs, W):
+        """K(Xs, X) W^T (m, nw) for W (nw, n), nw <= 1025, without storing K(Xs, X)."""
+        Xs, W = self._iter_cache_points(Xs), _f64(W, 2)
+        if W.shape[1] != self._iter_shape[0] or not 1 <= W.shape[0] <= 1 + self.ITER_CACHE_KMAX:
+            raise ValueError('W must be (1 .. %d, %d)'
+                             % (1 + self.ITER_CACHE_KMAX, self._iter_shape[0]))
+        out = np.empty((Xs.shape[0], W.shape[0]))
+        check(self._L.gpx_icache_cross_apply(self._h, _ptr(Xs), Xs.shape[0], _ptr(W), W.shape[0],
+                                           _ptr(out)))
+        return out
+
+    def iter_cache_get(self):
+        """dict of pivots (k_eff,), Q (k_eff, n), H (k_eff, k_eff), C (k_eff, n)."""
+        k, n = self._iter_cache_rank, self._iter_shape[0]
+        if k == 0 or n == 0:
+            raise GpxError('no cache (call iter_cache_build)')
+        piv = np.zeros(k, dtype=np.int64)
+        Q, H, Cm = np.empty((k, n)), np.empty((k, k)), np.empty((k, n))
+        check(self._L.gpx_icache_get(self._h, _ptr(piv), _ptr(Q), _ptr(H), _ptr(Cm)))
+        return dict(pivots=piv, Q=Q, H=H, C=Cm)
+
+    def iter_cache_timings(self):
+        """ms of the last build and eval by name (ITER_CACHE_TIMES)."""
+        ms = np.zeros(len(self.ITER_CACHE_TIMES))
+        check(self._L.gpx_icache_timings(self._h, _ptr(ms)))
+        return dict(zip(self.ITER_CACHE_TIMES, ms))
 
     def sparse_get_state(self, p):
         F1, F2, v = np.empty((p, p)), np.empty((p, p)), np.empty(p)

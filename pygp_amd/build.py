@@ -21,7 +21,8 @@ SOURCES = ['gpx_handle.hip', 'gpx_batch.hip', 'gpx_kernels.hip', 'gpx_exact.hip'
            'gpx_labels.hip', 'gpx_sparse.hip', 'gpx_fourier.hip', 'gpx_iter.hip', 'gpx_la.hip',
            'kmat.hip', 'kgrad.hip', 'kderiv.hip', 'gemm_f64.hip', 'chol.hip', 'leaf.hip',
            'panel.hip', 'panel_graph.hip', 'vec.hip', 'multi.hip', 'group.hip',
-           'sparse.hip', 'loo.hip', 'select.hip', 'laplace.hip', 'ep.hip', 'fourier.hip', 'path.hip', 'iter.hip']
+           'sparse.hip', 'loo.hip', 'select.hip', 'laplace.hip', 'ep.hip', 'fourier.hip', 'path.hip', 'iter.hip',
+           'iter_cache.hip']
 HEADERS = [os.path.join(CSRC, 'gpx_internal.h'), os.path.join(CSRC, 'gpx_env.h'),
            os.path.join(CSRC, 'gpx_ctx.h'),
            os.path.join(CSRC, 'gemm_tile.h'), os.path.join(CSRC, 'leaf_dev.h'),

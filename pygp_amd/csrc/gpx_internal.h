@@ -641,6 +641,33 @@ int gpx_iter_run_get(GpxIter *st, hipStream_t s, double *alpha, double *U, doubl
                      double *b, double *nit, double *rz0, double *logdetP);
 int gpx_iter_run_timings(const GpxIter *st, double *ms);
 void gpx_iter_destroy(GpxIter *st);
+// the variance cache of the model (state inside GpxIter; kernels in iter_cache.hip)
+bool gpx_iter_cache_ready(const GpxIter *st);
+int gpx_iter_cache_rank(const GpxIter *st);
+int gpx_iter_rows(const GpxIter *st);
+int gpx_iter_run_cache_build(GpxIter *st, hipStream_t s, const double *X, int k, int64_t *k_eff);
+int gpx_iter_run_cache_eval(GpxIter *st, hipStream_t s, const double *X, const double *Xt,
+                            int64_t m, double *mu, double *s2, double *dmu, double *ds2);
+int gpx_iter_run_cross_apply(GpxIter *st, hipStream_t s, const double *Xt, int64_t m,
+                             const double *W, int nw, double *out);
+int gpx_iter_run_cache_get(GpxIter *st, hipStream_t s, int64_t *pivots, double *Q, double *H,
+                           double *C);
+int gpx_iter_run_cache_timings(const GpxIter *st, double *ms);
+// ---- iter_cache.hip: see the comments at the definitions ---------------------------------------
+size_t gpx_ic_orth_work(int k, int n);
+int gpx_ic_orthonormalise(hipStream_t s, double *Q, long long ld, int k, int n, double *work);
+int gpx_ic_xscale(hipStream_t s, const KParams &kp, const double *Xt, int m, int d, int mp,
+                  double *Xts);
+size_t gpx_ic_cross_slab(int np, int m, int wrows);
+int gpx_ic_cross(hipStream_t s, const KParams &kp, const double *Xs, int np, int d,
+                 const double *Xts, int m, const double *W, long long ldw, int wrows, double *O,
+                 double *slab);
+int gpx_ic_finish(hipStream_t s, const double *O, int ldo, int nw, int m, double mean,
+                  double prior, double *mu, double *s2);
+size_t gpx_ic_grad_slab(int np, int m, int d);
+int gpx_ic_grad(hipStream_t s, const KParams &kp, const double *X, int n, int d, int np,
+                const double *Xt, int m, const double *O, const double *W, long long ldw,
+                int wrows, double *slab, double *dmu, double *ds2);
 // The trace pass with the low-rank pair weight q_ij = sum_c (a_ic b_jc + b_ic a_jc) / 2 and no
 // K^-1: acc[0] = tr(q), acc[1 + h] = sum_ij q_ij dK_ij/dtheta_h. A, B: C <= GPX_ITER_CMAX
 // columns, vs apart. partial: gpx_pairs_trace_scratch(kp, np) doubles (0: the per-tile form at

@@ -188,4 +188,79 @@ int gpx_iter_timings(gpx_t *h, double *ms)
     return gpx_iter_run_timings(h->iter, ms);
 }
 
+// ---- the variance cache ---------------------------------------------------------------------------
+int gpx_icache_build(gpx_t *h, int64_t k, int64_t *k_eff)
+{
+    CHECK_H(h);
+    if (k_eff) *k_eff = 0;
+    GPX_TRY(iter_ready(h, "gpx_icache_build"));
+    // gpx_select_pivots' limits on the count
+    const long long pp = round_up(k, GPX_TILE), np = round_up(h->n, GPX_TILE);
+    if (k < 1 || k > std::min<int64_t>(h->n, GPX_ITER_CACHE_KMAX) ||
+        (GPX_TILE + pp) * np >= (1LL << 31)) {
+        gpx_set_error("gpx_icache_build: need 1 <= k <= min(n, %d) and (128 + k_pad) * N_pad "
+                      "= %lld x %lld below 2^31", GPX_ITER_CACHE_KMAX, GPX_TILE + pp, np);
+        return -1;
+    }
+    return gpx_iter_run_cache_build(h->iter, h->stream, h->X.as<double>(), (int)k, k_eff);
+}
+
+int gpx_icache_eval(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2, double *dmu,
+                        double *ds2)
+{
+    CHECK_H(h);
+    GPX_TRY(iter_ready(h, "gpx_icache_eval"));
+    if (!gpx_iter_cache_ready(h->iter)) {
+        gpx_set_error("gpx_icache_eval: no cache of this model (call gpx_icache_build)");
+        return -1;
+    }
+    if (!Xs || !mu || !s2 || (dmu == nullptr) != (ds2 == nullptr) || m < 1 || m > (1 << 20)) {
+        gpx_set_error("gpx_icache_eval: bad arguments (1 <= m <= 2^20; dmu and ds2: both or "
+                      "neither)");
+        return -1;
+    }
+    GPX_TRY(iter_finite("gpx_icache_eval", "Xs", Xs, m * gpx_iter_dim(h->iter)));
+    return gpx_iter_run_cache_eval(h->iter, h->stream, h->X.as<double>(), Xs, m, mu, s2, dmu, ds2);
+}
+
+int gpx_icache_cross_apply(gpx_t *h, const double *Xs, int64_t m, const double *W, int64_t nw,
+                         double *out)
+{
+    CHECK_H(h);
+    GPX_TRY(iter_ready(h, "gpx_icache_cross_apply"));
+    if (!Xs || !W || !out || m < 1 || m > (1 << 20) || nw < 1 || nw > 1 + GPX_ITER_CACHE_KMAX) {
+        gpx_set_error("gpx_icache_cross_apply: bad arguments (1 <= m <= 2^20, 1 <= nw <= %d)",
+                      1 + GPX_ITER_CACHE_KMAX);
+        return -1;
+    }
+    if ((long long)round_up(nw, GPX_TILE) * round_up(h->n, GPX_TILE) >= (1LL << 31)) {
+        gpx_set_error("gpx_icache_cross_apply: nw_pad * N_pad must stay below 2^31");
+        return -1;
+    }
+    GPX_TRY(iter_finite("gpx_icache_cross_apply", "Xs", Xs, m * gpx_iter_dim(h->iter)));
+    GPX_TRY(iter_finite("gpx_icache_cross_apply", "W", W, nw * (int64_t)h->n));
+    return gpx_iter_run_cross_apply(h->iter, h->stream, Xs, m, W, (int)nw, out);
+}
+
+int gpx_icache_get(gpx_t *h, int64_t *pivots, double *Q, double *H, double *C)
+{
+    CHECK_H(h);
+    GPX_TRY(iter_ready(h, "gpx_icache_get"));
+    if (!gpx_iter_cache_ready(h->iter)) {
+        gpx_set_error("gpx_icache_get: no cache of this model (call gpx_icache_build)");
+        return -1;
+    }
+    return gpx_iter_run_cache_get(h->iter, h->stream, pivots, Q, H, C);
+}
+
+int gpx_icache_timings(gpx_t *h, double *ms)
+{
+    CHECK_H(h);
+    if (!ms) {
+        gpx_set_error("gpx_icache_timings: ms is null");
+        return -1;
+    }
+    return gpx_iter_run_cache_timings(h->iter, ms);
+}
+
 }  // extern "C"

@@ -17,6 +17,7 @@
 #include "gpx_internal.h"
 #include "kmat_dev.h"
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 
@@ -532,6 +533,18 @@ static int it_chunks(int T) { return std::min(T, std::max(1, 2048 / T)); }
 }  // namespace
 
 // ---- state ----------------------------------------------------------------------------------
+// the variance cache: W = [alpha; C] and what built it
+struct ItCache {
+    GpxSelect *sel = nullptr;          // a selection state of the cache's own: its panel is Q
+    bool valid = false;
+    int k_eff = 0, wrows = 0;          // pivots; rows of W in use, a multiple of 16
+    std::vector<int64_t> piv;
+    std::vector<double> H;             // k_eff x k_eff
+    DevBuf W, work, T, Wu, Xt, Xts, O, slab, gslab, res;
+    hipEvent_t ev[4] = {};
+    double ms[GPX_ITER_CACHE_NTIMES] = {};
+};
+
 struct GpxIter {
     GpxSelect *sel = nullptr;          // a selection state of the model's own: its panel is L
     KParams kp;
@@ -558,12 +571,16 @@ struct GpxIter {
     double h_fin[2] = {};
     double ms[GPX_ITER_NTIMES] = {};
     int hist_cap = 0;
+    ItCache cache;
 };
 
 void gpx_iter_destroy(GpxIter *st)
 {
     if (!st) return;
     if (st->sel) gpx_select_destroy(st->sel);
+    if (st->cache.sel) gpx_select_destroy(st->cache.sel);
+    for (hipEvent_t e : st->cache.ev)
+        if (e) (void)hipEventDestroy(e);
     if (st->host) (void)hipHostFree(st->host);
     for (hipEvent_t e : st->ev)
         if (e) (void)hipEventDestroy(e);
@@ -600,6 +617,7 @@ int gpx_iter_run_set_probes(GpxIter **state, hipStream_t s, const double *G1, co
     GPX_TRY(it_state(state));
     GpxIter *st = *state;
     st->ready = false;
+    st->cache.valid = false;
     st->have_probes = false;
     st->t = 0;
     GPX_TRY(st->G1.reserve(std::max<size_t>(8, (size_t)t * rank * 8)));
@@ -906,6 +924,7 @@ int gpx_iter_run_update(GpxIter **state, hipStream_t s, const KParams &kp, doubl
     GPX_TRY(it_state(state));
     GpxIter *st = *state;
     st->ready = false;
+    st->cache.valid = false;
     st->kp = kp;
     st->n = n;
     st->d = d;
@@ -1258,5 +1277,245 @@ int gpx_iter_run_get(GpxIter *st, hipStream_t s, double *alpha, double *U, doubl
 int gpx_iter_run_timings(const GpxIter *st, double *ms)
 {
     for (int i = 0; i < GPX_ITER_NTIMES; ++i) ms[i] = st ? st->ms[i] : 0.0;
+    return 0;
+}
+
+// ---- the variance cache (kernels in iter_cache.hip) ------------------------
+bool gpx_iter_cache_ready(const GpxIter *st) { return st && st->ready && st->cache.valid; }
+int gpx_iter_cache_rank(const GpxIter *st) { return st ? st->cache.k_eff : 0; }
+int gpx_iter_rows(const GpxIter *st) { return st ? st->n : 0; }
+
+// H (r x r, symmetric, row-major) = Lh Lh^T -> Winv = Lh^-1 (lower, r x r, ld ldw, the rest of
+// Winv untouched). Returns the failing pivot (> 0) if H is not positive definite.
+static int it_host_chol_inverse(const std::vector<double> &H, int r, std::vector<double> &Winv,
+                                int ldw)
+{
+    std::vector<double> C((size_t)r * r, 0.0);
+    for (int j = 0; j < r; ++j) {
+        double dj = H[(size_t)j * r + j];
+        for (int k = 0; k < j; ++k) dj -= C[(size_t)j * r + k] * C[(size_t)j * r + k];
+        if (!(dj > 0.0)) return j + 1;
+        dj = sqrt(dj);
+        C[(size_t)j * r + j] = dj;
+        for (int i = j + 1; i < r; ++i) {
+            double v = H[(size_t)i * r + j];
+            for (int k = 0; k < j; ++k) v -= C[(size_t)i * r + k] * C[(size_t)j * r + k];
+            C[(size_t)i * r + j] = v / dj;
+        }
+    }
+    // column j of the inverse by forward substitution; the column is kept contiguous (Wt is the
+    // transpose) so that the inner loop walks two rows
+    std::vector<double> Wt((size_t)r * r, 0.0);
+    for (int j = 0; j < r; ++j) {
+        double *w = &Wt[(size_t)j * r];
+        w[j] = 1.0 / C[(size_t)j * r + j];
+        for (int i = j + 1; i < r; ++i) {
+            const double *c = &C[(size_t)i * r];
+            double v = 0.0;
+            for (int k = j; k < i; ++k) v -= c[k] * w[k];
+            w[i] = v / c[i];
+        }
+    }
+    for (int i = 0; i < r; ++i)
+        for (int j = 0; j <= i; ++j) Winv[(size_t)i * ldw + j] = Wt[(size_t)j * r + i];
+    return 0;
+}
+
+static int it_cache_events(ItCache &c)
+{
+    for (hipEvent_t &e : c.ev)
+        if (!e) GPX_HIP(hipEventCreate(&e));
+    return 0;
+}
+
+static double it_elapsed(hipEvent_t a, hipEvent_t b)
+{
+    float t = 0;
+    return hipEventElapsedTime(&t, a, b) == hipSuccess ? t : -1.0;
+}
+
+int gpx_iter_run_cache_build(GpxIter *st, hipStream_t s, const double *X, int k, int64_t *k_eff)
+{
+    ItCache &c = st->cache;
+    c.valid = false;
+    GPX_TRY(it_cache_events(c));
+    for (int i = 0; i <= GPX_ITER_CACHE_MS_C; ++i) c.ms[i] = 0.0;
+    const int n = st->n, np = st->np;
+    // 1. the pivots: tol = 1e-10, so that float64 stops where extended precision would
+    std::vector<int64_t> idx(k);
+    int64_t count = 0;
+    GPX_TRY(gpx_select_run(&c.sel, s, st->kp, X, nullptr, n, st->d, k, 1e-10, idx.data(), nullptr,
+                           nullptr, &count));
+    const int ke = (int)count, pp = round_up(k, GPX_TILE);
+    long long ld = 0;
+    double *Q = const_cast<double *>(gpx_select_panel(c.sel, &ld));
+    c.ms[GPX_ITER_CACHE_MS_SELECT] = gpx_select_ms(c.sel);
+    if (ke < 1 || ld != np) {
+        gpx_set_error("gpx_icache_build: the selection returned no pivot");
+        return -1;
+    }
+    idx.resize(ke);
+    // rows of the panel behind the last pivot are not written by the selection
+    if (pp > ke)
+        GPX_HIP(hipMemsetAsync(Q + (size_t)ke * ld, 0, (size_t)(pp - ke) * ld * 8, s));
+    // 2. Q: the rows orthonormalised in order
+    GPX_TRY(c.work.reserve(gpx_ic_orth_work(ke, n) * 8));
+    GPX_HIP(hipEventRecord(c.ev[0], s));
+    GPX_TRY(gpx_ic_orthonormalise(s, Q, ld, ke, n, c.work.d()));
+    GPX_HIP(hipEventRecord(c.ev[1], s));
+    // 3. Kh Q^T into the rows 1 .. of W (row 0 will be alpha; 128 + pp rows, zero elsewhere)
+    const size_t wbytes = (size_t)(GPX_TILE + pp) * np * 8;
+    GPX_TRY(c.W.reserve(wbytes));
+    GPX_HIP(hipMemsetAsync(c.W.p, 0, wbytes, s));
+    double *KQ = c.W.d() + np;
+    GPX_TRY(it_apply(st, s, Q, ke, KQ));
+    GPX_HIP(hipEventRecord(c.ev[2], s));
+    // 4. H = Q (Kh Q^T): split-K on the tile engine; its factor and the factor's inverse on the
+    // host (plain C++, as the preconditioner's M)
+    GPX_TRY(it_abt(st, s, Q, KQ, ld, pp));
+    std::vector<double> full((size_t)pp * pp);
+    GPX_HIP(hipMemcpyAsync(full.data(), st->mm.p, full.size() * 8, hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipEventRecord(c.ev[3], s));
+    GPX_HIP(hipStreamSynchronize(s));
+    c.ms[GPX_ITER_CACHE_MS_ORTH] = it_elapsed(c.ev[0], c.ev[1]);
+    c.ms[GPX_ITER_CACHE_MS_KQ] = it_elapsed(c.ev[1], c.ev[2]);
+    c.ms[GPX_ITER_CACHE_MS_H] = it_elapsed(c.ev[2], c.ev[3]);
+    const auto t0 = std::chrono::steady_clock::now();
+    c.H.assign((size_t)ke * ke, 0.0);
+    for (int i = 0; i < ke; ++i)
+        for (int j = 0; j < ke; ++j)
+            // (one value for both triangles: the upper one)
+            c.H[(size_t)i * ke + j] = full[(size_t)std::min(i, j) * pp + std::max(i, j)];
+    std::fill(full.begin(), full.end(), 0.0);
+    const int piv = it_host_chol_inverse(c.H, ke, full, pp);
+    if (piv) {
+        gpx_set_error("gpx_icache_build: Q Kh Q^T is not positive definite (pivot %d)", piv);
+        return -1;
+    }
+    c.ms[GPX_ITER_CACHE_MS_H] +=
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    // 5. C = Lh^-1 Q over Kh Q^T's rows, one product; alpha into row 0
+    GPX_TRY(c.T.reserve(full.size() * 8));
+    GPX_HIP(hipMemcpyAsync(c.T.p, full.data(), full.size() * 8, hipMemcpyHostToDevice, s));
+    GPX_HIP(hipEventRecord(c.ev[0], s));
+    GemmArgs g;
+    g.A = c.T.d(); g.B = Q; g.C = KQ;
+    g.lda = pp; g.ldb = (int)ld; g.ldc = np;
+    g.M = pp; g.N = np; g.K = pp;
+    GPX_TRY(gpx_gemm(s, 0, 0, g));
+    GPX_HIP(hipMemcpyAsync(c.W.p, st->X.p, (size_t)np * 8, hipMemcpyDeviceToDevice, s));
+    GPX_HIP(hipEventRecord(c.ev[1], s));
+    GPX_HIP(hipStreamSynchronize(s));
+    c.ms[GPX_ITER_CACHE_MS_C] = it_elapsed(c.ev[0], c.ev[1]);
+    c.piv = idx;
+    c.k_eff = ke;
+    c.wrows = round_up(1 + ke, 16);
+    c.valid = true;
+    if (k_eff) *k_eff = ke;
+    return 0;
+}
+
+#define IT_CACHE_CHUNK 16384        // test points of one product
+#define IT_CACHE_GCHUNK 4096        // ... when gradients are asked for
+
+// O (c.O, ld wrows) = K(Xt, X) W^T for the mc host points Xt; they stay on the device in c.Xt
+static int it_cache_product(GpxIter *st, hipStream_t s, const double *Xt, int mc, const double *W,
+                            int wrows)
+{
+    ItCache &c = st->cache;
+    const int d = st->d, mp = round_up(mc, 64);
+    GPX_TRY(c.Xt.reserve((size_t)mc * d * 8));
+    GPX_TRY(c.Xts.reserve((size_t)st->kp.nparts * mp * st->dmax * 8));
+    GPX_TRY(c.O.reserve((size_t)mp * wrows * 8));
+    const size_t slab = gpx_ic_cross_slab(st->np, mc, wrows);
+    GPX_TRY(c.slab.reserve(std::max<size_t>(8, slab * 8)));
+    GPX_HIP(hipMemcpyAsync(c.Xt.p, Xt, (size_t)mc * d * 8, hipMemcpyHostToDevice, s));
+    GPX_HIP(hipEventRecord(c.ev[0], s));
+    GPX_TRY(gpx_ic_xscale(s, st->kp, c.Xt.d(), mc, d, mp, c.Xts.d()));
+    GPX_TRY(gpx_ic_cross(s, st->kp, st->Xs.d(), st->np, d, c.Xts.d(), mc, W, st->np, wrows,
+                         c.O.d(), c.slab.d()));
+    GPX_HIP(hipEventRecord(c.ev[1], s));
+    return 0;
+}
+
+int gpx_iter_run_cache_eval(GpxIter *st, hipStream_t s, const double *X, const double *Xt,
+                            int64_t m, double *mu, double *s2, double *dmu, double *ds2)
+{
+    ItCache &c = st->cache;
+    const int d = st->d, chunk = dmu ? IT_CACHE_GCHUNK : IT_CACHE_CHUNK;
+    for (int i = GPX_ITER_CACHE_MS_CROSS; i < GPX_ITER_CACHE_NTIMES; ++i) c.ms[i] = 0.0;
+    GPX_TRY(c.res.reserve((size_t)chunk * (2 + 2 * d) * 8));
+    double *rmu = c.res.d(), *rs2 = rmu + chunk, *rdm = rs2 + chunk, *rds = rdm + (size_t)chunk * d;
+    for (int64_t c0 = 0; c0 < m; c0 += chunk) {
+        const int mc = (int)std::min<int64_t>(chunk, m - c0);
+        GPX_TRY(it_cache_product(st, s, Xt + c0 * d, mc, c.W.d(), c.wrows));
+        GPX_TRY(gpx_ic_finish(s, c.O.d(), c.wrows, 1 + c.k_eff, mc, st->mean, st->prior, rmu, rs2));
+        GPX_HIP(hipEventRecord(c.ev[2], s));
+        if (dmu) {
+            GPX_TRY(c.gslab.reserve(gpx_ic_grad_slab(st->np, mc, d) * 8));
+            GPX_TRY(gpx_ic_grad(s, st->kp, X, st->n, d, st->np, c.Xt.d(), mc, c.O.d(), c.W.d(),
+                                st->np, c.wrows, c.gslab.d(), rdm, rds));
+        }
+        GPX_HIP(hipEventRecord(c.ev[3], s));
+        GPX_HIP(hipMemcpyAsync(mu + c0, rmu, (size_t)mc * 8, hipMemcpyDeviceToHost, s));
+        GPX_HIP(hipMemcpyAsync(s2 + c0, rs2, (size_t)mc * 8, hipMemcpyDeviceToHost, s));
+        if (dmu) {
+            GPX_HIP(hipMemcpyAsync(dmu + c0 * d, rdm, (size_t)mc * d * 8, hipMemcpyDeviceToHost, s));
+            GPX_HIP(hipMemcpyAsync(ds2 + c0 * d, rds, (size_t)mc * d * 8, hipMemcpyDeviceToHost, s));
+        }
+        GPX_HIP(hipStreamSynchronize(s));
+        c.ms[GPX_ITER_CACHE_MS_CROSS] += it_elapsed(c.ev[0], c.ev[1]);
+        c.ms[GPX_ITER_CACHE_MS_FINISH] += it_elapsed(c.ev[1], c.ev[2]);
+        if (dmu) c.ms[GPX_ITER_CACHE_MS_GRAD] += it_elapsed(c.ev[2], c.ev[3]);
+    }
+    return 0;
+}
+
+int gpx_iter_run_cross_apply(GpxIter *st, hipStream_t s, const double *Xt, int64_t m,
+                             const double *W, int nw, double *out)
+{
+    ItCache &c = st->cache;
+    GPX_TRY(it_cache_events(c));
+    const int n = st->n, np = st->np, d = st->d, wrows = round_up(nw, 16);
+    // the caller's rows, zero in the padding (rows up to a multiple of 128, columns up to np)
+    const size_t wbytes = (size_t)round_up(nw, GPX_TILE) * np * 8;
+    GPX_TRY(c.Wu.reserve(wbytes));
+    GPX_HIP(hipMemsetAsync(c.Wu.p, 0, wbytes, s));
+    GPX_HIP(hipMemcpy2DAsync(c.Wu.p, (size_t)np * 8, W, (size_t)n * 8, (size_t)n * 8, nw,
+                             hipMemcpyHostToDevice, s));
+    c.ms[GPX_ITER_CACHE_MS_CROSS] = 0.0;
+    for (int64_t c0 = 0; c0 < m; c0 += IT_CACHE_CHUNK) {
+        const int mc = (int)std::min<int64_t>(IT_CACHE_CHUNK, m - c0);
+        GPX_TRY(it_cache_product(st, s, Xt + c0 * d, mc, c.Wu.d(), wrows));
+        GPX_HIP(hipMemcpy2DAsync(out + c0 * nw, (size_t)nw * 8, c.O.p, (size_t)wrows * 8,
+                                 (size_t)nw * 8, mc, hipMemcpyDeviceToHost, s));
+        GPX_HIP(hipStreamSynchronize(s));
+        c.ms[GPX_ITER_CACHE_MS_CROSS] += it_elapsed(c.ev[0], c.ev[1]);
+    }
+    return 0;
+}
+
+int gpx_iter_run_cache_get(GpxIter *st, hipStream_t s, int64_t *pivots, double *Q, double *H,
+                           double *C)
+{
+    ItCache &c = st->cache;
+    const int ke = c.k_eff, n = st->n, np = st->np;
+    if (pivots) memcpy(pivots, c.piv.data(), (size_t)ke * sizeof(int64_t));
+    if (H) memcpy(H, c.H.data(), (size_t)ke * ke * 8);
+    long long ld = 0;
+    const double *Qd = gpx_select_panel(c.sel, &ld);
+    if (Q)
+        GPX_HIP(hipMemcpy2DAsync(Q, (size_t)n * 8, Qd, (size_t)ld * 8, (size_t)n * 8, ke,
+                                 hipMemcpyDeviceToHost, s));
+    if (C)
+        GPX_HIP(hipMemcpy2DAsync(C, (size_t)n * 8, c.W.d() + np, (size_t)np * 8, (size_t)n * 8, ke,
+                                 hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+int gpx_iter_run_cache_timings(const GpxIter *st, double *ms)
+{
+    for (int i = 0; i < GPX_ITER_CACHE_NTIMES; ++i) ms[i] = st ? st->cache.ms[i] : 0.0;
     return 0;
 }
