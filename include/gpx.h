@@ -341,6 +341,45 @@ int gpx_ep_get_sites(gpx_t *h, int64_t n, double *tau, double *nu, double *mu, d
  * solve and vector work between them, and the row-norm and site passes (needs
  * gpx_enable_timing) */
 int gpx_ep_timings(gpx_t *h, double *ms);
+/* ---- multi-class classification by Laplace's approximation (own design; GPML section 3.5,
+ * algorithms 3.3 and 3.4, no mean) ----
+ * Labels 0 .. C-1 at X under the softmax likelihood, 2 <= C <= GPX_SOFTMAX_CMAX: C latent
+ * functions f_c = K a_c share one kernel. With Pi the softmax of the rows of F and D_c =
+ * diag(Pi[:, c]): B_c = I + D_c^1/2 K D_c^1/2 = R_c^T R_c, E_c = D_c^1/2 B_c^-1 D_c^1/2,
+ * M^T M = sum_c E_c. gpx_softmax_update builds K once into a buffer of the handle and finds the
+ * mode by Newton's method: every step factorises and inverts the C matrices B_c and sum_c E_c
+ * with the code of gpx_exact_update and multiplies by the stored K and E_c. The safeguard and the
+ * stopping rule are gpx_laplace_update's (Psi = -1/2 sum_c a_c.f_c + sum_i log p(y_i | F_i),
+ * max |dF| <= tol (1 + max |F|)), the start is F = 0. At the mode the terms are recomputed:
+ * lZ = Psi - sum_c sum_i log (R_c)_ii - sum_i log M_ii.
+ * Upload: replaces whatever data the handle held; labels outside [0, C), C outside
+ * 2 .. GPX_SOFTMAX_CMAX, d > GPX_MAX_DIM and n > 8192 are refused. While a handle holds such
+ * labels every entry of another family but a set_data returns < 0 with an error text and
+ * touches nothing; the gpx_softmax_* entries refuse a handle in another state. The same call
+ * gives the same bits. */
+#define GPX_SOFTMAX_CMAX 8
+int gpx_softmax_set_data(gpx_t *h, const double *X, int64_t n, int64_t d, const int32_t *labels,
+                         int C);
+/* *iters: Newton steps taken; *info as gpx_exact_update. One host synchronisation per Newton
+ * step and per halving. After a failure the data stay resident and the handle has no mode: its
+ * other calls fail until the next successful update. */
+int gpx_softmax_update(gpx_t *h, const gpx_kspec *k, double tol, int max_iter, int *iters,
+                       int *info);
+/* lZ of the last update; dlZ (may be NULL) [nhyper_kernel]: d lZ / d theta = 1/2 sum_ij dK_ij
+ * [sum_c g_ic g_jc - Z_ij + sum_c (u_ic g_jc + g_ic u_jc)] with Z = sum_c E_c - sum_c H_c^T H_c,
+ * H_c = M^-T E_c, and u the implicit term of the mode's dependence on theta; computed once per
+ * update (about 4 C products of order n) and kept. */
+int gpx_softmax_loglik(gpx_t *h, double *lZ, double *dlZ);
+/* the latent posterior: mu[m][C] = K*^T g_c and Sigma[m][C][C] = delta_cc' (k** - colsum(K* o
+ * U_c)) + coldot(V_c, V_c'), U_c = E_c K*, V_c = M^-T U_c */
+int gpx_softmax_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma);
+/* the mode F[n][C] and G[n][C] = Y - Pi there (F = K G); either may be NULL */
+int gpx_softmax_get_mode(gpx_t *h, int64_t n, double *F, double *G);
+/* HIP-event ms (needs gpx_enable_timing): ms[0] the last update, ms[1] its build of K, ms[2..4]
+ * of its FIRST Newton step the C class blocks (B_c, its factor and inverse, E_c), the factor and
+ * inverse of sum_c E_c, and the products and vector work; ms[5] the last gradient, ms[6] the last
+ * posterior call */
+int gpx_softmax_timings(gpx_t *h, double *ms);
 /* host copies of gp._R (n*n row-major upper, zero below the diagonal) and gp._a;
  * either may be NULL. n: the point count the caller sized R and a for; the call
  * fails when it is not the factor's. */

@@ -19,10 +19,11 @@ from . import learning
 from . import batch
 from . import meta
 from .inference import (BasicGP, ExactGP, GradientGP, MultiOutputGP, CoregionalGP, LaplaceGP,
-                        EPGP, FITC, DTC, VFE, select_pseudoinputs, FourierSample, SSGP,
+                        EPGP, MulticlassLaplaceGP, FITC, DTC, VFE, select_pseudoinputs, FourierSample, SSGP,
                         PathwiseSample, IterativeGP)
 from .learning import optimize
 
 __all__ = ['BasicGP', 'ExactGP', 'GradientGP', 'MultiOutputGP', 'CoregionalGP', 'LaplaceGP', 'EPGP',
+           'MulticlassLaplaceGP',
            'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'FourierSample', 'SSGP', 'PathwiseSample', 'IterativeGP', 'optimize', 'kernels', 'likelihoods', 'inference', 'learning',
            'batch', 'meta']

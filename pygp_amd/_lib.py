@@ -107,6 +107,12 @@ SIGNATURES = {
     'gpx_laplace_posterior_full': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     'gpx_laplace_get_mode': (C.c_int, [_vp, _i64, _vp, _vp]),
     'gpx_laplace_timings': (C.c_int, [_vp, _vp]),
+    'gpx_softmax_set_data': (C.c_int, [_vp, _vp, _i64, _i64, _vp, C.c_int]),
+    'gpx_softmax_update': (C.c_int, [_vp, C.POINTER(_KSpec), C.c_double, C.c_int, _ip, _ip]),
+    'gpx_softmax_loglik': (C.c_int, [_vp, _dp, _vp]),
+    'gpx_softmax_posterior': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    'gpx_softmax_get_mode': (C.c_int, [_vp, _i64, _vp, _vp]),
+    'gpx_softmax_timings': (C.c_int, [_vp, _vp]),
     'gpx_ep_update': (C.c_int, [_vp, C.POINTER(_KSpec), C.c_double, C.c_double, C.c_int,
                                 C.c_double, _ip, _ip]),
     'gpx_ep_loglik': (C.c_int, [_vp, _dp, _vp]),
@@ -575,6 +581,49 @@ class Handle(object):
         ms = np.zeros(5)
         check(self._L.gpx_laplace_timings(self._h, _ptr(ms)))
         return dict(zip(('update', 'build_scale', 'factor', 'matvec', 'solve'), ms))
+
+    # -- multi-class classification by Laplace's approximation (MulticlassLaplaceGP) --
+    def softmax_set_data(self, X, labels, nclass):
+        """Labels 0 .. nclass - 1 at X."""
+        X = _f64(X, 2)
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        if labels.ndim != 1 or X.shape[0] != labels.shape[0]:
+            raise ValueError('X and the labels disagree')
+        check(self._L.gpx_softmax_set_data(self._h, _ptr(X), X.shape[0], X.shape[1], _ptr(labels),
+                                           int(nclass)))
+
+    def softmax_update(self, spec, tol=1e-8, max_iter=50):
+        """Newton's method to the mode; returns the number of steps."""
+        iters, info = C.c_int(0), C.c_int(0)
+        check(self._L.gpx_softmax_update(self._h, spec.ref(), float(tol), int(max_iter),
+                                         C.byref(iters), C.byref(info)))
+        return iters.value
+
+    def softmax_loglik(self, nhyper_kernel, grad=False):
+        return self._loglik(self._L.gpx_softmax_loglik, nhyper_kernel, grad)
+
+    def softmax_posterior(self, Xs, nclass):
+        """(mu (m, C), Sigma (m, C, C)) of the latents at the rows of Xs."""
+        Xs = _f64(Xs, 2)
+        m = Xs.shape[0]
+        mu, Sigma = np.empty((m, nclass)), np.empty((m, nclass, nclass))
+        check(self._L.gpx_softmax_posterior(self._h, _ptr(Xs), m, _ptr(mu), _ptr(Sigma)))
+        return mu, Sigma
+
+    def softmax_get_mode(self, n, nclass):
+        """(F, G), each (n, C): the mode and Y - Pi there."""
+        F, G = np.empty((n, nclass)), np.empty((n, nclass))
+        check(self._L.gpx_softmax_get_mode(self._h, n, _ptr(F), _ptr(G)))
+        return F, G
+
+    def softmax_timings(self):
+        """HIP-event ms (enable_timing): the last softmax_update and its build of K, of its
+        first Newton step the class blocks, the factor and inverse of sum_c E_c and the products
+        and vector work; the last gradient; the last posterior call."""
+        ms = np.zeros(7)
+        check(self._L.gpx_softmax_timings(self._h, _ptr(ms)))
+        return dict(zip(('update', 'build', 'class_blocks', 'm_block', 'vectors', 'gradient',
+                         'posterior'), ms))
 
     # -- binary classification by expectation propagation (EPGP); the labels come in through
     # laplace_set_data --

@@ -18,10 +18,10 @@ CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(CSRC, '_obj')
 LIB = os.path.join(HERE, 'libgpx.so')
 SOURCES = ['gpx_handle.hip', 'gpx_batch.hip', 'gpx_kernels.hip', 'gpx_exact.hip', 'gpx_posterior.hip',
-           'gpx_labels.hip', 'gpx_sparse.hip', 'gpx_fourier.hip', 'gpx_iter.hip', 'gpx_la.hip',
+           'gpx_labels.hip', 'gpx_softmax.hip', 'gpx_sparse.hip', 'gpx_fourier.hip', 'gpx_iter.hip', 'gpx_la.hip',
            'kmat.hip', 'kgrad.hip', 'kderiv.hip', 'gemm_f64.hip', 'chol.hip', 'leaf.hip',
            'panel.hip', 'panel_graph.hip', 'vec.hip', 'multi.hip', 'group.hip',
-           'sparse.hip', 'loo.hip', 'select.hip', 'laplace.hip', 'ep.hip', 'fourier.hip', 'path.hip', 'iter.hip',
+           'sparse.hip', 'loo.hip', 'select.hip', 'laplace.hip', 'ep.hip', 'softmax.hip', 'fourier.hip', 'path.hip', 'iter.hip',
            'iter_cache.hip']
 HEADERS = [os.path.join(CSRC, 'gpx_internal.h'), os.path.join(CSRC, 'gpx_env.h'),
            os.path.join(CSRC, 'gpx_ctx.h'),

@@ -1,5 +1,5 @@
 // The handle behind gpx_t and what the units of the C ABI (gpx_handle.hip, gpx_batch.hip,
-// gpx_kernels.hip, gpx_exact.hip, gpx_posterior.hip, gpx_labels.hip, gpx_sparse.hip,
+// gpx_kernels.hip, gpx_exact.hip, gpx_posterior.hip, gpx_labels.hip, gpx_softmax.hip, gpx_sparse.hip,
 // gpx_fourier.hip, gpx_iter.hip, gpx_la.hip) share among themselves: the handle's state, the stage clock, and the host functions that cross
 // a unit, in the namespace gpxh. Private to those units: the device-side units see
 // gpx_internal.h only.
@@ -14,7 +14,7 @@ enum { T_BUILD = 0, T_POTRF, T_TRSV, T_TRTRI, T_TRMV, T_LAUUM, T_TRACE, T_SCALAR
 
 // What the resident data of a handle is: set by the family's set_data (data_end), asked for
 // by every entry that reads the data (require_state).
-enum { ST_PLAIN = 0, ST_GRADOBS, ST_MO, ST_LAPLACE, ST_ICM };
+enum { ST_PLAIN = 0, ST_GRADOBS, ST_MO, ST_LAPLACE, ST_ICM, ST_SOFTMAX };
 // ... and which approximation filled a handle that holds labels
 enum { LP_NONE = 0, LP_LAPLACE, LP_EP };
 
@@ -63,6 +63,20 @@ struct gpx_ctx {
     hipEvent_t lb_ev[9] = {};      // the timed update's events, whichever approximation ran it
     double lp_ms[5] = {};          // ... and each approximation's own last timed update
     double ep_ms[6] = {};
+    // ST_SOFTMAX, labels 0 .. sm_C - 1 under the softmax likelihood (gpx_softmax_set_data): sm_lab
+    // holds the n labels, sm_K the kernel matrix of the last update (np x ld, zero in the
+    // padding), sm_E the sm_C matrices E_c at the mode and sm_SE their sum, sm_vec the vectors of
+    // the Newton iteration (SV_* below); the factorisation below is that of sum_c E_c = M^T M.
+    // sm_T, sm_H, sm_Z, sm_tr: the matrices of the gradient; sm_post, sm_dot: the panels and
+    // column sums of a posterior pass or of the gradient. Every matrix is np x ld.
+    int sm_C = 0;
+    bool sm_mode = false;          // sm_vec, sm_E and the factorisation belong to a converged mode
+    int sm_iters = 0;
+    DevBuf sm_lab, sm_K, sm_E, sm_SE, sm_T, sm_H, sm_Z, sm_tr, sm_vec, sm_sc, sm_post, sm_dot;
+    std::vector<double> sm_dlz;    // the gradient of the last update, once computed
+    std::vector<double> sm_host;   // staging of the results that the host transposes
+    hipEvent_t sm_ev[8] = {};      // the timed update's events
+    double sm_ms[7] = {};
     // factorisation state
     DevBuf A, W, Kinv, r, a, alpha, scalars, partial, info, gv_part, pctl;
     double *acc = nullptr;         // the trace accumulators: a view of scalars
@@ -179,6 +193,14 @@ static inline int ld_for(int np)
 enum { LV_A = 0, LV_F, LV_G, LV_W, LV_SW, LV_D3, LV_B, LV_T, LV_C, LV_X, LV_AN, LV_FN, LV_S2, LV_U,
        LV_COUNT };
 static inline double *lpv(const gpx_ctx *h, int k) { return h->lp_vec.d() + (size_t)k * h->cap; }
+
+// the vectors of the softmax state: GPX_SOFTMAX_CMAX columns of cap doubles each in sm_vec
+enum { SV_F = 0, SV_A, SV_PI, SV_G, SV_SW, SV_B, SV_T1, SV_CC, SV_T2, SV_AN, SV_FN, SV_TA, SV_TF,
+       SV_S, SV_U, SV_X, SV_COUNT };
+static inline double *smv(const gpx_ctx *h, int k, int c = 0)
+{
+    return h->sm_vec.d() + ((size_t)k * GPX_SOFTMAX_CMAX + c) * h->cap;
+}
 
 namespace gpxh {
 

@@ -42,6 +42,8 @@ static void drop_data(gpx_ctx *h)
     h->icm_T = 0;
     h->lp_mode = false;
     h->lp_approx = LP_NONE;
+    h->sm_C = 0;
+    h->sm_mode = false;
     h->data_version++;
 }
 
@@ -59,11 +61,12 @@ namespace gpxh {
 
 int require_state(const gpx_ctx *h, int want, const char *what)
 {
-    static const char *holds[5] = {"plain data (gpx_set_data)",
+    static const char *holds[6] = {"plain data (gpx_set_data)",
                                    "gradient observations (gpx_gradobs_*)",
                                    "multi-output data (gpx_mo_*)",
                                    "classification labels (gpx_laplace_*)",
-                                   "coregionalised outputs (gpx_icm_*)"};
+                                   "coregionalised outputs (gpx_icm_*)",
+                                   "multi-class labels (gpx_softmax_*)"};
     if (h->state == want) return 0;
     gpx_set_error("%s: the handle holds %s%s", what, holds[h->state],
                   want == ST_PLAIN ? "; gpx_set_data returns it to plain data" : "");
@@ -268,12 +271,15 @@ int gpx_destroy(gpx_t *h)
                       &h->alpha, &h->scalars, &h->partial, &h->info, &h->gv_part, &h->pctl, &h->Ks, &h->KsT, &h->Vc,
                       &h->Xs, &h->mu, &h->s2, &h->post_part, &h->t0, &h->t1, &h->t2, &h->split, &h->gpart,
                       &h->loo_S, &h->loo_M, &h->loo_vec, &h->loo_out, &h->lp_vec, &h->lp_kmv,
-                      &h->lp_sc, &h->lp_mu};
+                      &h->lp_sc, &h->lp_mu, &h->sm_lab, &h->sm_K, &h->sm_E, &h->sm_SE, &h->sm_T,
+                      &h->sm_H, &h->sm_Z, &h->sm_tr, &h->sm_vec, &h->sm_sc, &h->sm_post, &h->sm_dot};
     for (DevBuf *b : bufs) b->release();
     DLOG("events");
     for (int i = 0; i <= GPX_NTIMERS; ++i)
         if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     for (hipEvent_t e : h->lb_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : h->sm_ev)
         if (e) (void)hipEventDestroy(e);
     DLOG("host buffers");
     if (h->hres) (void)hipHostFree(h->hres);

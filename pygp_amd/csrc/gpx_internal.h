@@ -883,3 +883,43 @@ int gpx_ep_site(hipStream_t s, const double *y, const double *Sii, const double 
 // Sii_i = (1 - sum_j W_ij^2) / tau_i from the rows of W = R^-1 as gpx_trtri leaves it
 int gpx_ep_rownorm(hipStream_t s, const double *W, int ld, int n, int np, const double *tau,
                    double *Sii);
+
+// ---- multi-class Laplace under the softmax likelihood (softmax.hip; driver in gpx_softmax.hip) -----
+// Column c of a set of vectors lies c * vs doubles behind column 0; C <= GPX_SOFTMAX_CMAX.
+// Pi, g = y - pi, sW = sqrt pi, b = pi o f - pi (pi.f) + g at F (zero in the padding up to np)
+int gpx_softmax_terms(hipStream_t s, const double *F, const int *lab, int n, int np, long long vs,
+                      int C, double *Pi, double *G, double *SW, double *B);
+// out[0] = Psi(A, F), out[1] = max |F - F_old|, out[2] = max |F|
+int gpx_softmax_psi(hipStream_t s, const double *A, const double *F, const double *F_old,
+                    const int *lab, int n, long long vs, int C, double *out);
+// out_c = p_c - q_c + r_c; out_c = p_c + t (q_c - p_c); out = sum_c p_c (zero beyond n)
+int gpx_softmax_combine(hipStream_t s, const double *p, const double *q, const double *r, int n,
+                        int np, long long vs, int C, double *out);
+int gpx_softmax_lerp(hipStream_t s, const double *p, const double *q, double t, int n, int np,
+                     long long vs, int C, double *out);
+int gpx_softmax_colsum(hipStream_t s, const double *p, int n, int np, long long vs, int C,
+                       double *out);
+// out_c = M_c v_c over the n x n live part of full matrices ms apart and vectors vin apart (0:
+// the same one for every column)
+int gpx_softmax_matvec(hipStream_t s, const double *M, int ld, long long ms, const double *V,
+                       long long vin, int n, int C, double *out, long long vout);
+// the upper triangle of the stored src -> the factorisation's tile placement (A, S; identity in
+// the padding): I + sW sW^T o src, or src itself (sW null)
+int gpx_softmax_place(hipStream_t s, const double *src, int ld, int n, int np, const double *sW,
+                      double *A, double *S);
+// E = sW sW^T o B^-1 (full, symmetric, zero in the padding) from the upper triangle of B^-1;
+// sum = E (first) or sum + E
+int gpx_softmax_e(hipStream_t s, const double *Binv, int ld, int n, int np, const double *sW,
+                  bool first, double *E, double *sum);
+// out[j] = sum_{i < rows} P[i][j] Q[i][j], j < cols
+int gpx_softmax_coldot(hipStream_t s, const double *P, const double *Q, int ld, int rows, int cols,
+                       double *out);
+// mu[c][j] = Ks[:, j].g_c, j < cols, rows of mu ldm apart
+int gpx_softmax_cross_mean(hipStream_t s, const double *Ks, int ldk, int n, int cols,
+                           const double *G, long long vs, int C, double *mu, int ldm);
+// s = the third-derivative term of the gradient from D = [colsum(K o P_c) | coldot(T_c, T_c'), c <= c']
+int gpx_softmax_third(hipStream_t s, const double *K, int ld, const double *Pi, const double *D,
+                      int n, int np, long long vs, int C, double *S);
+// upper triangle of Wt = [Z - sum_c (u_c g_c^T + g_c u_c^T)] / C
+int gpx_softmax_weight(hipStream_t s, const double *Z, int ld, int n, const double *G,
+                       const double *U, long long vs, int C, double *Wt);

@@ -5,6 +5,7 @@ from .multiout import MultiOutputGP
 from .coreg import CoregionalGP
 from .laplace import LaplaceGP
 from .ep import EPGP
+from .softmax import MulticlassLaplaceGP
 from .fitc import FITC
 from .dtc import DTC
 from .vfe import VFE
@@ -15,5 +16,5 @@ from .pathwise import PathwiseSample
 from .iterative import IterativeGP
 
 __all__ = ['GP', 'ExactGP', 'BasicGP', 'GradientGP', 'MultiOutputGP', 'CoregionalGP', 'LaplaceGP',
-           'EPGP', 'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'FourierSample', 'SSGP',
+           'EPGP', 'MulticlassLaplaceGP', 'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'FourierSample', 'SSGP',
            'PathwiseSample', 'IterativeGP']

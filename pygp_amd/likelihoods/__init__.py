@@ -1,13 +1,14 @@
 """Gaussian observation noise, the only likelihood exact inference admits
 (/root/reference/pygp/likelihoods/gaussian.py:23-49, _base.py:41-46), and the two
 likelihoods of binary labels y in {-1, +1} that `LaplaceGP` takes: p(y | f) = sigma(y f)
-(Logistic) and Phi(y f) (Probit, which `EPGP` takes too). Neither has a hyperparameter."""
+(Logistic) and Phi(y f) (Probit, which `EPGP` takes too), and the softmax likelihood of labels
+0 .. C-1 that `MulticlassLaplaceGP` builds for itself. None of them has a hyperparameter."""
 
 import numpy as np
 
 from ..utils.models import Parameterized, printable
 
-__all__ = ['Gaussian', 'Likelihood', 'Logistic', 'Probit']
+__all__ = ['Gaussian', 'Likelihood', 'Logistic', 'Probit', 'Softmax']
 
 
 class Likelihood(Parameterized):
@@ -116,3 +117,35 @@ class Probit(_Binary):
         from scipy.special import ndtr
         mu, s2 = np.asarray(mu, dtype=float), np.asarray(s2, dtype=float)
         return ndtr(mu / np.sqrt(1 + np.maximum(s2, 0.0)))
+
+
+class Softmax(Likelihood):
+    """p(y = c | f) = exp(f_c) / sum_c' exp(f_c') for labels 0 .. nclass - 1 and nclass latents."""
+
+    nhyper = 0
+
+    def __init__(self, nclass):
+        self.nclass = int(nclass)
+
+    def __repr__(self):
+        return 'Softmax(nclass=%d)' % self.nclass
+
+    def _params(self):
+        return []
+
+    def get_hyper(self):
+        return np.empty(0)
+
+    def set_hyper(self, hyper):
+        if len(hyper):
+            raise ValueError('Softmax has no hyperparameters')
+
+    def transform(self, y):
+        """Integer labels (a float array of integral values is accepted) as int64."""
+        y = np.array(y, ndmin=1)
+        if y.ndim != 1 or y.dtype.kind not in 'iuf' or not np.all(np.isfinite(y)):
+            raise ValueError('labels must be integers 0 .. %d' % (self.nclass - 1))
+        lab = y.astype(np.int64)
+        if not (np.all(lab == y) and np.all((lab >= 0) & (lab < self.nclass))):
+            raise ValueError('labels must be integers 0 .. %d' % (self.nclass - 1))
+        return lab

@@ -58,6 +58,10 @@ class HyperEnsemble(object):
             # ... with Gaussian noise: a classifier's hypers have no noise slot
             raise TypeError('HyperEnsemble runs exact GPs only; %s is a classifier'
                             % type(model).__name__)
+        from .inference.softmax import MulticlassLaplaceGP
+        if isinstance(model, MulticlassLaplaceGP):
+            raise TypeError('HyperEnsemble runs exact GPs only; %s is a classifier'
+                            % type(model).__name__)
         if getattr(model, 'ngrad', 0) > 0:
             # ... on (X, y) alone: the gradient observations would be left out
             raise TypeError('HyperEnsemble runs GPs on function values only; this %s holds '
