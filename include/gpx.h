@@ -507,6 +507,47 @@ int gpx_sparse_loglik_pseudo(gpx_t *h, double *lZ, double *dlZ, double *dU);
  * update) */
 int gpx_sparse_pseudo_timing(gpx_t *h, double *ms);
 
+/* ---- sparse Laplace classification (own design) --------------------------- */
+/* Binary classification on pseudo-inputs: Laplace's approximation under the subset-of-regressors
+ * prior f = mean + V0^T z, z ~ N(0, I_p), V0 = L^-T K(U, X), L = chol(Kuu + jitter I), with DTC's
+ * predictive variance. The data are the handle's resident data from plain gpx_set_data (NOT
+ * gpx_laplace_set_data, whose n <= 65536 does not apply), y holding the labels -1 / +1: any other
+ * value is refused with an error text before anything is launched. lik: a gpx_likelihood; hypers
+ * [kernel | mean]; jitter >= 0 is absolute and has no gradient. Newton's method in z from z = 0
+ * (the same call gives the same bits), a step that lowers Psi = sum log p(y | f) - z.z / 2 by more
+ * than 1e-10 (1 + |Psi|) halved up to 10 times, until max |f_new - f_old| <= tol (1 + max |f_new|);
+ * *iters: the steps taken. After max_iter steps without convergence: -1 with an error text, no
+ * model (the calls below fail until an update succeeds). Limits: those of gpx_sparse_update,
+ * N <= 2^20, 1 <= p <= GPX_SPARSE_MAX_P, round_up(p, 128) * round_up(N, 128) < 2^31,
+ * d <= GPX_MAX_DIM. A non-positive-definite Kuu + jitter I returns its pivot (> 0, also in *info).
+ * State: the model shares the state and the panels of gpx_sparse_update. An update of either kind
+ * makes the other's model stale: its calls fail with an error text until its own next update, and
+ * never answer from the other model's numbers. gpx_set_data makes both stale. As with
+ * gpx_sparse_update, every call of this entry, a refused one included (bad p, bad labels), leaves
+ * the handle without a current model of either kind, though nothing was launched. */
+int gpx_sparse_laplace_update(gpx_t *h, const gpx_kspec *k, int lik, double mean, const double *U,
+                              int64_t p, double jitter, double tol, int max_iter, int *iters,
+                              int *info);
+/* lZ = Psi - sum log chol(I + V0 W V0^T)_ii at the mode; dlZ == NULL: value only, else
+ * dlZ[nhyper + 1] in order [kernel..., mean] */
+int gpx_sparse_laplace_loglik(gpx_t *h, double *lZ, double *dlZ);
+/* ... plus dU[p*d] row-major = d lZ / d U (lZ and dlZ: the bits of gpx_sparse_laplace_loglik) */
+int gpx_sparse_laplace_loglik_pseudo(gpx_t *h, double *lZ, double *dlZ, double *dU);
+/* the latent posterior through the sparse posterior pass (gpx_sparse_posterior and _full: the
+ * stored statistics are DTC's with Ruu = L, Rux = chol(I + V0 W V0^T) L): mu[m], s2[m] and
+ * dmu, ds2 [m*d] (both or neither); mu[m], Sigma[m][m], 1 <= m <= 8192 */
+int gpx_sparse_laplace_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2,
+                                 double *dmu, double *ds2);
+int gpx_sparse_laplace_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu,
+                                      double *Sigma);
+/* the mode: z[p], f[n] = mean + V0^T z and g[n] = d log p / d f there (any may be NULL) */
+int gpx_sparse_laplace_get_mode(gpx_t *h, double *z, double *f, double *g);
+/* ms[8]: HIP-event ms of the last update, of its first Newton step and of that step's two panel
+ * passes (events around the scaling kernel, and around the terms kernel with the one-workgroup
+ * reduction and the z.z dot behind it: approximate, not a kernel trace); of the last gradient stage and the contraction pass inside it (0 if none since the
+ * update); of the last dU pass; then the Newton steps and the halvings of the last update */
+int gpx_sparse_laplace_timings(gpx_t *h, double *ms);
+
 /* ---- greedy pseudo-input selection --------------------------------------- */
 /* Greedy conditional-variance selection = pivoted partial Cholesky of K(X,X) (own design).
  * X == NULL: the handle's resident data (gpx_set_data); else X[n*d] is copied to buffers of

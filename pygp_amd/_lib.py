@@ -141,6 +141,14 @@ SIGNATURES = {
     'gpx_sparse_timings': (C.c_int, [_vp, _vp]),
     'gpx_sparse_loglik_pseudo': (C.c_int, [_vp, _vp, _vp, _vp]),
     'gpx_sparse_pseudo_timing': (C.c_int, [_vp, _vp]),
+    'gpx_sparse_laplace_update': (C.c_int, [_vp, C.POINTER(_KSpec), C.c_int, C.c_double, _vp,
+                                            _i64, C.c_double, C.c_double, C.c_int, _ip, _ip]),
+    'gpx_sparse_laplace_loglik': (C.c_int, [_vp, _dp, _vp]),
+    'gpx_sparse_laplace_loglik_pseudo': (C.c_int, [_vp, _vp, _vp, _vp]),
+    'gpx_sparse_laplace_posterior': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    'gpx_sparse_laplace_posterior_full': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    'gpx_sparse_laplace_get_mode': (C.c_int, [_vp, _vp, _vp, _vp]),
+    'gpx_sparse_laplace_timings': (C.c_int, [_vp, _vp]),
     'gpx_select_pivots': (C.c_int, [_vp, C.POINTER(_KSpec), _vp, _i64, _i64, _i64, C.c_double,
                                     _vp, _vp, _vp, C.POINTER(_i64)]),
     'gpx_select_timing': (C.c_int, [_vp, _vp]),
@@ -773,6 +781,58 @@ class Handle(object):
         ms = np.zeros(1)
         check(self._L.gpx_sparse_pseudo_timing(self._h, _ptr(ms)))
         return float(ms[0])
+
+    # -- sparse Laplace classification (SparseLaplaceGP) on the resident data: labels as y --
+    def sparse_laplace_update(self, spec, lik, mean, U, jitter=1e-6, tol=1e-8, max_iter=50):
+        """Newton's method in the p-dimensional space to the mode; returns the number of steps."""
+        U = _f64(U, 2)
+        iters, info = C.c_int(0), C.c_int(0)
+        check(self._L.gpx_sparse_laplace_update(self._h, spec.ref(), int(lik), float(mean),
+                                                _ptr(U), U.shape[0], float(jitter), float(tol),
+                                                int(max_iter), C.byref(iters), C.byref(info)))
+        return iters.value
+
+    def sparse_laplace_loglik(self, nhyper_kernel, grad=False):
+        return self._loglik(self._L.gpx_sparse_laplace_loglik, nhyper_kernel + 1, grad)
+
+    def sparse_laplace_loglik_pseudo(self, nhyper_kernel, p, d):
+        """lZ, dlZ (as sparse_laplace_loglik with grad) and dU = d lZ / d U (p x d)."""
+        lZ = C.c_double(0)
+        dlZ, dU = np.empty(nhyper_kernel + 1), np.empty((p, d))
+        check(self._L.gpx_sparse_laplace_loglik_pseudo(self._h, C.byref(lZ), _ptr(dlZ),
+                                                       _ptr(dU)))
+        return lZ.value, dlZ, dU
+
+    def sparse_laplace_posterior(self, Xs, grad=False):
+        Xs = _f64(Xs, 2)
+        m, d = Xs.shape
+        mu, s2 = np.empty(m), np.empty(m)
+        dmu, ds2 = (np.empty((m, d)), np.empty((m, d))) if grad else (None, None)
+        if m:
+            check(self._L.gpx_sparse_laplace_posterior(self._h, _ptr(Xs), m, _ptr(mu), _ptr(s2),
+                                                       _ptr(dmu), _ptr(ds2)))
+        return (mu, s2, dmu, ds2) if grad else (mu, s2)
+
+    def sparse_laplace_posterior_full(self, Xs):
+        return self._posterior(self._L.gpx_sparse_laplace_posterior_full, Xs, True)
+
+    def sparse_laplace_get_mode(self, p, n):
+        """(z, f, g): the mode in the p-dimensional space, the latent at the data and the gradient
+        of log p(y | f) there."""
+        z, f, g = np.empty(p), np.empty(n), np.empty(n)
+        check(self._L.gpx_sparse_laplace_get_mode(self._h, _ptr(z), _ptr(f), _ptr(g)))
+        return z, f, g
+
+    def sparse_laplace_timings(self):
+        """HIP-event ms of the last update, its first Newton step and that step's two panel
+        passes, the last gradient stage, its contraction pass and the dU pass; then the Newton
+        steps and halvings of the last update."""
+        ms = np.zeros(8)
+        check(self._L.gpx_sparse_laplace_timings(self._h, _ptr(ms)))
+        out = dict(zip(('update', 'step', 'panel_passes', 'gradient', 'contraction', 'pseudo'),
+                       ms))
+        out.update(iters=int(ms[6]), halvings=int(ms[7]))
+        return out
 
     def select_pivots(self, spec, X, p, tol=0.0):
         """Greedy conditional-variance selection (pivoted partial Cholesky of K(X, X)) of at

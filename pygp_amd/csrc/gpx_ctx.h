@@ -114,6 +114,8 @@ struct gpx_ctx {
     // exact-GP state above stays valid beside it. Valid for the data of sparse_version only.
     GpxSparse *sparse = nullptr;
     long sparse_version = -1;
+    // ... and the data version whose y gpx_sparse_laplace_update has found to be labels -1 / +1
+    long labels_version = -1;
     // greedy pseudo-input selection (select.hip), created on first use; buffers of its own
     GpxSelect *select = nullptr;
     // Fourier-feature function sample (fourier.hip), created on first use; buffers of its own

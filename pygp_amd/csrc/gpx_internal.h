@@ -597,6 +597,22 @@ int gpx_sparse_run_state(GpxSparse *st, hipStream_t s, double *F1, double *F2, d
 int gpx_sparse_nhyper(const GpxSparse *st);
 int gpx_sparse_run_timings(GpxSparse *st, double *ms);
 void gpx_sparse_destroy(GpxSparse *st);
+// Which model the state holds: a gpx_sparse_method, GPX_SPARSE_KIND_LAPLACE, or 0 (none ready)
+#define GPX_SPARSE_KIND_LAPLACE 4
+int gpx_sparse_kind(const GpxSparse *st);
+// Binary labels y (+-1, device) under the subset-of-regressors prior, Laplace's approximation
+// (DESIGN.md section 26), in the same state and panels: an update of either kind replaces the
+// other's model. The posterior pass is gpx_sparse_run_posterior on what the update leaves.
+// -1 with an error text after max_iter Newton steps without convergence.
+int gpx_sparse_laplace_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, int lik,
+                                  const double *U, int p, double jitter, double mean, double tol,
+                                  int max_iter, const double *X, const double *y, int n, int d,
+                                  int cap, int *iters, int *info);
+int gpx_sparse_laplace_run_loglik(GpxSparse *st, hipStream_t s, const double *X, double *lZ,
+                                  double *dlZ, double *dU);
+int gpx_sparse_laplace_run_mode(GpxSparse *st, hipStream_t s, double *z, double *f, double *g);
+// ms[8]: six times and the step and halving counts of the last update
+int gpx_sparse_laplace_run_timings(GpxSparse *st, double *ms);
 
 // ---- greedy pseudo-input selection (select.hip) ----------------------------------------
 // out[j] = k(x_j, x*) for j < n, 0 for n <= j < np; x* = xs[0 .. d) on the device, written by

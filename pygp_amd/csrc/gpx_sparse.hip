@@ -1,4 +1,5 @@
-// C ABI of libgpx.so, the wrappers of the sparse models (gpx_sparse_*: FITC, DTC, VFE) and of
+// C ABI of libgpx.so, the wrappers of the sparse models (gpx_sparse_*: FITC, DTC, VFE; and
+// gpx_sparse_laplace_*: the classifier on pseudo-inputs, in the same state) and of
 // the greedy pseudo-input selection (gpx_select_*): argument checks and the handle's book-keeping
 // (which data the sparse model belongs to) around the entry points of sparse.hip and select.hip,
 // which own their buffers and kernels.
@@ -11,14 +12,24 @@ using namespace gpxh;
 
 extern "C" {
 
-static int sparse_ready(gpx_ctx *h, const char *what)
+// Is the handle's sparse model current, and of the kind the calling entry belongs to? The
+// regression models and the sparse Laplace classifier live in the same state and panels: an update
+// of either kind replaces the other's model, whose entries must not answer from these numbers.
+static int sparse_ready(gpx_ctx *h, const char *what, bool laplace = false)
 {
+    const char *model = laplace ? "sparse Laplace model" : "sparse model";
+    const char *update = laplace ? "gpx_sparse_laplace_update" : "gpx_sparse_update";
     if (!h->sparse || h->sparse_version < 0) {
-        gpx_set_error("%s: no sparse model (call gpx_sparse_update)", what);
+        gpx_set_error("%s: no %s (call %s)", what, model, update);
         return -1;
     }
     if (h->sparse_version != h->data_version) {
-        gpx_set_error("%s: the data changed since gpx_sparse_update (stale model)", what);
+        gpx_set_error("%s: the data changed since %s (stale model)", what, update);
+        return -1;
+    }
+    if ((gpx_sparse_kind(h->sparse) == GPX_SPARSE_KIND_LAPLACE) != laplace) {
+        gpx_set_error("%s: %s replaced the %s (stale model: call %s)", what,
+                      laplace ? "gpx_sparse_update" : "gpx_sparse_laplace_update", model, update);
         return -1;
     }
     return 0;
@@ -82,7 +93,7 @@ int gpx_sparse_append(gpx_t *h, const double *Xnew, const double *ynew, int64_t 
         return -1;
     }
     if (!h->sparse || h->sparse_version < 0 || h->sparse_version != h->data_version ||
-        h->n <= 0 || h->n + m > h->cap)
+        gpx_sparse_kind(h->sparse) == GPX_SPARSE_KIND_LAPLACE || h->n <= 0 || h->n + m > h->cap)
         return -3;
     const int n_old = h->n;
     const size_t xrow = (size_t)h->d * 8;
@@ -183,6 +194,134 @@ int gpx_sparse_pseudo_timing(gpx_t *h, double *ms)
         return -1;
     }
     return gpx_sparse_run_pseudo_timing(h->sparse, ms);
+}
+
+// ---- sparse Laplace classification (sparse.hip) -----------------------
+int gpx_sparse_laplace_update(gpx_t *h, const gpx_kspec *k, int lik, double mean, const double *U,
+                              int64_t p, double jitter, double tol, int max_iter, int *iters,
+                              int *info)
+{
+    CHECK_H(h);
+    GPX_TRY(require_state(h, ST_PLAIN, "gpx_sparse_laplace_update"));
+    if (info) *info = 0;
+    if (iters) *iters = 0;
+    h->sparse_version = -1;
+    if (h->n <= 0) {
+        gpx_set_error("gpx_sparse_laplace_update: no data: call gpx_set_data first");
+        return -1;
+    }
+    if (lik != GPX_LIK_LOGISTIC && lik != GPX_LIK_PROBIT) {
+        gpx_set_error("gpx_sparse_laplace_update: lik must be GPX_LIK_LOGISTIC or GPX_LIK_PROBIT "
+                      "(got %d)", lik);
+        return -1;
+    }
+    if (!U || p < 1 || p > GPX_SPARSE_MAX_P) {
+        gpx_set_error("gpx_sparse_laplace_update: need 1 <= p <= %d pseudo-inputs (got %lld)",
+                      GPX_SPARSE_MAX_P, (long long)p);
+        return -1;
+    }
+    const long long pp = round_up(p, GPX_TILE), np = round_up(h->n, GPX_TILE);
+    if (pp * np >= (1LL << 31)) {
+        gpx_set_error("gpx_sparse_laplace_update: p_pad * N_pad = %lld x %lld must stay below 2^31",
+                      pp, np);
+        return -1;
+    }
+    if (!std::isfinite(mean) || !std::isfinite(jitter) || jitter < 0.0 || !std::isfinite(tol) ||
+        !(tol > 0.0) || max_iter < 1) {
+        gpx_set_error("gpx_sparse_laplace_update: need a finite mean, jitter >= 0, tol > 0 and "
+                      "max_iter >= 1");
+        return -1;
+    }
+    for (int64_t i = 0; i < p * h->d; ++i)
+        if (!std::isfinite(U[i])) {
+            gpx_set_error("gpx_sparse_laplace_update: non-finite pseudo-inputs");
+            return -1;
+        }
+    KParams kp;
+    GPX_TRY(gpx_flatten_kspec(k, h->d, &kp));
+    // the resident y must be labels: read back once per data version (a copy, no launch)
+    if (h->labels_version != h->data_version) {
+        std::vector<double> yh((size_t)h->n);
+        GPX_HIP(hipMemcpy(yh.data(), h->y.p, (size_t)h->n * 8, hipMemcpyDeviceToHost));
+        for (int i = 0; i < h->n; ++i)
+            if (yh[i] != 1.0 && yh[i] != -1.0) {
+                gpx_set_error("gpx_sparse_laplace_update: labels must be -1 or +1 (y[%d] = %g)", i,
+                              yh[i]);
+                return -1;
+            }
+        h->labels_version = h->data_version;
+    }
+    const int r = gpx_sparse_laplace_run_update(&h->sparse, h->stream, kp, lik, U, (int)p, jitter,
+                                                mean, tol, max_iter, h->X.as<double>(),
+                                                h->y.as<double>(), h->n, h->d, h->cap, iters, info);
+    if (r == 0) h->sparse_version = h->data_version;
+    return r;
+}
+
+int gpx_sparse_laplace_loglik(gpx_t *h, double *lZ, double *dlZ)
+{
+    CHECK_H(h);
+    GPX_TRY(sparse_ready(h, "gpx_sparse_laplace_loglik", true));
+    if (!lZ) {
+        gpx_set_error("gpx_sparse_laplace_loglik: lZ is null");
+        return -1;
+    }
+    return gpx_sparse_laplace_run_loglik(h->sparse, h->stream, h->X.as<double>(), lZ, dlZ,
+                                         nullptr);
+}
+
+int gpx_sparse_laplace_loglik_pseudo(gpx_t *h, double *lZ, double *dlZ, double *dU)
+{
+    CHECK_H(h);
+    GPX_TRY(sparse_ready(h, "gpx_sparse_laplace_loglik_pseudo", true));
+    if (!lZ || !dlZ || !dU) {
+        gpx_set_error("gpx_sparse_laplace_loglik_pseudo: lZ, dlZ and dU must not be null");
+        return -1;
+    }
+    return gpx_sparse_laplace_run_loglik(h->sparse, h->stream, h->X.as<double>(), lZ, dlZ, dU);
+}
+
+int gpx_sparse_laplace_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2,
+                                 double *dmu, double *ds2)
+{
+    CHECK_H(h);
+    GPX_TRY(sparse_ready(h, "gpx_sparse_laplace_posterior", true));
+    if (!Xs || !mu || !s2 || m < 0 || (!dmu) != (!ds2)) {
+        gpx_set_error("gpx_sparse_laplace_posterior: bad arguments");
+        return -1;
+    }
+    if (m == 0) return 0;
+    return gpx_sparse_run_posterior(h->sparse, h->stream, Xs, m, mu, s2, dmu, ds2, nullptr);
+}
+
+int gpx_sparse_laplace_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu,
+                                      double *Sigma)
+{
+    CHECK_H(h);
+    GPX_TRY(sparse_ready(h, "gpx_sparse_laplace_posterior_full", true));
+    if (!Xs || !mu || !Sigma || m < 1 || m > 8192) {
+        gpx_set_error("gpx_sparse_laplace_posterior_full: bad arguments (1 <= m <= 8192)");
+        return -1;
+    }
+    return gpx_sparse_run_posterior(h->sparse, h->stream, Xs, m, mu, nullptr, nullptr, nullptr,
+                                    Sigma);
+}
+
+int gpx_sparse_laplace_get_mode(gpx_t *h, double *z, double *f, double *g)
+{
+    CHECK_H(h);
+    GPX_TRY(sparse_ready(h, "gpx_sparse_laplace_get_mode", true));
+    return gpx_sparse_laplace_run_mode(h->sparse, h->stream, z, f, g);
+}
+
+int gpx_sparse_laplace_timings(gpx_t *h, double *ms)
+{
+    CHECK_H(h);
+    if (!ms) {
+        gpx_set_error("gpx_sparse_laplace_timings: ms is null");
+        return -1;
+    }
+    return gpx_sparse_laplace_run_timings(h->sparse, ms);
 }
 
 // ---- greedy pseudo-input selection (select.hip) ---------------------------------------

@@ -20,7 +20,12 @@
 // (ldn, the handle's data capacity) so that the columns have somewhere to go. The update and
 // the append run one column stage, sp_refined_v0 and sp_column_kernel, on the panel and on the
 // strip: what holds the append to the one-shot model is that there is one copy of it.
+//
+// The last part of the file is the sparse Laplace classifier: binary labels
+// under the subset-of-regressors prior on the same V0, Newton's method in the p-dimensional space
+// on the same split-K product, factorisation, contractions and posterior pass, in the same state.
 #include "gpx_internal.h"
+#include "lik_dev.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -81,10 +86,23 @@ struct GpxSparse {
     double hsc[S_COUNT];
     // HIP events around the last update, gradient stage and contraction pass, then the dU
     // pass (ms)
-    hipEvent_t ev[7] = {};
+    // (7 .. 18: the sparse Laplace model's, SLE_* below)
+    hipEvent_t ev[19] = {};
     double ms[3] = {0, 0, 0};
     double ms_pseudo = 0;
+    // method SP_LAPLACE, binary labels under the subset-of-regressors prior (DESIGN.md section
+    // 26). P2 holds the unscaled V0 from the update on, A / Aw the factor of I + V0 W V0^T at the
+    // mode and its inverse, beta = A^-T V0 (W (f - m) + g): what the posterior pass above reads.
+    // slv: the N-vectors (SLV_*, ldn doubles each); slz: the p-vectors (SLZ_*, pp doubles each);
+    // sl_cur: which of the two sets of per-point terms belongs to the mode.
+    int lik = 0, sl_cur = 0, sl_iters = 0, sl_halvings = 0;
+    double sl_psi = 0, sl_lZ = 0;
+    DevBuf slv, slz, slpart, slsc;
+    double sl_ms[6] = {0, 0, 0, 0, 0, 0};
 };
+
+// the fourth method of a GpxSparse, beside gpx_sparse_method of gpx.h: it has entries of its own
+#define SP_LAPLACE GPX_SPARSE_KIND_LAPLACE
 
 static int sp_event(GpxSparse *st, hipStream_t s, int i)
 {
@@ -551,8 +569,10 @@ static int sp_dot(hipStream_t s, const double *a, const double *b, long long n, 
 
 // upper factor of the symmetric pp x pp matrix in F (ld ldp) in place, its inverse in Fw;
 // Fk is the factorisation's scratch. Returns > 0 (pivot) when not positive definite.
-static int sp_factor(GpxSparse *st, hipStream_t s, double *F, double *Fw, double *Fk,
-                     int *gates)
+// (sp_factor_enqueue: the launches alone, the pivot left in st->info on the device for a caller
+// that reads it with its own results)
+static int sp_factor_enqueue(GpxSparse *st, hipStream_t s, double *F, double *Fw, double *Fk,
+                             int *gates)
 {
     DenseWs w;
     w.A = F;
@@ -570,11 +590,20 @@ static int sp_factor(GpxSparse *st, hipStream_t s, double *F, double *Fw, double
     hipLaunchKernelGGL(sp_zero_lower_kernel, grid, dim3(SP_T), 0, s, F, st->ldp, st->pp);
     hipLaunchKernelGGL(sp_zero_lower_kernel, grid, dim3(SP_T), 0, s, Fw, st->ldp, st->pp);
     GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+static int sp_factor(GpxSparse *st, hipStream_t s, double *F, double *Fw, double *Fk,
+                     int *gates)
+{
+    GPX_TRY(sp_factor_enqueue(st, s, F, Fw, Fk, gates));
     int inf = 0;
-    GPX_HIP(hipMemcpyAsync(&inf, w.info, sizeof(int), hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipMemcpyAsync(&inf, st->info.p, sizeof(int), hipMemcpyDeviceToHost, s));
     GPX_HIP(hipStreamSynchronize(s));
     if (inf) {
-        gpx_set_error("gpx_sparse_update: matrix is not positive definite: pivot %d", inf);
+        gpx_set_error("%s: matrix is not positive definite: pivot %d",
+                      st->method == SP_LAPLACE ? "gpx_sparse_laplace_update" : "gpx_sparse_update",
+                      inf);
         return inf;
     }
     return 0;
@@ -621,9 +650,12 @@ static int sp_finish(GpxSparse *st, hipStream_t s, int *info)
     return 0;
 }
 
-int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, int method,
-                          const double *U, int p, double log_sn, double mean,
-                          const double *X, const double *y, int n, int d, int cap, int *info)
+// The head of every update: the state's shapes and buffers, L = chol(Kuu + su2 I) and the refined
+// V0 = L^-T Kux in P2 (P1, P3: scratch). Returns the pivot (> 0, also in *info) when
+// Kuu + su2 I is not positive definite.
+static int sp_setup(GpxSparse **state, hipStream_t s, const KParams &kp, int method,
+                    const double *U, int p, double sn2, double su2, double mean, const double *X,
+                    int n, int d, int cap, int *info)
 {
     if (!*state) *state = new GpxSparse();
     GpxSparse *st = *state;
@@ -638,13 +670,12 @@ int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, i
                                                                                       : st->np;
     st->d = d;
     st->kp = kp;
-    st->sn2 = exp(2 * log_sn);             // gaussian.py
-    // the two forms of the jitter are not bitwise equal (fitc.py, dtc.py)
-    st->su2 = method == GPX_FITC ? st->sn2 / 1e6 : st->sn2 * 1e-6;
+    st->sn2 = sn2;
+    st->su2 = su2;
     st->mean = mean;
     st->prior = gpx_kernel_prior(kp);
     const int pp = st->pp, ldp = st->ldp, np = st->np, ldn = st->ldn;
-    const size_t mat = (size_t)pp * ldp * 8, panel = (size_t)pp * ldn * 8, vec = (size_t)ldn * 8;
+    const size_t mat = (size_t)pp * ldp * 8, panel = (size_t)pp * ldn * 8;
     GPX_TRY(st->U.reserve((size_t)p * d * 8));
     GPX_TRY(st->L.reserve(mat));
     GPX_TRY(st->Lw.reserve(mat));
@@ -652,7 +683,6 @@ int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, i
     GPX_TRY(st->A.reserve(mat));
     GPX_TRY(st->Aw.reserve(mat));
     GPX_TRY(st->Ak.reserve(mat));
-    GPX_TRY(st->VV.reserve(mat));
     if (!st->pctl.p) {
         GPX_TRY(st->info.reserve(64));
         GPX_TRY(st->pctl.reserve(gpx_panel_ctl_bytes()));
@@ -661,12 +691,7 @@ int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, i
     GPX_TRY(st->P1.reserve(panel));
     GPX_TRY(st->P2.reserve(panel));
     GPX_TRY(st->P3.reserve(panel));
-    GPX_TRY(st->ell.reserve(vec));
-    GPX_TRY(st->rt.reserve(vec));
     GPX_TRY(st->beta.reserve((size_t)pp * 8));
-    GPX_TRY(st->gam.reserve((size_t)pp * 8));
-    GPX_TRY(st->vrt.reserve((size_t)pp * 8));
-    const int nbc = (np + SP_T - 1) / SP_T;
     // (the block partials of the column kernels: for every n an append can reach)
     GPX_TRY(st->part.reserve((size_t)std::max((ldn + SP_T - 1) / SP_T * 5, pp * 2) * 8));
     GPX_TRY(st->scal.reserve(S_COUNT * 8));
@@ -683,8 +708,29 @@ int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, i
         if (r > 0 && info) *info = r;
         return r;
     }
-    // V0 = L^-T Kux (zero outside p x n), then ell, rt, V = V0 / ell in place and the sums
-    GPX_TRY(sp_refined_v0(st, s, X, n, np, st->P2.d(), ldn, st->P1.d(), st->P3.d()));
+    // V0 = L^-T Kux (zero outside p x n)
+    return sp_refined_v0(st, s, X, n, np, st->P2.d(), ldn, st->P1.d(), st->P3.d());
+}
+
+int gpx_sparse_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, int method,
+                          const double *U, int p, double log_sn, double mean,
+                          const double *X, const double *y, int n, int d, int cap, int *info)
+{
+    const double sn2 = exp(2 * log_sn);    // gaussian.py
+    // the two forms of the jitter are not bitwise equal (fitc.py, dtc.py)
+    const double su2 = method == GPX_FITC ? sn2 / 1e6 : sn2 * 1e-6;
+    const int r0 = sp_setup(state, s, kp, method, U, p, sn2, su2, mean, X, n, d, cap, info);
+    if (r0 != 0) return r0;
+    GpxSparse *st = *state;
+    const int pp = st->pp, ldp = st->ldp, np = st->np, ldn = st->ldn;
+    const int nbc = (np + SP_T - 1) / SP_T;
+    // what the regression models keep beside the shared head: ell, rt, gamma and the kept sums
+    GPX_TRY(st->ell.reserve((size_t)ldn * 8));
+    GPX_TRY(st->rt.reserve((size_t)ldn * 8));
+    GPX_TRY(st->gam.reserve((size_t)pp * 8));
+    GPX_TRY(st->vrt.reserve((size_t)pp * 8));
+    GPX_TRY(st->VV.reserve((size_t)pp * ldp * 8));
+    // ell, rt, V = V0 / ell in place and the sums
     hipLaunchKernelGGL(sp_column_kernel, dim3(nbc), dim3(SP_T), 0, s, st->P2.d(), (long long)ldn,
                        pp, 0, n, np, (double *)nullptr, 0LL, y, mean, st->prior, st->sn2,
                        method == GPX_FITC ? 1 : 0, st->ell.d(), st->rt.d(), st->part.d());
@@ -1067,5 +1113,544 @@ int gpx_sparse_run_timings(GpxSparse *st, double *ms)
         return -1;
     }
     for (int i = 0; i < 3; ++i) ms[i] = st->ms[i];
+    return 0;
+}
+
+int gpx_sparse_kind(const GpxSparse *st) { return st && st->ready ? st->method : 0; }
+
+// ==== sparse Laplace: binary labels under the subset-of-regressors prior ====
+// f = m + V0^T z, z ~ N(0, I_p); Psi(z) = sum log p(y | f) - z.z / 2. A Newton step is
+// z_new = A^-1 V0 (W (f - m) + g) with A = I + V0 W V0^T: two passes over the p x N panel V0 (the
+// terms of a candidate z; the panel scaled by sqrt W), the split-K product and the p x p
+// factorisation of the models above. Nothing divides by W.
+
+// the N-vectors in slv (ldn doubles each): two sets of per-point terms, the current one and the
+// candidate's (ft = f - m = V0^T z, g, W, d3, b = W ft + g), and the gradient stage's
+enum { SLV_FT = 0, SLV_G = 2, SLV_W = 4, SLV_D3 = 6, SLV_B = 8, SLV_S2 = 10, SLV_Q, SLV_T2, SLV_C,
+       SLV_AC, SLV_COUNT };
+// the p-vectors in slz (pp doubles each)
+enum { SLZ_Z = 0, SLZ_NEW, SLZ_TRY, SLZ_V, SLZ_T, SLZ_Q1, SLZ_T1, SLZ_WA, SLZ_WC, SLZ_COUNT };
+// events (GpxSparse::ev)
+enum { SLE_END = 7, SLE_STEP0, SLE_STEP1, SLE_P2A, SLE_P2B, SLE_P1A, SLE_P1B, SLE_GRAD0,
+       SLE_GRAD1, SLE_GRAD2, SLE_DU0, SLE_DU1 };
+
+#define SL_COLS 128   // columns of a workgroup's strip: 64 lanes x 2 (16-byte loads)
+#define SL_ROWS 4     // row groups of a workgroup, one wave each
+#define SL_FLY 8      // rows a lane has in flight
+
+static inline double *slv(const GpxSparse *st, int k) { return st->slv.d() + (size_t)k * st->ldn; }
+static inline double *slz(const GpxSparse *st, int k) { return st->slz.d() + (size_t)k * st->pp; }
+
+// The first panel pass: ft_j = sum_i V0_ij z_i on a strip of SL_COLS columns a workgroup, then
+// the likelihood's terms at f_j = mean + ft_j. Wave w takes the rows w, w + 4, ... with SL_FLY
+// 16-byte loads in flight a lane; the four partial dots of a column meet in LDS in a fixed order.
+// Columns j >= n weigh 0: every vector is written 0 there. V0 is zero in its rows >= p.
+// part[block][3]: sum log p, max |ft - ft_old|, max |mean + ft| over the block's live columns.
+__global__ __launch_bounds__(SP_T) void sl_terms_kernel(
+    const double *__restrict__ V0, long long ld, int pp, int n, const double *__restrict__ z,
+    const double *__restrict__ y, double mean, int lik, const double *__restrict__ ft_old,
+    double *__restrict__ ft, double *__restrict__ g, double *__restrict__ W,
+    double *__restrict__ d3, double *__restrict__ b, double *__restrict__ part)
+{
+    __shared__ double dots[SL_ROWS][SL_COLS];
+    __shared__ double red[SP_T];
+    const int t = threadIdx.x, cp = t & 63, rg = t >> 6;
+    const double *col = V0 + (size_t)blockIdx.x * SL_COLS + 2 * cp;
+    double a0 = 0.0, a1 = 0.0;
+    for (int i = rg; i < pp; i += SL_ROWS * SL_FLY) {
+        double2 v[SL_FLY];
+#pragma unroll
+        for (int u = 0; u < SL_FLY; ++u)
+            v[u] = *reinterpret_cast<const double2 *>(col + (size_t)(i + SL_ROWS * u) * ld);
+#pragma unroll
+        for (int u = 0; u < SL_FLY; ++u) {
+            const double zi = z[i + SL_ROWS * u];
+            a0 += v[u].x * zi;
+            a1 += v[u].y * zi;
+        }
+    }
+    dots[rg][2 * cp] = a0;
+    dots[rg][2 * cp + 1] = a1;
+    __syncthreads();
+    double lp = 0.0, df = 0.0, fm = 0.0;
+    if (t < SL_COLS) {
+        const int j = blockIdx.x * SL_COLS + t;
+        const double x = ((dots[0][t] + dots[1][t]) + dots[2][t]) + dots[3][t];
+        if (j < n) {
+            const LikTerms q = lik_point(lik, y[j], mean + x);
+            ft[j] = x;
+            g[j] = q.g;
+            W[j] = q.W;
+            d3[j] = q.d3;
+            b[j] = q.W * x + q.g;
+            lp = q.lp;
+            df = fabs(x - ft_old[j]);
+            fm = fabs(mean + x);
+        } else {
+            ft[j] = g[j] = W[j] = d3[j] = b[j] = 0.0;
+        }
+    }
+    const double s0 = block_sum<SP_T>(lp, red);
+    const double s1 = block_max<SP_T>(df, red);
+    const double s2 = block_max<SP_T>(fm, red);
+    if (t == 0) {
+        double *po = part + (size_t)blockIdx.x * 3;
+        po[0] = s0;
+        po[1] = s1;
+        po[2] = s2;
+    }
+}
+
+// out[0] = sum_b part[b][0], out[1] = max_b part[b][1], out[2] = max_b part[b][2]; one block, fixed
+// order
+__global__ __launch_bounds__(SP_T) void sl_reduce_kernel(const double *__restrict__ part, int nb,
+                                                        double *__restrict__ out)
+{
+    __shared__ double red[SP_T];
+    double s = 0.0, m1 = 0.0, m2 = 0.0;
+    for (int k = threadIdx.x; k < nb; k += SP_T) {
+        s += part[(size_t)k * 3];
+        m1 = fmax(m1, part[(size_t)k * 3 + 1]);
+        m2 = fmax(m2, part[(size_t)k * 3 + 2]);
+    }
+    s = block_sum<SP_T>(s, red);
+    m1 = block_max<SP_T>(m1, red);
+    m2 = block_max<SP_T>(m2, red);
+    if (threadIdx.x == 0) {
+        out[0] = s;
+        out[1] = m1;
+        out[2] = m2;
+    }
+}
+
+// The second panel pass: out[:, j] = in[:, j] * sqrt(W_j) (W_j >= 0 up to rounding; 0 for the
+// padding and for Probit's far points), a strip of SL_COLS columns and SL_ROWS * SL_FLY rows a
+// workgroup, 16-byte loads and stores
+__global__ __launch_bounds__(SP_T) void sl_scale_kernel(const double *__restrict__ in,
+                                                       double *__restrict__ out, long long ld,
+                                                       const double *__restrict__ W)
+{
+    const int t = threadIdx.x, cp = t & 63, rg = t >> 6;
+    const size_t j = (size_t)blockIdx.x * SL_COLS + 2 * cp;
+    const double2 w = *reinterpret_cast<const double2 *>(W + j);
+    const double s0 = sqrt(fmax(w.x, 0.0)), s1 = sqrt(fmax(w.y, 0.0));
+    const size_t o = ((size_t)blockIdx.y * SL_ROWS * SL_FLY + rg) * ld + j;
+    double2 v[SL_FLY];
+#pragma unroll
+    for (int u = 0; u < SL_FLY; ++u)
+        v[u] = *reinterpret_cast<const double2 *>(in + o + (size_t)(SL_ROWS * u) * ld);
+#pragma unroll
+    for (int u = 0; u < SL_FLY; ++u) {
+        v[u].x *= s0;
+        v[u].y *= s1;
+        *reinterpret_cast<double2 *>(out + o + (size_t)(SL_ROWS * u) * ld) = v[u];
+    }
+}
+
+// out_i = a_i + step (b_i - a_i) for i < pp
+__global__ __launch_bounds__(SP_T) void sl_lerp_kernel(const double *__restrict__ a,
+                                                      const double *__restrict__ b, double step,
+                                                      int pp, double *__restrict__ out)
+{
+    const int i = blockIdx.x * SP_T + threadIdx.x;
+    if (i < pp) out[i] = a[i] + step * (b[i] - a[i]);
+}
+
+// The gradient's panel pass over T0 = A^-T V0 (in place): sigma_j = sum_i T0_ij^2,
+// s2_j = sigma_j d3_j / 2, and T = T0 W. The layout of sl_terms_kernel.
+__global__ __launch_bounds__(SP_T) void sl_sigma_kernel(double *__restrict__ T, long long ld,
+                                                       int pp, const double *__restrict__ W,
+                                                       const double *__restrict__ d3,
+                                                       double *__restrict__ s2)
+{
+    __shared__ double dots[SL_ROWS][SL_COLS];
+    const int t = threadIdx.x, cp = t & 63, rg = t >> 6;
+    const size_t j0 = (size_t)blockIdx.x * SL_COLS + 2 * cp;
+    double *col = T + j0;
+    const double2 w = *reinterpret_cast<const double2 *>(W + j0);
+    double a0 = 0.0, a1 = 0.0;
+    for (int i = rg; i < pp; i += SL_ROWS * SL_FLY) {
+        double2 v[SL_FLY];
+#pragma unroll
+        for (int u = 0; u < SL_FLY; ++u)
+            v[u] = *reinterpret_cast<const double2 *>(col + (size_t)(i + SL_ROWS * u) * ld);
+#pragma unroll
+        for (int u = 0; u < SL_FLY; ++u) {
+            a0 += v[u].x * v[u].x;
+            a1 += v[u].y * v[u].y;
+            v[u].x *= w.x;
+            v[u].y *= w.y;
+            *reinterpret_cast<double2 *>(col + (size_t)(i + SL_ROWS * u) * ld) = v[u];
+        }
+    }
+    dots[rg][2 * cp] = a0;
+    dots[rg][2 * cp + 1] = a1;
+    __syncthreads();
+    if (t < SL_COLS) {
+        const size_t j = (size_t)blockIdx.x * SL_COLS + t;
+        const double sg = ((dots[0][t] + dots[1][t]) + dots[2][t]) + dots[3][t];
+        s2[j] = 0.5 * sg * d3[j];
+    }
+}
+
+// c_j = s2_j - (W_j q_j - t2_j), ac_j = g_j + c_j for j < n, 0 for the padding;
+// part[block] = sum ac
+__global__ __launch_bounds__(SP_T) void sl_c_kernel(const double *__restrict__ s2,
+                                                   const double *__restrict__ W,
+                                                   const double *__restrict__ q,
+                                                   const double *__restrict__ t2,
+                                                   const double *__restrict__ g, int n, int np,
+                                                   double *__restrict__ c, double *__restrict__ ac,
+                                                   double *__restrict__ part)
+{
+    __shared__ double red[SP_T];
+    const int j = blockIdx.x * SP_T + threadIdx.x;
+    double cj = 0.0, aj = 0.0;
+    if (j < n) {
+        cj = s2[j] - (W[j] * q[j] - t2[j]);
+        aj = g[j] + cj;
+    }
+    if (j < np) {
+        c[j] = cj;
+        ac[j] = aj;
+    }
+    const double s = block_sum<SP_T>(aj, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// G_ux in place over (B0 T^T) T: G_ij + wa_i (a_j + c_j) + wc_i a_j - B0_ij W_j inside p x n, 0
+// outside. The layout of sl_scale_kernel.
+__global__ __launch_bounds__(SP_T) void sl_gux_kernel(double *__restrict__ G,
+                                                     const double *__restrict__ B0, long long ld,
+                                                     int p, int n, const double *__restrict__ wa,
+                                                     const double *__restrict__ wc,
+                                                     const double *__restrict__ ac,
+                                                     const double *__restrict__ a,
+                                                     const double *__restrict__ W)
+{
+    const int t = threadIdx.x, cp = t & 63, rg = t >> 6;
+    const size_t j = (size_t)blockIdx.x * SL_COLS + 2 * cp;
+    const double2 acj = *reinterpret_cast<const double2 *>(ac + j);
+    const double2 aj = *reinterpret_cast<const double2 *>(a + j);
+    const double2 wj = *reinterpret_cast<const double2 *>(W + j);
+    const bool in0 = j < (size_t)n, in1 = j + 1 < (size_t)n;
+    const int i0 = blockIdx.y * SL_ROWS * SL_FLY + rg;
+    double2 v[SL_FLY], bb[SL_FLY];
+#pragma unroll
+    for (int u = 0; u < SL_FLY; ++u) {
+        const size_t o = (size_t)(i0 + SL_ROWS * u) * ld + j;
+        v[u] = *reinterpret_cast<const double2 *>(G + o);
+        bb[u] = *reinterpret_cast<const double2 *>(B0 + o);
+    }
+#pragma unroll
+    for (int u = 0; u < SL_FLY; ++u) {
+        const int i = i0 + SL_ROWS * u;
+        double2 r;
+        r.x = r.y = 0.0;
+        if (i < p) {
+            const double ai = wa[i], ci = wc[i];
+            if (in0) r.x = v[u].x + ai * acj.x + ci * aj.x - bb[u].x * wj.x;
+            if (in1) r.y = v[u].y + ai * acj.y + ci * aj.y - bb[u].y * wj.y;
+        }
+        *reinterpret_cast<double2 *>(G + (size_t)i * ld + j) = r;
+    }
+}
+
+// G_uu = -S / 2 inside p x p, 0 outside, in place (ld pp)
+__global__ __launch_bounds__(SP_T) void sl_guu_kernel(double *__restrict__ G, int p, int pp)
+{
+    const int j = blockIdx.x * SP_T + threadIdx.x;
+    const int i = blockIdx.y;
+    if (j >= pp) return;
+    const size_t o = (size_t)i * pp + j;
+    G[o] = i < p && j < p ? -0.5 * G[o] : 0.0;
+}
+
+// ---- host -------------------------------------------------------------------------------------
+// the terms of the candidate z (device, pp) into set `to`, against the ft of set `from`; the
+// three sums to sc[0 .. 2] and z.z to sc[3]
+static int sl_terms(GpxSparse *st, hipStream_t s, const double *z, const double *y, int from,
+                    int to)
+{
+    const int nb = st->np / SL_COLS;
+    hipLaunchKernelGGL(sl_terms_kernel, dim3(nb), dim3(SP_T), 0, s, st->P2.d(),
+                       (long long)st->ldn, st->pp, st->n, z, y, st->mean, st->lik,
+                       slv(st, SLV_FT + from), slv(st, SLV_FT + to), slv(st, SLV_G + to),
+                       slv(st, SLV_W + to), slv(st, SLV_D3 + to), slv(st, SLV_B + to),
+                       st->slpart.d());
+    hipLaunchKernelGGL(sl_reduce_kernel, dim3(1), dim3(SP_T), 0, s, st->slpart.d(), nb,
+                       st->slsc.d());
+    GPX_HIP(hipGetLastError());
+    return sp_dot(s, z, nullptr, st->pp, st->slsc.d() + 3);
+}
+
+// P1 = V0 sqrt(W) for the W of set `cur`
+static int sl_scaled_panel(GpxSparse *st, hipStream_t s, int cur)
+{
+    hipLaunchKernelGGL(sl_scale_kernel, dim3(st->np / SL_COLS, st->pp / (SL_ROWS * SL_FLY)),
+                       dim3(SP_T), 0, s, st->P2.d(), st->P1.d(), (long long)st->ldn,
+                       slv(st, SLV_W + cur));
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+int gpx_sparse_laplace_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, int lik,
+                                  const double *U, int p, double jitter, double mean, double tol,
+                                  int max_iter, const double *X, const double *y, int n, int d,
+                                  int cap, int *iters, int *info)
+{
+    const int r0 = sp_setup(state, s, kp, SP_LAPLACE, U, p, 0.0, jitter, mean, X, n, d, cap, info);
+    if (r0 != 0) return r0;
+    GpxSparse *st = *state;
+    st->lik = lik;
+    const int pp = st->pp, ldp = st->ldp, np = st->np, ldn = st->ldn;
+    GPX_TRY(st->slv.reserve((size_t)SLV_COUNT * ldn * 8));
+    GPX_TRY(st->slz.reserve((size_t)SLZ_COUNT * pp * 8));
+    GPX_TRY(st->slpart.reserve((size_t)(ldn / SL_COLS + 1) * 3 * 8));
+    GPX_TRY(st->slsc.reserve(8 * 8));
+    // start: z = 0, cold every time; both sets' ft = 0
+    GPX_HIP(hipMemsetAsync(st->slz.p, 0, (size_t)SLZ_COUNT * pp * 8, s));
+    GPX_HIP(hipMemsetAsync(st->slv.p, 0, (size_t)2 * ldn * 8, s));
+    double *z = slz(st, SLZ_Z), *zn = slz(st, SLZ_NEW), *zt = slz(st, SLZ_TRY);
+    double *P1 = st->P1.d(), *P2 = st->P2.d();
+    const dim3 pgrid((pp + SP_T - 1) / SP_T);
+    double h0[4], hs[4];
+    int cur = 0, it = 0, halved = 0, inf = 0;
+    bool converged = false;
+    GPX_TRY(sl_terms(st, s, z, y, 1, 0));
+    GPX_HIP(hipMemcpyAsync(h0, st->slsc.p, 4 * 8, hipMemcpyDeviceToHost, s));
+    double psi_old = 0.0;
+    while (it < max_iter) {
+        ++it;
+        const bool timed = it == 1;
+        if (timed) GPX_TRY(sp_event(st, s, SLE_STEP0));
+        // A = I + V0 W V0^T and its factor; the pivot is read with the step's sums (the matrix is
+        // positive definite by construction)
+        if (timed) GPX_TRY(sp_event(st, s, SLE_P2A));
+        GPX_TRY(sl_scaled_panel(st, s, cur));
+        if (timed) GPX_TRY(sp_event(st, s, SLE_P2B));
+        GPX_TRY(sp_abt_split(st, s, P1, P1, ldn, np, st->A.d(), ldp, 1.0));
+        GPX_TRY(sp_factor_enqueue(st, s, st->A.d(), st->Aw.d(), st->Ak.d(), st->gates_a));
+        // z_new = A^-1 V0 b
+        hipLaunchKernelGGL(sp_gemv_rows_kernel, dim3(pp), dim3(SP_T), 0, s, P2, (long long)ldn, n,
+                           slv(st, SLV_B + cur), slz(st, SLZ_V));
+        hipLaunchKernelGGL(sp_gemv_cols_kernel, pgrid, dim3(SP_T), 0, s, st->Aw.d(),
+                           (long long)ldp, pp, pp, slz(st, SLZ_V), slz(st, SLZ_T));
+        hipLaunchKernelGGL(sp_gemv_rows_kernel, dim3(pp), dim3(SP_T), 0, s, st->Aw.d(),
+                           (long long)ldp, pp, slz(st, SLZ_T), zn);
+        GPX_HIP(hipGetLastError());
+        if (timed) GPX_TRY(sp_event(st, s, SLE_P1A));
+        GPX_TRY(sl_terms(st, s, zn, y, cur, 1 - cur));
+        if (timed) GPX_TRY(sp_event(st, s, SLE_P1B));
+        GPX_HIP(hipMemcpyAsync(hs, st->slsc.p, 4 * 8, hipMemcpyDeviceToHost, s));
+        GPX_HIP(hipMemcpyAsync(&inf, st->info.p, sizeof(int), hipMemcpyDeviceToHost, s));
+        if (timed) GPX_TRY(sp_event(st, s, SLE_STEP1));
+        GPX_HIP(hipStreamSynchronize(s));
+        if (inf) {
+            gpx_set_error("gpx_sparse_laplace_update: I + V0 W V0^T is not positive definite: "
+                          "pivot %d", inf);
+            if (info) *info = inf;
+            return inf;
+        }
+        if (it == 1) psi_old = h0[0] - 0.5 * h0[3];
+        double psi_new = hs[0] - 0.5 * hs[3];
+        // the safeguard of gpx_laplace_update: a step that lowers Psi is halved,
+        // z_old + step (z_new - z_old); a decrease below 1e-10 (1 + |Psi|) is rounding
+        const double floor_psi = psi_old - 1e-10 * (1.0 + fabs(psi_old));
+        const double *acc = zn;
+        double step = 1.0;
+        for (int k = 0; !(psi_new >= floor_psi) && k < 10; ++k) {
+            step *= 0.5;
+            ++halved;
+            hipLaunchKernelGGL(sl_lerp_kernel, pgrid, dim3(SP_T), 0, s, z, zn, step, pp, zt);
+            GPX_HIP(hipGetLastError());
+            GPX_TRY(sl_terms(st, s, zt, y, cur, 1 - cur));
+            GPX_HIP(hipMemcpyAsync(hs, st->slsc.p, 4 * 8, hipMemcpyDeviceToHost, s));
+            GPX_HIP(hipStreamSynchronize(s));
+            psi_new = hs[0] - 0.5 * hs[3];
+            acc = zt;
+        }
+        GPX_HIP(hipMemcpyAsync(z, acc, (size_t)pp * 8, hipMemcpyDeviceToDevice, s));
+        cur = 1 - cur;
+        psi_old = psi_new;
+        if (hs[1] <= tol * (1.0 + hs[2])) {
+            converged = true;
+            break;
+        }
+    }
+    if (iters) *iters = it;
+    st->sl_iters = it;
+    st->sl_halvings = halved;
+    if (!converged) {
+        (void)hipStreamSynchronize(s);
+        gpx_set_error("gpx_sparse_laplace_update: no convergence in %d Newton steps (max_iter)",
+                      it);
+        return -1;
+    }
+    // at the mode (the accepted candidate's terms are those of z): A once more, its factor with
+    // the inverse, beta = A^-T V0 b and sum log A_ii
+    st->sl_cur = cur;
+    st->sl_psi = psi_old;
+    GPX_TRY(sl_scaled_panel(st, s, cur));
+    GPX_TRY(sp_abt_split(st, s, P1, P1, ldn, np, st->A.d(), ldp, 1.0));
+    const int r = sp_factor(st, s, st->A.d(), st->Aw.d(), st->Ak.d(), st->gates_a);
+    if (r != 0) {
+        if (r > 0 && info) *info = r;
+        return r;
+    }
+    hipLaunchKernelGGL(sp_gemv_rows_kernel, dim3(pp), dim3(SP_T), 0, s, P2, (long long)ldn, n,
+                       slv(st, SLV_B + cur), slz(st, SLZ_V));
+    hipLaunchKernelGGL(sp_gemv_cols_kernel, pgrid, dim3(SP_T), 0, s, st->Aw.d(), (long long)ldp,
+                       pp, pp, slz(st, SLZ_V), st->beta.d());
+    hipLaunchKernelGGL(sp_factor_terms_kernel, dim3(p), dim3(SP_T), 0, s, st->A.d(), st->Aw.d(),
+                       ldp, p, st->part.d());
+    GPX_HIP(hipGetLastError());
+    GPX_TRY(sp_reduce(s, st->part.d(), p, 2, st->scal.d() + S_LOGA));
+    GPX_HIP(hipMemcpyAsync(st->hsc, st->scal.p, S_COUNT * 8, hipMemcpyDeviceToHost, s));
+    GPX_TRY(sp_event(st, s, SLE_END));
+    GPX_HIP(hipStreamSynchronize(s));
+    st->sl_lZ = st->sl_psi - st->hsc[S_LOGA];
+    st->sl_ms[0] = sp_elapsed(st, 0, SLE_END);
+    st->sl_ms[1] = sp_elapsed(st, SLE_STEP0, SLE_STEP1);
+    st->sl_ms[2] = sp_elapsed(st, SLE_P2A, SLE_P2B) + sp_elapsed(st, SLE_P1A, SLE_P1B);
+    st->sl_ms[3] = st->sl_ms[4] = st->sl_ms[5] = 0.0;
+    st->ready = true;
+    return 0;
+}
+
+static int sl_ready(const GpxSparse *st, const char *what)
+{
+    if (!st || !st->ready || st->method != SP_LAPLACE) {
+        gpx_set_error("%s: no sparse Laplace model (call gpx_sparse_laplace_update)", what);
+        return -1;
+    }
+    return 0;
+}
+
+// lZ; with dlZ the gradient [kernel | mean]; with dU also d lZ / d U (p x d, host)
+int gpx_sparse_laplace_run_loglik(GpxSparse *st, hipStream_t s, const double *X, double *lZ,
+                                  double *dlZ, double *dU)
+{
+    GPX_TRY(sl_ready(st, "gpx_sparse_laplace_loglik"));
+    *lZ = st->sl_lZ;
+    if (!dlZ) return 0;
+    const int p = st->p, pp = st->pp, ldp = st->ldp, n = st->n, np = st->np, d = st->d;
+    const int ldn = st->ldn, cur = st->sl_cur;
+    const long long ld = ldn;
+    const size_t panel = (size_t)pp * ldn * 8;
+    GPX_TRY(st->P3.reserve(panel));
+    GPX_TRY(st->P4.reserve(panel));
+    GPX_TRY(st->Cm.reserve((size_t)pp * pp * 8));
+    GPX_TRY(st->Guu.reserve((size_t)pp * pp * 8));
+    const int nacc = 1 + st->kp.nhyper;
+    GPX_TRY(st->acc_uu.reserve((size_t)nacc * 8));
+    GPX_TRY(st->acc_ux.reserve((size_t)nacc * 8));
+    GPX_TRY(st->pg_part.reserve(gpx_pair_grad_scratch(pp) * 8));
+    double *P1 = st->P1.d(), *P2 = st->P2.d(), *P3 = st->P3.d(), *P4 = st->P4.d();
+    const double *a = slv(st, SLV_G + cur), *W = slv(st, SLV_W + cur);
+    const int nbc = (np + SP_T - 1) / SP_T;
+    const dim3 cgrid(nbc), sgrid(np / SL_COLS, pp / (SL_ROWS * SL_FLY));
+    GPX_TRY(sp_event(st, s, SLE_GRAD0));
+    // T0 = A^-T V0, then sigma, s2 and T = T0 W in one pass
+    GPX_TRY(sp_gemm(s, 1, 0, st->Aw.d(), ldp, P2, ldn, P3, ldn, pp, np, pp, 1.0, 0.0));
+    hipLaunchKernelGGL(sl_sigma_kernel, dim3(np / SL_COLS), dim3(SP_T), 0, s, P3, ld, pp, W,
+                       slv(st, SLV_D3 + cur), slv(st, SLV_S2));
+    // c = s2 - Rm Q s2: q = V0^T (V0 s2), t2 = T^T (T q)
+    hipLaunchKernelGGL(sp_gemv_rows_kernel, dim3(pp), dim3(SP_T), 0, s, P2, ld, n,
+                       slv(st, SLV_S2), slz(st, SLZ_Q1));
+    hipLaunchKernelGGL(sp_gemv_cols_kernel, cgrid, dim3(SP_T), 0, s, P2, ld, pp, np,
+                       slz(st, SLZ_Q1), slv(st, SLV_Q));
+    hipLaunchKernelGGL(sp_gemv_rows_kernel, dim3(pp), dim3(SP_T), 0, s, P3, ld, n, slv(st, SLV_Q),
+                       slz(st, SLZ_T1));
+    hipLaunchKernelGGL(sp_gemv_cols_kernel, cgrid, dim3(SP_T), 0, s, P3, ld, pp, np,
+                       slz(st, SLZ_T1), slv(st, SLV_T2));
+    hipLaunchKernelGGL(sl_c_kernel, cgrid, dim3(SP_T), 0, s, slv(st, SLV_S2), W, slv(st, SLV_Q),
+                       slv(st, SLV_T2), a, n, np, slv(st, SLV_C), slv(st, SLV_AC),
+                       st->part.d());
+    GPX_HIP(hipGetLastError());
+    GPX_TRY(sp_reduce(s, st->part.d(), nbc, 1, st->slsc.d() + 4));
+    // B0 = L^-1 V0, B0 a, B0 c
+    GPX_TRY(sp_gemm(s, 0, 0, st->Lw.d(), ldp, P2, ldn, P1, ldn, pp, np, pp, 1.0, 0.0));
+    hipLaunchKernelGGL(sp_gemv_rows_kernel, dim3(pp), dim3(SP_T), 0, s, P1, ld, n, a,
+                       slz(st, SLZ_WA));
+    hipLaunchKernelGGL(sp_gemv_rows_kernel, dim3(pp), dim3(SP_T), 0, s, P1, ld, n,
+                       slv(st, SLV_C), slz(st, SLZ_WC));
+    GPX_HIP(hipGetLastError());
+    // (B0 T^T) T, then G_ux over it; G_uu = -G_ux B0^T / 2
+    GPX_TRY(sp_abt_split(st, s, P1, P3, ld, np, st->Cm.d(), pp, 0.0));
+    GPX_TRY(sp_gemm(s, 0, 0, st->Cm.d(), pp, P3, ldn, P4, ldn, pp, np, pp, 1.0, 0.0));
+    hipLaunchKernelGGL(sl_gux_kernel, sgrid, dim3(SP_T), 0, s, P4, P1, ld, p, n, slz(st, SLZ_WA),
+                       slz(st, SLZ_WC), slv(st, SLV_AC), a, W);
+    GPX_HIP(hipGetLastError());
+    GPX_TRY(sp_abt_split(st, s, P4, P1, ld, np, st->Guu.d(), pp, 0.0));
+    hipLaunchKernelGGL(sl_guu_kernel, dim3((pp + SP_T - 1) / SP_T, pp), dim3(SP_T), 0, s,
+                       st->Guu.d(), p, pp);
+    GPX_HIP(hipGetLastError());
+    // the contractions with the kernel derivatives
+    GPX_TRY(sp_event(st, s, SLE_GRAD1));
+    GPX_TRY(gpx_pair_grad(s, st->kp, st->U.d(), p, st->U.d(), p, d, st->Guu.d(), pp,
+                          st->pg_part.d(), st->acc_uu.d()));
+    GPX_TRY(gpx_pair_grad(s, st->kp, st->U.d(), p, X, n, d, P4, ld, st->pg_part.d(),
+                          st->acc_ux.d()));
+    std::vector<double> auu(nacc), aux(nacc);
+    double dm = 0.0;
+    GPX_HIP(hipMemcpyAsync(auu.data(), st->acc_uu.p, nacc * 8, hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipMemcpyAsync(aux.data(), st->acc_ux.p, nacc * 8, hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipMemcpyAsync(&dm, st->slsc.d() + 4, 8, hipMemcpyDeviceToHost, s));
+    GPX_TRY(sp_event(st, s, SLE_GRAD2));
+    st->sl_ms[5] = 0.0;
+    if (dU) {
+        GPX_TRY(st->px_part.reserve(std::max(gpx_pair_gradx_scratch(p, p, d),
+                                             gpx_pair_gradx_scratch(p, n, d)) * 8));
+        GPX_TRY(st->dU.reserve((size_t)p * d * 8));
+        GPX_TRY(sp_event(st, s, SLE_DU0));
+        GPX_TRY(gpx_pair_gradx(s, st->kp, st->U.d(), p, st->U.d(), p, d, st->Guu.d(), pp, true,
+                               st->px_part.d(), st->dU.d(), false));
+        GPX_TRY(gpx_pair_gradx(s, st->kp, st->U.d(), p, X, n, d, P4, ld, false,
+                               st->px_part.d(), st->dU.d(), true));
+        GPX_TRY(sp_event(st, s, SLE_DU1));
+        GPX_HIP(hipMemcpyAsync(dU, st->dU.p, (size_t)p * d * 8, hipMemcpyDeviceToHost, s));
+    }
+    GPX_HIP(hipStreamSynchronize(s));
+    st->sl_ms[3] = sp_elapsed(st, SLE_GRAD0, SLE_GRAD2);
+    st->sl_ms[4] = sp_elapsed(st, SLE_GRAD1, SLE_GRAD2);
+    if (dU) st->sl_ms[5] = sp_elapsed(st, SLE_DU0, SLE_DU1);
+    const int nh = st->kp.nhyper;
+    for (int k = 0; k < nh; ++k) dlZ[k] = auu[1 + k] + aux[1 + k];
+    dlZ[nh] = dm;
+    return 0;
+}
+
+// z (p), f (n) and g (n) at the mode, on the host; any may be null
+int gpx_sparse_laplace_run_mode(GpxSparse *st, hipStream_t s, double *z, double *f, double *g)
+{
+    GPX_TRY(sl_ready(st, "gpx_sparse_laplace_get_mode"));
+    const int cur = st->sl_cur;
+    if (z)
+        GPX_HIP(hipMemcpyAsync(z, slz(st, SLZ_Z), (size_t)st->p * 8, hipMemcpyDeviceToHost, s));
+    if (f)
+        GPX_HIP(hipMemcpyAsync(f, slv(st, SLV_FT + cur), (size_t)st->n * 8, hipMemcpyDeviceToHost,
+                               s));
+    if (g)
+        GPX_HIP(hipMemcpyAsync(g, slv(st, SLV_G + cur), (size_t)st->n * 8, hipMemcpyDeviceToHost,
+                               s));
+    GPX_HIP(hipStreamSynchronize(s));
+    if (f)
+        for (int j = 0; j < st->n; ++j) f[j] = st->mean + f[j];
+    return 0;
+}
+
+// ms[0] the last update, ms[1] its first Newton step, ms[2] that step's two panel passes, ms[3]
+// the last gradient stage, ms[4] its contraction pass, ms[5] the dU pass; iters / halvings: the
+// counts of the last update
+int gpx_sparse_laplace_run_timings(GpxSparse *st, double *ms)
+{
+    if (!st || st->method != SP_LAPLACE) {
+        gpx_set_error("gpx_sparse_laplace_timings: no sparse Laplace model");
+        return -1;
+    }
+    for (int i = 0; i < 6; ++i) ms[i] = st->sl_ms[i];
+    ms[6] = st->sl_iters;
+    ms[7] = st->sl_halvings;
     return 0;
 }

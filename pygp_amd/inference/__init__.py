@@ -4,6 +4,7 @@ from .gradobs import GradientGP
 from .multiout import MultiOutputGP
 from .coreg import CoregionalGP
 from .laplace import LaplaceGP
+from .sparse_laplace import SparseLaplaceGP
 from .ep import EPGP
 from .softmax import MulticlassLaplaceGP
 from .fitc import FITC
@@ -16,5 +17,5 @@ from .pathwise import PathwiseSample
 from .iterative import IterativeGP
 
 __all__ = ['GP', 'ExactGP', 'BasicGP', 'GradientGP', 'MultiOutputGP', 'CoregionalGP', 'LaplaceGP',
-           'EPGP', 'MulticlassLaplaceGP', 'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'FourierSample', 'SSGP',
+           'SparseLaplaceGP', 'EPGP', 'MulticlassLaplaceGP', 'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'FourierSample', 'SSGP',
            'PathwiseSample', 'IterativeGP']

@@ -17,21 +17,13 @@ from ..likelihoods import Gaussian
 from ._device import DeviceGP
 from .select import select_pseudoinputs, _check as select_check
 
-__all__ = ['SparseGP']
+__all__ = ['SparseGP', 'PseudoInputs']
 
 
-class SparseGP(DeviceGP):
-    """Base of FITC, DTC and VFE: a Gaussian likelihood and p pseudo-inputs U."""
-
-    _method = None          # _lib.GPX_FITC / GPX_DTC / GPX_VFE
-    # (_appends_in_place: append_data calls served by gpx_sparse_append)
-    _transient = dict(DeviceGP._transient, _appends_in_place=0)
-
-    def __init__(self, likelihood, kernel, mean, U):
-        if not isinstance(likelihood, Gaussian):
-            raise ValueError('sparse inference requires a Gaussian likelihood')
-        super(SparseGP, self).__init__(likelihood, kernel, mean)
-        self._U = np.array(U, ndmin=2, dtype=float, copy=True)
+class PseudoInputs(object):
+    """The pseudo-inputs of a model on resident data, for a DeviceGP to inherit beside it: the
+    model keeps them in `_U` (p x d), uploads its data as plain `set_data` and refactors on its
+    next use once `_factored` is cleared."""
 
     @property
     def pseudoinputs(self):
@@ -49,6 +41,34 @@ class SparseGP(DeviceGP):
             raise ValueError('array must not contain infs or NaNs')
         self._U = U
         self._factored = False
+
+    def reselect(self, p=None, tol=0.0):
+        """Select the pseudo-inputs again at the current hypers, on the resident data of the
+        model's own handle (p: at most that many, default the current number), and move to
+        them (set_pseudoinputs): the natural alternation with optimize. Returns
+        (idx, trace) of the selection."""
+        if self.ndata == 0:
+            raise ValueError('no data')
+        p = self._U.shape[0] if p is None else p
+        select_check(self._X.shape[0], self._X.shape[1], p, tol)
+        dev = self._upload('set_data', (self._X, self._y))
+        idx, _, trace = dev.select_pivots(self._kernel._kspec(), None, int(p), tol)
+        self.set_pseudoinputs(self._X[idx])
+        return idx, trace
+
+
+class SparseGP(PseudoInputs, DeviceGP):
+    """Base of FITC, DTC and VFE: a Gaussian likelihood and p pseudo-inputs U."""
+
+    _method = None          # _lib.GPX_FITC / GPX_DTC / GPX_VFE
+    # (_appends_in_place: append_data calls served by gpx_sparse_append)
+    _transient = dict(DeviceGP._transient, _appends_in_place=0)
+
+    def __init__(self, likelihood, kernel, mean, U):
+        if not isinstance(likelihood, Gaussian):
+            raise ValueError('sparse inference requires a Gaussian likelihood')
+        super(SparseGP, self).__init__(likelihood, kernel, mean)
+        self._U = np.array(U, ndmin=2, dtype=float, copy=True)
 
     @classmethod
     def from_gp(cls, gp, U=None, p=None, tol=0.0):
@@ -70,20 +90,6 @@ class SparseGP(DeviceGP):
         if gp.ndata > 0:
             new.add_data(*gp.data)
         return new
-
-    def reselect(self, p=None, tol=0.0):
-        """Select the pseudo-inputs again at the current hypers, on the resident data of the
-        model's own handle (p: at most that many, default the current number), and move to
-        them (set_pseudoinputs): the natural alternation with optimize. Returns
-        (idx, trace) of the selection."""
-        if self.ndata == 0:
-            raise ValueError('no data')
-        p = self._U.shape[0] if p is None else p
-        select_check(self._X.shape[0], self._X.shape[1], p, tol)
-        dev = self._upload('set_data', (self._X, self._y))
-        idx, _, trace = dev.select_pivots(self._kernel._kspec(), None, int(p), tol)
-        self.set_pseudoinputs(self._X[idx])
-        return idx, trace
 
     # -- the hot path -------------------------------------------------------
     def _update(self):
