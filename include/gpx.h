@@ -548,6 +548,47 @@ int gpx_sparse_laplace_get_mode(gpx_t *h, double *z, double *f, double *g);
  * update); of the last dU pass; then the Newton steps and the halvings of the last update */
 int gpx_sparse_laplace_timings(gpx_t *h, double *ms);
 
+/* ---- sparse EP classification (own design) -------------------------------- */
+/* Binary classification on pseudo-inputs by expectation propagation, Probit likelihood, under the
+ * prior of gpx_sparse_laplace_update: f = mean + V0^T z, z ~ N(0, I_p), V0 = L^-T K(U, X),
+ * L = chol(Kuu + jitter I), DTC's predictive variance. The data are the handle's resident data
+ * from plain gpx_set_data with the labels -1 / +1 as y: any other value is refused with an error
+ * text before anything is launched. Hypers [kernel | mean]; jitter >= 0 is absolute and has no
+ * gradient. Damped parallel EP from zero sites (the same call gives the same bits):
+ * tau <- max((1 - damping) tau + damping tau_new, 1e-10 / k_ii), nu alike, 0 < damping <= 1, until
+ * max(max |tau_new - tau|, max |nu_new - nu|) <= tol (1 + max(max tau, max |nu|)) before a step,
+ * never on the pass over the prior marginals; *iters: the sweeps taken. After max_iter sweeps
+ * without convergence: -1 with an error text, no model (the calls below fail until an update
+ * succeeds). Limits and the pivot of Kuu + jitter I: as gpx_sparse_laplace_update. State: a third
+ * kind of model in the state and panels of gpx_sparse_update and gpx_sparse_laplace_update. An
+ * update of one kind makes the others' model stale: their calls fail with an error text until their
+ * own next update, and never answer from another model's numbers. gpx_set_data makes all stale;
+ * every call of this entry, a refused one included, leaves the handle without a current model. */
+int gpx_sparse_ep_update(gpx_t *h, const gpx_kspec *k, double mean, const double *U, int64_t p,
+                         double jitter, double tol, int max_iter, double damping, int *iters,
+                         int *info);
+/* lZ: the EP evidence from the sites, marginals and factor of the last pass; dlZ == NULL: value
+ * only, else dlZ[nhyper + 1] in order [kernel..., mean] (the sites are stationary at the fixed
+ * point: the explicit part alone) */
+int gpx_sparse_ep_loglik(gpx_t *h, double *lZ, double *dlZ);
+/* ... plus dU[p*d] row-major = d lZ / d U (lZ and dlZ: the bits of gpx_sparse_ep_loglik) */
+int gpx_sparse_ep_loglik_pseudo(gpx_t *h, double *lZ, double *dlZ, double *dU);
+/* the latent posterior through the sparse posterior pass, as gpx_sparse_laplace_posterior and
+ * _full (Ruu = L, Rux = chol(I + V0 diag(tau) V0^T) L) */
+int gpx_sparse_ep_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2,
+                            double *dmu, double *ds2);
+int gpx_sparse_ep_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu,
+                                 double *Sigma);
+/* the sites and the marginals at the data: tau[n], nu[n], mu[n], s2[n] (any may be NULL); n must
+ * be the model's point count */
+int gpx_sparse_ep_get_sites(gpx_t *h, int64_t n, double *tau, double *nu, double *mu, double *s2);
+/* ms[12]: HIP-event ms of the last update, of its first sweep and of that sweep's stages (the
+ * damped sites with the scaled panel, the product A, its factorisation, the product T0 = A^-T V0,
+ * the fused pass with its one-workgroup reduction: events around launches, approximate, not a
+ * kernel trace); of the last gradient stage and the contraction pass inside it (0 if none since
+ * the update); of the last dU pass; then the sweeps of the last update and a spare 0 */
+int gpx_sparse_ep_timings(gpx_t *h, double *ms);
+
 /* ---- greedy pseudo-input selection --------------------------------------- */
 /* Greedy conditional-variance selection = pivoted partial Cholesky of K(X,X) (own design).
  * X == NULL: the handle's resident data (gpx_set_data); else X[n*d] is copied to buffers of

@@ -149,6 +149,14 @@ SIGNATURES = {
     'gpx_sparse_laplace_posterior_full': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     'gpx_sparse_laplace_get_mode': (C.c_int, [_vp, _vp, _vp, _vp]),
     'gpx_sparse_laplace_timings': (C.c_int, [_vp, _vp]),
+    'gpx_sparse_ep_update': (C.c_int, [_vp, C.POINTER(_KSpec), C.c_double, _vp, _i64, C.c_double,
+                                       C.c_double, C.c_int, C.c_double, _ip, _ip]),
+    'gpx_sparse_ep_loglik': (C.c_int, [_vp, _dp, _vp]),
+    'gpx_sparse_ep_loglik_pseudo': (C.c_int, [_vp, _vp, _vp, _vp]),
+    'gpx_sparse_ep_posterior': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    'gpx_sparse_ep_posterior_full': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    'gpx_sparse_ep_get_sites': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    'gpx_sparse_ep_timings': (C.c_int, [_vp, _vp]),
     'gpx_select_pivots': (C.c_int, [_vp, C.POINTER(_KSpec), _vp, _i64, _i64, _i64, C.c_double,
                                     _vp, _vp, _vp, C.POINTER(_i64)]),
     'gpx_select_timing': (C.c_int, [_vp, _vp]),
@@ -832,6 +840,57 @@ class Handle(object):
         out = dict(zip(('update', 'step', 'panel_passes', 'gradient', 'contraction', 'pseudo'),
                        ms))
         out.update(iters=int(ms[6]), halvings=int(ms[7]))
+        return out
+
+    # -- sparse EP classification (SparseEPGP) on the resident data: labels as y --
+    def sparse_ep_update(self, spec, mean, U, jitter=1e-6, tol=1e-10, max_iter=200, damping=0.8):
+        """Damped parallel EP on the pseudo-inputs to a fixed point of the sites; returns the
+        number of sweeps."""
+        U = _f64(U, 2)
+        iters, info = C.c_int(0), C.c_int(0)
+        check(self._L.gpx_sparse_ep_update(self._h, spec.ref(), float(mean), _ptr(U), U.shape[0],
+                                           float(jitter), float(tol), int(max_iter),
+                                           float(damping), C.byref(iters), C.byref(info)))
+        return iters.value
+
+    def sparse_ep_loglik(self, nhyper_kernel, grad=False):
+        return self._loglik(self._L.gpx_sparse_ep_loglik, nhyper_kernel + 1, grad)
+
+    def sparse_ep_loglik_pseudo(self, nhyper_kernel, p, d):
+        """lZ, dlZ (as sparse_ep_loglik with grad) and dU = d lZ / d U (p x d)."""
+        lZ = C.c_double(0)
+        dlZ, dU = np.empty(nhyper_kernel + 1), np.empty((p, d))
+        check(self._L.gpx_sparse_ep_loglik_pseudo(self._h, C.byref(lZ), _ptr(dlZ), _ptr(dU)))
+        return lZ.value, dlZ, dU
+
+    def sparse_ep_posterior(self, Xs, grad=False):
+        Xs = _f64(Xs, 2)
+        m, d = Xs.shape
+        mu, s2 = np.empty(m), np.empty(m)
+        dmu, ds2 = (np.empty((m, d)), np.empty((m, d))) if grad else (None, None)
+        if m:
+            check(self._L.gpx_sparse_ep_posterior(self._h, _ptr(Xs), m, _ptr(mu), _ptr(s2),
+                                                  _ptr(dmu), _ptr(ds2)))
+        return (mu, s2, dmu, ds2) if grad else (mu, s2)
+
+    def sparse_ep_posterior_full(self, Xs):
+        return self._posterior(self._L.gpx_sparse_ep_posterior_full, Xs, True)
+
+    def sparse_ep_get_sites(self, n):
+        """(tau, nu, mu, s2): the sites and the marginals at the data."""
+        out = [np.empty(n) for _ in range(4)]
+        check(self._L.gpx_sparse_ep_get_sites(self._h, n, *[_ptr(a) for a in out]))
+        return tuple(out)
+
+    def sparse_ep_timings(self):
+        """HIP-event ms of the last update, its first sweep and that sweep's stages (scaled
+        panel, A, factorisation, T0 product, fused pass), the last gradient stage, its contraction
+        pass and the dU pass; then the sweeps of the last update."""
+        ms = np.zeros(12)
+        check(self._L.gpx_sparse_ep_timings(self._h, _ptr(ms)))
+        out = dict(zip(('update', 'sweep', 'scale', 'product_a', 'factor', 'product_t0',
+                        'fused_pass', 'gradient', 'contraction', 'pseudo'), ms))
+        out.update(sweeps=int(ms[10]))
         return out
 
     def select_pivots(self, spec, X, p, tol=0.0):

@@ -613,6 +613,21 @@ int gpx_sparse_laplace_run_loglik(GpxSparse *st, hipStream_t s, const double *X,
 int gpx_sparse_laplace_run_mode(GpxSparse *st, hipStream_t s, double *z, double *f, double *g);
 // ms[8]: six times and the step and halving counts of the last update
 int gpx_sparse_laplace_run_timings(GpxSparse *st, double *ms);
+// The same labels and prior under expectation propagation (Probit), a third
+// kind of model in the same state and panels: damped parallel EP from zero sites, one fused pass
+// over the p x N panel a sweep. -1 with an error text after max_iter sweeps without convergence.
+#define GPX_SPARSE_KIND_EP 5
+int gpx_sparse_ep_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, const double *U,
+                             int p, double jitter, double mean, double tol, int max_iter,
+                             double damping, const double *X, const double *y, int n, int d,
+                             int cap, int *iters, int *info);
+int gpx_sparse_ep_run_loglik(GpxSparse *st, hipStream_t s, const double *X, double *lZ,
+                             double *dlZ, double *dU);
+// the sites and the marginals at the data (host, n each; any may be null)
+int gpx_sparse_ep_run_sites(GpxSparse *st, hipStream_t s, double *tau, double *nu, double *mu,
+                            double *s2);
+// ms[12]: ten times and the sweep count of the last update (see sparse.hip)
+int gpx_sparse_ep_run_timings(GpxSparse *st, double *ms);
 
 // ---- greedy pseudo-input selection (select.hip) ----------------------------------------
 // out[j] = k(x_j, x*) for j < n, 0 for n <= j < np; x* = xs[0 .. d) on the device, written by

@@ -1,5 +1,5 @@
 // C ABI of libgpx.so, the wrappers of the sparse models (gpx_sparse_*: FITC, DTC, VFE; and
-// gpx_sparse_laplace_*: the classifier on pseudo-inputs, in the same state) and of
+// gpx_sparse_laplace_*, gpx_sparse_ep_*: the classifiers on pseudo-inputs, in the same state) and of
 // the greedy pseudo-input selection (gpx_select_*): argument checks and the handle's book-keeping
 // (which data the sparse model belongs to) around the entry points of sparse.hip and select.hip,
 // which own their buffers and kernels.
@@ -12,13 +12,23 @@ using namespace gpxh;
 
 extern "C" {
 
-// Is the handle's sparse model current, and of the kind the calling entry belongs to? The
-// regression models and the sparse Laplace classifier live in the same state and panels: an update
-// of either kind replaces the other's model, whose entries must not answer from these numbers.
-static int sparse_ready(gpx_ctx *h, const char *what, bool laplace = false)
+// Is the handle's sparse model current, and of the kind the calling entry belongs to (0: the
+// regression models; GPX_SPARSE_KIND_LAPLACE; GPX_SPARSE_KIND_EP)? The three kinds live in the same
+// state and panels: an update of one kind replaces the others' model, whose entries must not
+// answer from these numbers.
+static const char *sparse_update_name(int kind)
 {
-    const char *model = laplace ? "sparse Laplace model" : "sparse model";
-    const char *update = laplace ? "gpx_sparse_laplace_update" : "gpx_sparse_update";
+    return kind == GPX_SPARSE_KIND_LAPLACE ? "gpx_sparse_laplace_update"
+           : kind == GPX_SPARSE_KIND_EP    ? "gpx_sparse_ep_update"
+                                           : "gpx_sparse_update";
+}
+
+static int sparse_ready(gpx_ctx *h, const char *what, int kind = 0)
+{
+    const char *model = kind == GPX_SPARSE_KIND_LAPLACE ? "sparse Laplace model"
+                        : kind == GPX_SPARSE_KIND_EP    ? "sparse EP model"
+                                                        : "sparse model";
+    const char *update = sparse_update_name(kind);
     if (!h->sparse || h->sparse_version < 0) {
         gpx_set_error("%s: no %s (call %s)", what, model, update);
         return -1;
@@ -27,9 +37,11 @@ static int sparse_ready(gpx_ctx *h, const char *what, bool laplace = false)
         gpx_set_error("%s: the data changed since %s (stale model)", what, update);
         return -1;
     }
-    if ((gpx_sparse_kind(h->sparse) == GPX_SPARSE_KIND_LAPLACE) != laplace) {
+    int have = gpx_sparse_kind(h->sparse);
+    if (have != GPX_SPARSE_KIND_LAPLACE && have != GPX_SPARSE_KIND_EP) have = 0;
+    if (have != kind) {
         gpx_set_error("%s: %s replaced the %s (stale model: call %s)", what,
-                      laplace ? "gpx_sparse_update" : "gpx_sparse_laplace_update", model, update);
+                      sparse_update_name(have), model, update);
         return -1;
     }
     return 0;
@@ -93,7 +105,7 @@ int gpx_sparse_append(gpx_t *h, const double *Xnew, const double *ynew, int64_t 
         return -1;
     }
     if (!h->sparse || h->sparse_version < 0 || h->sparse_version != h->data_version ||
-        gpx_sparse_kind(h->sparse) == GPX_SPARSE_KIND_LAPLACE || h->n <= 0 || h->n + m > h->cap)
+        gpx_sparse_kind(h->sparse) >= GPX_SPARSE_KIND_LAPLACE || h->n <= 0 || h->n + m > h->cap)
         return -3;
     const int n_old = h->n;
     const size_t xrow = (size_t)h->d * 8;
@@ -196,7 +208,50 @@ int gpx_sparse_pseudo_timing(gpx_t *h, double *ms)
     return gpx_sparse_run_pseudo_timing(h->sparse, ms);
 }
 
-// ---- sparse Laplace classification (sparse.hip) -----------------------
+// ---- the classifiers on pseudo-inputs (sparse.hip, DESIGN.md sections 26 and 27) ---------------
+// What their updates check before anything is launched, after the entry's own arguments
+// (options_ok, with `need` the text for a failure): the data, p, the product of the padded sizes,
+// the numbers, the pseudo-inputs, the kernel, and that the resident y are labels -1 / +1, read back
+// once per data version (a copy, no launch).
+static int sparse_labels_begin(gpx_ctx *h, const char *who, const gpx_kspec *k, double mean,
+                               const double *U, int64_t p, double jitter, double tol, int max_iter,
+                               bool options_ok, const char *need, KParams *kp)
+{
+    if (!U || p < 1 || p > GPX_SPARSE_MAX_P) {
+        gpx_set_error("%s: need 1 <= p <= %d pseudo-inputs (got %lld)", who, GPX_SPARSE_MAX_P,
+                      (long long)p);
+        return -1;
+    }
+    const long long pp = round_up(p, GPX_TILE), np = round_up(h->n, GPX_TILE);
+    if (pp * np >= (1LL << 31)) {
+        gpx_set_error("%s: p_pad * N_pad = %lld x %lld must stay below 2^31", who, pp, np);
+        return -1;
+    }
+    if (!std::isfinite(mean) || !std::isfinite(jitter) || jitter < 0.0 || !std::isfinite(tol) ||
+        !(tol > 0.0) || max_iter < 1 || !options_ok) {
+        gpx_set_error("%s: need a finite mean, jitter >= 0, tol > 0%s max_iter >= 1%s", who,
+                      need[0] ? "," : " and", need);
+        return -1;
+    }
+    for (int64_t i = 0; i < p * h->d; ++i)
+        if (!std::isfinite(U[i])) {
+            gpx_set_error("%s: non-finite pseudo-inputs", who);
+            return -1;
+        }
+    GPX_TRY(gpx_flatten_kspec(k, h->d, kp));
+    if (h->labels_version != h->data_version) {
+        std::vector<double> yh((size_t)h->n);
+        GPX_HIP(hipMemcpy(yh.data(), h->y.p, (size_t)h->n * 8, hipMemcpyDeviceToHost));
+        for (int i = 0; i < h->n; ++i)
+            if (yh[i] != 1.0 && yh[i] != -1.0) {
+                gpx_set_error("%s: labels must be -1 or +1 (y[%d] = %g)", who, i, yh[i]);
+                return -1;
+            }
+        h->labels_version = h->data_version;
+    }
+    return 0;
+}
+
 int gpx_sparse_laplace_update(gpx_t *h, const gpx_kspec *k, int lik, double mean, const double *U,
                               int64_t p, double jitter, double tol, int max_iter, int *iters,
                               int *info)
@@ -215,42 +270,9 @@ int gpx_sparse_laplace_update(gpx_t *h, const gpx_kspec *k, int lik, double mean
                       "(got %d)", lik);
         return -1;
     }
-    if (!U || p < 1 || p > GPX_SPARSE_MAX_P) {
-        gpx_set_error("gpx_sparse_laplace_update: need 1 <= p <= %d pseudo-inputs (got %lld)",
-                      GPX_SPARSE_MAX_P, (long long)p);
-        return -1;
-    }
-    const long long pp = round_up(p, GPX_TILE), np = round_up(h->n, GPX_TILE);
-    if (pp * np >= (1LL << 31)) {
-        gpx_set_error("gpx_sparse_laplace_update: p_pad * N_pad = %lld x %lld must stay below 2^31",
-                      pp, np);
-        return -1;
-    }
-    if (!std::isfinite(mean) || !std::isfinite(jitter) || jitter < 0.0 || !std::isfinite(tol) ||
-        !(tol > 0.0) || max_iter < 1) {
-        gpx_set_error("gpx_sparse_laplace_update: need a finite mean, jitter >= 0, tol > 0 and "
-                      "max_iter >= 1");
-        return -1;
-    }
-    for (int64_t i = 0; i < p * h->d; ++i)
-        if (!std::isfinite(U[i])) {
-            gpx_set_error("gpx_sparse_laplace_update: non-finite pseudo-inputs");
-            return -1;
-        }
     KParams kp;
-    GPX_TRY(gpx_flatten_kspec(k, h->d, &kp));
-    // the resident y must be labels: read back once per data version (a copy, no launch)
-    if (h->labels_version != h->data_version) {
-        std::vector<double> yh((size_t)h->n);
-        GPX_HIP(hipMemcpy(yh.data(), h->y.p, (size_t)h->n * 8, hipMemcpyDeviceToHost));
-        for (int i = 0; i < h->n; ++i)
-            if (yh[i] != 1.0 && yh[i] != -1.0) {
-                gpx_set_error("gpx_sparse_laplace_update: labels must be -1 or +1 (y[%d] = %g)", i,
-                              yh[i]);
-                return -1;
-            }
-        h->labels_version = h->data_version;
-    }
+    GPX_TRY(sparse_labels_begin(h, "gpx_sparse_laplace_update", k, mean, U, p, jitter, tol,
+                                max_iter, true, "", &kp));
     const int r = gpx_sparse_laplace_run_update(&h->sparse, h->stream, kp, lik, U, (int)p, jitter,
                                                 mean, tol, max_iter, h->X.as<double>(),
                                                 h->y.as<double>(), h->n, h->d, h->cap, iters, info);
@@ -261,7 +283,7 @@ int gpx_sparse_laplace_update(gpx_t *h, const gpx_kspec *k, int lik, double mean
 int gpx_sparse_laplace_loglik(gpx_t *h, double *lZ, double *dlZ)
 {
     CHECK_H(h);
-    GPX_TRY(sparse_ready(h, "gpx_sparse_laplace_loglik", true));
+    GPX_TRY(sparse_ready(h, "gpx_sparse_laplace_loglik", GPX_SPARSE_KIND_LAPLACE));
     if (!lZ) {
         gpx_set_error("gpx_sparse_laplace_loglik: lZ is null");
         return -1;
@@ -273,7 +295,7 @@ int gpx_sparse_laplace_loglik(gpx_t *h, double *lZ, double *dlZ)
 int gpx_sparse_laplace_loglik_pseudo(gpx_t *h, double *lZ, double *dlZ, double *dU)
 {
     CHECK_H(h);
-    GPX_TRY(sparse_ready(h, "gpx_sparse_laplace_loglik_pseudo", true));
+    GPX_TRY(sparse_ready(h, "gpx_sparse_laplace_loglik_pseudo", GPX_SPARSE_KIND_LAPLACE));
     if (!lZ || !dlZ || !dU) {
         gpx_set_error("gpx_sparse_laplace_loglik_pseudo: lZ, dlZ and dU must not be null");
         return -1;
@@ -285,7 +307,7 @@ int gpx_sparse_laplace_posterior(gpx_t *h, const double *Xs, int64_t m, double *
                                  double *dmu, double *ds2)
 {
     CHECK_H(h);
-    GPX_TRY(sparse_ready(h, "gpx_sparse_laplace_posterior", true));
+    GPX_TRY(sparse_ready(h, "gpx_sparse_laplace_posterior", GPX_SPARSE_KIND_LAPLACE));
     if (!Xs || !mu || !s2 || m < 0 || (!dmu) != (!ds2)) {
         gpx_set_error("gpx_sparse_laplace_posterior: bad arguments");
         return -1;
@@ -298,7 +320,7 @@ int gpx_sparse_laplace_posterior_full(gpx_t *h, const double *Xs, int64_t m, dou
                                       double *Sigma)
 {
     CHECK_H(h);
-    GPX_TRY(sparse_ready(h, "gpx_sparse_laplace_posterior_full", true));
+    GPX_TRY(sparse_ready(h, "gpx_sparse_laplace_posterior_full", GPX_SPARSE_KIND_LAPLACE));
     if (!Xs || !mu || !Sigma || m < 1 || m > 8192) {
         gpx_set_error("gpx_sparse_laplace_posterior_full: bad arguments (1 <= m <= 8192)");
         return -1;
@@ -310,7 +332,7 @@ int gpx_sparse_laplace_posterior_full(gpx_t *h, const double *Xs, int64_t m, dou
 int gpx_sparse_laplace_get_mode(gpx_t *h, double *z, double *f, double *g)
 {
     CHECK_H(h);
-    GPX_TRY(sparse_ready(h, "gpx_sparse_laplace_get_mode", true));
+    GPX_TRY(sparse_ready(h, "gpx_sparse_laplace_get_mode", GPX_SPARSE_KIND_LAPLACE));
     return gpx_sparse_laplace_run_mode(h->sparse, h->stream, z, f, g);
 }
 
@@ -322,6 +344,99 @@ int gpx_sparse_laplace_timings(gpx_t *h, double *ms)
         return -1;
     }
     return gpx_sparse_laplace_run_timings(h->sparse, ms);
+}
+
+// ---- sparse EP classification (sparse.hip) ------------------------------
+int gpx_sparse_ep_update(gpx_t *h, const gpx_kspec *k, double mean, const double *U, int64_t p,
+                         double jitter, double tol, int max_iter, double damping, int *iters,
+                         int *info)
+{
+    CHECK_H(h);
+    GPX_TRY(require_state(h, ST_PLAIN, "gpx_sparse_ep_update"));
+    if (info) *info = 0;
+    if (iters) *iters = 0;
+    h->sparse_version = -1;
+    if (h->n <= 0) {
+        gpx_set_error("gpx_sparse_ep_update: no data: call gpx_set_data first");
+        return -1;
+    }
+    KParams kp;
+    GPX_TRY(sparse_labels_begin(h, "gpx_sparse_ep_update", k, mean, U, p, jitter, tol, max_iter,
+                                damping > 0.0 && damping <= 1.0, " and 0 < damping <= 1", &kp));
+    const int r = gpx_sparse_ep_run_update(&h->sparse, h->stream, kp, U, (int)p, jitter, mean, tol,
+                                           max_iter, damping, h->X.as<double>(), h->y.as<double>(),
+                                           h->n, h->d, h->cap, iters, info);
+    if (r == 0) h->sparse_version = h->data_version;
+    return r;
+}
+
+int gpx_sparse_ep_loglik(gpx_t *h, double *lZ, double *dlZ)
+{
+    CHECK_H(h);
+    GPX_TRY(sparse_ready(h, "gpx_sparse_ep_loglik", GPX_SPARSE_KIND_EP));
+    if (!lZ) {
+        gpx_set_error("gpx_sparse_ep_loglik: lZ is null");
+        return -1;
+    }
+    return gpx_sparse_ep_run_loglik(h->sparse, h->stream, h->X.as<double>(), lZ, dlZ, nullptr);
+}
+
+int gpx_sparse_ep_loglik_pseudo(gpx_t *h, double *lZ, double *dlZ, double *dU)
+{
+    CHECK_H(h);
+    GPX_TRY(sparse_ready(h, "gpx_sparse_ep_loglik_pseudo", GPX_SPARSE_KIND_EP));
+    if (!lZ || !dlZ || !dU) {
+        gpx_set_error("gpx_sparse_ep_loglik_pseudo: lZ, dlZ and dU must not be null");
+        return -1;
+    }
+    return gpx_sparse_ep_run_loglik(h->sparse, h->stream, h->X.as<double>(), lZ, dlZ, dU);
+}
+
+int gpx_sparse_ep_posterior(gpx_t *h, const double *Xs, int64_t m, double *mu, double *s2,
+                            double *dmu, double *ds2)
+{
+    CHECK_H(h);
+    GPX_TRY(sparse_ready(h, "gpx_sparse_ep_posterior", GPX_SPARSE_KIND_EP));
+    if (!Xs || !mu || !s2 || m < 0 || (!dmu) != (!ds2)) {
+        gpx_set_error("gpx_sparse_ep_posterior: bad arguments");
+        return -1;
+    }
+    if (m == 0) return 0;
+    return gpx_sparse_run_posterior(h->sparse, h->stream, Xs, m, mu, s2, dmu, ds2, nullptr);
+}
+
+int gpx_sparse_ep_posterior_full(gpx_t *h, const double *Xs, int64_t m, double *mu, double *Sigma)
+{
+    CHECK_H(h);
+    GPX_TRY(sparse_ready(h, "gpx_sparse_ep_posterior_full", GPX_SPARSE_KIND_EP));
+    if (!Xs || !mu || !Sigma || m < 1 || m > 8192) {
+        gpx_set_error("gpx_sparse_ep_posterior_full: bad arguments (1 <= m <= 8192)");
+        return -1;
+    }
+    return gpx_sparse_run_posterior(h->sparse, h->stream, Xs, m, mu, nullptr, nullptr, nullptr,
+                                    Sigma);
+}
+
+int gpx_sparse_ep_get_sites(gpx_t *h, int64_t n, double *tau, double *nu, double *mu, double *s2)
+{
+    CHECK_H(h);
+    GPX_TRY(sparse_ready(h, "gpx_sparse_ep_get_sites", GPX_SPARSE_KIND_EP));
+    if (n != h->n) {
+        gpx_set_error("gpx_sparse_ep_get_sites: n = %lld, the model has %d points", (long long)n,
+                      h->n);
+        return -1;
+    }
+    return gpx_sparse_ep_run_sites(h->sparse, h->stream, tau, nu, mu, s2);
+}
+
+int gpx_sparse_ep_timings(gpx_t *h, double *ms)
+{
+    CHECK_H(h);
+    if (!ms) {
+        gpx_set_error("gpx_sparse_ep_timings: ms is null");
+        return -1;
+    }
+    return gpx_sparse_ep_run_timings(h->sparse, ms);
 }
 
 // ---- greedy pseudo-input selection (select.hip) ---------------------------------------

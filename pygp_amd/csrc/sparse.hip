@@ -23,7 +23,8 @@
 //
 // The last part of the file is the sparse Laplace classifier: binary labels
 // under the subset-of-regressors prior on the same V0, Newton's method in the p-dimensional space
-// on the same split-K product, factorisation, contractions and posterior pass, in the same state.
+// on the same split-K product, factorisation, contractions and posterior pass, in the same state;
+// and behind it the sparse EP classifier (section 27) on the same prior and the same pieces.
 #include "gpx_internal.h"
 #include "lik_dev.h"
 #include <algorithm>
@@ -86,8 +87,8 @@ struct GpxSparse {
     double hsc[S_COUNT];
     // HIP events around the last update, gradient stage and contraction pass, then the dU
     // pass (ms)
-    // (7 .. 18: the sparse Laplace model's, SLE_* below)
-    hipEvent_t ev[19] = {};
+    // (7 .. 18: the sparse Laplace model's, SLE_* below; 19 .. 33: the sparse EP model's, SEE_*)
+    hipEvent_t ev[34] = {};
     double ms[3] = {0, 0, 0};
     double ms_pseudo = 0;
     // method SP_LAPLACE, binary labels under the subset-of-regressors prior (DESIGN.md section
@@ -99,10 +100,21 @@ struct GpxSparse {
     double sl_psi = 0, sl_lZ = 0;
     DevBuf slv, slz, slpart, slsc;
     double sl_ms[6] = {0, 0, 0, 0, 0, 0};
+    // method SP_EP, the same labels and prior under expectation propagation (DESIGN.md section
+    // 27). P2 holds V0, P3 the panel T0 = A^-T V0 of the sites the update stopped at (se_t0: it
+    // still does; the gradient stage scales it in place), A / Aw and beta as above.
+    // sev: the N-vectors (SEV_*, ldn doubles each); sez: the p-vectors (SEZ_*, pp doubles each).
+    int se_sweeps = 0;
+    bool se_t0 = false;
+    double se_lZ = 0;
+    DevBuf sev, sez, separt, sesc;
+    double se_ms[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
-// the fourth method of a GpxSparse, beside gpx_sparse_method of gpx.h: it has entries of its own
+// the fourth and fifth method of a GpxSparse, beside gpx_sparse_method of gpx.h: they have
+// entries of their own
 #define SP_LAPLACE GPX_SPARSE_KIND_LAPLACE
+#define SP_EP GPX_SPARSE_KIND_EP
 
 static int sp_event(GpxSparse *st, hipStream_t s, int i)
 {
@@ -602,7 +614,9 @@ static int sp_factor(GpxSparse *st, hipStream_t s, double *F, double *Fw, double
     GPX_HIP(hipStreamSynchronize(s));
     if (inf) {
         gpx_set_error("%s: matrix is not positive definite: pivot %d",
-                      st->method == SP_LAPLACE ? "gpx_sparse_laplace_update" : "gpx_sparse_update",
+                      st->method == SP_LAPLACE ? "gpx_sparse_laplace_update"
+                      : st->method == SP_EP    ? "gpx_sparse_ep_update"
+                                               : "gpx_sparse_update",
                       inf);
         return inf;
     }
@@ -1652,5 +1666,437 @@ int gpx_sparse_laplace_run_timings(GpxSparse *st, double *ms)
     for (int i = 0; i < 6; ++i) ms[i] = st->sl_ms[i];
     ms[6] = st->sl_iters;
     ms[7] = st->sl_halvings;
+    return 0;
+}
+
+// ==== sparse EP: the same labels and prior under expectation propagation ====
+// Sites tau_i >= 0, nu_i (nu' = nu - tau mean) on f = m + V0^T z: A = I + V0 diag(tau) V0^T,
+// T0 = A^-T V0, beta = A^-T V0 nu' give Sigma_ii = |T0_i|^2 and mu_i = m + T0_i . beta. A sweep of
+// damped parallel EP is the scaled panel, the split-K product, the factorisation and one product
+// of the models above, and one fused pass over T0 that turns it into marginals, cavities, moments
+// and new sites. Sigma_ii is exactly 0 for a point no pseudo-input sees: nothing divides by it or
+// by tau. The Probit likelihood only.
+
+// the N-vectors in sev (ldn doubles each) and the p-vectors in sez (pp doubles each)
+enum { SEV_TAU = 0, SEV_NU, SEV_NUP, SEV_TN, SEV_VN, SEV_MU, SEV_SII, SEV_B, SEV_SCR, SEV_COUNT };
+enum { SEZ_V = 0, SEZ_WA, SEZ_ZERO, SEZ_COUNT };
+// events (GpxSparse::ev): the update's end, the stages of its first sweep, the gradient stage
+enum { SEE_END = 19, SEE_S0, SEE_S1, SEE_S2, SEE_S3, SEE_S4, SEE_S5, SEE_S6, SEE_GRAD0, SEE_GRAD1,
+       SEE_GRAD2, SEE_DU0, SEE_DU1 };
+// what a site pass reduces: max |tau_new - tau|, max |nu_new - nu|, max tau, max |nu|; the four
+// sums of lZ at the sites that came in; the count of sites that left the numbers
+#define SE_NQ 9
+// The weak-site rule of gpx_ep_update (gpx_labels.hip): tau_i >= SE_FLOOR / k_ii
+#define SE_FLOOR 1e-10
+
+static inline double *sev(const GpxSparse *st, int k) { return st->sev.d() + (size_t)k * st->ldn; }
+static inline double *sez(const GpxSparse *st, int k) { return st->sez.d() + (size_t)k * st->pp; }
+
+// v summed (the largest v) over the 64 lanes of a wave into lane 0: the fixed shuffle tree
+__device__ __forceinline__ double sep_wave_sum(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+__device__ __forceinline__ double sep_wave_max(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
+    return v;
+}
+
+// The fused marginal and site pass: one read of the panel T0 (pp x N_pad, ld; V0 before the first
+// sweep, with beta = 0) in the strip layout of sl_terms_kernel. Per column j < n
+//   Sii = sum_i T0_ij^2, mu = mean + sum_i T0_ij beta_i
+//   cavity   D = 1 - tau Sii, s2c = Sii / D, muc = (mu - Sii nu) / D
+//   moments  c = 1 + s2c, z = y muc / sqrt c, r = N(z) / Phi(z), q = r (z + r) / c, w = s2c q
+//   new site tn = max(q / (1 - w), tfloor), vn = (muc q + y r / sqrt c) / (1 - w)
+// to tn, vn, mu, Sii; zeros for n <= j < N_pad. part[block][SE_NQ]: the block's share of the
+// quantities above, the sums of lZ being 1/2 log1p(tau s2c), log Phi(z),
+// (tau muc'^2 - 2 muc' nu' - s2c nu'^2) / (2 (1 + tau s2c)) and 1/2 nu' (mu - mean) with
+// muc' = muc - mean. The two waves that hold the columns reduce by shuffles and meet in LDS in
+// wave order.
+__global__ __launch_bounds__(SP_T) void sep_site_kernel(
+    const double *__restrict__ T0, long long ld, int pp, int n, const double *__restrict__ beta,
+    const double *__restrict__ y, const double *__restrict__ tau, const double *__restrict__ nu,
+    double mean, double tfloor, double *__restrict__ tn, double *__restrict__ vn,
+    double *__restrict__ mu, double *__restrict__ Sii, double *__restrict__ part)
+{
+    __shared__ double dots[2][SL_ROWS][SL_COLS];
+    __shared__ double red[2][SE_NQ];
+    const int t = threadIdx.x, cp = t & 63, rg = t >> 6;
+    const double *col = T0 + (size_t)blockIdx.x * SL_COLS + 2 * cp;
+    double a0 = 0.0, a1 = 0.0, q0 = 0.0, q1 = 0.0;
+    for (int i = rg; i < pp; i += SL_ROWS * SL_FLY) {
+        double2 v[SL_FLY];
+#pragma unroll
+        for (int u = 0; u < SL_FLY; ++u)
+            v[u] = *reinterpret_cast<const double2 *>(col + (size_t)(i + SL_ROWS * u) * ld);
+#pragma unroll
+        for (int u = 0; u < SL_FLY; ++u) {
+            const double bi = beta[i + SL_ROWS * u];
+            a0 += v[u].x * bi;
+            a1 += v[u].y * bi;
+            q0 += v[u].x * v[u].x;
+            q1 += v[u].y * v[u].y;
+        }
+    }
+    dots[0][rg][2 * cp] = q0;
+    dots[0][rg][2 * cp + 1] = q1;
+    dots[1][rg][2 * cp] = a0;
+    dots[1][rg][2 * cp + 1] = a1;
+    __syncthreads();
+    if (t < SL_COLS) {
+        const int j = blockIdx.x * SL_COLS + t;
+        double dt = 0.0, dv = 0.0, mt = 0.0, mv = 0.0, s4 = 0.0, s5 = 0.0, s6 = 0.0, s7 = 0.0;
+        double bad = 0.0, tni = 0.0, vni = 0.0, mi = 0.0, S = 0.0;
+        if (j < n) {
+            S = ((dots[0][0][t] + dots[0][1][t]) + dots[0][2][t]) + dots[0][3][t];
+            const double dm = ((dots[1][0][t] + dots[1][1][t]) + dots[1][2][t]) + dots[1][3][t];
+            mi = mean + dm;
+            const double yi = y[j], ti = tau[j], vi = nu[j];
+            const double D = 1.0 - ti * S;
+            const double s2c = S / D, muc = (mi - S * vi) / D;
+            const double c = 1.0 + s2c, den = sqrt(c);
+            const double z = yi * muc / den;
+            const LikTerms lt = lik_point(GPX_LIK_PROBIT, 1.0, z);   // lt.g = r, lt.lp = log Phi(z)
+            const double r = lt.g;
+            const double q = r * (z + r) / c;
+            const double w = s2c * q;
+            tni = fmax(q / (1.0 - w), tfloor);
+            vni = (muc * q + yi * r / den) / (1.0 - w);
+            // (fmax drops a NaN, so a site that left the numbers is counted instead)
+            dt = fabs(tni - ti);
+            dv = fabs(vni - vi);
+            if (dt != dt || dv != dv) bad = 1.0;
+            mt = ti;
+            mv = fabs(vi);
+            const double vp = vi - ti * mean, mcp = muc - mean;
+            s4 = 0.5 * log1p(ti * s2c);
+            s5 = lt.lp;
+            s6 = (ti * mcp * mcp - 2.0 * mcp * vp - s2c * vp * vp) / (2.0 * (1.0 + ti * s2c));
+            s7 = 0.5 * vp * dm;
+        }
+        tn[j] = tni;
+        vn[j] = vni;
+        mu[j] = mi;
+        Sii[j] = S;
+        dt = sep_wave_max(dt);
+        dv = sep_wave_max(dv);
+        mt = sep_wave_max(mt);
+        mv = sep_wave_max(mv);
+        s4 = sep_wave_sum(s4);
+        s5 = sep_wave_sum(s5);
+        s6 = sep_wave_sum(s6);
+        s7 = sep_wave_sum(s7);
+        bad = sep_wave_sum(bad);
+        if (cp == 0) {
+            double *r_ = red[rg];
+            r_[0] = dt; r_[1] = dv; r_[2] = mt; r_[3] = mv;
+            r_[4] = s4; r_[5] = s5; r_[6] = s6; r_[7] = s7; r_[8] = bad;
+        }
+    }
+    __syncthreads();
+    if (t < SE_NQ)
+        part[(size_t)blockIdx.x * SE_NQ + t] = t < 4 ? fmax(red[0][t], red[1][t])
+                                                     : red[0][t] + red[1][t];
+}
+
+// out[q] over the nb blocks' partials, q < 4 the largest, else the sum; with sites that left the
+// numbers out[0] = out[1] = NaN (the host refuses the update). One workgroup, a fixed order.
+__global__ __launch_bounds__(SP_T) void sep_reduce_kernel(const double *__restrict__ part, int nb,
+                                                         double *__restrict__ out)
+{
+    __shared__ double red[SP_T];
+    double v[SE_NQ];
+#pragma unroll
+    for (int q = 0; q < SE_NQ; ++q) v[q] = 0.0;
+    for (int k = threadIdx.x; k < nb; k += SP_T) {
+        const double *pk = part + (size_t)k * SE_NQ;
+#pragma unroll
+        for (int q = 0; q < SE_NQ; ++q) v[q] = q < 4 ? fmax(v[q], pk[q]) : v[q] + pk[q];
+    }
+#pragma unroll
+    for (int q = 0; q < SE_NQ; ++q)
+        v[q] = q < 4 ? block_max<SP_T>(v[q], red) : block_sum<SP_T>(v[q], red);
+    if (threadIdx.x == 0) {
+        if (v[8] > 0.0) v[0] = v[1] = NAN;
+#pragma unroll
+        for (int q = 0; q < SE_NQ; ++q) out[q] = v[q];
+    }
+}
+
+// The damped step: tau <- max(tau + eta (tn - tau), tfloor), nu <- nu + eta (vn - nu) and
+// nu' = nu - tau mean for j < n, zeros in the padding up to np (the scaled panel is
+// sl_scale_kernel's with W = tau, which takes the root itself)
+__global__ __launch_bounds__(SP_T) void sep_damp_kernel(const double *__restrict__ tn,
+                                                       const double *__restrict__ vn, double eta,
+                                                       double tfloor, double mean, int n, int np,
+                                                       double *__restrict__ tau,
+                                                       double *__restrict__ nu,
+                                                       double *__restrict__ nup)
+{
+    const int j = blockIdx.x * SP_T + threadIdx.x;
+    if (j >= np) return;
+    double ti = 0.0, vi = 0.0;
+    if (j < n) {
+        ti = fmax(tau[j] + eta * (tn[j] - tau[j]), tfloor);
+        vi = nu[j] + eta * (vn[j] - nu[j]);
+    }
+    tau[j] = ti;
+    nu[j] = vi;
+    nup[j] = vi - ti * mean;
+}
+
+// b_j = nu'_j - tau_j (mu_j - mean) for j < n, 0 for the padding; part[block] = sum b
+__global__ __launch_bounds__(SP_T) void sep_b_kernel(const double *__restrict__ nup,
+                                                    const double *__restrict__ tau,
+                                                    const double *__restrict__ mu, double mean,
+                                                    int n, int np, double *__restrict__ b,
+                                                    double *__restrict__ part)
+{
+    __shared__ double red[SP_T];
+    const int j = blockIdx.x * SP_T + threadIdx.x;
+    const double bj = j < n ? nup[j] - tau[j] * (mu[j] - mean) : 0.0;
+    if (j < np) b[j] = bj;
+    const double s = block_sum<SP_T>(bj, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// ---- host -------------------------------------------------------------------------------------
+// the site pass over `panel` with beta, and its nine reduced doubles to sesc
+static int sep_site(GpxSparse *st, hipStream_t s, const double *panel, const double *y)
+{
+    const int nb = st->np / SL_COLS;
+    hipLaunchKernelGGL(sep_site_kernel, dim3(nb), dim3(SP_T), 0, s, panel, (long long)st->ldn,
+                       st->pp, st->n, st->beta.d(), y, sev(st, SEV_TAU), sev(st, SEV_NU),
+                       st->mean, SE_FLOOR / st->prior, sev(st, SEV_TN), sev(st, SEV_VN),
+                       sev(st, SEV_MU), sev(st, SEV_SII), st->separt.d());
+    hipLaunchKernelGGL(sep_reduce_kernel, dim3(1), dim3(SP_T), 0, s, st->separt.d(), nb,
+                       st->sesc.d());
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+int gpx_sparse_ep_run_update(GpxSparse **state, hipStream_t s, const KParams &kp, const double *U,
+                             int p, double jitter, double mean, double tol, int max_iter,
+                             double damping, const double *X, const double *y, int n, int d,
+                             int cap, int *iters, int *info)
+{
+    const int r0 = sp_setup(state, s, kp, SP_EP, U, p, 0.0, jitter, mean, X, n, d, cap, info);
+    if (r0 != 0) return r0;
+    GpxSparse *st = *state;
+    st->lik = GPX_LIK_PROBIT;
+    const int pp = st->pp, ldp = st->ldp, np = st->np, ldn = st->ldn;
+    GPX_TRY(st->sev.reserve((size_t)SEV_COUNT * ldn * 8));
+    GPX_TRY(st->sez.reserve((size_t)SEZ_COUNT * pp * 8));
+    GPX_TRY(st->separt.reserve((size_t)(ldn / SL_COLS + 1) * SE_NQ * 8));
+    GPX_TRY(st->sesc.reserve(16 * 8));
+    // start: zero sites, cold every time; the prior's marginals are the pass over V0 with beta = 0
+    GPX_HIP(hipMemsetAsync(st->sev.p, 0, (size_t)SEV_COUNT * ldn * 8, s));
+    GPX_HIP(hipMemsetAsync(st->sez.p, 0, (size_t)SEZ_COUNT * pp * 8, s));
+    GPX_HIP(hipMemsetAsync(st->beta.p, 0, (size_t)pp * 8, s));
+    double *P1 = st->P1.d(), *P2 = st->P2.d(), *P3 = st->P3.d();
+    double *tau = sev(st, SEV_TAU), *nu = sev(st, SEV_NU), *nup = sev(st, SEV_NUP);
+    const double tfloor = SE_FLOOR / st->prior;
+    const dim3 pgrid((pp + SP_T - 1) / SP_T), cgrid((np + SP_T - 1) / SP_T);
+    double hs[SE_NQ];
+    int it = 0, inf = 0;
+    const double *panel = P2;
+    for (;;) {
+        // the site pass on the marginals of sweep `it`, and the one read of the sweep: its nine
+        // doubles and, behind a factorisation, sum log (R_A)_ii and the status word
+        GPX_TRY(sep_site(st, s, panel, y));
+        if (it == 1) GPX_TRY(sp_event(st, s, SEE_S6));
+        GPX_HIP(hipMemcpyAsync(hs, st->sesc.p, SE_NQ * 8, hipMemcpyDeviceToHost, s));
+        if (it > 0) {
+            GPX_HIP(hipMemcpyAsync(st->hsc, st->scal.p, S_COUNT * 8, hipMemcpyDeviceToHost, s));
+            GPX_HIP(hipMemcpyAsync(&inf, st->info.p, sizeof(int), hipMemcpyDeviceToHost, s));
+        }
+        GPX_HIP(hipStreamSynchronize(s));
+        if (iters) *iters = it;
+        st->se_sweeps = it;
+        if (inf) {
+            gpx_set_error("gpx_sparse_ep_update: I + V0 diag(tau) V0^T is not positive definite: "
+                          "pivot %d", inf);
+            if (info) *info = inf;
+            return inf;
+        }
+        if (!std::isfinite(hs[0]) || !std::isfinite(hs[1])) {
+            gpx_set_error("gpx_sparse_ep_update: the sites left the numbers at sweep %d", it);
+            return -1;
+        }
+        // (never on the pass over the prior marginals, which no factorisation stands behind)
+        if (it > 0 && std::max(hs[0], hs[1]) <= tol * (1.0 + std::max(hs[2], hs[3]))) break;
+        if (it == max_iter) {
+            gpx_set_error("gpx_sparse_ep_update: no convergence in %d sweeps (max_iter)", it);
+            return -1;
+        }
+        ++it;
+        const bool timed = it == 1;
+        if (timed) GPX_TRY(sp_event(st, s, SEE_S0));
+        // the damped sites, A = I + Vs Vs^T with Vs = V0 sqrt(tau), its factor and inverse
+        hipLaunchKernelGGL(sep_damp_kernel, cgrid, dim3(SP_T), 0, s, sev(st, SEV_TN),
+                           sev(st, SEV_VN), damping, tfloor, mean, n, np, tau, nu, nup);
+        hipLaunchKernelGGL(sl_scale_kernel, dim3(np / SL_COLS, pp / (SL_ROWS * SL_FLY)),
+                           dim3(SP_T), 0, s, P2, P1, (long long)ldn, tau);
+        GPX_HIP(hipGetLastError());
+        if (timed) GPX_TRY(sp_event(st, s, SEE_S1));
+        GPX_TRY(sp_abt_split(st, s, P1, P1, ldn, np, st->A.d(), ldp, 1.0));
+        if (timed) GPX_TRY(sp_event(st, s, SEE_S2));
+        GPX_TRY(sp_factor_enqueue(st, s, st->A.d(), st->Aw.d(), st->Ak.d(), st->gates_a));
+        if (timed) GPX_TRY(sp_event(st, s, SEE_S3));
+        // T0 = A^-T V0 beside V0, beta = A^-T V0 nu', sum log A_ii
+        GPX_TRY(sp_gemm(s, 1, 0, st->Aw.d(), ldp, P2, ldn, P3, ldn, pp, np, pp, 1.0, 0.0));
+        if (timed) GPX_TRY(sp_event(st, s, SEE_S4));
+        hipLaunchKernelGGL(sp_gemv_rows_kernel, dim3(pp), dim3(SP_T), 0, s, P2, (long long)ldn, n,
+                           nup, sez(st, SEZ_V));
+        hipLaunchKernelGGL(sp_gemv_cols_kernel, pgrid, dim3(SP_T), 0, s, st->Aw.d(),
+                           (long long)ldp, pp, pp, sez(st, SEZ_V), st->beta.d());
+        hipLaunchKernelGGL(sp_factor_terms_kernel, dim3(p), dim3(SP_T), 0, s, st->A.d(),
+                           st->Aw.d(), ldp, p, st->part.d());
+        GPX_HIP(hipGetLastError());
+        GPX_TRY(sp_reduce(s, st->part.d(), p, 2, st->scal.d() + S_LOGA));
+        if (timed) GPX_TRY(sp_event(st, s, SEE_S5));
+        panel = P3;
+    }
+    // at the stop the sites that came in, their marginals and the factor are one consistent set:
+    // lZ = -sum log (R_A)_ii + the four sums of the last site pass
+    st->se_lZ = -st->hsc[S_LOGA] + hs[4] + hs[5] + hs[6] + hs[7];
+    st->se_t0 = true;
+    GPX_TRY(sp_event(st, s, SEE_END));
+    GPX_HIP(hipStreamSynchronize(s));
+    st->se_ms[0] = sp_elapsed(st, 0, SEE_END);
+    st->se_ms[1] = sp_elapsed(st, SEE_S0, SEE_S6);
+    for (int k = 0; k < 4; ++k) st->se_ms[2 + k] = sp_elapsed(st, SEE_S0 + k, SEE_S1 + k);
+    st->se_ms[6] = sp_elapsed(st, SEE_S5, SEE_S6);
+    st->se_ms[7] = st->se_ms[8] = st->se_ms[9] = 0.0;
+    st->ready = true;
+    return 0;
+}
+
+static int sep_ready(const GpxSparse *st, const char *what)
+{
+    if (!st || !st->ready || st->method != SP_EP) {
+        gpx_set_error("%s: no sparse EP model (call gpx_sparse_ep_update)", what);
+        return -1;
+    }
+    return 0;
+}
+
+// lZ; with dlZ the gradient [kernel | mean]; with dU also d lZ / d U (p x d, host). At a fixed
+// point the sites carry no derivative: section 26's explicit part with W := tau, a := b, c := 0.
+int gpx_sparse_ep_run_loglik(GpxSparse *st, hipStream_t s, const double *X, double *lZ,
+                             double *dlZ, double *dU)
+{
+    GPX_TRY(sep_ready(st, "gpx_sparse_ep_loglik"));
+    *lZ = st->se_lZ;
+    if (!dlZ) return 0;
+    const int p = st->p, pp = st->pp, ldp = st->ldp, n = st->n, np = st->np, d = st->d;
+    const int ldn = st->ldn;
+    const long long ld = ldn;
+    const size_t panel = (size_t)pp * ldn * 8;
+    GPX_TRY(st->P4.reserve(panel));
+    GPX_TRY(st->Cm.reserve((size_t)pp * pp * 8));
+    GPX_TRY(st->Guu.reserve((size_t)pp * pp * 8));
+    const int nacc = 1 + st->kp.nhyper;
+    GPX_TRY(st->acc_uu.reserve((size_t)nacc * 8));
+    GPX_TRY(st->acc_ux.reserve((size_t)nacc * 8));
+    GPX_TRY(st->pg_part.reserve(gpx_pair_grad_scratch(pp) * 8));
+    double *P1 = st->P1.d(), *P2 = st->P2.d(), *P3 = st->P3.d(), *P4 = st->P4.d();
+    const double *tau = sev(st, SEV_TAU), *b = sev(st, SEV_B);
+    const int nbc = (np + SP_T - 1) / SP_T;
+    const dim3 cgrid(nbc), sgrid(np / SL_COLS, pp / (SL_ROWS * SL_FLY));
+    GPX_TRY(sp_event(st, s, SEE_GRAD0));
+    // b and its sum; T = T0 diag(tau) in place (a second call builds T0 again: the same product)
+    hipLaunchKernelGGL(sep_b_kernel, cgrid, dim3(SP_T), 0, s, sev(st, SEV_NUP), tau,
+                       sev(st, SEV_MU), st->mean, n, np, sev(st, SEV_B), st->part.d());
+    GPX_HIP(hipGetLastError());
+    GPX_TRY(sp_reduce(s, st->part.d(), nbc, 1, st->sesc.d() + 10));
+    if (!st->se_t0)
+        GPX_TRY(sp_gemm(s, 1, 0, st->Aw.d(), ldp, P2, ldn, P3, ldn, pp, np, pp, 1.0, 0.0));
+    st->se_t0 = false;
+    hipLaunchKernelGGL(sl_sigma_kernel, dim3(np / SL_COLS), dim3(SP_T), 0, s, P3, ld, pp, tau,
+                       tau, sev(st, SEV_SCR));
+    // B0 = L^-1 V0, B0 b
+    GPX_TRY(sp_gemm(s, 0, 0, st->Lw.d(), ldp, P2, ldn, P1, ldn, pp, np, pp, 1.0, 0.0));
+    hipLaunchKernelGGL(sp_gemv_rows_kernel, dim3(pp), dim3(SP_T), 0, s, P1, ld, n, b,
+                       sez(st, SEZ_WA));
+    GPX_HIP(hipGetLastError());
+    // (B0 T^T) T, then G_ux over it (sl_gux_kernel with c = 0); G_uu = -G_ux B0^T / 2
+    GPX_TRY(sp_abt_split(st, s, P1, P3, ld, np, st->Cm.d(), pp, 0.0));
+    GPX_TRY(sp_gemm(s, 0, 0, st->Cm.d(), pp, P3, ldn, P4, ldn, pp, np, pp, 1.0, 0.0));
+    hipLaunchKernelGGL(sl_gux_kernel, sgrid, dim3(SP_T), 0, s, P4, P1, ld, p, n, sez(st, SEZ_WA),
+                       sez(st, SEZ_ZERO), b, b, tau);
+    GPX_HIP(hipGetLastError());
+    GPX_TRY(sp_abt_split(st, s, P4, P1, ld, np, st->Guu.d(), pp, 0.0));
+    hipLaunchKernelGGL(sl_guu_kernel, dim3((pp + SP_T - 1) / SP_T, pp), dim3(SP_T), 0, s,
+                       st->Guu.d(), p, pp);
+    GPX_HIP(hipGetLastError());
+    // the contractions with the kernel derivatives
+    GPX_TRY(sp_event(st, s, SEE_GRAD1));
+    GPX_TRY(gpx_pair_grad(s, st->kp, st->U.d(), p, st->U.d(), p, d, st->Guu.d(), pp,
+                          st->pg_part.d(), st->acc_uu.d()));
+    GPX_TRY(gpx_pair_grad(s, st->kp, st->U.d(), p, X, n, d, P4, ld, st->pg_part.d(),
+                          st->acc_ux.d()));
+    std::vector<double> auu(nacc), aux(nacc);
+    double dm = 0.0;
+    GPX_HIP(hipMemcpyAsync(auu.data(), st->acc_uu.p, nacc * 8, hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipMemcpyAsync(aux.data(), st->acc_ux.p, nacc * 8, hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipMemcpyAsync(&dm, st->sesc.d() + 10, 8, hipMemcpyDeviceToHost, s));
+    GPX_TRY(sp_event(st, s, SEE_GRAD2));
+    st->se_ms[9] = 0.0;
+    if (dU) {
+        GPX_TRY(st->px_part.reserve(std::max(gpx_pair_gradx_scratch(p, p, d),
+                                             gpx_pair_gradx_scratch(p, n, d)) * 8));
+        GPX_TRY(st->dU.reserve((size_t)p * d * 8));
+        GPX_TRY(sp_event(st, s, SEE_DU0));
+        GPX_TRY(gpx_pair_gradx(s, st->kp, st->U.d(), p, st->U.d(), p, d, st->Guu.d(), pp, true,
+                               st->px_part.d(), st->dU.d(), false));
+        GPX_TRY(gpx_pair_gradx(s, st->kp, st->U.d(), p, X, n, d, P4, ld, false,
+                               st->px_part.d(), st->dU.d(), true));
+        GPX_TRY(sp_event(st, s, SEE_DU1));
+        GPX_HIP(hipMemcpyAsync(dU, st->dU.p, (size_t)p * d * 8, hipMemcpyDeviceToHost, s));
+    }
+    GPX_HIP(hipStreamSynchronize(s));
+    st->se_ms[7] = sp_elapsed(st, SEE_GRAD0, SEE_GRAD2);
+    st->se_ms[8] = sp_elapsed(st, SEE_GRAD1, SEE_GRAD2);
+    if (dU) st->se_ms[9] = sp_elapsed(st, SEE_DU0, SEE_DU1);
+    const int nh = st->kp.nhyper;
+    for (int k = 0; k < nh; ++k) dlZ[k] = auu[1 + k] + aux[1 + k];
+    dlZ[nh] = dm;
+    return 0;
+}
+
+// tau, nu and the marginals mu, Sigma_ii at the data (n each, host); any may be null
+int gpx_sparse_ep_run_sites(GpxSparse *st, hipStream_t s, double *tau, double *nu, double *mu,
+                            double *s2)
+{
+    GPX_TRY(sep_ready(st, "gpx_sparse_ep_get_sites"));
+    const int slot[4] = {SEV_TAU, SEV_NU, SEV_MU, SEV_SII};
+    double *dst[4] = {tau, nu, mu, s2};
+    for (int k = 0; k < 4; ++k)
+        if (dst[k])
+            GPX_HIP(hipMemcpyAsync(dst[k], sev(st, slot[k]), (size_t)st->n * 8,
+                                   hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+// ms[0] the last update, ms[1] its first sweep, ms[2 .. 6] that sweep's stages: the damped sites
+// and the scaled panel, A, its factorisation, the product T0 = A^-T V0, the fused pass with its
+// reduction (the three gemvs between the last two belong to ms[1] alone); ms[7] the last gradient
+// stage, ms[8] its contraction pass, ms[9] the dU pass; ms[10] the sweeps of the last update
+int gpx_sparse_ep_run_timings(GpxSparse *st, double *ms)
+{
+    if (!st || st->method != SP_EP) {
+        gpx_set_error("gpx_sparse_ep_timings: no sparse EP model");
+        return -1;
+    }
+    for (int i = 0; i < 10; ++i) ms[i] = st->se_ms[i];
+    ms[10] = st->se_sweeps;
+    ms[11] = 0.0;
     return 0;
 }

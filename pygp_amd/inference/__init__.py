@@ -6,6 +6,7 @@ from .coreg import CoregionalGP
 from .laplace import LaplaceGP
 from .sparse_laplace import SparseLaplaceGP
 from .ep import EPGP
+from .sparse_ep import SparseEPGP
 from .softmax import MulticlassLaplaceGP
 from .fitc import FITC
 from .dtc import DTC
@@ -17,5 +18,5 @@ from .pathwise import PathwiseSample
 from .iterative import IterativeGP
 
 __all__ = ['GP', 'ExactGP', 'BasicGP', 'GradientGP', 'MultiOutputGP', 'CoregionalGP', 'LaplaceGP',
-           'SparseLaplaceGP', 'EPGP', 'MulticlassLaplaceGP', 'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'FourierSample', 'SSGP',
+           'SparseLaplaceGP', 'EPGP', 'SparseEPGP', 'MulticlassLaplaceGP', 'FITC', 'DTC', 'VFE', 'select_pseudoinputs', 'FourierSample', 'SSGP',
            'PathwiseSample', 'IterativeGP']
